@@ -366,9 +366,34 @@ def test_bench_flow_with_four_ranks_on_one_device():
     for run in range(3):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "2",
                             "--dist-backend", "gloo", "--force-device", "0", "--batch", "65536", "--sustain", "0",
-                            "--no-cpu", "--no-configs", "--no-live-counters"], capture_output=True, text=True, timeout=900, cwd=root)
+                            "--full", "--no-cpu", "--no-configs", "--no-live-counters"], capture_output=True, text=True, timeout=900,
+                           cwd=root)
         assert p.returncode == 0 and "PARITY FAILURE" not in p.stderr, (run, p.stdout[-1500:], p.stderr[-3000:])
         line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == 4 and line["rccl"]["nranks_seen"] == 4, line.get("rccl")
         assert "equals the global batch's expected mask" in line["strong"]["parity"], line["strong"]
         assert len(line["per_rank"]) == 4
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline fields of exactly --steps timed steps and none of
+    the --full measurements; --dump-outputs writes the last step's verify mask as float32, equal to the
+    mask the batch was built with (every 100th tuple corrupted, all others valid)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps = 65536, 3
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--batch", str(n), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == steps and line["unit"] == "verifies/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0 and abs(line["ms_per_step"] * steps - line["timed_region_s"] * 1e3) < 1e-6 * line["ms_per_step"]
+    assert abs(line["value"] - n * steps / line["timed_region_s"]) < 1e-6 * line["value"]
+    for key in ("roofline", "one_in_flight", "sustained", "configs", "cpu_baseline"):
+        assert key not in line, key
+    got = np.load(str(tmp_path / "verify_ok.npy"))
+    want = np.ones(n, np.float32)
+    want[::100] = 0
+    assert got.dtype == np.float32 and np.array_equal(got, want)

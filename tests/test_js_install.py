@@ -4,9 +4,8 @@ CPU: the reference's own, unmodified mocha suite must pass with install()
 applied to the reference library; in this GPU-less container the addon is
 pointed at the CPU unit-test build of the device code (tests/hostsim), so what
 is exercised is the marshalling, the prototype patch and the device code's
-logic.  Needs Node and a copy of the reference: /root/reference (build container)
-or the git-ignored oracle/_ref that oracle/make_ref.py fills from it and that travels
-to the GPU box.
+logic.  Needs Node and the copy of the reference that build() places in the
+git-ignored oracle/_ref (oracle/make_ref.py).
 GPU (-m gpu): the same two gates -- the reference's unmodified suite and the golden
 replay incl. every exception message -- through install() on the REAL libellgpu.so
 (generated-asm multiplier, 16-bit comb: the shipped hot path), and the batch API
@@ -30,13 +29,11 @@ HOSTSIM_ENV = {"ELLGPU_WIDE_GRID": "0"}
 
 
 def _reference():
-    """directory of a reference copy (ELLIPTIC_REFERENCE for tools/ref_loader.js), or skip"""
-    if os.path.exists("/root/reference/dist/elliptic.js"):
-        return "/root/reference"
+    """directory of the reference copy in oracle/_ref (ELLIPTIC_REFERENCE for tools/ref_loader.js), or skip"""
     from oracle import make_ref
     d = make_ref.present()
     if d is None:
-        pytest.skip("no copy of the reference (neither /root/reference nor oracle/_ref)")
+        pytest.skip("no copy of the reference in oracle/_ref (made by build())")
     return d
 
 
