@@ -31,6 +31,9 @@ _SIGS = {
                                                  ctypes.POINTER(ctypes.c_int)]),
     "ellgpu_curve_define_edwards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                                    ctypes.POINTER(ctypes.c_int)]),
+    "ellgpu_curve_define_short_domain": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                        ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                                        ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
     "ellgpu_ctx_destroy": (None, [ctypes.c_void_p]),
     "ellgpu_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "ellgpu_ctx_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]),

@@ -212,8 +212,9 @@ int ellgpu_ctx_comb_bits(ellgpu_ctx* ctx, int curve) {
   return ctx->eng->comb_bits(curve);
 }
 
+// dom: n, gx, gy of an ECDSA domain (edwards = 0), else null
 static int define_custom(ellgpu_ctx* ctx, int edwards, const uint8_t* p, const uint8_t* a, const uint8_t* b,
-                         int* out_curve) {
+                         int* out_curve, const uint8_t* const* dom = nullptr) {
   if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
   ELL_LOCK(ctx);
   if (!ctx->members.empty()) {
@@ -223,21 +224,22 @@ static int define_custom(ellgpu_ctx* ctx, int edwards, const uint8_t* p, const u
     // first half (Engine::custom_slot_for)
     int id = -1;
     for (size_t i = 0; i < ctx->members.size(); i++) {
-      int mid = ctx->members[i]->eng->custom_slot_for(edwards, p, a, b);
+      int mid = ctx->members[i]->eng->custom_slot_for(edwards, p, a, b, dom);
       if (mid < 0) return set_err(ELLGPU_E_UNSUPPORTED, "user-defined curve table of a group member is full");
       if (i && mid != id) return set_err(ELLGPU_E_ARG, "group members disagree on the curve id (curves were defined on a member directly)");
       id = mid;
     }
     for (size_t i = 0; i < ctx->members.size(); i++) {
       int mid = -1;
-      int rc = define_custom(ctx->members[i], edwards, p, a, b, &mid);
+      int rc = define_custom(ctx->members[i], edwards, p, a, b, &mid, dom);
       if (rc) return rc;                             // (parameter errors are the same on every member: member 0 fails first)
     }
     if (out_curve) *out_curve = id;
     return ELLGPU_OK;
   }
   ctx->eng->err.clear();
-  int rc = edwards ? ctx->eng->define_edwards(p, a, b, out_curve) : ctx->eng->define_short(p, a, b, out_curve);
+  int rc = dom ? ctx->eng->define_short_domain(p, a, b, dom[0], dom[1], dom[2], out_curve)
+               : edwards ? ctx->eng->define_edwards(p, a, b, out_curve) : ctx->eng->define_short(p, a, b, out_curve);
   if (rc) g_last_error = ctx->eng->err.empty() ? "ellgpu error" : ctx->eng->err;
   return rc;
 }
@@ -248,6 +250,12 @@ int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* 
 int ellgpu_curve_define_edwards(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* d,
                                 int* out_curve) {
   return define_custom(ctx, 1, p, a, d, out_curve);
+}
+int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
+                                     const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve) {
+  const uint8_t* dom[3] = {n, gx, gy};
+  if (!n || !gx || !gy) return set_err(ELLGPU_E_ARG, "null pointer");
+  return define_custom(ctx, 0, p, a, b, out_curve, dom);
 }
 
 #define ELL_ENTER(ctx, stream)                                      \

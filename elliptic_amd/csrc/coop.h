@@ -592,6 +592,7 @@ struct CvSecp256k1CT {
   static constexpr int A_KIND = 0;
   static constexpr bool ENDO = true;
   static constexpr bool JTABLE = false;
+  static constexpr bool RT_ORDER = false;
   static constexpr int ID = CURVE_SECP256K1;
 };
 typedef CvSecp256k1CT<false> CvSecp256k1C;

@@ -384,6 +384,7 @@ struct CoopNist {
     static constexpr int A_KIND = CV1::A_KIND;
     static constexpr bool ENDO = false;
     static constexpr bool JTABLE = false;
+    static constexpr bool RT_ORDER = false;
     static constexpr int ID = CV1::ID;
   };
   typedef typename CV::F F;

@@ -45,6 +45,7 @@ struct CvSecp256k1 {
   static constexpr int A_KIND = 0;
   static constexpr bool ENDO = true;
   static constexpr bool JTABLE = false;
+  static constexpr bool RT_ORDER = false;
   static constexpr int ID = CURVE_SECP256K1;
 };
 
@@ -58,6 +59,7 @@ struct CvNist {
   static constexpr int A_KIND = 3;
   static constexpr bool ENDO = false;
   static constexpr bool JTABLE = false;
+  static constexpr bool RT_ORDER = false;
   static constexpr int ID = ID_;
 };
 
@@ -88,7 +90,24 @@ struct CvCustom {
   static constexpr int A_KIND = 1;
   static constexpr bool ENDO = false;
   static constexpr bool JTABLE = true;
+  static constexpr bool RT_ORDER = false;
   static constexpr int ID = 16;
+};
+// A user-defined ECDSA domain (ellgpu_curve_define_short_domain): the same curve arithmetic as
+// CvCustom, plus the order field over the run-time n (FpMontRTn) and a fixed-base comb of the
+// run-time G -- 8-bit UNSIGNED windows over all 256 scalar bits, built without reducing anything
+// mod n (n need not be G's order).  RT_ORDER: Work reads n and G from the parameter block
+// (Work::order_words, eq_x_to_p) instead of C.  ID only names the kernels: the comb of each
+// domain lives in its own slot (Engine::comb_idx).
+struct CvCustomDomain {
+  typedef FpMontRT F;
+  typedef FpMontRTn Fn;
+  typedef consts::CUSTOM_C C;
+  static constexpr int A_KIND = 1;
+  static constexpr bool ENDO = false;
+  static constexpr bool JTABLE = true;
+  static constexpr bool RT_ORDER = true;
+  static constexpr int ID = 17;
 };
 constexpr int CURVE_CUSTOM0 = 16;                 // C-ABI ids 16..31: ellgpu_curve_define_short / _edwards
 constexpr int CURVE_CUSTOM_MAX = 16;

@@ -163,14 +163,22 @@ struct FnCombGen {
       if (l == li) v[l] = d << bs;
       if (l == li + 1 && bs) v[l] = d >> (32 - bs);
     }
+    u32 kk[W::L], gx[W::L], gy[W::L];
+    if constexpr (CV::RT_ORDER) {
+      // a user-defined domain: the unsigned comb's values d << sh stay below 2^256, and are NOT
+      // reduced mod n -- n need not be G's order (curves.h CvCustomDomain)
+      W::generator_words(gx, gy);
+      ELL_UNROLL
+      for (int l = 0; l < W::L; l++) kk[l] = v[l];
+    } else {
     u8 vb[8 * LN];
     store_be<2 * LN>(vb, v, 8 * LN);
     typename W::Nl km = W::bytes_mod_n(vb, 8 * LN);
     u32 kn[LN];
     W::Fn::to_plain(kn, km);
-    u32 kk[W::L], gx[W::L], gy[W::L];
     ELL_UNROLL
     for (int l = 0; l < W::L; l++) { kk[l] = l < LN ? kn[l] : 0u; gx[l] = W::C::gx_plain[l]; gy[l] = W::C::gy_plain[l]; }
+    }
     store_be<W::L>(k + i * W::BYTES, kk, W::BYTES);
     store_be<W::L>(xy + i * 2 * W::BYTES, gx, W::BYTES);
     store_be<W::L>(xy + i * 2 * W::BYTES + W::BYTES, gy, W::BYTES);
@@ -1139,11 +1147,11 @@ class Engine {
   static constexpr size_t CHUNK = 1u << 21;   // max items per launch (bounds the scratch arena)
 
   explicit Engine(const BK& b) : bk(b) {
-    for (int i = 0; i < CURVE_COUNT; i++) { comb_[i] = nullptr; comb_base_[i] = nullptr; comb_bits_[i] = 0; }
+    for (int i = 0; i < COMB_SLOTS; i++) { comb_[i] = nullptr; comb_base_[i] = nullptr; comb_bits_[i] = 0; }
     init_tuning();
   }
   ~Engine() {
-    for (int i = 0; i < CURVE_COUNT; i++)
+    for (int i = 0; i < COMB_SLOTS; i++)
       if (comb_[i]) bk.free_(comb_base_[i] ? comb_base_[i] : comb_[i]);
     for (auto& a : scratch_)
       for (auto& s : a)
@@ -1297,31 +1305,71 @@ class Engine {
     bn_sub<8>(f.pm2, f.p, two);
     return E_OK;
   }
-  static void rt_times_r(const RtField& f, u32 (&r)[8]) {          // r * 2^256 mod p, r < p
+  static void rt_times_r(const RtField& f, u32 (&r)[8]) { mod_times_r(f.p, r); }
+  static void rt_to_mont(const RtField& f, u32 (&out)[8], const u32 (&x)[8]) { mod_to_mont(f.p, out, x); }
+  // host arithmetic modulo any odd m < 2^256, bit by bit (a definition is rare; these are not hot)
+  static void mod_times_r(const u32 (&m)[8], u32 (&r)[8]) {        // r * 2^256 mod m, r < m
     for (int i = 0; i < 256; i++) {
       u32 t[8];
-      mod_add<8>(t, r, r, f.p);
+      mod_add<8>(t, r, r, m);
       bn_copy<8>(r, t);
     }
   }
-  // out = x * 2^256 mod p for any x < 2^256 (reduced bit by bit first)
-  static void rt_to_mont(const RtField& f, u32 (&out)[8], const u32 (&x)[8]) {
+  // out = x mod m for any x < 2^256
+  static void mod_reduce(const u32 (&m)[8], u32 (&out)[8], const u32 (&x)[8]) {
     u32 r[8];
     bn_zero<8>(r);
     for (int i = 255; i >= 0; i--) {
       u32 t[8];
-      mod_add<8>(t, r, r, f.p);
+      mod_add<8>(t, r, r, m);
       bn_copy<8>(r, t);
       if ((x[i >> 5] >> (i & 31)) & 1u) {
         u32 o[8];
         bn_zero<8>(o);
         o[0] = 1;
-        mod_add<8>(t, r, o, f.p);
+        mod_add<8>(t, r, o, m);
         bn_copy<8>(r, t);
       }
     }
-    rt_times_r(f, r);
     bn_copy<8>(out, r);
+  }
+  // out = x * 2^256 mod m for any x < 2^256 (reduced bit by bit first)
+  static void mod_to_mont(const u32 (&m)[8], u32 (&out)[8], const u32 (&x)[8]) {
+    u32 r[8];
+    mod_reduce(m, r, x);
+    mod_times_r(m, r);
+    bn_copy<8>(out, r);
+  }
+  // out = a * b mod m, a and b < m
+  static void mod_mul(const u32 (&m)[8], u32 (&out)[8], const u32 (&a)[8], const u32 (&b)[8]) {
+    u32 r[8];
+    bn_zero<8>(r);
+    for (int i = 255; i >= 0; i--) {
+      u32 t[8];
+      mod_add<8>(t, r, r, m);
+      bn_copy<8>(r, t);
+      if ((b[i >> 5] >> (i & 31)) & 1u) {
+        mod_add<8>(t, r, a, m);
+        bn_copy<8>(r, t);
+      }
+    }
+    bn_copy<8>(out, r);
+  }
+  // the Montgomery constants of a modulus m: -m^-1 mod 2^32, R mod m, R^2 mod m, m - 2
+  static void mont_consts(const u32 (&m)[8], u32& n0, u32 (&one)[8], u32 (&r2)[8], u32 (&mm2)[8]) {
+    u32 inv = 1;                                          // m^-1 mod 2^32 (Newton)
+    for (int i = 0; i < 5; i++) inv *= 2u - m[0] * inv;
+    n0 = 0u - inv;
+    u32 o[8];
+    bn_zero<8>(o);
+    o[0] = 1;
+    mod_to_mont(m, one, o);
+    bn_copy<8>(r2, one);
+    mod_times_r(m, r2);
+    u32 two[8];
+    bn_zero<8>(two);
+    two[0] = 2;
+    bn_sub<8>(mm2, m, two);
   }
   int register_custom(const RtField& f, int* out_curve) {
     for (size_t i = 0; i < custom_.size(); i++)
@@ -1364,6 +1412,75 @@ class Engine {
     int rc = build_custom(0, p_be, a_be, b_be, f);
     return rc ? rc : register_custom(f, out_curve);
   }
+  // An ECDSA domain on a user-defined short curve (ellgpu_curve_define_short_domain): the curve's
+  // block plus the order n and the generator G -- EC#verify, k*G and mulAdd with G on the device.
+  // Refused: n even or < 3, G not on the curve (coordinates >= p included), 4a^3 + 27b^2 = 0.
+  // n's primality is not checked (s^-1 is Fermat's s^(n-2) here).
+  int build_domain(const u8* p_be, const u8* a_be, const u8* b_be, const u8* n_be, const u8* gx_be,
+                   const u8* gy_be, RtField& f) {
+    if (!n_be || !gx_be || !gy_be) return fail(E_ARG, "null pointer");
+    int rc = build_custom(0, p_be, a_be, b_be, f);
+    if (rc) return rc;
+    u32 a[8], b[8], n[8], gx[8], gy[8];
+    load_be<8>(a, a_be, 32);
+    load_be<8>(b, b_be, 32);
+    mod_reduce(f.p, a, a);
+    mod_reduce(f.p, b, b);
+    load_be<8>(n, n_be, 32);
+    load_be<8>(gx, gx_be, 32);
+    load_be<8>(gy, gy_be, 32);
+    bool small = true;
+    for (int i = 1; i < 8; i++) small = small && n[i] == 0;
+    if (!(n[0] & 1u) || (small && n[0] < 3)) return fail(E_ARG, "ECDSA domain: the order must be odd and >= 3");
+    // 4 a^3 + 27 b^2 != 0 (mod p): a curve, not a singular cubic
+    u32 t[8], u[8], k[8];
+    mod_mul(f.p, t, a, a);
+    mod_mul(f.p, t, t, a);
+    bn_zero<8>(k);
+    k[0] = 4;
+    mod_reduce(f.p, k, k);
+    mod_mul(f.p, t, t, k);
+    mod_mul(f.p, u, b, b);
+    bn_zero<8>(k);
+    k[0] = 27;
+    mod_reduce(f.p, k, k);
+    mod_mul(f.p, u, u, k);
+    mod_add<8>(k, t, u, f.p);
+    if (bn_is_zero<8>(k)) return fail(E_ARG, "ECDSA domain: singular curve (4a^3 + 27b^2 = 0 mod p)");
+    // G on the curve: y^2 == x^3 + a x + b, with x, y < p
+    if (bn_geq<8>(gx, f.p) || bn_geq<8>(gy, f.p)) return fail(E_ARG, "ECDSA domain: G is not on the curve");
+    mod_mul(f.p, t, gx, gx);
+    mod_add<8>(t, t, a, f.p);
+    mod_mul(f.p, t, t, gx);
+    mod_add<8>(t, t, b, f.p);
+    mod_mul(f.p, u, gy, gy);
+    if (!bn_eq<8>(t, u)) return fail(E_ARG, "ECDSA domain: G is not on the curve");
+    f.domain = 1;
+    bn_copy<8>(f.n, n);
+    mont_consts(n, f.nn0, f.n_one, f.n_r2, f.nm2);
+    int nb = 256;
+    while (nb > 0 && !((n[(nb - 1) >> 5] >> ((nb - 1) & 31)) & 1u)) nb--;
+    f.nbits = (u32)nb;
+    mod_to_mont(f.p, f.n_p, n);
+    // floor(p / n), as far as 101 (base.js:33-40: the Maxwell trick for <= 100)
+    u32 q = 0, rem[8];
+    bn_copy<8>(rem, f.p);
+    while (q <= 100 && bn_geq<8>(rem, n)) {
+      bn_sub<8>(rem, rem, n);
+      q++;
+    }
+    f.ncand = q <= 100 ? q : RT_NO_MAXWELL;
+    bn_copy<8>(f.gx, gx);
+    bn_copy<8>(f.gy, gy);
+    return E_OK;
+  }
+  int define_short_domain(const u8* p_be, const u8* a_be, const u8* b_be, const u8* n_be, const u8* gx_be,
+                          const u8* gy_be, int* out_curve) {
+    if (!out_curve) return fail(E_ARG, "null pointer");
+    RtField f;
+    int rc = build_domain(p_be, a_be, b_be, n_be, gx_be, gy_be, f);
+    return rc ? rc : register_custom(f, out_curve);
+  }
   // `new elliptic.curve.edwards({p, a, c: 1, d})` (edwards.js:11-31) with parameters that are not
   // ed25519's: a x^2 + y^2 = 1 + d x^2 y^2 over an odd prime p < 2^256; Point#mul, mulAdd and
   // Point#add run on the device in projective coordinates (edcustom.h).
@@ -1376,10 +1493,12 @@ class Engine {
   // the id a definition WOULD get (the existing one for parameters already registered, else the
   // next free one), -1 when the table is full; registers nothing.  Invalid parameters report the
   // next free id: the definition itself then fails with its own message, on the first member.
-  int custom_slot_for(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be) {
+  // dom: n, gx, gy of an ECDSA domain (edwards = 0), else null
+  int custom_slot_for(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be,
+                      const u8* const* dom = nullptr) {
     RtField f;
     std::string keep = err;
-    int rc = build_custom(edwards, p_be, a_be, bd_be, f);
+    int rc = dom ? build_domain(p_be, a_be, bd_be, dom[0], dom[1], dom[2], f) : build_custom(edwards, p_be, a_be, bd_be, f);
     err = keep;
     if (rc == E_OK)
       for (size_t i = 0; i < custom_.size(); i++)
@@ -1396,6 +1515,14 @@ class Engine {
     size_t slot = (size_t)(curve - CURVE_CUSTOM0);
     return is_custom(curve) && slot < custom_.size() && custom_[slot].kind == 1;
   }
+  bool custom_is_domain(int curve) const {
+    size_t slot = (size_t)(curve - CURVE_CUSTOM0);
+    return is_custom(curve) && slot < custom_.size() && custom_[slot].domain == 1;
+  }
+  // where the fixed-base table of a curve type lives: the presets' by their id, a domain's in the
+  // slot of the curve the current call is on (CustomScope)
+  template <class CV>
+  int comb_idx() const { return CV::RT_ORDER ? custom_curve_ : CV::ID; }
   // Brackets one call on a user-defined curve: takes the device's custom-curve lock, uploads the
   // curve's parameter block (synchronously: every earlier user of the block has finished, see the
   // destructor) and, at the end, waits for the call's device work before the lock is released.
@@ -1411,6 +1538,7 @@ class Engine {
       custom_mutex(e->bk.device_index()).lock();
       owner = true;
       e->custom_active_ = true;
+      e->custom_curve_ = curve;
       e->bk.rt_upload(e->custom_[slot]);
     }
     ~CustomScope() {
@@ -1438,12 +1566,16 @@ class Engine {
     if (curve == CURVE_CURVE25519)
       return fail(E_UNSUPPORTED, "curve25519 has no affine fixed-base form; use x25519_ladder");
     if (n && (!k || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    int rc = prepare_curve(curve);
+    const bool dom = custom_is_domain(curve);
+    CustomScope sc(this, dom ? curve : -1);
+    if (sc.rc) return sc.rc;
+    int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
     if (rc) return rc;
     const size_t B = ci->field_bytes;
     for (size_t o = 0; o < n; o += CHUNK) {
       size_t m = n - o < CHUNK ? n - o : CHUNK;
-      if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
+      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
+      else if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
       else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, k + o * B, out_xy + o * 2 * B, out_inf + o));
       if (rc) return rc;
     }
@@ -1490,20 +1622,25 @@ class Engine {
       return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");     // mont.js:155-157
     if (n && (!k1 || !k2 || !xy2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
     int rc = E_OK;
-    if (is_custom(curve) && !xy1)
-      return fail(E_UNSUPPORTED, "user-defined curves have no fixed-base table: pass the generator as p1");
-    if (!xy1) { rc = prepare_curve(curve); if (rc) return rc; }
+    const bool dom = custom_is_domain(curve);
+    if (is_custom(curve) && !xy1 && !dom)
+      return fail(E_UNSUPPORTED, "user-defined curves without a generator have no fixed-base table: pass the generator as p1");
+    if (!xy1 && !dom) { rc = prepare_curve(curve); if (rc) return rc; }
     const size_t B = ci->field_bytes;
     if (overlap(xy2, out_xy, n * 2 * B) || (xy1 && overlap(xy1, out_xy, n * 2 * B)))   // see mul_var_dev
       return fail(E_ARG, "p1_xy / p2_xy and out_xy must not overlap");
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
+    if (!xy1 && dom) { rc = ensure_comb<CvCustomDomain>(); if (rc) return rc; }
     for (size_t o = 0; o < n; o += CHUNK) {
       size_t m = n - o < CHUNK ? n - o : CHUNK;
       const u8* p1 = xy1 ? xy1 + o * 2 * B : nullptr;
       if (custom_is_edwards(curve))
         rc = edc_chunk(1, m, k1 + o * B, p1, k2 + o * B, xy2 + o * 2 * B, nullptr, nullptr, out_xy + o * 2 * B,
                        out_inf + o);
+      else if (is_custom(curve) && !p1)
+        rc = mul_add_g_chunk<CvCustomDomain>(m, k1 + o * B, k2 + o * B, xy2 + o * 2 * B, out_xy + o * 2 * B,
+                                             out_inf + o);
       else if (is_custom(curve))
         rc = mul_add2_chunk<CvCustom>(m, k1 + o * B, p1, k2 + o * B, xy2 + o * 2 * B, out_xy + o * 2 * B,
                                       out_inf + o);
@@ -1528,22 +1665,31 @@ class Engine {
                        const u8* r, const u8* s, const u8* pub, u8* ok, u8* st) {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve >= CURVE_ED25519)
-      return fail(E_UNSUPPORTED, "ECDSA verify is implemented for the short Weierstrass presets");
+    const bool dom = custom_is_domain(curve);
+    if (curve >= CURVE_ED25519 && !dom)
+      return fail(E_UNSUPPORTED, is_custom(curve) ? "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"
+                                                  : "ECDSA verify is implemented for the short Weierstrass presets");
     if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0 || msg_bits < 0) return fail(E_ARG, "bad hash_len / msg_bits");
-    // _truncateToN (ec/index.js:97-102): delta = bitLength - n.bitLength()
+    // _truncateToN (ec/index.js:97-102): delta = bitLength - n.bitLength() (a domain's own n)
+    const int order_bits = dom ? (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits : ci->order_bits;
     int bits = msg_bits ? msg_bits : hash_len * 8;
-    int shift = bits - ci->order_bits;
+    int shift = bits - order_bits;
     if (shift < 0) shift = 0;
-    int ln = (ci->order_bits + 31) / 32;
+    int ln = dom ? 8 : (order_bits + 31) / 32;
     if (hash_len * 8 - shift > 32 * ln || hash_len - (shift >> 3) > 4 * (ln + 1))
       return fail(E_ARG, "hash_len / msg_bits combination leaves more bits than the order width");
-    int rc = prepare_curve(curve);
+    CustomScope sc(this, dom ? curve : -1);
+    if (sc.rc) return sc.rc;
+    int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
     if (rc) return rc;
     const size_t B = ci->field_bytes, NB = ci->order_bytes;
     for (size_t o = 0; o < n; o += CHUNK) {
       size_t m = n - o < CHUNK ? n - o : CHUNK;
+      if (dom)
+        rc = ecdsa_chunk<CvCustomDomain>(m, hash + o * hash_len, hash_len, shift, r + o * NB, s + o * NB,
+                                         pub + o * 2 * B, ok + o, st ? st + o : nullptr);
+      else
       ELL_SHORT_DISPATCH(curve, rc = ecdsa_chunk<CV>(m, hash + o * hash_len, hash_len, shift,
                                                      r + o * NB, s + o * NB, pub + o * 2 * B,
                                                      ok + o, st ? st + o : nullptr));
@@ -2309,6 +2455,8 @@ class Engine {
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!k || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
     size_t B = ci->field_bytes;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
     u8* dk = out_buf(G_IN0, n * B);
     u8* dxy = out_buf(G_OUT0, n * 2 * B);
     u8* dinf = out_buf(G_OUT1, n);
@@ -2368,6 +2516,8 @@ class Engine {
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
     size_t B = ci->field_bytes, NB = ci->order_bytes;
     size_t HL = (size_t)hash_len;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
     u8* dh = out_buf(G_IN0, n * HL);
     u8* dr = out_buf(G_IN1, n * NB);
     u8* dsg = out_buf(G_IN2, n * NB);
@@ -2424,14 +2574,17 @@ class Engine {
   }
 
  private:
-  void* comb_[CURVE_COUNT];                  // entry 0 of the fixed-base table (the slot in front of it: its geometry)
-  void* comb_base_[CURVE_COUNT];             // what was allocated
-  int comb_bits_[CURVE_COUNT];               // window width in use (signed combs may be narrower than the default)
+  // (indexed by preset id, and by user-defined id for the combs of ECDSA domains: comb_idx)
+  static constexpr int COMB_SLOTS = CURVE_CUSTOM0 + CURVE_CUSTOM_MAX;
+  void* comb_[COMB_SLOTS];                   // entry 0 of the fixed-base table (the slot in front of it: its geometry)
+  void* comb_base_[COMB_SLOTS];              // what was allocated
+  int comb_bits_[COMB_SLOTS];                // window width in use (signed combs may be narrower than the default)
   Buf scratch_[2][S_COUNT];   // one scratch arena per compute lane (see pipelined())
   int lane_ = 0;
   Buf staging_[G_COUNT];
   std::vector<RtField> custom_;  // user-defined curves of this context (id = CURVE_CUSTOM0 + index)
   bool custom_active_ = false;
+  int custom_curve_ = 0;         // the user-defined curve of the call in progress (CustomScope)
   size_t pipe_step_ = pipe_step_default();   // chunks after the first, in quanta
 };
 
@@ -2441,7 +2594,7 @@ template <class BK>
 template <class CV>
 int Engine<BK>::ensure_comb() {
   typedef Work<CV> W;
-  if (comb_[CV::ID]) return E_OK;
+  if (comb_[comb_idx<CV>()]) return E_OK;
   // Built by the engine itself: the variable-base kernel on the scalars d << (COMB_BITS w) and
   // the generator, in slices of at most 2^20 entries (the 22-bit signed comb of the 256-bit
   // curves has 25 M entries = 1.6 GB; a slice needs 1 GB of window-table scratch).
@@ -2469,16 +2622,19 @@ int Engine<BK>::ensure_comb() {
         const size_t m = n - first < slice ? n - first : slice;
         FnCombGen<CV> g{m, first, dk, dp, cb};
         bk.launch(g, m);
-        rc = mul_var_chunk<CV>(m, dk, dp, nullptr, nullptr, comb + first);
+        // (a domain's entries come from the user-defined curves' own ladder: the same field and
+        // points, no second instantiation of it)
+        typedef typename std::conditional<CV::RT_ORDER, CvCustom, CV>::type CVL;
+        rc = mul_var_chunk<CVL>(m, dk, dp, nullptr, nullptr, comb + first);
       }
       const int src = bk.sync();                   // a failed launch (comb_gen included) surfaces here
       if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
       if (rc == E_OK) {
         bk.free_(dk);
         bk.free_(dp);
-        comb_[CV::ID] = comb;
-        comb_base_[CV::ID] = base;
-        comb_bits_[CV::ID] = cb;
+        comb_[comb_idx<CV>()] = comb;
+        comb_base_[comb_idx<CV>()] = base;
+        comb_bits_[comb_idx<CV>()] = cb;
         return E_OK;
       }
     }
@@ -2581,7 +2737,7 @@ int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_inf) 
   if constexpr ((row_k256 || row_nist) && W::NBYTES == W::BYTES) {
     if (n <= coop_grid_of<CV>() && out_inf) {
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
-      FnMulFixedC<CV, CW> fc{n, k, (const typename W::A*)comb_[CV::ID], out_xy, out_inf};
+      FnMulFixedC<CV, CW> fc{n, k, (const typename W::A*)comb_[comb_idx<CV>()], out_xy, out_inf};
       bk.launch_coop(fc, n);
       return E_OK;
     }
@@ -2589,10 +2745,10 @@ int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_inf) 
   u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
   if (!jac) return fail(E_NOMEM, "scratch allocation failed");
   if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnMulFixed<CV, (W::L > 12 ? 2 : 0)> f{n, k, (const typename W::A*)comb_[CV::ID], jac};
+    FnMulFixed<CV, (W::L > 12 ? 2 : 0)> f{n, k, (const typename W::A*)comb_[comb_idx<CV>()], jac};
     bk.launch(f, n);
   } else {
-    FnMulFixed<CV> f{n, k, (const typename W::A*)comb_[CV::ID], jac};
+    FnMulFixed<CV> f{n, k, (const typename W::A*)comb_[comb_idx<CV>()], jac};
     bk.launch(f, n);
   }
   return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
@@ -2630,14 +2786,14 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
       typename W::VT* pt = (typename W::VT*)scratch(S_TBL, 2 * n * (size_t)W::template stride<true>() * sizeof(typename W::VT));
       if (!pt || !pj) return fail(E_NOMEM, "scratch allocation failed");
       if (!rows_for(n) && n <= coop_grid()) {
-        FnMulPartsC fc{n, k2, xy2, pj, k1, (const typename W::A*)comb_[CV::ID]};
+        FnMulPartsC fc{n, k2, xy2, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
         bk.launch_coop(fc, 3 * n);
       } else if (rows_for(n)) {
-        FnMulPartsR fr{n, k2, xy2, pj, k1, (const typename W::A*)comb_[CV::ID]};
+        FnMulPartsR fr{n, k2, xy2, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
         bk.launch_coop(fr, 3 * ((n + 3) / 4));
       } else {
       const size_t npad = (n + 127) & ~(size_t)127;
-      FnMulParts<CV> fp{n, npad, k2, xy2, pt, pj, k1, (const typename W::A*)comb_[CV::ID]};
+      FnMulParts<CV> fp{n, npad, k2, xy2, pt, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
       launch_fn(fp, 2 * npad + n);
       }
       FnMulJoin<CV> fj{n, pj, true, xy2, out_xy, out_inf, nullptr};
@@ -2648,7 +2804,7 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
     if (n <= coop_grid_of<CV>()) {                 // the ladder of k2 and the comb of k1 on a wave each, joined on one lane
       u32* pj = (u32*)scratch(S_JAC, 2 * n * 3 * W::NS * 4);
       if (!pj) return fail(E_NOMEM, "scratch allocation failed");
-      FnMulPartsN<CV> fc{n, k2, xy2, pj, k1, (const typename W::A*)comb_[CV::ID]};
+      FnMulPartsN<CV> fc{n, k2, xy2, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
       bk.launch_coop(fc, 2 * n);
       FnMulJoin<CV> fj{n, pj, false, xy2, out_xy, out_inf, nullptr};
       return launch_fn(fj, n);
@@ -2658,10 +2814,10 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
   typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
   if (!tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
   if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnMulAddG<CV, (W::L > 12 ? 2 : 0)> f{n, k1, k2, xy2, (const typename W::A*)comb_[CV::ID], tbl, jac};
+    FnMulAddG<CV, (W::L > 12 ? 2 : 0)> f{n, k1, k2, xy2, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
     bk.launch(f, n);
   } else {
-    FnMulAddG<CV> f{n, k1, k2, xy2, (const typename W::A*)comb_[CV::ID], tbl, jac};
+    FnMulAddG<CV> f{n, k1, k2, xy2, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
     bk.launch(f, n);
   }
   int rc = normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
@@ -2757,20 +2913,20 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
         if (!jac) return fail(E_NOMEM, "scratch allocation failed");
         if (!rows && n <= coop_grid()) {
           // a handful of items: every part on a wave of its own, lanes-per-item arithmetic
-          FnEcdsaPartsC fc{n, u12, (const typename W::A*)comb_[CV::ID], tbl, jac};
+          FnEcdsaPartsC fc{n, u12, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
           bk.launch_coop(fc, 3 * n);
         } else if (rows) {
-          FnEcdsaPartsR fr{n, u12, (const typename W::A*)comb_[CV::ID], tbl, jac};
+          FnEcdsaPartsR fr{n, u12, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
           bk.launch_coop(fr, 3 * ((n + 3) / 4));
         } else {
         const size_t npad = (n + 127) & ~(size_t)127;          // whole workgroups per part
-        FnEcdsaParts<CV> fp{n, npad, u12, (const typename W::A*)comb_[CV::ID], tbl, jac};
+        FnEcdsaParts<CV> fp{n, npad, u12, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
         launch_fn(fp, 2 * npad + n);
         }
         FnEcdsaJoin<CV> fj{n, valid, r, pub, tbl, jac, ok, st};
         return launch_fn(fj, n);
       }
-      FnEcdsaLadder<CV, true> fl{n, u12, valid, r, pub, (const typename W::A*)comb_[CV::ID], tbl, ok, st};
+      FnEcdsaLadder<CV, true> fl{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
       return launch_fn(fl, n);
     }
   }
@@ -2787,7 +2943,7 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
       FnEcdsaPrepTableN<CV> fpt{n, hash, hash_len, shift, r, s, pre, u12, valid, pub, gt};
       bk.launch_coop(fpt, 2 * n);
       // ... then the ladder over that table and the comb
-      FnEcdsaPartsN<CV> fc{n, u12, pub, (const typename W::A*)comb_[CV::ID], jac, gt};
+      FnEcdsaPartsN<CV> fc{n, u12, pub, (const typename W::A*)comb_[comb_idx<CV>()], jac, gt};
       bk.launch_coop(fc, 2 * n);
       FnEcdsaJoin2<CV> fj{n, valid, r, pub, jac, ok, st};
       return launch_fn(fj, n);
@@ -2795,17 +2951,17 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
   }
   launch_fn(f1, T);
   if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnEcdsaMain<CV, (W::L > 12 ? 2 : 0)> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[CV::ID], tbl, ok, st};
+    FnEcdsaMain<CV, (W::L > 12 ? 2 : 0)> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
     bk.launch(f2, n);
     return E_OK;
   }
   if constexpr (CV::ENDO && W::L <= 8) {
     if (wide) {                             // at most three waves per SIMD: the register-rich tuning
-      FnEcdsaMain<CV, 3, true> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[CV::ID], tbl, ok, st};
+      FnEcdsaMain<CV, 3, true> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
       return launch_fn(f2, n);
     }
   }
-  FnEcdsaMain<CV> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[CV::ID], tbl, ok, st};
+  FnEcdsaMain<CV> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
   bk.launch(f2, n);
   return E_OK;
 }
@@ -3193,7 +3349,7 @@ int Engine<BK>::sign_chunk(size_t n, const u8* hash, int hash_len, int shift, co
       if (!kinv) return fail(E_NOMEM, "scratch allocation failed");
       u32* pre2 = kinv + n * (W::LN > W::NS ? W::LN : W::NS);
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
-      FnSignPartsC<CV, CW> fc{n, nonces, (const typename W::A*)comb_[CV::ID], kg, kg_inf, kinv};
+      FnSignPartsC<CV, CW> fc{n, nonces, (const typename W::A*)comb_[comb_idx<CV>()], kg, kg_inf, kinv};
       bk.launch_coop(fc, 2 * n);
       FnSignFinish<CV> f2{n, n, 1, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre2,
                           out_r, out_s, out_recid, out_ok, kinv};
@@ -3201,10 +3357,10 @@ int Engine<BK>::sign_chunk(size_t n, const u8* hash, int hash_len, int shift, co
     }
   }
   if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnSignMul<CV, (W::L > 12 ? 2 : 0)> f1{n, nonces, (const typename W::A*)comb_[CV::ID], jac};
+    FnSignMul<CV, (W::L > 12 ? 2 : 0)> f1{n, nonces, (const typename W::A*)comb_[comb_idx<CV>()], jac};
     bk.launch(f1, n);
   } else {
-    FnSignMul<CV> f1{n, nonces, (const typename W::A*)comb_[CV::ID], jac};
+    FnSignMul<CV> f1{n, nonces, (const typename W::A*)comb_[comb_idx<CV>()], jac};
     bk.launch(f1, n);
   }
   int rc = normalize_chunk<CV>(n, jac, kg, kg_inf, nullptr);

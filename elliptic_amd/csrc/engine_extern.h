@@ -79,6 +79,18 @@ namespace ell {
                                                                 const u8*, u8*, u8*);                \
   KW template int Engine<HipBackend>::edc_chunk<0>(int, size_t, const u8*, const u8*, const u8*,     \
                                                    const u8*, const u8*, const u8*, u8*, u8*);
+// user-defined ECDSA domains (CvCustomDomain): verify, k*G and k1*G + k2*Q -- their own translation
+// unit (group 17, with its own parameter block); the window ladder of the comb build is CvCustom's
+#define ELL_DECL_DOMAIN(KW)                                                                          \
+  KW template int Engine<HipBackend>::ensure_comb<CvCustomDomain>();                                 \
+  KW template int Engine<HipBackend>::normalize_chunk<CvCustomDomain>(size_t, const u32*, u8*, u8*,  \
+                                                                      Work<CvCustomDomain>::A*);     \
+  KW template int Engine<HipBackend>::mul_fixed_chunk<CvCustomDomain>(size_t, const u8*, u8*, u8*);  \
+  KW template int Engine<HipBackend>::mul_add_g_chunk<CvCustomDomain>(size_t, const u8*, const u8*,  \
+                                                                      const u8*, u8*, u8*);          \
+  KW template int Engine<HipBackend>::ecdsa_chunk<CvCustomDomain>(size_t, const u8*, int, int,       \
+                                                                  const u8*, const u8*, const u8*,   \
+                                                                  u8*, u8*);
 #define ELL_DECL_ED2(KW)                                                                            \
   KW template int Engine<HipBackend>::ed_decompress_chunk<0>(size_t, const u8*, const u8*, u8*, u8*); \
   KW template int Engine<HipBackend>::ed_codec_chunk<0>(int, size_t, const u8*, int, const u8*, u8*, u8*); \
@@ -116,6 +128,7 @@ ELL_DECL_ED2(extern)
 ELL_DECL_ED3(extern)
 ELL_DECL_ED4(extern)
 ELL_DECL_CUSTOM(extern)
+ELL_DECL_DOMAIN(extern)
 ELL_DECL_G7(extern)
 ELL_DECL_G8(extern)
 

@@ -28,30 +28,53 @@ struct RtField {
   u32 a_kind;      // 0: a == 0, 3: a == p - 3, 1: anything else
   u32 d_m[8];      // Edwards curves (edcustom.h): coefficient d, Montgomery form; a_m holds a
   u32 kind;        // 0: short Weierstrass (a_m, b_m), 1: (twisted) Edwards with c = 1 (a_m, d_m)
+  // ECDSA domain (ellgpu_curve_define_short_domain): the order n and the generator G.  Zero for a
+  // plain curve, so that a domain and the plain curve with the same (p, a, b) are different blocks.
+  u32 domain;      // 1: the fields below are set
+  u32 n[8];        // order
+  u32 nn0;         // -n^-1 mod 2^32
+  u32 n_one[8];    // R mod n
+  u32 n_r2[8];     // R^2 mod n
+  u32 nm2[8];      // n - 2            (Fermat inversion mod n)
+  u32 nbits;       // n.bitLength()    (_truncateToN's shift is the host's)
+  u32 n_p[8];      // n mod p, Montgomery form (JPoint#eqXToP's redN)
+  u32 ncand;       // floor(p / n) when <= 100 (_maxwellTrick: eqXToP's further candidates), else RT_NO_MAXWELL
+  u32 gx[8];       // G, plain
+  u32 gy[8];
 };
 
+constexpr u32 RT_NO_MAXWELL = 0xFFFFFFFFu;
+
 #if defined(__HIP_DEVICE_COMPILE__)
-extern __constant__ RtField g_rt;
-#define ELL_RT (g_rt)
+// one block per code object: each translation unit that holds custom-curve kernels names its own
+// (inst.hip; Engine::CustomScope uploads to every one)
+#ifndef ELL_RT_SYMBOL
+#define ELL_RT_SYMBOL g_rt
+#endif
+extern __constant__ RtField ELL_RT_SYMBOL;
+#define ELL_RT (ELL_RT_SYMBOL)
 #else
 inline RtField& rt_host_block() { static RtField f; return f; }
 #define ELL_RT (rt_host_block())
 #endif
 
-struct FpMontRT {
+// MOD = 0: the base field (p); MOD = 1: the scalar field of an ECDSA domain (n) -- the same
+// Montgomery arithmetic over the other modulus of the block
+template <int MOD>
+struct FpMontRTm {
   static constexpr int L = 8;
   typedef Fe<8> El;
   static constexpr bool HAS_SQRT = false;      // Red#sqrt of a generic prime stays in the reference's JavaScript
 
   ELL_HD static void get_p(u32 (&p)[8]) {
     ELL_UNROLL
-    for (int i = 0; i < 8; i++) p[i] = ELL_RT.p[i];
+    for (int i = 0; i < 8; i++) p[i] = MOD ? ELL_RT.n[i] : ELL_RT.p[i];
   }
   ELL_HD static El zero() { El r; bn_zero<8>(r.v); return r; }
   ELL_HD static El one() {
     El r;
     ELL_UNROLL
-    for (int i = 0; i < 8; i++) r.v[i] = ELL_RT.one[i];
+    for (int i = 0; i < 8; i++) r.v[i] = MOD ? ELL_RT.n_one[i] : ELL_RT.one[i];
     return r;
   }
   ELL_HD static El curve_a() {
@@ -89,7 +112,7 @@ struct FpMontRT {
   // modulus read from the parameter block)
   ELL_HD static El redc(u32 (&t)[16]) {
     u32 p[8]; get_p(p);
-    const u32 n0 = ELL_RT.n0;
+    const u32 n0 = MOD ? ELL_RT.nn0 : ELL_RT.n0;
     u32 top = 0;
     ELL_UNROLL
     for (int i = 0; i < 8; i++) {
@@ -142,7 +165,7 @@ struct FpMontRT {
     El x, r2;
     bn_copy<8>(x.v, a);
     ELL_UNROLL
-    for (int i = 0; i < 8; i++) r2.v[i] = ELL_RT.r2[i];
+    for (int i = 0; i < 8; i++) r2.v[i] = MOD ? ELL_RT.n_r2[i] : ELL_RT.r2[i];
     return mul(x, r2);
   }
   ELL_HD static void to_plain(u32 (&r)[8], const El& a) {
@@ -157,11 +180,13 @@ struct FpMontRT {
     ELL_NOUNROLL
     for (int i = 255; i >= 0; i--) {
       r = sqr(r);
-      if ((ELL_RT.pm2[i >> 5] >> (i & 31)) & 1u) r = mul(r, a);
+      if (((MOD ? ELL_RT.nm2[i >> 5] : ELL_RT.pm2[i >> 5]) >> (i & 31)) & 1u) r = mul(r, a);
     }
     return r;
   }
   static ELL_HD_NOINLINE El sqrt(const El& a) { return a; }     // never called (HAS_SQRT = false)
 };
+typedef FpMontRTm<0> FpMontRT;       // base field of a user-defined curve
+typedef FpMontRTm<1> FpMontRTn;      // order field of a user-defined ECDSA domain
 
 }  // namespace ell

@@ -80,6 +80,7 @@ struct TimedLaunch {
 // defined next to `__constant__ RtField g_rt` (inst.hip, group 16): blocking copy of a
 // user-defined curve's parameter block into the current device's constant memory
 int rt_upload_device(const RtField* f);
+int rt_upload_device_dom(const RtField* f);      // the same block for the ECDSA-domain kernels (group 17)
 
 struct HipBackend {
   int device = 0;
@@ -174,7 +175,12 @@ struct HipBackend {
   size_t one_wave_groups = (size_t)256 * 4 * 64 * 4;
   int compute_units() const { return cus; }
   void* own_stream() const { return (void*)own; }
-  void rt_upload(const RtField& f) { note((hipError_t)rt_upload_device(&f)); }
+  // (the ECDSA-domain kernels' block only for a domain: a plain user-defined curve's calls never
+  // launch them, and pay one blocking copy as before)
+  void rt_upload(const RtField& f) {
+    note((hipError_t)rt_upload_device(&f));
+    if (f.domain) note((hipError_t)rt_upload_device_dom(&f));
+  }
   void note(hipError_t e) {
     if (e != hipSuccess && !last) last = (int)e;
   }

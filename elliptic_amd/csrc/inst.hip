@@ -1,6 +1,9 @@
 // ellgpu -- one translation unit per (curve, operation group): explicit
 // instantiation of the Engine<HipBackend> member that launches the kernels.
 //   hipcc -c inst.hip -DELL_INST_CURVE=CvP384 -DELL_INST_GROUP=4   (see build.py)
+#if ELL_INST_GROUP == 17
+#define ELL_RT_SYMBOL g_rt_dom      // this code object's own parameter block (fp_rt.h)
+#endif
 #include "engine_extern.h"
 
 namespace ell {
@@ -42,6 +45,13 @@ int rt_upload_device(const RtField* f) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rt), f, sizeof(RtField), 0, hipMemcpyHostToDevice);
 }
 ELL_DECL_CUSTOM(ELL_NOKW)
+#elif ELL_INST_GROUP == 17
+// the ECDSA-domain kernels of user-defined curves, with a parameter block of their own
+__constant__ RtField g_rt_dom;
+int rt_upload_device_dom(const RtField* f) {
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rt_dom), f, sizeof(RtField), 0, hipMemcpyHostToDevice);
+}
+ELL_DECL_DOMAIN(ELL_NOKW)
 #else
 #error "unknown ELL_INST_GROUP"
 #endif

@@ -112,8 +112,11 @@ struct Work {
   // fixed-base comb: COMB_BITS-bit unsigned windows, table of d * 2^(COMB_BITS*w) * G.
   // 16-bit windows for the 256-bit curves (16 adds per k*G, 67 MB table that lives in
   // MALL/HBM and is gathered 64 B at a time); 8-bit windows otherwise.
-  static constexpr int COMB_BITS = (L == 8) ? ELL_COMB_BITS_SHORT256 : 8;
-  static constexpr bool COMB_SIGNED = (L == 8) && ELL_COMB_SIGNED_256;
+  // A user-defined domain (RT_ORDER): 8-bit unsigned windows over all 256 bits (32 x 255 entries,
+  // 0.5 MB per domain) -- unsigned, because the signed recoding's carry window would have to be
+  // folded with n, and n need not be G's order.
+  static constexpr int COMB_BITS = (L == 8 && !CV::RT_ORDER) ? ELL_COMB_BITS_SHORT256 : 8;
+  static constexpr bool COMB_SIGNED = (L == 8) && !CV::RT_ORDER && ELL_COMB_SIGNED_256;
   // signed windows: one more bit for the recoding's carry out of the top data window
   static constexpr int COMB_W = (8 * BYTES + (COMB_SIGNED ? 1 : 0) + COMB_BITS - 1) / COMB_BITS;
   static constexpr int COMB_DIG = COMB_SIGNED ? (1 << (COMB_BITS - 1)) : (1 << COMB_BITS) - 1;   // table entries per window
@@ -689,10 +692,31 @@ struct Work {
     for (int i = 0; i < LN; i++) e[i] = bs ? ((t[i] >> bs) | (t[i + 1] << (32 - bs))) : t[i];
   }
 
+  // the group order n: a compile-time constant for the presets, the parameter block's for a
+  // user-defined domain (fp_rt.h)
+  ELL_HD static void order_words(u32 (&nn)[LN]) {
+    if constexpr (CV::RT_ORDER) {
+      ELL_UNROLL
+      for (int i = 0; i < LN; i++) nn[i] = ELL_RT.n[i];
+    } else {
+      ELL_UNROLL
+      for (int i = 0; i < LN; i++) nn[i] = C::n[i];
+    }
+  }
+  // the generator, plain (FnCombGen)
+  ELL_HD static void generator_words(u32 (&gx)[L], u32 (&gy)[L]) {
+    if constexpr (CV::RT_ORDER) {
+      ELL_UNROLL
+      for (int l = 0; l < L; l++) { gx[l] = ELL_RT.gx[l]; gy[l] = ELL_RT.gy[l]; }
+    } else {
+      ELL_UNROLL
+      for (int l = 0; l < L; l++) { gx[l] = C::gx_plain[l]; gy[l] = C::gy_plain[l]; }
+    }
+  }
+
   ELL_HD static bool scalar_in_range(const u32 (&x)[LN]) {      // 1 <= x < n
     u32 nn[LN];
-    ELL_UNROLL
-    for (int i = 0; i < LN; i++) nn[i] = C::n[i];
+    order_words(nn);
     return !bn_is_zero<LN>(x) && !bn_geq<LN>(x, nn);
   }
 
@@ -1114,6 +1138,7 @@ struct Work {
   // (for every preset p < 2n, so one retry at most)
   ELL_HD static bool eq_x_to_p(const J& p, const u32 (&r)[LN]) {
     static_assert(LN <= L, "order wider than field");
+    if constexpr (CV::RT_ORDER) return eq_x_rt(p, r);
     u32 rx[L], pp[L];
     ELL_UNROLL
     for (int i = 0; i < L; i++) { rx[i] = i < LN ? r[i] : 0u; pp[i] = C::p[i]; }
@@ -1125,6 +1150,44 @@ struct Work {
     u32 cy = bn_add<L>(rn, rx, nn);
     if (cy || bn_geq<L>(rn, pp)) return false;
     return F::eq(p.X, F::mul(F::from_plain(rn), zz));
+  }
+
+  // The comparison of EC#verify (ec/index.js:215-228) on a user-defined domain, n and p from the
+  // parameter block.  With _maxwellTrick (floor(p/n) <= 100, base.js:33-40 -- n > p included)
+  // JPoint#eqXToP: X == (r mod p) Z^2 -- r.toRed(red) reduces r mod p, so where n > p an r in
+  // [p, n) matches x = r - p -- then X == (r + k n) Z^2 for k = 1, 2, ... while r + k n < p, i.e.
+  // at most floor(p/n) more candidates (eight on a cofactor-8 curve).  Without it (n < p / 100):
+  // getX().umod(n) == r, on the affine x (one inversion per item on that rare path).
+  ELL_HD static bool eq_x_rt(const J& p, const u32 (&r)[LN]) {
+    static_assert(L == 8 && LN == 8, "user-defined domains are 32-byte wide");
+    const u32 ncand = ELL_RT.ncand;                        // wave-uniform
+    if (ncand == RT_NO_MAXWELL) {
+      El zi = F::inv(p.Z);
+      u32 x[L], xn[LN];
+      F::to_plain(x, F::mul(p.X, F::sqr(zi)));
+      Fn::to_plain(xn, Fn::from_plain(x));                // x mod n: x R mod n, then out of Montgomery form
+      return bn_eq<LN>(xn, r);
+    }
+    El zz = F::sqr(p.Z);
+    El rx = F::mul(F::from_plain(r), zz);                  // from_plain takes any value < 2^256: r mod p
+    if (F::eq(p.X, rx)) return true;
+    u32 nn[L], pp[L], xc[L];
+    order_words(nn);
+    F::get_p(pp);
+    bn_copy<L>(xc, r);
+    El np;
+    ELL_UNROLL
+    for (int l = 0; l < L; l++) np.v[l] = ELL_RT.n_p[l];
+    const El t = F::mul(np, zz);
+    bool hit = false, live = true;
+    ELL_NOUNROLL
+    for (u32 k = 0; k < ncand; k++) {
+      u32 cy = bn_add<L>(xc, xc, nn);
+      live = live && !cy && !bn_geq<L>(xc, pp);
+      rx = F::add(rx, t);
+      hit = hit || (live && F::eq(p.X, rx));
+    }
+    return hit;
   }
 
   // ---- the small-grid form of pass 2, in two kernels (secp256k1) ---------------------------

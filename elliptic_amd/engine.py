@@ -116,6 +116,18 @@ class Context:
         self._check(self._lib.ellgpu_curve_define_short(self._ctx, enc[0], enc[1], enc[2], ctypes.byref(cid)))
         return cid.value
 
+    def define_short_domain(self, p, a, b, n, gx, gy):
+        """Register an ECDSA domain: the curve of define_short plus its order n and generator
+        G = (gx, gy) (`new elliptic.ec({curve: {type: 'short', p, a, b, n, g}})`), and return its
+        curve id.  Beside what a define_short id allows, mul_fixed, mul_add2 with p1=None and
+        ecdsa_verify (and their _dev forms) take it.  Raises EllgpuError (ELLGPU_E_ARG) for n even
+        or < 3, G off the curve or a singular curve; n and p are not tested for primality."""
+        cid = ctypes.c_int(-1)
+        p = int(p)
+        enc = [int(v).to_bytes(32, "big") for v in (p, int(a) % p, int(b) % p, int(n), int(gx), int(gy))]
+        self._check(self._lib.ellgpu_curve_define_short_domain(self._ctx, *enc, ctypes.byref(cid)))
+        return cid.value
+
     def define_edwards(self, p, a, d):
         """Register a x^2 + y^2 = 1 + d x^2 y^2 over the odd prime p < 2^256 (`new curve.edwards({p, a,
         c: 1, d})` with parameters that are not ed25519's) and return its curve id (as define_short)."""

@@ -79,6 +79,8 @@ static struct {
   int (*group_size)(const ellgpu_ctx*);
   int (*define_short)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, int*);
   int (*define_edwards)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, int*);
+  int (*define_short_domain)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
+                             const uint8_t*, const uint8_t*, int*);
   void (*ctx_destroy)(ellgpu_ctx*);
   int (*mul_fixed)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*);
   int (*mul_var)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
@@ -149,6 +151,7 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(group_create, "ellgpu_group_create"); SYM(group_size, "ellgpu_group_size");
   SYM(define_short, "ellgpu_curve_define_short");
   SYM(define_edwards, "ellgpu_curve_define_edwards");
+  SYM(define_short_domain, "ellgpu_curve_define_short_domain");
   SYM(ctx_destroy, "ellgpu_ctx_destroy"); SYM(mul_fixed, "ellgpu_mul_fixed"); SYM(mul_var, "ellgpu_mul_var");
   SYM(mul_add2, "ellgpu_mul_add2"); SYM(ecdsa_verify, "ellgpu_ecdsa_verify"); SYM(x25519, "ellgpu_x25519_ladder");
   SYM(x25519_derive, "ellgpu_x25519_derive");
@@ -351,6 +354,24 @@ static napi_value define_common(napi_env env, napi_callback_info info, int edwar
 }
 static napi_value fn_define_short(napi_env e, napi_callback_info i) { return define_common(e, i, 0); }
 static napi_value fn_define_edwards(napi_env e, napi_callback_info i) { return define_common(e, i, 1); }
+/* defineShortDomain(ctx, p, a, b, n, gx, gy) -> curve id: 32-byte big-endian Buffers
+ * (ellgpu_curve_define_short_domain) */
+static napi_value fn_define_short_domain(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 7; napi_value argv[7];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) THROW(env, "defineShortDomain(ctx, p, a, b, n, gx, gy)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  const uint8_t* b[6]; size_t l[6];
+  for (int i = 0; i < 6; i++) {
+    if (!get_buf(env, argv[1 + i], &b[i], &l[i], 0)) return NULL;
+    if (l[i] != 32) THROW(env, "defineShortDomain: p, a, b, n, gx, gy are 32-byte big-endian Buffers");
+  }
+  int id = -1;
+  if (L.define_short_domain(c, b[0], b[1], b[2], b[3], b[4], b[5], &id) != 0) THROW(env, L.last_error());
+  napi_value v; CHECK(env, napi_create_int32(env, id, &v));
+  return v;
+}
 /* destroyContext(ctx): releases the context's device memory and streams (ellgpu_ctx_destroy) and the
  * addon's pin on the external; any later call with that external throws.  Refused while Promise-form
  * batches are in flight (a worker thread is inside the context). */
@@ -967,7 +988,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"open", fn_open}, {"createContext", fn_create}, {"destroyContext", fn_destroy},
     {"defer", fn_defer}, {"collect", fn_collect}, {"combBits", fn_comb_bits},
     {"curveId", fn_curve_id}, {"fieldBytes", fn_field_bytes}, {"orderBytes", fn_order_bytes},
-    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
+    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"defineShortDomain", fn_define_short_domain}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
     {"mulAdd2", fn_mul_add2}, {"ecdsaVerify", fn_verify}, {"x25519", fn_x25519}, {"x25519Derive", fn_x25519_derive},
     {"callAsync", fn_call_async}, {"decompress", fn_decompress},
     {"eddsaVerify", fn_eddsa_verify}, {"eddsaSign", fn_eddsa_sign}, {"ecdsaSign", fn_sign}, {"ecdsaRecover", fn_recover}, {"ecdsaSignDet", fn_sign_det},

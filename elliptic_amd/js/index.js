@@ -80,6 +80,16 @@ Engine.prototype.defineShort = function defineShort(p, a, b) {
   }
   return this.addon.defineShort(this.ctx, buf(p), buf(a), buf(b));
 };
+// An ECDSA domain on such a curve: the curve plus its order n and generator G = (gx, gy)
+// (ellgpu_curve_define_short_domain).  Its id takes what a defineShort id takes, and also
+// mulBatch(id, k, null) (k*G), mulAddBatch(id, k1, null, ...) and ecdsaVerifyBatch (r and s 32
+// bytes wide).  All six arguments: BN-like (toArray) or 32-byte Buffers.
+Engine.prototype.defineShortDomain = function defineShortDomain(p, a, b, n, gx, gy) {
+  function buf(v) {
+    return Buffer.isBuffer(v) ? v : Buffer.from(v.toArray('be', 32));
+  }
+  return this.addon.defineShortDomain(this.ctx, buf(p), buf(a), buf(b), buf(n), buf(gx), buf(gy));
+};
 // The same for a (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) that is not ed25519
 // (`new elliptic.curve.edwards({p, a, c: 1, d})`, lib/elliptic/curve/edwards.js:11-31)
 Engine.prototype.defineEdwards = function defineEdwards(p, a, d) {
@@ -397,7 +407,8 @@ function install(elliptic, options) {
   }
   // What is remembered is kept in WeakMaps of this install(), keyed by the caller's object: nothing is
   // written onto the caller's objects (frozen ones included), and nobody else can plant a verdict.
-  var memo = { _ellgpu: new WeakMap(), _ellgpuCustom: new WeakMap(), _ellgpuEndo: new WeakMap(), _ellgpuOK: new WeakMap() };
+  var memo = { _ellgpu: new WeakMap(), _ellgpuCustom: new WeakMap(), _ellgpuDomain: new WeakMap(), _ellgpuEndo: new WeakMap(),
+    _ellgpuOK: new WeakMap() };
   function hide(o, k, v) {
     if (o !== null && (typeof o === 'object' || typeof o === 'function')) memo[k].set(o, v);
   }
@@ -640,6 +651,63 @@ function install(elliptic, options) {
       } catch (e) { d = null; }
     }
     return remember(d);
+  }
+  // ---- ECDSA on a user-defined short curve: the curve, its n and its G as ONE domain on the device ----
+  // (ellgpu_curve_define_short_domain: EC#verify as one engine call, s^-1, u1, u2 and the comparison
+  // included).  Taken only where the device computes what the reference computes: the curve is one
+  // customDomain() takes (prime p <= 256 bits, non-singular; options.customCurves === false keeps it on
+  // the reference), the EC multiplies the curve's own G and reduces by the curve's own n (ecOK), n is
+  // odd, >= 3, <= 256 bits and passes the same Miller-Rabin test as p (s^-1 is Fermat's on the device,
+  // BN#invm in the reference), G is an affine point of the curve, and the curve's _maxwellTrick / redN
+  // are what base.js:33-40 derives from p and n (the device's comparison rule is derived from them).
+  // The verdict is remembered with a WITNESS over p, a, b, n, G's coordinates, redN and the trick: a
+  // change after first use -- in place or by replacement -- is seen on the next call, which then stays
+  // on the reference.  G's precomputed tables are the callers' business (guarded / tablesOK), as on
+  // the presets.
+  function domainWitness(curve, g, n) {
+    var w = [curve.p.clone(), curve.a.fromRed(), curve.b.fromRed(), n.clone(), g.x.fromRed(), g.y.fromRed(),
+      curve.redN ? curve.redN.fromRed() : null];
+    w.trick = !!curve._maxwellTrick;
+    return w;
+  }
+  function sameWitness(a, b) {
+    if (a.length !== b.length || a.trick !== b.trick) return false;
+    for (var i = 0; i < a.length; i++) {
+      if ((a[i] === null) !== (b[i] === null)) return false;
+      if (a[i] !== null && a[i].cmp(b[i]) !== 0) return false;
+    }
+    return true;
+  }
+  function customVerifyDomain(ec) {
+    try { return customVerifyDomain0(ec); } catch (e) { return null; }
+  }
+  function customVerifyDomain0(ec) {
+    var curve = ec.curve;
+    if (!curve || curve.type !== 'short' || !ecOK(ec)) return null;
+    // (a preset -- whose endomorphism or tables protocolDomainLazy has just refused -- is never
+    // re-taken as a user-defined curve, and a curve with GLV constants runs the reference's GLV
+    // ladder, whose constants the device does not use: both stay on the reference)
+    if (domain(curve) || curve.endo) return null;
+    var base = customDomain(curve);
+    if (!base || base.name !== 'custom') return null;
+    var g = curve.g, n = curve.n;
+    if (!g || !BN.isBN(n) || n.red || g.curve !== curve || g.type !== 'affine' || g.inf) return null;
+    var w = domainWitness(curve, g, n);
+    var cc = recall(curve, '_ellgpuDomain');
+    if (cc !== undefined && cc.g === g && cc.n === n && cc.red === curve.red && sameWitness(cc.w, w)) return cc.d;
+    var d = null;
+    var gxy = affineBuf(curve, g, 32);
+    var maxwell = curve.p.div(n).cmpn(100) <= 0;             // base.js:33-40 (0 included: n > p)
+    if (gxy && n.negative === 0 && n.isOdd() && n.cmpn(3) >= 0 && n.bitLength() <= 256 &&
+        !!curve._maxwellTrick === maxwell && (!maxwell || (w[6] !== null && w[6].cmp(n.umod(curve.p)) === 0)) &&
+        probablyPrime(n)) {
+      try {
+        d = { name: 'custom-domain', custom: true, domain: true, B: 32,
+          id: eng.defineShortDomain(curve.p, curve.a.fromRed(), curve.b.fromRed(), n, gxy.slice(0, 32), gxy.slice(32)) };
+      } catch (e) { d = null; }
+    }
+    hide(curve, '_ellgpuDomain', { d: d, g: g, n: n, red: curve.red, w: w });
+    return d;
   }
   function scalarBuf(k, B) {
     if (!BN.isBN(k) || k.isNeg() || k.byteLength() > B) return null;
@@ -1215,8 +1283,8 @@ function install(elliptic, options) {
   // the original method, which throws / answers by itself.
   orig.verify = ecProto.verify;
   ecProto.verify = function verify(msg, signature, key, enc, options) {
-    var d = refOnly ? null : protocolDomainLazy(this.curve);
-    if (!d || d.custom || this.curve.type !== 'short' || !ecOK(this) || !byteMessage(msg) || !plainMsgBits(options))
+    var d = refOnly ? null : verifyDomainLazy(this);
+    if (!d || this.curve.type !== 'short' || !ecOK(this) || !byteMessage(msg) || !plainMsgBits(options))
       return orig.verify.apply(this, arguments);
     var m, ok;
     try {
@@ -1438,15 +1506,37 @@ function install(elliptic, options) {
   // items: [{ msg: Buffer|Array, signature, key, enc? }] -> [bool]
   // a preset whose G carries tables that are not G's multiples, or whose endomorphism constants are
   // not the curve's (protocolDomain): every item through EC#verify, whose ladders decide by themselves
-  function untrusted(ec, d) { return d && !(lazyBeta(ec.curve, [ec.curve.g]) && protocolDomain(ec.curve) && ecOK(ec)); }
+  function untrusted(ec, d) {
+    return d && !(lazyBeta(ec.curve, [ec.curve.g]) && (d.domain ? tablesOK(ec.curve, ec.curve.g) : protocolDomain(ec.curve)) && ecOK(ec));
+  }
+  // the engine's domain for EC#verify of this EC instance (G's tables not yet looked at): a preset's,
+  // or a user-defined curve's ECDSA domain (customVerifyDomain)
+  function verifyDomainLazy(ec) {
+    var d = protocolDomainLazy(ec.curve);
+    if (d) return d.custom ? null : d;
+    return customVerifyDomain(ec);
+  }
+  // ... for the batch forms, which take no one-item route: the preset's (domain()) or the custom one
+  function batchDomain(ec) {
+    if (!ec || !ec.curve) return null;
+    return domain(ec.curve) || customVerifyDomain(ec);
+  }
+  // a domain's digest after _truncateToN must fit the 256-bit order field (ELLGPU_E_ARG otherwise):
+  // such batches go item by item to EC#verify, i.e. to the reference
+  function domainWidthOK(ec, d, hl, mb) {
+    if (!d.domain) return true;
+    var bits = mb || 8 * hl, shift = Math.max(0, bits - ec.n.bitLength());
+    return 8 * hl - shift <= 256 && hl - (shift >> 3) <= 36;
+  }
   function verifyEach(ec, items) {
     return items.map(function(it) { return ec.verify(it.msg, it.signature, it.key, it.enc, it.options); });
   }
   eng.verifyMany = function verifyMany(ec, items) {
     // (a curve object that is no preset -- or is one no longer --: EC#verify of every item, which is what
     // this call stands for in every case)
-    var d = ec && ec.curve ? domain(ec.curve) : null;
+    var d = batchDomain(ec);
     if (!d || ec.curve.type !== 'short' || untrusted(ec, d)) return verifyEach(ec, items);
+    if (items.length && !domainWidthOK(ec, d, items[0].msg.length, msgBitsOf(items[0]))) return verifyEach(ec, items);
     var m = marshalVerify(ec, d, items);
     m.o.status = Buffer.alloc(items.length);
     var ok = eng.ecdsaVerifyBatch(d.id, m.o);
@@ -1472,7 +1562,7 @@ function install(elliptic, options) {
   }
   // one (msg, signature, key) as the engine's fixed-width fields; throws what EC#verify throws
   function marshalOne(ec, d, it, lazyTables) {
-    var NB = ec.n.byteLength();
+    var NB = d.domain ? 32 : ec.n.byteLength();
     var Signature = signatureClass(ec);
     var key = ec.keyFromPublic(it.key, it.enc);
     var sig = new Signature(it.signature, 'hex');
@@ -1507,8 +1597,10 @@ function install(elliptic, options) {
     }), hl, mb);
   }
   eng.verifyManyAsync = function verifyManyAsync(ec, items) {
-    var d = ec && ec.curve ? domain(ec.curve) : null;
-    if (!d || ec.curve.type !== 'short' || untrusted(ec, d)) return new Promise(function(resolve) { resolve(verifyEach(ec, items)); });
+    var d = batchDomain(ec);
+    if (!d || ec.curve.type !== 'short' || untrusted(ec, d) ||
+        (items.length && !domainWidthOK(ec, d, items[0].msg.length, msgBitsOf(items[0]))))
+      return new Promise(function(resolve) { resolve(verifyEach(ec, items)); });
     var m;
     try { m = marshalVerify(ec, d, items); } catch (e) { return Promise.reject(e); }
     if (!items.length) return Promise.resolve([]);
@@ -1539,13 +1631,13 @@ function install(elliptic, options) {
     });
     groups.forEach(function(g) {
       var good = [], ms = [];
-      var d = domain(g.ec.curve);
+      var d = batchDomain(g.ec);
       function each(ps) {                  // every call by itself, through the (patched) synchronous path
         ps.forEach(function(p) {
           try { p.resolve(g.ec.verify(p.item.msg, p.item.signature, p.item.key, p.item.enc, p.item.options)); } catch (e) { p.reject(e); }
         });
       }
-      if (!d) return each(g.ps);
+      if (!d || !domainWidthOK(g.ec, d, g.hl, g.mb)) return each(g.ps);
       g.ps.forEach(function(p) {           // a throwing item rejects alone
         try { ms.push(marshalOne(g.ec, d, p.item)); good.push(p); }
         catch (e) { p.reject(e); }
@@ -1559,7 +1651,7 @@ function install(elliptic, options) {
       // G's tables: looked at once per batch (the calls of one tick see one state of the library),
       // HERE -- in the tick of the calls, while the worker thread already runs the batch; a table
       // that is not G's multiples leaves every call to the synchronous path, the batch's verdicts unused
-      var trusted = lazyBeta(g.ec.curve, [g.ec.curve.g]) && tablesOK(g.ec.curve, g.ec.curve.g);
+      var trusted = lazyBeta(g.ec.curve, [g.ec.curve.g]) && tablesOK(g.ec.curve, g.ec.curve.g) && (!d.domain || ecOK(g.ec));
       if (!trusted) { job.catch(function() {}); return each(good); }
       job.then(function(ok) {
         good.forEach(function(p, i) {
@@ -1579,7 +1671,7 @@ function install(elliptic, options) {
   }
   eng.verifyAsync = function verifyAsync(ec, msg, signature, key, enc, options) {
     if (typeof enc === 'object' && enc !== null && options === undefined) { options = enc; enc = undefined; }
-    var d = ecOK(ec) ? protocolDomainLazy(ec.curve) : null;        // (G's tables: flushVerify, once per batch)
+    var d = ecOK(ec) ? verifyDomainLazy(ec) : null;        // (G's tables: flushVerify, once per batch)
     if (!d || ec.curve.type !== 'short' || !byteMessage(msg) || !plainMsgBits(options)) {
       // outside the engine's batch domain: the (patched) synchronous path, as a Promise
       return new Promise(function(resolve) { resolve(ec.verify(msg, signature, key, enc, options)); });

@@ -176,7 +176,7 @@ int ellgpu_ctx_collect(ellgpu_ctx* ctx);
  * Registers the curve with the context (a group: with every member) and returns its id
  * (>= ELLGPU_CURVE_CUSTOM0, at most 16 per context; defining the same parameters twice returns the
  * same id).  The id is valid for ellgpu_mul_var / _mul_add2 (both points given) / _point_add and
- * their _dev forms, with 32-byte scalars and coordinates whatever p's size: Point#mul, mulAdd /
+ * their _dev forms (an ECDSA domain, below, adds mul_fixed and verify), with 32-byte scalars and coordinates whatever p's size: Point#mul, mulAdd /
  * jmulAdd and Point#add with the generic-a doubling of JPoint#_dbl / dblp (short.js:802-830,
  * 605-654) on the device.  Every other entry point answers ELLGPU_E_UNSUPPORTED for it (the
  * reference's own JavaScript keeps serving those).  The primality of p is not checked, as the
@@ -188,6 +188,35 @@ int ellgpu_ctx_collect(ellgpu_ctx* ctx);
 #define ELLGPU_CURVE_CUSTOM0 16
 int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                               int* out_curve);
+/* User-defined ECDSA domain: the short curve y^2 = x^3 + a x + b over p as above, plus its order n
+ * and generator G = (gx, gy) -- `new elliptic.ec({curve: {type: 'short', p, a, b, n, g}})`.  All
+ * six arguments are 32-byte big-endian.  Returns an id in the same space as
+ * ellgpu_curve_define_short (ELLGPU_CURVE_CUSTOM0 + i, at most 16 per context, shared with plain
+ * curves); defining the same six values twice returns the same id, and a domain never shares the
+ * id of the plain curve with the same (p, a, b).  ELLGPU_E_ARG for p even or <= 3, n even or < 3,
+ * G not on the curve (a coordinate >= p included) or 4a^3 + 27b^2 = 0 (mod p).  Neither p nor n
+ * is tested for primality: inversion mod p and mod n is Fermat's, so for a composite modulus the
+ * results differ from the reference's (install() runs its Miller-Rabin test on both before it
+ * registers a domain; Engine#defineShortDomain passes them through as given).  On a
+ * group, either every member registers the domain or none does.
+ * On a domain id, with the widths of a plain user-defined id (32-byte scalars, coordinates, r, s)
+ * and the same synchronous semantics, these work beside ellgpu_mul_var / _point_add / _mul_add2:
+ *   ellgpu_mul_fixed (+ _dev)      k*G for any 32-byte k, not reduced mod n (a comb of 8-bit windows
+ *                                  over all 256 bits, 0.5 MB per domain, built on first use; subject
+ *                                  to ELLGPU_COMB_MAX_BYTES)
+ *   ellgpu_mul_add2 (+ _dev)       p1_xy == NULL means G
+ *   ellgpu_ecdsa_verify (+ _dev)   EC#verify (ec/index.js:188-229): the digest truncated with the
+ *                                  domain's n.bitLength(), 1 <= r, s < n, u1 G + u2 Q = O false, and
+ *                                  the reference's comparison -- JPoint#eqXToP where floor(p/n) <= 100
+ *                                  (n > p included: r is reduced mod p there, so an r in [p, n)
+ *                                  matches x = r - p), x mod n == r otherwise.  out_ok is a strict
+ *                                  0 / 1 mask; out_status is 2 for an off-curve key whose r and s
+ *                                  are in range, as on the presets.
+ * Every other entry point (wire / DER, sign, sign_det, recover, decompress, decode, validate)
+ * answers ELLGPU_E_UNSUPPORTED on a domain id; on a plain ellgpu_curve_define_short id, mul_fixed,
+ * mul_add2 without p1 and ecdsa_verify stay ELLGPU_E_UNSUPPORTED. */
+int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
+                                     const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve);
 /* User-defined (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) over an odd prime
  * p < 2^256 -- `new elliptic.curve.edwards({p, a, c: 1, d, ...})` (lib/elliptic/curve/edwards.js:
  * 11-31) with parameters that are not ed25519's.  Same id space, widths (32 bytes) and entry
