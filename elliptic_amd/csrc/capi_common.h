@@ -46,7 +46,12 @@ static void ell_complete_deferred(ellgpu_ctx* ctx) {
   if (rc && !ctx->deferred_rc) { ctx->deferred_rc = rc; ctx->deferred_msg = ctx->eng->err; }
   ctx->eng->bk.end_call(false);
 }
-#define ELL_LOCK(ctx) std::lock_guard<std::recursive_mutex> ell_ctx_lock_((ctx)->mu); ell_complete_deferred(ctx)
+// the context's lock for the rest of the scope, taken with the pending call completed
+struct EllLock {
+  std::lock_guard<std::recursive_mutex> g;
+  explicit EllLock(ellgpu_ctx* ctx) : g(ctx->mu) { ell_complete_deferred(ctx); }
+};
+#define ELL_LOCK(ctx) EllLock ell_ctx_lock_(ctx)
 
 static thread_local std::string g_last_error;
 

@@ -1163,7 +1163,6 @@ class Engine {
   // ---- scratch arena: a few grow-only device buffers ----------------------
   struct Buf { void* p = nullptr; size_t cap = 0; };
   enum { S_TBL = 0, S_JAC, S_PRE, S_U12, S_VALID, S_WIRE, S_COUNT };
-  enum { G_IN0 = 0, G_IN1, G_IN2, G_IN3, G_IN4, G_OUT0, G_OUT1, G_OUT2, G_COUNT };
 
   void* grow(Buf& b, size_t bytes) {
     if (bytes <= b.cap) return b.p;
@@ -1176,7 +1175,6 @@ class Engine {
     return b.p;
   }
   void* scratch(int which, size_t bytes) { return grow(scratch_[lane_][which], bytes); }
-  void* staging(int which, size_t bytes) { return grow(staging_[which], bytes); }
 
   int fail(int code, const char* msg) { err = msg; return code; }
 
@@ -1559,6 +1557,25 @@ class Engine {
     ELL_SHORT_DISPATCH(curve, rc = ensure_comb<CV>());
     return rc;
   }
+  // f(o, m) on the items [o, o + m) of [0, n), at most `step` per launch; stops at the first error
+  template <class F>
+  static int for_chunks(size_t n, size_t step, F f) {
+    for (size_t o = 0; o < n; o += step) {
+      const int rc = f(o, n - o < step ? n - o : step);
+      if (rc) return rc;
+    }
+    return E_OK;
+  }
+  // _truncateToN (ec/index.js:97-102): the right shift that brings a hash of msg_bits bits (0: all
+  // hash_len bytes) to the bit length of an order of order_bits bits held in ln 32-bit words
+  int truncate_shift(int hash_len, int msg_bits, int order_bits, int ln, int& shift) {
+    if (hash_len <= 0 || msg_bits < 0) return fail(E_ARG, "bad hash_len / msg_bits");
+    shift = (msg_bits ? msg_bits : hash_len * 8) - order_bits;
+    if (shift < 0) shift = 0;
+    if (hash_len * 8 - shift > 32 * ln || hash_len - (shift >> 3) > 4 * (ln + 1))
+      return fail(E_ARG, "hash_len / msg_bits combination leaves more bits than the order width");
+    return E_OK;
+  }
 
   int mul_fixed_dev(int curve, size_t n, const u8* k, u8* out_xy, u8* out_inf) {
     const CurveInfo* ci = curve_info(curve);
@@ -1572,14 +1589,12 @@ class Engine {
     int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
     if (rc) return rc;
     const size_t B = ci->field_bytes;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
       else if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
       else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, k + o * B, out_xy + o * 2 * B, out_inf + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
 
   static bool overlap(const u8* a, const u8* b, size_t bytes) {
@@ -1598,8 +1613,7 @@ class Engine {
     int rc = E_OK;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       if (custom_is_edwards(curve))
         rc = edc_chunk(0, m, k + o * B, xy + o * 2 * B, nullptr, nullptr, nullptr, nullptr, out_xy + o * 2 * B, out_inf + o);
       else if (is_custom(curve))
@@ -1609,9 +1623,8 @@ class Engine {
       else
         ELL_SHORT_DISPATCH(curve, rc = mul_var_chunk<CV>(m, k + o * B, xy + o * 2 * B,
                                                          out_xy + o * 2 * B, out_inf + o, nullptr));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
 
   int mul_add2_dev(int curve, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
@@ -1632,8 +1645,7 @@ class Engine {
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
     if (!xy1 && dom) { rc = ensure_comb<CvCustomDomain>(); if (rc) return rc; }
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       const u8* p1 = xy1 ? xy1 + o * 2 * B : nullptr;
       if (custom_is_edwards(curve))
         rc = edc_chunk(1, m, k1 + o * B, p1, k2 + o * B, xy2 + o * 2 * B, nullptr, nullptr, out_xy + o * 2 * B,
@@ -1654,9 +1666,8 @@ class Engine {
                                               : mul_add_g_chunk<CV>(m, k1 + o * B, k2 + o * B,
                                                                     xy2 + o * 2 * B,
                                                                     out_xy + o * 2 * B, out_inf + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
 
   // ok: the verdicts, strictly 0 / 1.  st (may be null): the domain status per item -- 2 where the
@@ -1670,22 +1681,16 @@ class Engine {
       return fail(E_UNSUPPORTED, is_custom(curve) ? "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"
                                                   : "ECDSA verify is implemented for the short Weierstrass presets");
     if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0 || msg_bits < 0) return fail(E_ARG, "bad hash_len / msg_bits");
-    // _truncateToN (ec/index.js:97-102): delta = bitLength - n.bitLength() (a domain's own n)
-    const int order_bits = dom ? (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits : ci->order_bits;
-    int bits = msg_bits ? msg_bits : hash_len * 8;
-    int shift = bits - order_bits;
-    if (shift < 0) shift = 0;
-    int ln = dom ? 8 : (order_bits + 31) / 32;
-    if (hash_len * 8 - shift > 32 * ln || hash_len - (shift >> 3) > 4 * (ln + 1))
-      return fail(E_ARG, "hash_len / msg_bits combination leaves more bits than the order width");
+    int shift;                     // a domain's own n, in 8 words
+    int rc = dom ? truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift)
+                 : truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
+    if (rc) return rc;
     CustomScope sc(this, dom ? curve : -1);
     if (sc.rc) return sc.rc;
-    int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
+    rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
     if (rc) return rc;
     const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       if (dom)
         rc = ecdsa_chunk<CvCustomDomain>(m, hash + o * hash_len, hash_len, shift, r + o * NB, s + o * NB,
                                          pub + o * 2 * B, ok + o, st ? st + o : nullptr);
@@ -1693,21 +1698,16 @@ class Engine {
       ELL_SHORT_DISPATCH(curve, rc = ecdsa_chunk<CV>(m, hash + o * hash_len, hash_len, shift,
                                                      r + o * NB, s + o * NB, pub + o * 2 * B,
                                                      ok + o, st ? st + o : nullptr));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
 
   // out_bad (may be null): out_bad[i] = 1 where x[i] is no abscissa of the curve (KeyPair#derive's validate)
   int x25519_dev(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
     if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
-    int rc = E_OK;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
-      rc = x25519_chunk(m, k + o * 32, x + o * 32, out_x + o * 32, out_inf + o, out_bad ? out_bad + o : nullptr);
-      if (rc) return rc;
-    }
-    return E_OK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return x25519_chunk(m, k + o * 32, x + o * 32, out_x + o * 32, out_inf + o, out_bad ? out_bad + o : nullptr);
+    });
   }
 
   // ECDSA sign with caller-supplied nonces (one pass of EC#sign's loop per item)
@@ -1719,24 +1719,18 @@ class Engine {
       return fail(E_UNSUPPORTED, "ECDSA sign is implemented for the short Weierstrass presets");
     if (n && (!hash || !priv || !nonces || !out_r || !out_s || !out_recid || !out_ok))
       return fail(E_ARG, "null pointer");
-    if (hash_len <= 0 || msg_bits < 0) return fail(E_ARG, "bad hash_len / msg_bits");
-    int bits = msg_bits ? msg_bits : hash_len * 8;
-    int shift = bits - ci->order_bits;
-    if (shift < 0) shift = 0;
-    int ln = (ci->order_bits + 31) / 32;
-    if (hash_len * 8 - shift > 32 * ln || hash_len - (shift >> 3) > 4 * (ln + 1))
-      return fail(E_ARG, "hash_len / msg_bits combination leaves more bits than the order width");
-    int rc = prepare_curve(curve);
+    int shift;
+    int rc = truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
+    if (rc) return rc;
+    rc = prepare_curve(curve);
     if (rc) return rc;
     const size_t NB = ci->order_bytes;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       ELL_SHORT_DISPATCH(curve, rc = sign_chunk<CV>(m, hash + o * hash_len, hash_len, shift, priv + o * NB,
                                                     nonces + o * NB, canonical, out_r + o * NB,
                                                     out_s + o * NB, out_recid + o, out_ok + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int ecdsa_sign_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
                       const u8* nonces, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
@@ -1745,21 +1739,10 @@ class Engine {
     if (n && (!hash || !priv || !nonces || !out_r || !out_s || !out_recid || !out_ok))
       return fail(E_ARG, "null pointer");
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    size_t NB = ci->order_bytes;
-    const size_t HL = (size_t)hash_len;
-    u8* dh = out_buf(G_IN0, n * HL);
-    u8* dd = out_buf(G_IN1, n * NB);
-    u8* dk = out_buf(G_IN2, n * NB);
-    u8* dr = out_buf(G_OUT0, n * NB * 2 + 2 * n);
-    if (!dh || !dd || !dk || !dr) return fail(E_NOMEM, "staging allocation failed");
-    u8* dsg = dr + n * NB;
-    u8* drec = dsg + n * NB;
-    u8* dok = drec + n;
-    HostIn ins[3] = {{dh, hash, HL}, {dd, priv, NB}, {dk, nonces, NB}};
-    HostOut outs[4] = {{out_r, dr, NB}, {out_s, dsg, NB}, {out_recid, drec, 1}, {out_ok, dok, 1}};
-    return pipelined(n, ins, 3, outs, 4, [&](size_t o, size_t m) {
-      return ecdsa_sign_dev(curve, m, dh + o * HL, hash_len, msg_bits, dd + o * NB, dk + o * NB, canonical,
-                            dr + o * NB, dsg + o * NB, drec + o, dok + o);
+    const size_t NB = ci->order_bytes;
+    return staged(n, {In{hash, (size_t)hash_len}, In{priv, NB}, In{nonces, NB}},
+                  {Out{out_r, NB}, Out{out_s, NB}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
+      return ecdsa_sign_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], canonical, r[0], r[1], r[2], r[3]);
     });
   }
 
@@ -1772,24 +1755,18 @@ class Engine {
     if (curve >= CURVE_ED25519)
       return fail(E_UNSUPPORTED, "ECDSA sign is implemented for the short Weierstrass presets");
     if (n && (!hash || !priv || !out_r || !out_s || !out_recid || !out_ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0 || msg_bits < 0) return fail(E_ARG, "bad hash_len / msg_bits");
-    int bits = msg_bits ? msg_bits : hash_len * 8;
-    int shift = bits - ci->order_bits;
-    if (shift < 0) shift = 0;
-    int ln = (ci->order_bits + 31) / 32;
-    if (hash_len * 8 - shift > 32 * ln || hash_len - (shift >> 3) > 4 * (ln + 1))
-      return fail(E_ARG, "hash_len / msg_bits combination leaves more bits than the order width");
-    int rc = prepare_curve(curve);
+    int shift;
+    int rc = truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
+    if (rc) return rc;
+    rc = prepare_curve(curve);
     if (rc) return rc;
     const size_t NB = ci->order_bytes;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       ELL_SHORT_DISPATCH(curve, rc = sign_det_chunk<CV>(m, hash + o * hash_len, hash_len, shift, priv + o * NB,
                                                         canonical, out_r + o * NB, out_s + o * NB,
                                                         out_recid + o, out_ok + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int ecdsa_sign_det_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
                           int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
@@ -1798,19 +1775,9 @@ class Engine {
     if (n && (!hash || !priv || !out_r || !out_s || !out_recid || !out_ok)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
     const size_t NB = ci->order_bytes;
-    const size_t HL = (size_t)hash_len;
-    u8* dh = out_buf(G_IN0, n * HL);
-    u8* dd = out_buf(G_IN1, n * NB);
-    u8* dr = out_buf(G_OUT0, n * NB);
-    u8* dsg = out_buf(G_OUT1, n * NB);
-    u8* drec = out_buf(G_IN3, n);
-    u8* dok = out_buf(G_IN4, n);
-    if (!dh || !dd || !dr || !dsg || !drec || !dok) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dh, hash, HL}, {dd, priv, NB}};
-    HostOut outs[4] = {{out_r, dr, NB}, {out_s, dsg, NB}, {out_recid, drec, 1}, {out_ok, dok, 1}};
-    return pipelined(n, ins, 2, outs, 4, [&](size_t o, size_t m) {
-      return ecdsa_sign_det_dev(curve, m, dh + o * HL, hash_len, msg_bits, dd + o * NB, canonical,
-                                dr + o * NB, dsg + o * NB, drec + o, dok + o);
+    return staged(n, {In{hash, (size_t)hash_len}, In{priv, NB}},
+                  {Out{out_r, NB}, Out{out_s, NB}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
+      return ecdsa_sign_det_dev(curve, m, d[0], hash_len, msg_bits, d[1], canonical, r[0], r[1], r[2], r[3]);
     });
   }
 
@@ -1828,13 +1795,11 @@ class Engine {
     int rc = prepare_curve(curve);
     if (rc) return rc;
     const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       ELL_SHORT_DISPATCH(curve, rc = recover_chunk<CV>(m, hash + o * hash_len, hash_len, r + o * NB, s + o * NB,
                                                        recid + o, out_xy + o * 2 * B, out_status + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int ecdsa_recover_host(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
                          const u8* recid, u8* out_xy, u8* out_status) {
@@ -1843,19 +1808,9 @@ class Engine {
     if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
     const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    const size_t HL = (size_t)hash_len;
-    u8* dh = out_buf(G_IN0, n * HL);
-    u8* dr = out_buf(G_IN1, n * NB);
-    u8* dsg = out_buf(G_IN2, n * NB);
-    u8* dj = out_buf(G_IN3, n);
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dst = out_buf(G_OUT1, n);
-    if (!dh || !dr || !dsg || !dj || !dxy || !dst) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[4] = {{dh, hash, HL}, {dr, r, NB}, {dsg, s, NB}, {dj, recid, 1}};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_status, dst, 1}};
-    return pipelined(n, ins, 4, outs, 2, [&](size_t o, size_t m) {
-      return ecdsa_recover_dev(curve, m, dh + o * HL, hash_len, dr + o * NB, dsg + o * NB, dj + o,
-                               dxy + o * 2 * B, dst + o);
+    return staged(n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{recid, 1}},
+                  {Out{out_xy, 2 * B}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      return ecdsa_recover_dev(curve, m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]);
     });
   }
 
@@ -1866,12 +1821,10 @@ class Engine {
     if (n && (!sigs || !pubs || !ok || (!msgs && (off || msg_len)))) return fail(E_ARG, "null pointer");
     int rc = prepare_curve(CURVE_ED25519);
     if (rc) return rc;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       rc = eddsa_chunk(m, o, msgs, off, msg_len, sigs, pubs, ok, err);
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int eddsa_verify_host(size_t n, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
                         const u8* pubs, u8* ok, u8* err) {
@@ -1881,34 +1834,11 @@ class Engine {
         if (off[i] > off[i + 1]) return fail(E_ARG, "message offsets must be non-decreasing");
     size_t total = off ? (size_t)off[n] : n * msg_len;
     if (total && !msgs) return fail(E_ARG, "null message pointer");
-    if (n && n <= bk.pipeline_quantum()) {
-      // a few items: through the pinned buffer, one synchronisation (or none: ellgpu_ctx_defer)
-      u8* dm = out_buf(G_IN0, total);
-      u64* doff = off ? (u64*)out_buf(G_IN1, (n + 1) * sizeof(u64)) : nullptr;
-      u8* dsg = out_buf(G_IN2, n * 64);
-      u8* dpk = out_buf(G_IN3, n * 32);
-      u8* dok = out_buf(G_OUT0, n);
-      u8* derr = out_buf(G_OUT1, n);
-      if (!dm || !dsg || !dpk || !dok || !derr || (off && !doff)) return fail(E_NOMEM, "staging allocation failed");
-      SpanIn si[4] = {{dm, msgs ? msgs : (const u8*)"", total}, {(u8*)doff, (const u8*)off, off ? (n + 1) * sizeof(u64) : 0},
-                      {dsg, sigs, n * 64}, {dpk, pubs, n * 32}};
-      SpanOut so[2] = {{ok, dok, n}, {err, derr, n}};
-      int rc = E_OK;
-      if (small_call(si, 4, so, 2, [&]() { return eddsa_verify_dev(n, dm, doff, msg_len, dsg, dpk, dok, derr); }, &rc)) return rc;
-    }
-    defer_skip();
-    u8* dm = put(G_IN0, msgs ? msgs : (const u8*)"", total);
-    u64* doff = off ? (u64*)put(G_IN1, off, (n + 1) * sizeof(u64)) : nullptr;
-    u8* dsg = put(G_IN2, sigs, n * 64);
-    u8* dpk = put(G_IN3, pubs, n * 32);
-    u8* dok = out_buf(G_OUT0, n);
-    u8* derr = out_buf(G_OUT1, n);
-    if (!dm || !dsg || !dpk || !dok || !derr || (off && !doff)) return fail(E_NOMEM, "staging allocation failed");
-    int rc = eddsa_verify_dev(n, dm, doff, msg_len, dsg, dpk, dok, derr);
-    if (rc) return rc;
-    bk.d2h(ok, dok, n);
-    if (err) bk.d2h(err, derr, n);
-    return bk.sync();
+    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
+                            In{sigs, n * 64}, In{pubs, n * 32}},
+                        {Out{ok, n}, Out{err, n}}, [&](auto d, auto r) {
+      return eddsa_verify_dev(n, d[0], (const u64*)d[1], msg_len, d[2], d[3], r[0], r[1]);
+    });
   }
 
   // EdDSA (ed25519) sign from 32-byte secrets: EDDSA#sign with KeyPair.fromSecret.  Messages as
@@ -1918,13 +1848,9 @@ class Engine {
     if (n && (!secrets || !sig || (!msgs && (off || msg_len)))) return fail(E_ARG, "null pointer");
     int rc = prepare_curve(CURVE_ED25519);
     if (rc) return rc;
-    const size_t step = CHUNK / 2;                 // two fixed-base multiplications per item
-    for (size_t o = 0; o < n; o += step) {
-      size_t m = n - o < step ? n - o : step;
-      rc = eddsa_sign_chunk(m, o, secrets, msgs, off, msg_len, sig, pub);
-      if (rc) return rc;
-    }
-    return E_OK;
+    return for_chunks(n, CHUNK / 2, [&](size_t o, size_t m) {     // two fixed-base multiplications per item
+      return eddsa_sign_chunk(m, o, secrets, msgs, off, msg_len, sig, pub);
+    });
   }
   int eddsa_sign_host(size_t n, const u8* secrets, const u8* msgs, const u64* off, size_t msg_len,
                       u8* sig, u8* pub) {
@@ -1934,31 +1860,11 @@ class Engine {
         if (off[i] > off[i + 1]) return fail(E_ARG, "message offsets must be non-decreasing");
     size_t total = off ? (size_t)off[n] : n * msg_len;
     if (total && !msgs) return fail(E_ARG, "null message pointer");
-    if (n && n <= bk.pipeline_quantum()) {
-      u8* dm = out_buf(G_IN0, total);
-      u64* doff = off ? (u64*)out_buf(G_IN1, (n + 1) * sizeof(u64)) : nullptr;
-      u8* dsec = out_buf(G_IN2, n * 32);
-      u8* dsig = out_buf(G_OUT0, n * 64);
-      u8* dpub = out_buf(G_OUT1, n * 32);
-      if (!dm || !dsec || !dsig || !dpub || (off && !doff)) return fail(E_NOMEM, "staging allocation failed");
-      SpanIn si[3] = {{dm, msgs ? msgs : (const u8*)"", total}, {(u8*)doff, (const u8*)off, off ? (n + 1) * sizeof(u64) : 0},
-                      {dsec, secrets, n * 32}};
-      SpanOut so[2] = {{sig, dsig, n * 64}, {pub, dpub, n * 32}};
-      int rc = E_OK;
-      if (small_call(si, 3, so, 2, [&]() { return eddsa_sign_dev(n, dsec, dm, doff, msg_len, dsig, dpub); }, &rc)) return rc;
-    }
-    defer_skip();
-    u8* dm = put(G_IN0, msgs ? msgs : (const u8*)"", total);
-    u64* doff = off ? (u64*)put(G_IN1, off, (n + 1) * sizeof(u64)) : nullptr;
-    u8* dsec = put(G_IN2, secrets, n * 32);
-    u8* dsig = out_buf(G_OUT0, n * 64);
-    u8* dpub = out_buf(G_OUT1, n * 32);
-    if (!dm || !dsec || !dsig || !dpub || (off && !doff)) return fail(E_NOMEM, "staging allocation failed");
-    int rc = eddsa_sign_dev(n, dsec, dm, doff, msg_len, dsig, dpub);
-    if (rc) return rc;
-    bk.d2h(sig, dsig, n * 64);
-    if (pub) bk.d2h(pub, dpub, n * 32);
-    return bk.sync();
+    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
+                            In{secrets, n * 32}},
+                        {Out{sig, n * 64}, Out{pub, n * 32}}, [&](auto d, auto r) {
+      return eddsa_sign_dev(n, d[2], d[0], (const u64*)d[1], msg_len, r[0], r[1]);
+    });
   }
 
   // point decompression: short curves from x (pointFromX), ed25519 from y (pointFromY)
@@ -1969,28 +1875,19 @@ class Engine {
     if (n && (!v || !odd || !out_xy || !out_ok)) return fail(E_ARG, "null pointer");
     const size_t B = ci->field_bytes;
     int rc = E_OK;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       if (curve == CURVE_ED25519) rc = ed_decompress_chunk(m, v + o * B, odd + o, out_xy + o * 2 * B, out_ok + o);
       else ELL_SHORT_DISPATCH(curve, rc = decompress_chunk<CV>(m, v + o * B, odd + o, out_xy + o * 2 * B, out_ok + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int decompress_host(int curve, size_t n, const u8* v, const u8* odd, u8* out_xy, u8* out_ok) {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!v || !odd || !out_xy || !out_ok)) return fail(E_ARG, "null pointer");
-    size_t B = ci->field_bytes;
-    u8* dv = out_buf(G_IN0, n * B);
-    u8* dodd = out_buf(G_IN1, n);
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dok = out_buf(G_OUT1, n);
-    if (!dv || !dodd || !dxy || !dok) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dv, v, B}, {dodd, odd, 1}};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_ok, dok, 1}};
-    return pipelined(n, ins, 2, outs, 2, [&](size_t o, size_t m) {
-      return decompress_dev(curve, m, dv + o * B, dodd + o, dxy + o * 2 * B, dok + o);
+    const size_t B = ci->field_bytes;
+    return staged(n, {In{v, B}, In{odd, 1}}, {Out{out_xy, 2 * B}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
+      return decompress_dev(curve, m, d[0], d[1], r[0], r[1]);
     });
   }
 
@@ -2006,16 +1903,14 @@ class Engine {
     if (curve == CURVE_ED25519 && enc_len != 32) return fail(E_ARG, "ed25519 encodings are 32 bytes");
     if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
     int rc = E_OK;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       if (curve == CURVE_ED25519)
         rc = ed_codec_chunk(OP_DECODE, m, enc + o * enc_len, 0, nullptr, out_xy + o * 2 * B, out_status + o);
       else
         ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_DECODE, m, enc + o * enc_len, enc_len, 0, nullptr,
                                                        out_xy + o * 2 * B, out_status + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   static size_t encoded_len(int curve, size_t B, int compact) {
     return curve == CURVE_ED25519 ? 32 : (compact ? 1 + B : 1 + 2 * B);
@@ -2028,16 +1923,14 @@ class Engine {
     if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
     const size_t B = ci->field_bytes, EL = encoded_len(curve, B, compact);
     int rc = E_OK;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       if (curve == CURVE_ED25519)
         rc = ed_codec_chunk(OP_ENCODE, m, xy + o * 2 * B, 0, nullptr, out_enc + o * EL, nullptr);
       else
         ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_ENCODE, m, xy + o * 2 * B, 0, compact, nullptr,
                                                        out_enc + o * EL, nullptr));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   // KeyPair#validate (ec/key.js:41-52): 0 ok, 1 'Invalid public key' (inf[i] set), 2 'Public key
   // is not a point', 3 'Public key * N != O' (only tested when check_order)
@@ -2048,45 +1941,32 @@ class Engine {
     if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
     const size_t B = ci->field_bytes;
     int rc = E_OK;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       const u8* fi = inf ? inf + o : nullptr;
       if (curve == CURVE_ED25519)
         rc = ed_codec_chunk(OP_VALIDATE, m, xy + o * 2 * B, check_order, fi, nullptr, out_status + o);
       else
         ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_VALIDATE, m, xy + o * 2 * B, 0, check_order, fi,
                                                        nullptr, out_status + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int decode_points_host(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     const size_t B = ci->field_bytes;
-    u8* de = out_buf(G_IN0, n * enc_len);
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dst = out_buf(G_OUT1, n);
-    if (!de || !dxy || !dst) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[1] = {{de, enc, enc_len}};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_status, dst, 1}};
-    return pipelined(n, ins, 1, outs, 2, [&](size_t o, size_t m) {
-      return decode_points_dev(curve, m, de + o * enc_len, enc_len, dxy + o * 2 * B, dst + o);
+    return staged(n, {In{enc, enc_len}}, {Out{out_xy, 2 * B}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return decode_points_dev(curve, m, d[0], enc_len, r[0], r[1]);
     });
   }
   int encode_points_host(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes, EL = encoded_len(curve, B, compact);
-    u8* dxy = out_buf(G_IN0, n * 2 * B);
-    u8* de = out_buf(G_OUT0, n * EL);
-    if (!dxy || !de) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[1] = {{dxy, xy, 2 * B}};
-    HostOut outs[1] = {{out_enc, de, EL}};
-    return pipelined(n, ins, 1, outs, 1, [&](size_t o, size_t m) {
-      return encode_points_dev(curve, m, dxy + o * 2 * B, compact, de + o * EL);
+    const size_t B = ci->field_bytes;
+    return staged(n, {In{xy, 2 * B}}, {Out{out_enc, encoded_len(curve, B, compact)}}, [&](size_t m, auto d, auto r) {
+      return encode_points_dev(curve, m, d[0], compact, r[0]);
     });
   }
   int validate_host(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
@@ -2094,14 +1974,8 @@ class Engine {
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
     const size_t B = ci->field_bytes;
-    u8* dxy = out_buf(G_IN0, n * 2 * B);
-    u8* dinf = inf ? out_buf(G_IN1, n) : nullptr;
-    u8* dst = out_buf(G_OUT0, n);
-    if (!dxy || !dst || (inf && !dinf)) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dxy, xy, 2 * B}, {dinf, inf, 1}};
-    HostOut outs[1] = {{out_status, dst, 1}};
-    return pipelined(n, ins, inf ? 2 : 1, outs, 1, [&](size_t o, size_t m) {
-      return validate_dev(curve, m, dxy + o * 2 * B, dinf ? dinf + o : nullptr, check_order, dst + o);
+    return staged(n, {In{xy, 2 * B}, In{inf, 1}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return validate_dev(curve, m, d[0], d[1], check_order, r[0]);
     });
   }
 
@@ -2116,8 +1990,7 @@ class Engine {
     int rc = E_OK;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       const u8* i1 = inf1 ? inf1 + o : nullptr;
       const u8* i2 = inf2 ? inf2 + o : nullptr;
       if (custom_is_edwards(curve))
@@ -2129,9 +2002,8 @@ class Engine {
       else
         ELL_SHORT_DISPATCH(curve, rc = point_add_chunk<CV>(m, xy1 + o * 2 * B, i1, xy2 + o * 2 * B, i2,
                                                            out_xy + o * 2 * B, out_inf + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int point_add_host(int curve, size_t n, const u8* xy1, const u8* inf1, const u8* xy2, const u8* inf2,
                      u8* out_xy, u8* out_inf) {
@@ -2141,21 +2013,9 @@ class Engine {
     const size_t B = ci->field_bytes;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    u8* d1 = out_buf(G_IN0, n * 2 * B);
-    u8* d2 = out_buf(G_IN1, n * 2 * B);
-    u8* di1 = inf1 ? out_buf(G_IN2, n) : nullptr;
-    u8* di2 = inf2 ? out_buf(G_IN3, n) : nullptr;
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dinf = out_buf(G_OUT1, n);
-    if (!d1 || !d2 || !dxy || !dinf || (inf1 && !di1) || (inf2 && !di2)) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[4] = {{d1, xy1, 2 * B}, {d2, xy2, 2 * B}, {nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
-    int ni = 2;
-    if (inf1) ins[ni++] = HostIn{di1, inf1, 1};
-    if (inf2) ins[ni++] = HostIn{di2, inf2, 1};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_inf, dinf, 1}};
-    return pipelined(n, ins, ni, outs, 2, [&](size_t o, size_t m) {
-      return point_add_dev(curve, m, d1 + o * 2 * B, di1 ? di1 + o : nullptr, d2 + o * 2 * B,
-                           di2 ? di2 + o : nullptr, dxy + o * 2 * B, dinf + o);
+    return staged(n, {In{xy1, 2 * B}, In{inf1, 1}, In{xy2, 2 * B}, In{inf2, 1}},
+                  {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
+      return point_add_dev(curve, m, d[0], d[1], d[2], d[3], r[0], r[1]);
     });
   }
 
@@ -2176,14 +2036,12 @@ class Engine {
     if (n && (!der || !der_len || !out_r || !out_s || !out_status)) return fail(E_ARG, "null pointer");
     if (stride == 0) return fail(E_ARG, "stride must be positive");
     const size_t NB = ci->order_bytes;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_FROM_DER, m, der + o * stride, nullptr, stride,
                                                    (u32*)der_len + o, out_r + o * NB, out_s + o * NB,
                                                    out_status + o));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   // Signature#toDER (ec/signature.js:149-176): out = n records of `stride` >= 2 NB + 9 bytes
   int sig_to_der_dev(int curve, size_t n, const u8* r, const u8* s, u8* out_der, size_t stride, u32* out_len) {
@@ -2193,13 +2051,11 @@ class Engine {
     if (n && (!r || !s || !out_der || !out_len)) return fail(E_ARG, "null pointer");
     const size_t NB = ci->order_bytes;
     if (stride < 2 * NB + 9) return fail(E_ARG, "stride must be at least 2 * order_bytes + 9");
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_TO_DER, m, r + o * NB, s + o * NB, stride, out_len + o,
                                                    out_der + o * stride, nullptr, nullptr));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   // EC#verify(msg, derSignature, encodedKey) (ec/index.js:188-229 with keyFromPublic ->
   // decodePoint and new Signature(der)): decode, parse and verify on the device
@@ -2212,8 +2068,7 @@ class Engine {
     if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
     const size_t B = ci->field_bytes, NB = ci->order_bytes, HL = (size_t)hash_len;
-    for (size_t o = 0; o < n; o += CHUNK) {
-      size_t m = n - o < CHUNK ? n - o : CHUNK;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
       u8* tmp = (u8*)scratch(S_WIRE, m * (2 * NB + 2 * B + 3));
       if (!tmp) return fail(E_NOMEM, "scratch allocation failed");
       u8* r = tmp;
@@ -2230,9 +2085,8 @@ class Engine {
       if (rc) return rc;
       ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_WIRE_STATUS, m, kst, sst, 0, nullptr, ok + o,
                                                    err ? err + o : nullptr, vst));
-      if (rc) return rc;
-    }
-    return E_OK;
+      return rc;
+    });
   }
   int sig_from_der_host(int curve, size_t n, const u8* der, size_t stride, const u32* der_len,
                         u8* out_r, u8* out_s, u8* out_status) {
@@ -2241,16 +2095,9 @@ class Engine {
     if (rc) return rc;
     if (n && (!der || !der_len || !out_r || !out_s || !out_status)) return fail(E_ARG, "null pointer");
     const size_t NB = ci->order_bytes;
-    u8* dd = out_buf(G_IN0, n * stride);
-    u8* dl = out_buf(G_IN1, n * 4);
-    u8* dr = out_buf(G_OUT0, n * NB);
-    u8* ds = out_buf(G_OUT1, n * NB);
-    u8* dst = out_buf(G_IN2, n);
-    if (!dd || !dl || !dr || !ds || !dst) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dd, der, stride}, {dl, (const u8*)der_len, 4}};
-    HostOut outs[3] = {{out_r, dr, NB}, {out_s, ds, NB}, {out_status, dst, 1}};
-    return pipelined(n, ins, 2, outs, 3, [&](size_t o, size_t m) {
-      return sig_from_der_dev(curve, m, dd + o * stride, stride, (const u32*)dl + o, dr + o * NB, ds + o * NB, dst + o);
+    return staged(n, {In{der, stride}, In{der_len, 4}}, {Out{out_r, NB}, Out{out_s, NB}, Out{out_status, 1}},
+                  [&](size_t m, auto d, auto r) {
+      return sig_from_der_dev(curve, m, d[0], stride, (const u32*)d[1], r[0], r[1], r[2]);
     });
   }
   int sig_to_der_host(int curve, size_t n, const u8* r, const u8* s, u8* out_der, size_t stride, u32* out_len) {
@@ -2259,15 +2106,8 @@ class Engine {
     if (rc) return rc;
     if (n && (!r || !s || !out_der || !out_len)) return fail(E_ARG, "null pointer");
     const size_t NB = ci->order_bytes;
-    u8* dr = out_buf(G_IN0, n * NB);
-    u8* ds = out_buf(G_IN1, n * NB);
-    u8* dd = out_buf(G_OUT0, n * stride);
-    u8* dl = out_buf(G_OUT1, n * 4);
-    if (!dr || !ds || !dd || !dl) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dr, r, NB}, {ds, s, NB}};
-    HostOut outs[2] = {{out_der, dd, stride}, {(u8*)out_len, dl, 4}};
-    return pipelined(n, ins, 2, outs, 2, [&](size_t o, size_t m) {
-      return sig_to_der_dev(curve, m, dr + o * NB, ds + o * NB, dd + o * stride, stride, (u32*)dl + o);
+    return staged(n, {In{r, NB}, In{s, NB}}, {Out{out_der, stride}, Out{out_len, 4}}, [&](size_t m, auto d, auto o) {
+      return sig_to_der_dev(curve, m, d[0], d[1], o[0], stride, (u32*)o[1]);
     });
   }
   int ecdsa_verify_wire_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
@@ -2278,30 +2118,82 @@ class Engine {
     if (rc) return rc;
     if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    const size_t HL = (size_t)hash_len;
-    u8* dh = out_buf(G_IN0, n * HL);
-    u8* dd = out_buf(G_IN1, n * der_stride);
-    u8* dl = out_buf(G_IN2, n * 4);
-    u8* dq = out_buf(G_IN3, n * pub_len);
-    u8* dok = out_buf(G_OUT0, n);
-    u8* derr = out_buf(G_OUT1, n);
-    if (!dh || !dd || !dl || !dq || !dok || !derr) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[4] = {{dh, hash, HL}, {dd, der, der_stride}, {dl, (const u8*)der_len, 4}, {dq, pub_enc, pub_len}};
-    HostOut outs[2] = {{ok, dok, 1}, {err, derr, 1}};
-    return pipelined(n, ins, 4, outs, err ? 2 : 1, [&](size_t o, size_t m) {
-      return ecdsa_verify_wire_dev(curve, m, dh + o * HL, hash_len, msg_bits, dd + o * der_stride, der_stride,
-                                   (const u32*)dl + o, dq + o * pub_len, pub_len, dok + o, derr + o);
+    return staged(n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
+                  {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto r) {
+      return ecdsa_verify_wire_dev(curve, m, d[0], hash_len, msg_bits, d[1], der_stride, (const u32*)d[2], d[3],
+                                   pub_len, r[0], r[1]);
     });
   }
 
   // ---- host-buffer wrappers: stage through device buffers --------------------
-  u8* put(int slot, const void* host, size_t bytes) {
-    if (!host) return nullptr;
-    u8* d = (u8*)staging(slot, bytes ? bytes : 1);
-    if (d && bytes) bk.h2d(d, host, bytes);
-    return d;
+  // An operand of a host-buffer call: n items of `stride` bytes.  A null host pointer is an absent
+  // optional operand (the wrappers have refused the required ones): it gets no device copy, and
+  // the body sees nullptr in its place.
+  struct In { const void* host; size_t stride; bool opt = false; };   // opt: see staged_whole()
+  struct Out { void* host; size_t stride; };
+  static constexpr int STAGED_MAX = 4;        // operands each way (pipelined(), small_call())
+  // gives every present operand a staging buffer of its own, inputs and outputs in order
+  template <int NI, int NO>
+  int stage(size_t n, const In (&in)[NI], const Out (&out)[NO], u8* (&d)[NI], u8* (&r)[NO]) {
+    static_assert(NI <= STAGED_MAX && NO <= STAGED_MAX, "too many operands");
+    auto slot = [&](int i, const void* host, size_t bytes) {
+      return host ? (u8*)grow(staging_[i], bytes ? bytes : 1) : nullptr;
+    };
+    bool ok = true;
+    for (int i = 0; i < NI; i++) ok &= (d[i] = slot(i, in[i].host, n * in[i].stride)) || !in[i].host;
+    for (int i = 0; i < NO; i++) ok &= (r[i] = slot(STAGED_MAX + i, out[i].host, n * out[i].stride)) || !out[i].host;
+    return ok ? E_OK : nomem();
   }
-  u8* out_buf(int slot, size_t bytes) { return (u8*)staging(slot, bytes ? bytes : 1); }
+  int nomem() { return fail(E_NOMEM, "staging allocation failed"); }
+  // One host-buffer call: stages its operands and runs body(m, d, r) through pipelined(), where
+  // d / r are the device copies of the inputs / outputs, already offset to the chunk's first item.
+  template <int NI, int NO, class Body>
+  int staged(size_t n, const In (&in)[NI], const Out (&out)[NO], Body body) {
+    u8* d[NI];
+    u8* r[NO];
+    if (int rc = stage(n, in, out, d, r)) return rc;
+    HostIn hi[NI];
+    HostOut ho[NO];
+    int ni = 0, no = 0;
+    for (int i = 0; i < NI; i++) if (d[i]) hi[ni++] = {d[i], (const u8*)in[i].host, in[i].stride};
+    for (int i = 0; i < NO; i++) if (r[i]) ho[no++] = {(u8*)out[i].host, r[i], out[i].stride};
+    return pipelined(n, hi, ni, ho, no, [&](size_t o, size_t m) {
+      const u8* di[NI];
+      u8* ro[NO];
+      for (int i = 0; i < NI; i++) di[i] = d[i] ? d[i] + o * in[i].stride : nullptr;
+      for (int i = 0; i < NO; i++) ro[i] = r[i] ? r[i] + o * out[i].stride : nullptr;
+      return body(m, di, ro);
+    });
+  }
+  // The EdDSA calls: their operands are whole buffers (`stride` = all their bytes), since the
+  // message offsets index the whole message buffer.  So no pipelining: a few items go through
+  // small_call(), more are copied in, run as one batch and copied out.  On that path only an
+  // optional input may be absent: a null one that is required (possible at n = 0 only, the
+  // wrappers refuse it sooner) fails as an allocation.
+  template <int NI, int NO, class Body>
+  int staged_whole(size_t n, const In (&in)[NI], const Out (&out)[NO], Body body) {
+    u8* d[NI];
+    u8* r[NO];
+    if (int rc = stage(1, in, out, d, r)) return rc;
+    if (n && n <= bk.pipeline_quantum()) {
+      SpanIn si[NI];
+      SpanOut so[NO];
+      for (int i = 0; i < NI; i++) si[i] = {d[i], (const u8*)in[i].host, in[i].stride};
+      for (int i = 0; i < NO; i++) so[i] = {(u8*)out[i].host, r[i], out[i].stride};
+      int rc = E_OK;
+      if (small_call(si, NI, so, NO, [&]() { return body(d, r); }, &rc)) return rc;
+    }
+    defer_skip();
+    for (int i = 0; i < NI; i++) {
+      if (!in[i].host && !in[i].opt) return nomem();
+      if (in[i].host && in[i].stride) bk.h2d(d[i], in[i].host, in[i].stride);
+    }
+    const int rc = body(d, r);
+    if (rc) return rc;
+    for (int i = 0; i < NO; i++)
+      if (r[i]) bk.d2h(out[i].host, r[i], out[i].stride);
+    return bk.sync();
+  }
 
   // Host-buffer calls are software-pipelined: the batch is cut into chunks that alternate
   // between two compute lanes (stream + scratch arena each), so chunk c+1's wavefronts fill
@@ -2454,35 +2346,22 @@ class Engine {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!k || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    size_t B = ci->field_bytes;
+    const size_t B = ci->field_bytes;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    u8* dk = out_buf(G_IN0, n * B);
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dinf = out_buf(G_OUT1, n);
-    if (!dk || !dxy || !dinf) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[1] = {{dk, k, B}};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_inf, dinf, 1}};
-    return pipelined(n, ins, 1, outs, 2, [&](size_t o, size_t m) {
-      return mul_fixed_dev(curve, m, dk + o * B, dxy + o * 2 * B, dinf + o);
+    return staged(n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
+      return mul_fixed_dev(curve, m, d[0], r[0], r[1]);
     });
   }
   int mul_var_host(int curve, size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!k || !xy || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    size_t B = ci->field_bytes;
+    const size_t B = ci->field_bytes;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    u8* dk = out_buf(G_IN0, n * B);
-    u8* dp = out_buf(G_IN1, n * 2 * B);
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dinf = out_buf(G_OUT1, n);
-    if (!dk || !dp || !dxy || !dinf) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dk, k, B}, {dp, xy, 2 * B}};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_inf, dinf, 1}};
-    return pipelined(n, ins, 2, outs, 2, [&](size_t o, size_t m) {
-      return mul_var_dev(curve, m, dk + o * B, dp + o * 2 * B, dxy + o * 2 * B, dinf + o);
+    return staged(n, {In{k, B}, In{xy, 2 * B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
+      return mul_var_dev(curve, m, d[0], d[1], r[0], r[1]);
     });
   }
   int mul_add2_host(int curve, size_t n, const u8* k1, const u8* xy1, const u8* k2,
@@ -2490,22 +2369,12 @@ class Engine {
     const CurveInfo* ci = curve_info(curve);
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!k1 || !k2 || !xy2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    size_t B = ci->field_bytes;
+    const size_t B = ci->field_bytes;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    u8* d1 = out_buf(G_IN0, n * B);
-    u8* dp1 = xy1 ? out_buf(G_IN1, n * 2 * B) : nullptr;
-    u8* d2 = out_buf(G_IN2, n * B);
-    u8* dp2 = out_buf(G_IN3, n * 2 * B);
-    u8* dxy = out_buf(G_OUT0, n * 2 * B);
-    u8* dinf = out_buf(G_OUT1, n);
-    if (!d1 || !d2 || !dp2 || !dxy || !dinf || (xy1 && !dp1))
-      return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[4] = {{d1, k1, B}, {dp1, xy1, 2 * B}, {d2, k2, B}, {dp2, xy2, 2 * B}};
-    HostOut outs[2] = {{out_xy, dxy, 2 * B}, {out_inf, dinf, 1}};
-    return pipelined(n, ins, 4, outs, 2, [&](size_t o, size_t m) {
-      return mul_add2_dev(curve, m, d1 + o * B, dp1 ? dp1 + o * 2 * B : nullptr, d2 + o * B,
-                          dp2 + o * 2 * B, dxy + o * 2 * B, dinf + o);
+    return staged(n, {In{k1, B}, In{xy1, 2 * B}, In{k2, B}, In{xy2, 2 * B}},
+                  {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
+      return mul_add2_dev(curve, m, d[0], d[1], d[2], d[3], r[0], r[1]);
     });
   }
   int ecdsa_verify_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
@@ -2514,37 +2383,18 @@ class Engine {
     if (!ci) return fail(E_ARG, "unknown curve id");
     if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    size_t B = ci->field_bytes, NB = ci->order_bytes;
-    size_t HL = (size_t)hash_len;
+    const size_t B = ci->field_bytes, NB = ci->order_bytes;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    u8* dh = out_buf(G_IN0, n * HL);
-    u8* dr = out_buf(G_IN1, n * NB);
-    u8* dsg = out_buf(G_IN2, n * NB);
-    u8* dq = out_buf(G_IN3, n * 2 * B);
-    u8* dok = out_buf(G_OUT0, n);
-    u8* dst = st ? out_buf(G_OUT1, n) : nullptr;
-    if (!dh || !dr || !dsg || !dq || !dok || (st && !dst)) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[4] = {{dh, hash, HL}, {dr, r, NB}, {dsg, s, NB}, {dq, pub, 2 * B}};
-    HostOut outs[2] = {{ok, dok, 1}, {st, dst, 1}};
-    return pipelined(n, ins, 4, outs, st ? 2 : 1, [&](size_t o, size_t m) {
-      return ecdsa_verify_dev(curve, m, dh + o * HL, hash_len, msg_bits, dr + o * NB, dsg + o * NB,
-                              dq + o * 2 * B, dok + o, dst ? dst + o : nullptr);
+    return staged(n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{pub, 2 * B}},
+                  {Out{ok, 1}, Out{st, 1}}, [&](size_t m, auto d, auto o) {
+      return ecdsa_verify_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], d[3], o[0], o[1]);
     });
   }
   int x25519_host(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
     if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
-    u8* dk = out_buf(G_IN0, n * 32);
-    u8* dx = out_buf(G_IN1, n * 32);
-    u8* dox = out_buf(G_OUT0, n * 32);
-    u8* dinf = out_buf(G_OUT1, n);
-    u8* dbad = out_bad ? out_buf(G_OUT2, n) : nullptr;
-    if (!dk || !dx || !dox || !dinf || (out_bad && !dbad)) return fail(E_NOMEM, "staging allocation failed");
-    HostIn ins[2] = {{dk, k, 32}, {dx, x, 32}};
-    HostOut outs[3] = {{out_x, dox, 32}, {out_inf, dinf, 1}, {out_bad, dbad, 1}};
-    return pipelined(n, ins, 2, outs, out_bad ? 3 : 2, [&](size_t o, size_t m) {
-      return x25519_dev(m, dk + o * 32, dx + o * 32, dox + o * 32, dinf + o, dbad ? dbad + o : nullptr);
-    });
+    return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_inf, 1}, Out{out_bad, 1}},
+                  [&](size_t m, auto d, auto r) { return x25519_dev(m, d[0], d[1], r[0], r[1], r[2]); });
   }
 
   // scratch arena of the current call (0 / 1: the compute lanes of pipelined(); a *_dev call takes
@@ -2581,7 +2431,7 @@ class Engine {
   int comb_bits_[COMB_SLOTS];                // window width in use (signed combs may be narrower than the default)
   Buf scratch_[2][S_COUNT];   // one scratch arena per compute lane (see pipelined())
   int lane_ = 0;
-  Buf staging_[G_COUNT];
+  Buf staging_[2 * STAGED_MAX];   // the host-buffer calls' device copies: inputs, then outputs (stage())
   std::vector<RtField> custom_;  // user-defined curves of this context (id = CURVE_CUSTOM0 + index)
   bool custom_active_ = false;
   int custom_curve_ = 0;         // the user-defined curve of the call in progress (CustomScope)
