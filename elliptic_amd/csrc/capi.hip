@@ -5,9 +5,14 @@
 #include <type_traits>
 #include <vector>
 
+#define ELL_RT_SYMBOL g_rt_probe    // this code object's own parameter block (fp_rt.h): the field probe's
 #include "engine_extern.h"
 
 namespace ell {
+
+// the run-time fields' parameter block of ellgpu_debug_field_op (fields 100+ / 200+): the probe's own,
+// never the product kernels' g_rt / g_rt_dom
+__constant__ RtField g_rt_probe;
 
 // ---- integer-VALU roofline probe ----------------------------------------------
 // Each lane runs `iters` rounds of 16 independent 32x32+64->64 multiply-adds
@@ -400,24 +405,53 @@ extern "C" int ellgpu_ctx_get_timing(ellgpu_ctx* ctx, char* buf, size_t cap) {
 // White-box probe (tests only): r[i] = a[i] <op> b[i] in one of the engine's fields, n items
 // of `limbs` 32-bit little-endian limbs each (host pointers).  field: 0 secp256k1 p,
 // 1 2^255-19, 10+c base field of short curve c as FpMont, 20+c order field of curve c
-// (26 = ed25519 order).  op: 0 add, 1 sub, 2 mul, 3 sqr, 4 inv, 5 neg.
+// (26 = ed25519 order); 100+s the run-time field FpMontRT over the modulus p of this context's
+// user-defined curve 16+s, 200+s FpMontRTn over the order n of that curve (an ECDSA domain),
+// 8 limbs, operands any value < 2^256, ops 0..8 only (ELLGPU_E_ARG otherwise).  op: 0 add, 1 sub,
+// 2 mul, 3 sqr, 4 inv, 5 neg, 6 / 7 / 8 multiply by 2 / 4 / 8.
 extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t n, const uint32_t* a,
                                      const uint32_t* b, uint32_t* r) {
   using namespace ell;
   ELL_ENTER(ctx, nullptr);
   int L = 0;
+  const RtField* rt = nullptr;
   switch (field) {
     case 0: case 1: case 2: case 10: case 13: case 20: case 23: case 26: L = 8; break;
     case 11: case 21: L = 6; break;
     case 12: case 22: L = 7; break;
     case 14: case 24: L = 12; break;
     case 15: case 25: L = 17; break;
-    default: return set_err(ELLGPU_E_ARG, "unknown field id");
+    default:
+      if (field >= 100 && field < 100 + CURVE_CUSTOM_MAX) rt = ctx->eng->custom_block(CURVE_CUSTOM0 + field - 100);
+      else if (field >= 200 && field < 200 + CURVE_CUSTOM_MAX) rt = ctx->eng->custom_block(CURVE_CUSTOM0 + field - 200);
+      else return set_err(ELLGPU_E_ARG, "unknown field id");
+      if (!rt) return set_err(ELLGPU_E_ARG, "field probe: no such user-defined curve");
+      if (field >= 200 && !rt->domain) return set_err(ELLGPU_E_ARG, "field probe: the curve has no order (not an ECDSA domain)");
+      if (op < 0 || op > 8) return set_err(ELLGPU_E_ARG, "field probe: the run-time fields take ops 0..8");
+      L = 8;
+      break;
   }
   HipBackend& bk = ctx->eng->bk;
+  // the run-time fields read the probe's own block: one per device, so such a probe holds the device's
+  // custom-curve lock from the (synchronous) upload to the end of its kernel
+  std::unique_lock<std::mutex> rt_lock;
+  if (rt) {
+    rt_lock = std::unique_lock<std::mutex>(custom_mutex(bk.device_index()));
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_rt_probe), rt, sizeof(RtField), 0, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->eng->err = "field probe: parameter block upload failed";
+      return finish(ctx, ELLGPU_E_HIP);
+    }
+  }
   size_t bytes = n * (size_t)L * 4;
   u32* da = (u32*)bk.alloc(bytes); u32* db = (u32*)bk.alloc(bytes); u32* dr = (u32*)bk.alloc(bytes);
-  if (!da || !db || !dr) return set_err(ELLGPU_E_NOMEM, "probe allocation failed");
+  if (!da || !db || !dr) {
+    if (da) bk.free_(da);
+    if (db) bk.free_(db);
+    if (dr) bk.free_(dr);
+    ctx->eng->err = "probe allocation failed";
+    return finish(ctx, ELLGPU_E_NOMEM);
+  }
   bk.h2d(da, a, bytes); bk.h2d(db, b, bytes);
   switch (field) {
     case 0: run_field_op<FpK256>(bk, op, n, da, db, dr); break;
@@ -436,6 +470,10 @@ extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t 
     case 24: run_field_op<CvP384::Fn>(bk, op, n, da, db, dr); break;
     case 25: run_field_op<CvP521::Fn>(bk, op, n, da, db, dr); break;
     case 26: run_field_op<FpMont<consts::ED25519_N>>(bk, op, n, da, db, dr); break;
+    default:
+      if (field < 200) run_field_op<FpMontRT>(bk, op, n, da, db, dr);
+      else run_field_op<FpMontRTn>(bk, op, n, da, db, dr);
+      break;
   }
   bk.note(hipGetLastError());
   bk.d2h(r, dr, bytes);

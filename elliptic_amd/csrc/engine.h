@@ -1517,6 +1517,12 @@ class Engine {
     size_t slot = (size_t)(curve - CURVE_CUSTOM0);
     return is_custom(curve) && slot < custom_.size() && custom_[slot].domain == 1;
   }
+  // the parameter block of a user-defined curve, null for an id that is none of this context's
+  // (the white-box field probes read it: ellgpu_debug_field_op, tests/hostsim)
+  const RtField* custom_block(int curve) const {
+    size_t slot = (size_t)(curve - CURVE_CUSTOM0);
+    return is_custom(curve) && slot < custom_.size() ? &custom_[slot] : nullptr;
+  }
   // where the fixed-base table of a curve type lives: the presets' by their id, a domain's in the
   // slot of the curve the current call is on (CustomScope)
   template <class CV>

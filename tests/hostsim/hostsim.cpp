@@ -241,6 +241,24 @@ int hs_field_op(int field, int op, const u32* a, const u32* b, u32* r) {
   }
   return 0;
 }
+// the run-time fields (csrc/fp_rt.h), as ellgpu_debug_field_op's ids 100+s / 200+s: FpMontRT over the
+// modulus p, FpMontRTn over the order n of ctx's user-defined curve 16+s; n items of 8 limbs, ops 0..8.
+// The block is the process-wide rt_host_block(), set here under the locks a product call takes.
+int hs_rt_field_op(ellgpu_ctx* ctx, int field, int op, size_t n, const u32* a, const u32* b, u32* r) {
+  if (!ctx || op < 0 || op > 8) return ELLGPU_E_ARG;
+  ELL_LOCK(ctx);
+  const RtField* rt = nullptr;
+  if (field >= 100 && field < 100 + CURVE_CUSTOM_MAX) rt = ctx->eng->custom_block(CURVE_CUSTOM0 + field - 100);
+  else if (field >= 200 && field < 200 + CURVE_CUSTOM_MAX) rt = ctx->eng->custom_block(CURVE_CUSTOM0 + field - 200);
+  if (!rt || (field >= 200 && !rt->domain)) return ELLGPU_E_ARG;
+  std::lock_guard<std::mutex> g(custom_mutex(0));
+  rt_host_block() = *rt;
+  for (size_t i = 0; i < n; i++) {
+    if (field < 200) field_op<FpMontRT>(op, a + 8 * i, b + 8 * i, r + 8 * i);
+    else field_op<FpMontRTn>(op, a + 8 * i, b + 8 * i, r + 8 * i);
+  }
+  return 0;
+}
 int hs_drbg_draws(int kind, const u8* seed, int nbytes, int ndraws, u8* out) {
   if (kind == 0 && nbytes == 24) { drbg256_draws<6>(seed, ndraws, out); return 0; }
   if (kind == 0 && nbytes == 28) { drbg256_draws<7>(seed, ndraws, out); return 0; }
