@@ -460,6 +460,43 @@ int ellgpu_ecdsa_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uin
                                                      der_len, pub_enc, pub_len, out_ok, out_err), true);
 }
 
+// wire formats on user-defined short curves (a group: member 0, like the presets' wire verify)
+int ellgpu_custom_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* x, const uint8_t* odd,
+                             uint8_t* out_xy, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_decompress_host(curve, n, x, odd, out_xy, out_status));
+}
+int ellgpu_custom_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* x, const uint8_t* odd,
+                                 uint8_t* out_xy, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_decompress_dev(curve, n, x, odd, out_xy, out_status), true);
+}
+int ellgpu_custom_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                uint8_t* out_xy, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_decode_points_host(curve, n, enc, enc_len, out_xy, out_status));
+}
+int ellgpu_custom_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                    uint8_t* out_xy, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_decode_points_dev(curve, n, enc, enc_len, out_xy, out_status), true);
+}
+int ellgpu_custom_verify_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                              int msg_bits, const uint8_t* der, size_t der_stride, const uint32_t* der_len,
+                              const uint8_t* pub_enc, size_t pub_len, uint8_t* out_ok, uint8_t* out_err) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_verify_wire_host(curve, n, hash, hash_len, msg_bits, der, der_stride,
+                                                       der_len, pub_enc, pub_len, out_ok, out_err));
+}
+int ellgpu_custom_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                                  int msg_bits, const uint8_t* der, size_t der_stride,
+                                  const uint32_t* der_len, const uint8_t* pub_enc, size_t pub_len,
+                                  uint8_t* out_ok, uint8_t* out_err, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_verify_wire_dev(curve, n, hash, hash_len, msg_bits, der, der_stride,
+                                                      der_len, pub_enc, pub_len, out_ok, out_err), true);
+}
+
 int ellgpu_ecdsa_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {

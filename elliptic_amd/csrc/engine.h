@@ -744,6 +744,25 @@ struct FnWireStatus {
     if (i < n) W::wire_status(i, key_st, sig_st, ver_st, ok, err);
   }
 };
+// user-defined curves: pointFromX and decodePoint over the run-time modulus (Work::rt_*)
+struct FnRtDecompress {
+  static constexpr const char* NAME = "rt_decompress";
+  typedef Work<CvCustom> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* x; const u8* odd; u8* out_xy; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_decompress(i, x, odd, out_xy, status);
+  }
+};
+struct FnRtDecodePoint {
+  static constexpr const char* NAME = "rt_decode_point";
+  typedef Work<CvCustom> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* enc; size_t len; int pl; u8* out_xy; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_decode_point(i, enc, len, pl, out_xy, status);
+  }
+};
 template <class CV>
 struct FnPointAdd {
   static constexpr const char* NAME = "point_add";
@@ -1221,6 +1240,11 @@ class Engine {
   template <int U = 0>
   int edc_chunk(int op, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                 const u8* a, const u8* b, u8* out_xy, u8* out_inf);
+  // wire formats on user-defined short curves (OP_RT_*): pointFromX, decodePoint, the DER parser
+  // and the wire verify's status fold -- the kernels of one code object (inst.hip group 16)
+  template <int U = 0>
+  int rt_wire_chunk(int op, size_t n, const u8* a, const u8* b, size_t len, const u32* lens, u8* o1, u8* o2,
+                    u8* o3);
   template <class CV>
   int decompress_chunk(size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_ok);
   template <class CV>
@@ -1303,6 +1327,54 @@ class Engine {
     bn_sub<8>(f.pm2, f.p, two);
     return E_OK;
   }
+  // Red#sqrt's constants of a block's modulus (fp_rt.h) and p.byteLength().  Deterministic: z is
+  // the LEAST quadratic non-residue (Euler's criterion, candidates 2 .. 255), so that the same
+  // parameters always give the same block (register_custom compares blocks).  A modulus without
+  // such a z is no prime; its block gets c = 0 and its roots are outside the documented domain,
+  // like its inverses.
+  static void rt_sqrt_init(RtField& f) {
+    int pb = 256;
+    while (pb > 0 && !((f.p[(pb - 1) >> 5] >> ((pb - 1) & 31)) & 1u)) pb--;
+    f.pbytes = (u32)((pb + 7) / 8);
+    auto shr = [](u32 (&x)[8], int k) {
+      for (int i = 0; i < 8; i++) x[i] = (x[i] >> k) | (i + 1 < 8 ? x[i + 1] << (32 - k) : 0u);
+    };
+    u32 one[8];
+    bn_zero<8>(one);
+    one[0] = 1;
+    bn_copy<8>(f.sqrt_e, f.p);
+    if ((f.p[0] & 3u) == 3u) {
+      f.sqrt_kind = 0;
+      f.sqrt_s = 1;
+      shr(f.sqrt_e, 2);                                   // (p + 1) / 4 = (p >> 2) + 1
+      bn_add<8>(f.sqrt_e, f.sqrt_e, one);
+    } else {
+      f.sqrt_kind = 1;
+      u32 q[8], half[8], pm1[8];
+      bn_sub<8>(pm1, f.p, one);
+      bn_copy<8>(q, pm1);
+      f.sqrt_s = 0;
+      while (!(q[0] & 1u)) { shr(q, 1); f.sqrt_s++; }
+      bn_copy<8>(f.sqrt_e, q);
+      shr(f.sqrt_e, 1);                                   // (q - 1) / 2
+      bn_copy<8>(half, pm1);
+      shr(half, 1);
+      for (u32 z = 2; z < 256; z++) {
+        u32 zz[8], t[8];
+        bn_zero<8>(zz);
+        zz[0] = z;
+        if (bn_geq<8>(zz, f.p)) break;
+        mod_pow(f.p, t, zz, half);
+        if (!bn_eq<8>(t, pm1)) continue;
+        mod_pow(f.p, t, zz, q);
+        mod_to_mont(f.p, f.sqrt_c, t);
+        break;
+      }
+    }
+    int eb = 256;
+    while (eb > 0 && !((f.sqrt_e[(eb - 1) >> 5] >> ((eb - 1) & 31)) & 1u)) eb--;
+    f.sqrt_ebits = (u32)eb;
+  }
   static void rt_times_r(const RtField& f, u32 (&r)[8]) { mod_times_r(f.p, r); }
   static void rt_to_mont(const RtField& f, u32 (&out)[8], const u32 (&x)[8]) { mod_to_mont(f.p, out, x); }
   // host arithmetic modulo any odd m < 2^256, bit by bit (a definition is rare; these are not hot)
@@ -1353,6 +1425,18 @@ class Engine {
     }
     bn_copy<8>(out, r);
   }
+  // out = a^e mod m, a < m
+  static void mod_pow(const u32 (&m)[8], u32 (&out)[8], const u32 (&a)[8], const u32 (&e)[8]) {
+    u32 r[8], o[8];
+    bn_zero<8>(o);
+    o[0] = 1;
+    mod_reduce(m, r, o);
+    for (int i = 255; i >= 0; i--) {
+      mod_mul(m, r, r, r);
+      if ((e[i >> 5] >> (i & 31)) & 1u) mod_mul(m, r, r, a);
+    }
+    bn_copy<8>(out, r);
+  }
   // the Montgomery constants of a modulus m: -m^-1 mod 2^32, R mod m, R^2 mod m, m - 2
   static void mont_consts(const u32 (&m)[8], u32& n0, u32 (&one)[8], u32 (&r2)[8], u32 (&mm2)[8]) {
     u32 inv = 1;                                          // m^-1 mod 2^32 (Newton)
@@ -1396,6 +1480,7 @@ class Engine {
       rt_to_mont(f, m3, m3);
       f.a_kind = bn_is_zero<8>(f.a_m) ? 0u : (bn_eq<8>(f.a_m, m3) ? 3u : 1u);
       f.kind = 0;
+      rt_sqrt_init(f);
     } else {
       rt_to_mont(f, f.d_m, b);
       if (bn_is_zero<8>(f.a_m) || bn_is_zero<8>(f.d_m) || bn_eq<8>(f.a_m, f.d_m))
@@ -2131,6 +2216,114 @@ class Engine {
     });
   }
 
+  // ---- wire formats on user-defined short curves -------------------------------------------
+  // ShortCurve#pointFromX, BaseCurve#decodePoint and EC#verify(msg, der, key) where the curve
+  // is the caller's own (ellgpu_custom_*).  Entry points of their own: the preset-named ones
+  // refuse user-defined ids before a kernel is chosen, and keep doing so.  Coordinates in and
+  // out are 32 bytes; a SEC1 coordinate is p.byteLength() bytes, the block's pbytes.
+  enum { OP_RT_DECOMPRESS = 0, OP_RT_DECODE = 1, OP_RT_FROM_DER = 2, OP_RT_WIRE_STATUS = 3 };
+  int check_custom_short(int curve, bool need_domain) {
+    if (!is_custom(curve))
+      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (the presets have ellgpu_decompress, ellgpu_decode_points and ellgpu_ecdsa_verify_wire)")
+                               : fail(E_ARG, "unknown curve id");
+    const RtField* f = custom_block(curve);
+    if (!f) return fail(E_ARG, "unknown curve id");
+    if (f->kind != 0) return fail(E_UNSUPPORTED, "not available on user-defined Edwards curves");
+    if (need_domain && !f->domain)
+      return fail(E_UNSUPPORTED, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    return E_OK;
+  }
+  int custom_decompress_dev(int curve, size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!x || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_wire_chunk(OP_RT_DECOMPRESS, m, x + o * 32, odd + o, 0, nullptr, out_xy + o * 64, out_status + o, nullptr);
+    });
+  }
+  int custom_decompress_host(int curve, size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!x || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{x, 32}, In{odd, 1}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_decompress_dev(curve, m, d[0], d[1], r[0], r[1]);
+    });
+  }
+  // enc_len other than 1 + pbytes and 1 + 2 pbytes is no error of the call: every item is then
+  // 'Unknown point format', as in the reference
+  int custom_decode_points_dev(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_wire_chunk(OP_RT_DECODE, m, enc + o * enc_len, nullptr, enc_len, nullptr, out_xy + o * 64, out_status + o,
+                           nullptr);
+    });
+  }
+  int custom_decode_points_host(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{enc, enc_len}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_decode_points_dev(curve, m, d[0], enc_len, r[0], r[1]);
+    });
+  }
+  // EC#verify(msg, derSignature, encodedKey) on a domain: decode, parse and verify on the device,
+  // composed like ecdsa_verify_wire_dev
+  int custom_verify_wire_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* der,
+                             size_t der_stride, const u32* der_len, const u8* pub_enc, size_t pub_len, u8* ok,
+                             u8* err) {
+    int rc = check_custom_short(curve, true);
+    if (rc) return rc;
+    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
+    if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t HL = (size_t)hash_len;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      u8* tmp = (u8*)scratch(S_WIRE, m * (2 * 32 + 64 + 3));
+      if (!tmp) return fail(E_NOMEM, "scratch allocation failed");
+      u8* r = tmp;
+      u8* s = r + m * 32;
+      u8* xy = s + m * 32;
+      u8* kst = xy + m * 64;
+      u8* sst = kst + m;
+      u8* vst = sst + m;
+      rc = rt_wire_chunk(OP_RT_DECODE, m, pub_enc + o * pub_len, nullptr, pub_len, nullptr, xy, kst, nullptr);
+      if (rc) return rc;
+      rc = rt_wire_chunk(OP_RT_FROM_DER, m, der + o * der_stride, nullptr, der_stride, der_len + o, r, s, sst);
+      if (rc) return rc;
+      rc = ecdsa_verify_dev(curve, m, hash + o * HL, hash_len, msg_bits, r, s, xy, ok + o, vst);
+      if (rc) return rc;
+      return rt_wire_chunk(OP_RT_WIRE_STATUS, m, kst, sst, 0, nullptr, ok + o, err ? err + o : nullptr, vst);
+    });
+  }
+  int custom_verify_wire_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* der,
+                              size_t der_stride, const u32* der_len, const u8* pub_enc, size_t pub_len, u8* ok,
+                              u8* err) {
+    int rc = check_custom_short(curve, true);
+    if (rc) return rc;
+    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
+    if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
+                  {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_verify_wire_dev(curve, m, d[0], hash_len, msg_bits, d[1], der_stride, (const u32*)d[2], d[3],
+                                    pub_len, r[0], r[1]);
+    });
+  }
+
   // ---- host-buffer wrappers: stage through device buffers --------------------
   // An operand of a host-buffer call: n items of `stride` bytes.  A null host pointer is an absent
   // optional operand (the wrappers have refused the required ones): it gets no device copy, and
@@ -2684,6 +2877,26 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
   return rc;
 }
 
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_wire_chunk(int op, size_t n, const u8* a, const u8* b, size_t len, const u32* lens, u8* o1,
+                              u8* o2, u8* o3) {
+  if (op == OP_RT_DECOMPRESS) {
+    FnRtDecompress f{n, a, b, o1, o2};
+    bk.launch(f, n);
+  } else if (op == OP_RT_DECODE) {
+    FnRtDecodePoint f{n, a, len, (int)custom_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].pbytes, o1, o2};
+    bk.launch(f, n);
+  } else if (op == OP_RT_FROM_DER) {
+    FnSigFromDer<CvCustom> f{n, a, len, lens, o1, o2, o3};
+    bk.launch(f, n);
+  } else {
+    FnWireStatus<CvCustom> f{n, a, b, o3, o1, o2};
+    bk.launch(f, n);
+  }
+  return E_OK;
+}
 
 template <class BK>
 template <int U>

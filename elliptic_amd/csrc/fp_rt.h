@@ -11,6 +11,18 @@
 // One block per DEVICE: a call on a user-defined curve takes that device's lock, uploads the
 // curve's block, and waits for its own device work before releasing the lock (Engine::CustomScope,
 // engine.h) -- such calls are synchronous and serialised per device, whatever stream they name.
+//
+// Square root (Red#sqrt, dist/elliptic.js:7177-7232), for ShortCurve#pointFromX and the
+// compressed SEC1 encodings on user-defined curves: the block carries the constants that depend
+// on the modulus alone -- p - 1 = q 2^s, the exponent, c = z^q for a quadratic non-residue z --
+// computed on the host when the curve is defined (Engine::rt_sqrt_init).  p = 3 (mod 4): one
+// exponentiation a^((p+1)/4).  Otherwise Tonelli-Shanks, with the reference's inner search for
+// the order of t replaced by a schedule that s alone fixes: s - 1 rounds, round k squares t
+// k - 1 times and applies the correction under a per-lane select.  Every loop bound is read from
+// the block (wave-uniform), so the root terminates for any input and any modulus; a value without
+// a root comes back as something whose square differs, which the caller's y^2 == rhs test
+// (Work::lift_x) reports -- as 'invalid point' where p = 3 (mod 4), as the 'Assertion failed' of
+// bn.js's own loop (assert(i < m), dist/elliptic.js:7217-7229) where Tonelli-Shanks runs.
 #pragma once
 
 #include "fp.h"
@@ -41,6 +53,13 @@ struct RtField {
   u32 ncand;       // floor(p / n) when <= 100 (_maxwellTrick: eqXToP's further candidates), else RT_NO_MAXWELL
   u32 gx[8];       // G, plain
   u32 gy[8];
+  // Red#sqrt (a function of p alone; zero for an Edwards curve, which never takes a root)
+  u32 sqrt_kind;   // 0: p = 3 (mod 4), a^((p+1)/4); 1: Tonelli-Shanks
+  u32 sqrt_s;      // 2-adicity of p - 1:  p - 1 = q 2^s, q odd
+  u32 sqrt_ebits;  // bitLength of sqrt_e
+  u32 sqrt_e[8];   // (p + 1) / 4  or  (q - 1) / 2
+  u32 sqrt_c[8];   // z^q for a quadratic non-residue z, Montgomery form (Tonelli-Shanks only)
+  u32 pbytes;      // p.byteLength(): the width of a SEC1 coordinate (BaseCurve#decodePoint)
 };
 
 constexpr u32 RT_NO_MAXWELL = 0xFFFFFFFFu;
@@ -64,7 +83,7 @@ template <int MOD>
 struct FpMontRTm {
   static constexpr int L = 8;
   typedef Fe<8> El;
-  static constexpr bool HAS_SQRT = false;      // Red#sqrt of a generic prime stays in the reference's JavaScript
+  static constexpr bool HAS_SQRT = true;       // Red#sqrt of a generic prime: sqrt() below (base field only)
 
   ELL_HD static void get_p(u32 (&p)[8]) {
     ELL_UNROLL
@@ -184,7 +203,45 @@ struct FpMontRTm {
     }
     return r;
   }
-  static ELL_HD_NOINLINE El sqrt(const El& a) { return a; }     // never called (HAS_SQRT = false)
+  // a^e for the block's square-root exponent (wave-uniform: a scalar branch per bit)
+  ELL_HD static El pow_sqrt_e(const El& a) {
+    El r = one();
+    ELL_NOUNROLL
+    for (int i = (int)ELL_RT.sqrt_ebits - 1; i >= 0; i--) {
+      r = sqr(r);
+      if ((ELL_RT.sqrt_e[i >> 5] >> (i & 31)) & 1u) r = mul(r, a);
+    }
+    return r;
+  }
+  // Red#sqrt: a root of a where it has one (either of the two: pointFromX fixes the sign by
+  // parity), 0 for 0, otherwise a value whose square is not a.  Base field only.
+  static ELL_HD_NOINLINE El sqrt(const El& a) {
+    static_assert(MOD == 0, "square roots are the base field's");
+    El w = pow_sqrt_e(a);
+    if (ELL_RT.sqrt_kind == 0) return w;                   // a^((p+1)/4)
+    // Tonelli-Shanks: r = a^((q+1)/2), t = a^q, c = z^q of order 2^s.  Invariant of round k:
+    // r^2 = a t, c has order 2^(k+1), and t^(2^k) = 1 when a is a residue -- so t^(2^(k-1)) is 1
+    // or -1, and in the second case r c, t c^2 restore the invariant for k - 1.
+    El r = mul(a, w);
+    El t = mul(r, w);
+    El c;
+    ELL_UNROLL
+    for (int i = 0; i < 8; i++) c.v[i] = ELL_RT.sqrt_c[i];
+    const El o = one();
+    ELL_NOUNROLL
+    for (int k = (int)ELL_RT.sqrt_s - 1; k >= 1; k--) {
+      El u = t;
+      ELL_NOUNROLL
+      for (int j = 1; j < k; j++) u = sqr(u);
+      const bool fix = !eq(u, o);
+      const El rc = mul(r, c);
+      c = sqr(c);
+      const El tc = mul(t, c);
+      bn_select<8>(r.v, fix, rc.v, r.v);
+      bn_select<8>(t.v, fix, tc.v, t.v);
+    }
+    return r;
+  }
 };
 typedef FpMontRTm<0> FpMontRT;       // base field of a user-defined curve
 typedef FpMontRTm<1> FpMontRTn;      // order field of a user-defined ECDSA domain

@@ -462,6 +462,53 @@ struct Work {
     store_fe(out_xy + i * 2 * BYTES + BYTES, y);
     status[i] = (u8)st;
   }
+  // ---- the same on a user-defined curve (run-time modulus, fp_rt.h) ----------------------
+  // what a compressed x without a y is answered with: 'invalid point' (short.js:196-197) where
+  // p = 3 (mod 4); where bn.js runs Tonelli-Shanks its loop gives up first ('Assertion failed',
+  // dist/elliptic.js:7217-7229) -- as over p224 above.  Wave-uniform.
+  ELL_HD static u32 rt_no_root() { return ELL_RT.sqrt_kind ? (u32)DECODE_ASSERT : (u32)DECODE_INVALID; }
+  // ShortCurve#pointFromX (short.js:187-204): x is 32 bytes whatever p's size, reduced mod p as
+  // toRed does.  status 0 = point, else rt_no_root() and a zeroed point.
+  ELL_HD static void rt_decompress(size_t i, const u8* xs, const u8* odd, u8* out_xy, u8* status) {
+    El x = load_fe(xs + i * BYTES);
+    El y;
+    const bool ok = lift_x(y, x, odd[i] != 0);
+    if (!ok) { x = F::zero(); y = F::zero(); }
+    store_fe(out_xy + i * 2 * BYTES, x);
+    store_fe(out_xy + i * 2 * BYTES + BYTES, y);
+    status[i] = ok ? (u8)DECODE_OK : (u8)rt_no_root();
+  }
+  // a coordinate of pl <= BYTES bytes, big-endian, reduced mod p
+  ELL_HD static El load_fe_n(const u8* p, int pl) {
+    u32 t[L];
+    load_be<L>(t, p, pl);
+    return F::from_plain(t);
+  }
+  // BaseCurve#decodePoint (base.js:270-293) with len = p.byteLength() = pl: encodings of
+  // 1 + pl (02/03) or 1 + 2 pl (04/06/07) bytes, coordinates out BYTES wide.  status as
+  // decode_point's, with rt_no_root() for a compressed x without a y.
+  ELL_HD static void rt_decode_point(size_t i, const u8* enc, size_t len, int pl, u8* out_xy, u8* status) {
+    const u8* e = enc + i * len;
+    const u32 tag = len ? e[0] : 0u;
+    El x = F::zero(), y = F::zero();
+    u32 st = DECODE_FORMAT;
+    if ((tag == 4 || tag == 6 || tag == 7) && len == 1 + 2 * (size_t)pl) {
+      const u32 last = e[len - 1] & 1u;
+      if ((tag == 6 && last != 0) || (tag == 7 && last != 1)) st = DECODE_ASSERT;
+      else {
+        x = load_fe_n(e + 1, pl);
+        y = load_fe_n(e + 1 + pl, pl);
+        st = DECODE_OK;
+      }
+    } else if ((tag == 2 || tag == 3) && len == 1 + (size_t)pl) {
+      x = load_fe_n(e + 1, pl);
+      st = lift_x(y, x, tag == 3) ? (u32)DECODE_OK : rt_no_root();
+      if (st != DECODE_OK) { x = F::zero(); y = F::zero(); }
+    }
+    store_fe(out_xy + i * 2 * BYTES, x);
+    store_fe(out_xy + i * 2 * BYTES + BYTES, y);
+    status[i] = (u8)st;
+  }
   // BasePoint#_encode (base.js:299-307): 02/03 || x  or  04 || x || y, coordinates reduced
   ELL_HD static void encode_point(size_t i, const u8* xy, int compact, u8* out) {
     A a = load_affine(xy, i);

@@ -376,6 +376,82 @@ class Context:
             der.shape[1], der_len.data_ptr(), pubs.data_ptr(), pubs.shape[1], out_ok.data_ptr(),
             out_err.data_ptr() if out_err is not None else None, self._stream()))
 
+    # ---- wire formats on user-defined short curves (ellgpu_custom_*) ----------------------
+    # curve: an id from define_short / define_short_domain; coordinates are 32 bytes, a SEC1
+    # coordinate p.byteLength() bytes
+
+    @staticmethod
+    def _outs(out, shapes):
+        """result arrays: fresh zeroed ones, or the caller's (checked) to write into"""
+        if out is None:
+            return [np.zeros(sh, np.uint8) for sh in shapes]
+        for o, sh in zip(out, shapes):
+            assert o.dtype == np.uint8 and o.shape == sh and o.flags.c_contiguous
+        return list(out)
+
+    def custom_decompress(self, curve, x, odd, out=None):
+        """ShortCurve#pointFromX per item -> (xy, status); status 0 point, 2 'invalid point'
+        (p = 3 mod 4), 3 'Assertion failed' (p = 1 mod 4: bn.js's Tonelli-Shanks loop)"""
+        x = _u8(x, (-1, 32))
+        n = x.shape[0]
+        odd = _u8(odd, (n,))
+        xy, st = self._outs(out, [(n, 64), (n,)])
+        self._check(self._lib.ellgpu_custom_decompress(self._ctx, self._cid(curve), n, x.ctypes.data,
+                                                       odd.ctypes.data, xy.ctypes.data, st.ctypes.data))
+        return xy, st
+
+    def custom_decompress_dev(self, curve, x, odd, out_xy, out_status):
+        n = x.shape[0]
+        self._check(self._lib.ellgpu_custom_decompress_dev(self._ctx, self._cid(curve), n, x.data_ptr(),
+                                                           odd.data_ptr(), out_xy.data_ptr(),
+                                                           out_status.data_ptr(), self._stream()))
+
+    def custom_decode_points(self, curve, enc, out=None):
+        """BaseCurve#decodePoint per row of `enc` (n, enc_len) -> (xy, status) as decode_points;
+        a compressed x without a y is 3 where p = 1 (mod 4)"""
+        enc = _u8(enc)
+        if enc.ndim != 2:
+            raise ValueError("enc must be (n, enc_len)")
+        n, enc_len = enc.shape
+        xy, st = self._outs(out, [(n, 64), (n,)])
+        self._check(self._lib.ellgpu_custom_decode_points(self._ctx, self._cid(curve), n, enc.ctypes.data,
+                                                          enc_len, xy.ctypes.data, st.ctypes.data))
+        return xy, st
+
+    def custom_decode_points_dev(self, curve, enc, out_xy, out_status):
+        n, enc_len = enc.shape
+        self._check(self._lib.ellgpu_custom_decode_points_dev(self._ctx, self._cid(curve), n, enc.data_ptr(),
+                                                              enc_len, out_xy.data_ptr(),
+                                                              out_status.data_ptr(), self._stream()))
+
+    def custom_verify_wire(self, curve, hashes, sigs, pubs, msg_bits=0, out=None, want_err=True):
+        """EC#verify(msg, DER signature, encoded key) per item on a domain id; arguments and
+        (ok, err) as ecdsa_verify_wire.  want_err=False passes no err array -> (ok, None)"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        pubs = _u8(pubs)
+        if isinstance(sigs, tuple):                   # already packed: ((n, stride) uint8, (n,) uint32)
+            der, lens = _u8(sigs[0]), np.ascontiguousarray(sigs[1], np.uint32)
+        else:
+            der, lens = self._pack_records(sigs)
+        if pubs.ndim != 2 or pubs.shape[0] != n or der.shape[0] != n or lens.shape[0] != n:
+            raise ValueError("pubs must be (n, pub_len), sigs n byte strings (or packed records + lengths)")
+        ok, err = self._outs(out, [(n,), (n,)])
+        self._check(self._lib.ellgpu_custom_verify_wire(self._ctx, self._cid(curve), n, hashes.ctypes.data,
+                                                        hash_len, int(msg_bits), der.ctypes.data, der.shape[1],
+                                                        lens.ctypes.data, pubs.ctypes.data, pubs.shape[1],
+                                                        ok.ctypes.data, err.ctypes.data if want_err else None))
+        return ok, (err if want_err else None)
+
+    def custom_verify_wire_dev(self, curve, hashes, der, der_len, pubs, out_ok, out_err=None, msg_bits=0):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_verify_wire_dev(
+            self._ctx, self._cid(curve), n, hashes.data_ptr(), hash_len, int(msg_bits), der.data_ptr(),
+            der.shape[1], der_len.data_ptr(), pubs.data_ptr(), pubs.shape[1], out_ok.data_ptr(),
+            out_err.data_ptr() if out_err is not None else None, self._stream()))
+
     def ecdsa_sign(self, curve, hashes, priv, nonces, canonical=False, msg_bits=0):
         """one pass of EC#sign per item for supplied nonces -> (r, s, recid, ok)"""
         NB = ORDER_BYTES[curve]

@@ -39,12 +39,17 @@
  *           sigToDer(ctx, curve, r, s) -> {der, lens}     (stride = der.length / n)
  *           ecdsaVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)
  *             -> {ok, err};  lens: Buffer of n little-endian uint32
+ *           customDecompress(ctx, curve, x, odd) -> {xy, status}
+ *           customDecodePoints(ctx, curve, enc, encLen) -> {xy, status}
+ *           customVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)
+ *             -> {ok, err}: the same three on a user-defined short curve / domain (ellgpu_custom_*)
  *             offsets: Buffer of n+1 little-endian uint64 byte offsets into msgs
  *           callAsync(op, ctx, curve, hashLen, msgBits, b0, b1, b2, b3) -> Promise
  *             op 0 mulFixed(b0=k) 1 mulVar(k, xy) 2 mulAdd2(k1, p1|null, k2, p2)
  *             3 ecdsaVerify(hash, r, s, pub) 4 x25519(k, x) 5 ecdsaSignDet(hash, priv; i0 = canonical)
  *             6 ecdsaRecover(hash, r, s, recid) 7 ecdsaVerifyWire(hash, der, lens, keys; i0 = der
- *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length); runs on a libuv worker
+ *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length) 9 customVerifyWire (as 7);
+ *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
  *             index.js serialises them.
@@ -111,6 +116,10 @@ static struct {
   int (*sig_to_der)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, size_t, uint32_t*);
   int (*verify_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, size_t,
                      const uint32_t*, const uint8_t*, size_t, uint8_t*, uint8_t*);
+  int (*custom_decompress)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_decode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, size_t, uint8_t*, uint8_t*);
+  int (*custom_verify_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, size_t,
+                            const uint32_t*, const uint8_t*, size_t, uint8_t*, uint8_t*);
 } L;
 
 #define THROW(env, msg) do { napi_throw_error((env), NULL, (msg)); return NULL; } while (0)
@@ -168,6 +177,9 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(sig_from_der, "ellgpu_sig_from_der");
   SYM(sig_to_der, "ellgpu_sig_to_der");
   SYM(verify_wire, "ellgpu_ecdsa_verify_wire");
+  SYM(custom_decompress, "ellgpu_custom_decompress");
+  SYM(custom_decode_points, "ellgpu_custom_decode_points");
+  SYM(custom_verify_wire, "ellgpu_custom_verify_wire");
   L.h = h;
   napi_value t; CHECK(env, napi_get_boolean(env, 1, &t));
   return t;
@@ -519,7 +531,9 @@ static napi_value fn_x25519_derive(napi_env env, napi_callback_info info) {
   return mk_result(env, "x", bx, "status", bst);
 }
 
-static napi_value fn_decompress(napi_env env, napi_callback_info info) {
+/* decompress / customDecompress: the preset form reports ok (1 = point), the user-defined-curve
+ * form a status (0 = point) */
+static napi_value decompress_with(napi_env env, napi_callback_info info, int custom) {
   if (!need_lib(env)) return NULL;
   size_t argc = 4; napi_value argv[4];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -533,9 +547,12 @@ static napi_value fn_decompress(napi_env env, napi_callback_info info) {
   napi_value bxy, bok; void *dxy, *dok;
   CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
   CHECK(env, result_buffer(env, n, &dok, &bok));
-  if (L.decompress(c, curve, n, v, odd, (uint8_t*)dxy, (uint8_t*)dok) != 0) return lib_error(env);
-  return mk_result(env, "xy", bxy, "ok", bok);
+  if ((custom ? L.custom_decompress : L.decompress)(c, curve, n, v, odd, (uint8_t*)dxy, (uint8_t*)dok) != 0)
+    return lib_error(env);
+  return mk_result(env, "xy", bxy, custom ? "status" : "ok", bok);
 }
+static napi_value fn_decompress(napi_env env, napi_callback_info info) { return decompress_with(env, info, 0); }
+static napi_value fn_custom_decompress(napi_env env, napi_callback_info info) { return decompress_with(env, info, 1); }
 
 static napi_value fn_sign(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
@@ -624,7 +641,7 @@ static napi_value fn_recover(napi_env env, napi_callback_info info) {
   return mk_result(env, "xy", bxy, "status", bst);
 }
 
-static napi_value fn_decode_points(napi_env env, napi_callback_info info) {
+static napi_value decode_points_with(napi_env env, napi_callback_info info, int custom) {
   if (!need_lib(env)) return NULL;
   size_t argc = 4; napi_value argv[4];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -640,9 +657,12 @@ static napi_value fn_decode_points(napi_env env, napi_callback_info info) {
   napi_value bxy, bst; void *dxy, *dst;
   CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
   CHECK(env, result_buffer(env, n, &dst, &bst));
-  if (L.decode_points(c, curve, n, enc, (size_t)el, (uint8_t*)dxy, (uint8_t*)dst) != 0) return lib_error(env);
+  if ((custom ? L.custom_decode_points : L.decode_points)(c, curve, n, enc, (size_t)el, (uint8_t*)dxy,
+                                                          (uint8_t*)dst) != 0) return lib_error(env);
   return mk_result(env, "xy", bxy, "status", bst);
 }
+static napi_value fn_decode_points(napi_env env, napi_callback_info info) { return decode_points_with(env, info, 0); }
+static napi_value fn_custom_decode_points(napi_env env, napi_callback_info info) { return decode_points_with(env, info, 1); }
 
 static napi_value fn_encode_points(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
@@ -751,7 +771,7 @@ static napi_value fn_sig_to_der(napi_env env, napi_callback_info info) {
   return mk_result(env, "der", bd, "lens", bl);
 }
 
-static napi_value fn_verify_wire(napi_env env, napi_callback_info info) {
+static napi_value verify_wire_with(napi_env env, napi_callback_info info, int custom) {
   if (!need_lib(env)) return NULL;
   size_t argc = 10; napi_value argv[10];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -772,10 +792,13 @@ static napi_value fn_verify_wire(napi_env env, napi_callback_info info) {
   napi_value bok, berr; void *dok, *derr;
   CHECK(env, result_buffer(env, n, &dok, &bok));
   CHECK(env, result_buffer(env, n, &derr, &berr));
-  if (L.verify_wire(c, curve, n, h, hl, mb, der, (size_t)stride, (const uint32_t*)lens, keys, (size_t)kl,
-                    (uint8_t*)dok, (uint8_t*)derr) != 0) return lib_error(env);
+  if ((custom ? L.custom_verify_wire : L.verify_wire)(c, curve, n, h, hl, mb, der, (size_t)stride,
+                                                      (const uint32_t*)lens, keys, (size_t)kl, (uint8_t*)dok,
+                                                      (uint8_t*)derr) != 0) return lib_error(env);
   return mk_result(env, "ok", bok, "err", berr);
 }
+static napi_value fn_verify_wire(napi_env env, napi_callback_info info) { return verify_wire_with(env, info, 0); }
+static napi_value fn_custom_verify_wire(napi_env env, napi_callback_info info) { return verify_wire_with(env, info, 1); }
 
 static napi_value fn_eddsa_verify(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
@@ -862,6 +885,9 @@ static void job_execute(napi_env env, void* data) {
                                     j->out0, j->out1); break;
     case 7: j->rc = L.verify_wire(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], (size_t)j->i0,
                                   (const uint32_t*)j->in[2], j->in[3], (size_t)j->i1, j->out0, j->out1); break;
+    case 9: j->rc = L.custom_verify_wire(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1],
+                                         (size_t)j->i0, (const uint32_t*)j->in[2], j->in[3], (size_t)j->i1, j->out0,
+                                         j->out1); break;
     default: j->rc = L.decode_points(j->ctx, j->curve, j->n, j->in[0], (size_t)j->i0, j->out0, j->out1); break;
   }
   if (j->rc != 0) {               /* last_error is thread-local: read it on this thread */
@@ -875,9 +901,10 @@ static void job_complete(napi_env env, napi_status status, void* data) {
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
     /* result property names per op, in output order */
-    static const char* const names[9][4] = {
+    static const char* const names[10][4] = {
       {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
-      {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0}};
+      {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
+      {"ok", "err", 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -922,7 +949,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
   j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
   j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > 8 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
+  if (op < 0 || op > 9 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
   int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
@@ -949,7 +976,8 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
     case 6: ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB && len[2] == j->n * NB && len[3] == j->n; break;
-    case 7: ok = hl > 0 && i0 > 0 && i1 > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
+    case 7: case 9:
+            ok = hl > 0 && i0 > 0 && i1 > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * (size_t)i0 && len[2] == j->n * 4 && !((uintptr_t)j->in[2] & 3) &&
                  len[3] == j->n * (size_t)i1; break;
@@ -961,7 +989,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
     free(j);
     THROW(env, "callAsync: buffer length mismatch");
   }
-  j->out0_len = op == 3 || op == 7 ? j->n : op == 4 ? j->n * 32 : op == 5 ? j->n * NB : j->n * 2 * B;
+  j->out0_len = op == 3 || op == 7 || op == 9 ? j->n : op == 4 ? j->n * 32 : op == 5 ? j->n * NB : j->n * 2 * B;
   j->out1_len = op == 5 ? j->n * NB : j->n;
   j->out2_len = op == 5 ? j->n : 0;
   j->out3_len = op == 5 ? j->n : 0;
@@ -994,6 +1022,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"eddsaVerify", fn_eddsa_verify}, {"eddsaSign", fn_eddsa_sign}, {"ecdsaSign", fn_sign}, {"ecdsaRecover", fn_recover}, {"ecdsaSignDet", fn_sign_det},
     {"decodePoints", fn_decode_points}, {"encodePoints", fn_encode_points}, {"validate", fn_validate},
     {"pointAdd", fn_point_add}, {"sigFromDer", fn_sig_from_der}, {"sigToDer", fn_sig_to_der}, {"ecdsaVerifyWire", fn_verify_wire},
+    {"customDecompress", fn_custom_decompress}, {"customDecodePoints", fn_custom_decode_points},
+    {"customVerifyWire", fn_custom_verify_wire},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -267,6 +267,31 @@ Engine.prototype.ecdsaVerifyWireBatch = function ecdsaVerifyWireBatch(curve, o) 
     p.buf, p.stride, p.lens, o.keys, o.keyLen);
 };
 
+// The same three on a user-defined short curve or ECDSA domain (an id from defineShort /
+// defineShortDomain): entry points of their own, because the preset-named ones are documented to
+// refuse such ids and a SEC1 coordinate here is p.byteLength() bytes while x and y stay 32.
+// customDecompressBatch: ShortCurve#pointFromX; xs Buffer(n x 32), odd Buffer(n) ->
+// { xy: Buffer(n x 64), status: Buffer(n) }; status 0 point, 2 'invalid point' (p = 3 mod 4),
+// 3 'Assertion failed' (p = 1 mod 4: bn.js's Tonelli-Shanks loop gives up before pointFromX tests y)
+Engine.prototype.customDecompressBatch = function customDecompressBatch(curve, xs, odd) {
+  this.stats.gpuCalls++; this.stats.gpuItems += odd.length;
+  return this.addon.customDecompress(this.ctx, this._id(curve), xs, odd);
+};
+// customDecodePointBatch: BaseCurve#decodePoint; enc Buffer(n x encLen), encLen = 1 + PL or
+// 1 + 2 PL -> { xy, status } as decodePointBatch (a compressed x without a y: 3 where p = 1 mod 4)
+Engine.prototype.customDecodePointBatch = function customDecodePointBatch(curve, enc, encLen) {
+  this.stats.gpuCalls++; this.stats.gpuItems += enc.length / encLen;
+  return this.addon.customDecodePoints(this.ctx, this._id(curve), enc, encLen);
+};
+// customVerifyWireBatch: EC#verify(msg, derSignature, encodedKey) on a domain id; o and the result
+// as ecdsaVerifyWireBatch
+Engine.prototype.customVerifyWireBatch = function customVerifyWireBatch(curve, o) {
+  var p = packRecords(o.sigs);
+  this.stats.gpuCalls++; this.stats.gpuItems += o.sigs.length;
+  return this.addon.customVerifyWire(this.ctx, this._id(curve), o.hashes, o.hashLen, o.msgBits | 0,
+    p.buf, p.stride, p.lens, o.keys, o.keyLen);
+};
+
 // KeyPair#derive per item (ec/key.js:102-107): priv Buffer(n x B), pub Buffer(n x 2B) ->
 // { x: Buffer(n x B), status: Buffer(n) }; status 0 shared secret, 1 'public point not validated',
 // 2 the product is the point at infinity (the reference's getX throws)
@@ -352,6 +377,10 @@ Engine.prototype.ecdsaRecoverBatchAsync = function(curve, o) {
 Engine.prototype.ecdsaVerifyWireBatchAsync = function(curve, o) {
   var p = packRecords(o.sigs);
   return this._async(7, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
+};
+Engine.prototype.customVerifyWireBatchAsync = function(curve, o) {
+  var p = packRecords(o.sigs);
+  return this._async(9, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
 };
 Engine.prototype.decodePointBatchAsync = function(curve, enc, encLen) {
   return this._async(8, curve, 0, 0, enc, null, null, null, encLen, 0);

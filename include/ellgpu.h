@@ -178,8 +178,9 @@ int ellgpu_ctx_collect(ellgpu_ctx* ctx);
  * same id).  The id is valid for ellgpu_mul_var / _mul_add2 (both points given) / _point_add and
  * their _dev forms (an ECDSA domain, below, adds mul_fixed and verify), with 32-byte scalars and coordinates whatever p's size: Point#mul, mulAdd /
  * jmulAdd and Point#add with the generic-a doubling of JPoint#_dbl / dblp (short.js:802-830,
- * 605-654) on the device.  Every other entry point answers ELLGPU_E_UNSUPPORTED for it (the
- * reference's own JavaScript keeps serving those).  The primality of p is not checked, as the
+ * 605-654) on the device, and for ellgpu_custom_decompress / _custom_decode_points (below).
+ * Every other entry point answers ELLGPU_E_UNSUPPORTED for it (the reference's own JavaScript
+ * keeps serving those).  The primality of p is not checked, as the
  * reference does not check it either -- but field inversion here is Fermat's a^(p-2), so for a
  * composite p results differ from the reference's (its BN#invm is an extended Euclid); callers
  * that cannot vouch for p keep such curves on the reference (the JS layer runs a Miller-Rabin
@@ -212,11 +213,54 @@ int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* 
  *                                  matches x = r - p), x mod n == r otherwise.  out_ok is a strict
  *                                  0 / 1 mask; out_status is 2 for an off-curve key whose r and s
  *                                  are in range, as on the presets.
- * Every other entry point (wire / DER, sign, sign_det, recover, decompress, decode, validate)
- * answers ELLGPU_E_UNSUPPORTED on a domain id; on a plain ellgpu_curve_define_short id, mul_fixed,
- * mul_add2 without p1 and ecdsa_verify stay ELLGPU_E_UNSUPPORTED. */
+ * Every other preset-named entry point (wire / DER, sign, sign_det, recover, decompress, decode,
+ * validate) answers ELLGPU_E_UNSUPPORTED on a domain id; compressed keys, SEC1 encodings and DER
+ * signatures on a domain go through ellgpu_custom_decompress / _custom_decode_points /
+ * _custom_verify_wire below.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
+ * without p1 and ecdsa_verify stay ELLGPU_E_UNSUPPORTED. */
 int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                                      const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve);
+/* Wire formats on user-defined short curves: compressed points, SEC1 encodings and
+ * EC#verify(msg, der, key).  They are entry points of their own because the preset-named ones
+ * (ellgpu_decompress, _decode_points, _ecdsa_verify_wire) are documented to refuse user-defined
+ * ids, and their widths differ: a SEC1 coordinate here is PL = p.byteLength() bytes
+ * (lib/elliptic/curve/base.js:270-293), while coordinates in and out of the engine stay 32 bytes.
+ * The square root is Red#sqrt over the run-time modulus (dist/elliptic.js:7177-7232), on the
+ * device: a^((p+1)/4) where p = 3 (mod 4), Tonelli-Shanks otherwise.  Synchronous like every
+ * call on a user-defined curve; a group runs them on its first member.  ELLGPU_E_ARG for a
+ * preset id, ELLGPU_E_UNSUPPORTED for a user-defined Edwards curve.
+ * ellgpu_custom_decompress: ShortCurve#pointFromX (lib/elliptic/curve/short.js:187-204) on a
+ *   plain or domain id.  x: n x 32 bytes big-endian, reduced mod p as toRed does; odd: n bytes.
+ *   out_status 0 = point (out_xy = x || y, 64 bytes); 2 = 'invalid point' (x has no y,
+ *   p = 3 mod 4); 3 = 'Assertion failed' (x has no y, p = 1 mod 4: bn.js's Tonelli-Shanks loop
+ *   stops at assert(i < m), dist/elliptic.js:7217-7229, before pointFromX can test y).  out_xy is
+ *   zeroed unless 0.
+ * ellgpu_custom_decode_points: BaseCurve#decodePoint (base.js:270-293) on a plain or domain id:
+ *   encodings of enc_len = 1 + PL (02 / 03) or 1 + 2 PL (04 / 06 / 07) bytes -> x || y of 32
+ *   bytes each.  out_status as for ellgpu_decode_points (any other enc_len > 0 gives 1 on every
+ *   item), except that a compressed x without a y is 3 where p = 1 (mod 4), as above.
+ *   Uncompressed points are not tested against the curve equation, as in the reference.
+ * ellgpu_custom_verify_wire: EC#verify(msg, der, key) (lib/elliptic/ec/index.js:188-229, with
+ *   keyFromPublic -> decodePoint and new Signature(der), ec/signature.js:83-147) on a DOMAIN id
+ *   (ELLGPU_E_UNSUPPORTED on a plain one).  Keys as for ellgpu_custom_decode_points, pub_len
+ *   bytes each; DER records, out_ok and out_err as for ellgpu_ecdsa_verify_wire (r, s wider than
+ *   32 bytes or >= n: verdict 0, err 0); hash / hash_len / msg_bits as for ellgpu_ecdsa_verify
+ *   on a domain.  Decoding, parsing and the verify run on the device. */
+int ellgpu_custom_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* x, const uint8_t* odd,
+                             uint8_t* out_xy, uint8_t* out_status);
+int ellgpu_custom_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* x, const uint8_t* odd,
+                                 uint8_t* out_xy, uint8_t* out_status, void* stream);
+int ellgpu_custom_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                uint8_t* out_xy, uint8_t* out_status);
+int ellgpu_custom_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                    uint8_t* out_xy, uint8_t* out_status, void* stream);
+int ellgpu_custom_verify_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                              int msg_bits, const uint8_t* der, size_t der_stride, const uint32_t* der_len,
+                              const uint8_t* pub_enc, size_t pub_len, uint8_t* out_ok, uint8_t* out_err);
+int ellgpu_custom_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                                  int msg_bits, const uint8_t* der, size_t der_stride,
+                                  const uint32_t* der_len, const uint8_t* pub_enc, size_t pub_len,
+                                  uint8_t* out_ok, uint8_t* out_err, void* stream);
 /* User-defined (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) over an odd prime
  * p < 2^256 -- `new elliptic.curve.edwards({p, a, c: 1, d, ...})` (lib/elliptic/curve/edwards.js:
  * 11-31) with parameters that are not ed25519's.  Same id space, widths (32 bytes) and entry

@@ -8,7 +8,14 @@ Developer tool (GPU box).
 The signatures are drawn at random with 1 <= r, s < n over keys on the curve, so that every item
 runs the whole verify (the work does not depend on the verdict).
 
-    [ELLGPU_LIB=variant.so] python tools/bench_custom_ecdsa.py [log2 n ...]   (default: 18 20)"""
+    [ELLGPU_LIB=variant.so] python tools/bench_custom_ecdsa.py [log2 n ...]   (default: 18 20)
+
+--wire: the same signatures as DER records under compressed SEC1 keys through
+custom_verify_wire_dev, next to the raw-form ecdsa_verify_dev over the decoded rows, in one run --
+on brainpoolP256r1 (square root: one exponentiation) and secp224k1 (Tonelli-Shanks, p - 1 = q 2^2);
+and the key decoding alone (custom_decode_points_dev), which is where the square root is.
+
+    python tools/bench_custom_ecdsa.py --wire [log2 n ...]                     (default: 18)"""
 import json
 import os
 import sys
@@ -69,10 +76,68 @@ def run(ctx, spec, n):
     return out
 
 
+def run_wire(ctx, spec, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_domain_checks as CD
+    import custom_wire_checks as CW
+    cid = CD.define(ctx, spec)
+    nn = CD.I(spec["n"])
+    pl = (CD.I(spec["p"]).bit_length() + 7) // 8
+    keep = nn.bit_length() - 1                      # scalars below 2^(bitLength(n) - 1) < n
+    def below_n(tag):
+        a = bench.xof("custom-wire:%s:%s" % (spec["name"], tag), n * 32).reshape(n, 32).copy()
+        a[:, :32 - (keep + 7) // 8] = 0
+        if keep % 8:
+            a[:, 32 - (keep + 7) // 8] &= (1 << (keep % 8)) - 1
+        a[:, 31] |= 1
+        return a
+    d, r, s = below_n("d"), below_n("r"), below_n("s")
+    q, inf = ctx.mul_fixed(cid, d)
+    assert not inf.any()
+    h = bench.xof("custom-wire:h", n * 32).reshape(n, 32).copy()
+    keys = np.concatenate([(2 + (q[:, 63] & 1))[:, None], q[:, 32 - pl:32]], axis=1).astype(np.uint8)
+    sigs = [CW.der_sig(int.from_bytes(bytes(r[i]), "big"), int.from_bytes(bytes(s[i]), "big")) for i in range(n)]
+    der, lens = ctx._pack_records(sigs)
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    dh, dr, ds, dq, dk, dder = t(h), t(r), t(s), t(q), t(keys), t(der)
+    dlens = t(lens.view(np.int32))
+    ok = torch.zeros(n, dtype=torch.uint8, device=dev)
+    ok2 = torch.zeros(n, dtype=torch.uint8, device=dev)
+    err = torch.zeros(n, dtype=torch.uint8, device=dev)
+    dxy = torch.zeros(n, 64, dtype=torch.uint8, device=dev)
+    dst = torch.zeros(n, dtype=torch.uint8, device=dev)
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": spec["name"], "n": n,
+           "p_mod_4": CD.I(spec["p"]) % 4}
+    for name, fn in (("raw_verify", lambda: ctx.ecdsa_verify_dev(cid, dh, dr, ds, dq, ok)),
+                     ("wire_verify", lambda: ctx.custom_verify_wire_dev(cid, dh, dder, dlens, dk, ok2, out_err=err)),
+                     ("decode_keys", lambda: ctx.custom_decode_points_dev(cid, dk, dxy, dst))):
+        ms = timed(fn)
+        out[name + "_ms"] = round(ms, 3)
+        out[name + "_M_per_s"] = round(n / ms / 1e3, 2)
+    # the two forms answer alike, no key failed to decode, and the keys came back whole
+    assert torch.equal(ok, ok2) and not err.any().item() and not dst.any().item() and torch.equal(dxy, dq)
+    out["wire_over_raw"] = round(out["wire_verify_ms"] / out["raw_verify_ms"], 4)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
     import custom_domain_checks as CD
+    if sys.argv[1:2] == ["--wire"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            for name in ("brainpoolP256r1", "secp224k1"):
+                spec = next(c for c in CD.curves() if c["name"] == name)
+                for lg in [int(a) for a in sys.argv[2:]] or [18]:
+                    print(json.dumps(run_wire(ctx, spec, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
     spec = next(c for c in CD.curves() if c["name"] == "brainpoolP256r1")
     torch.zeros(1, device="cuda:0")          # the HIP runtime initialised by torch first, as in bench.py
     ctx = elliptic_amd.Context(0)
