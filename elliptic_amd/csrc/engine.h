@@ -23,6 +23,7 @@
 #include "edwards.h"
 #include "edcustom.h"
 #include "mont.h"
+#include "rt_define.h"
 #include "work.h"
 #include "coop_ed.h"
 
@@ -85,8 +86,6 @@
 #endif
 
 namespace ell {
-
-enum { E_OK = 0, E_NODEVICE = -1, E_ARG = -2, E_HIP = -3, E_NOMEM = -4, E_UNSUPPORTED = -5 };
 
 // ---- functors (one per kernel) ------------------------------------------------
 // WIDE: the small-grid tuning of the secp256k1 ladder (see FnEcdsaMain)
@@ -337,19 +336,40 @@ struct FnEcdsaJoin {
 // one unit = one part of one item on a wave of its own, its field elements spread over a 16-lane
 // row -- 2.2 x fewer instructions on the item's critical path.  Launched through BK::launch_coop
 // (k_run_coop: one unit per workgroup) for batches of at most Tuning::coop_grid items; the join
-// kernels are the one-lane ones.  secp256k1 only.
-struct FnEcdsaPartsC {
-  static constexpr const char* NAME = "ecdsa_parts_c";
+// kernels are the one-lane ones.
+// PR: the same parts with ONE ITEM PER ROW of the wave (coop.h FpK256R, coop_work.h CoopK256R): four
+// items per unit, for batches between Tuning::row_from and Tuning::row_grid -- too many for a wave
+// per part (that layer holds 1 365 verifies at four waves per SIMD), too few for the
+// one-item-per-lane kernels, whose chain is 4.4x longer (one 128-bit ladder: 573 us on a lone
+// one-lane wave, 130 us on the row layer; 4 096 verifies used 192 of the 1 024 SIMDs).
+// Unit u of a part takes items 4 u .. 4 u + 3; rows past the end redo the last item.
+ELL_HD size_t row_item(size_t group, int row, size_t n) {
+  const size_t i = group * 4 + (size_t)row;
+  return i < n ? i : n - 1;
+}
+// secp256k1's: the two half ladders and the comb of every item
+template <bool PR>
+struct FnEcdsaPartsK256 {
+  static constexpr const char* NAME = PR ? "ecdsa_parts_r" : "ecdsa_parts_c";
   typedef Work<CvSecp256k1> W;
-  static constexpr int DS_PER_LANE = CoopK256::E::NW;
-  static constexpr int ROW_BYTES = CoopK256::ROW_BYTES;
+  typedef CoopK256T<PR> CW;
+  static constexpr int DS_PER_LANE = CW::E::NW;
+  static constexpr int ROW_BYTES = CW::ROW_BYTES;
   size_t n; const u32* u12; const typename W::A* comb; const typename W::VT* tbl; u32* jac;
+  ELL_HD void item(int part, size_t i, const DigitStore& ds, u32* out, void* row_mem) const {
+    if (part == 2) CW::ecdsa_fixed(i, n, u12, comb, out);
+    else CW::ecdsa_half(i, n, part, u12, tbl, ds, out, row_mem);
+  }
   ELL_HD void operator()(size_t unit, const DigitStore& ds, void* row_mem) const {
-    const int part = (int)(unit / n);
-    const size_t i = unit - (size_t)part * n;
+    const size_t groups = PR ? (n + 3) / 4 : n;              // units per part
+    const int part = (int)(unit / groups);
+    const size_t g = unit - (size_t)part * groups;
     u32* out = jac + (size_t)part * 3 * W::NS * n;
-    if (part == 2) CoopK256::ecdsa_fixed(i, n, u12, comb, out);
-    else CoopK256::ecdsa_half(i, n, part, u12, tbl, ds, out, row_mem);
+    if constexpr (PR) {
+      ELL_FOR_ROWS(row) item(part, row_item(g, row, n), ds, out, row_mem);
+    } else {
+      item(part, g, ds, out, row_mem);
+    }
   }
 };
 // ... and in front of them, ONE launch: unit i < n runs the scalar-field prep of item i (the
@@ -369,53 +389,10 @@ struct FnEcdsaPrepTableC {
     else CoopK256::ecdsa_table(unit - n, pub, tbl, row_mem);
   }
 };
-struct FnMulPartsC {
-  static constexpr const char* NAME = "mul_parts_c";
-  typedef Work<CvSecp256k1> W;
-  static constexpr int DS_PER_LANE = CoopK256::E::NW;
-  static constexpr int ROW_BYTES = CoopK256::ROW_BYTES;
-  // kg != null: k*P + kg*G -- the units of a third range run the comb of kg
-  size_t n; const u8* k; const u8* xy; u32* jac; const u8* kg; const typename W::A* comb;
-  ELL_HD void operator()(size_t unit, const DigitStore& ds, void* row_mem) const {
-    const int part = (int)(unit / n);
-    const size_t i = unit - (size_t)part * n;
-    u32* out = jac + (size_t)part * 3 * W::NS * n;
-    if (part == 2) CoopK256::mul_fixed_part(i, n, kg, comb, out);
-    else CoopK256::mul_half(i, n, part, k, xy, ds, out, row_mem);
-  }
-};
-
-// The same parts with ONE ITEM PER ROW of the wave (coop.h FpK256R, coop_work.h CoopK256R): four
-// items per unit, for batches between Tuning::coop_grid and Tuning::row_grid -- too many for a wave
-// per part (that layer holds 1 365 verifies at four waves per SIMD), too few for the
-// one-item-per-lane kernels, whose chain is 4.4x longer (one 128-bit ladder: 573 us on a lone
-// one-lane wave, 130 us on the row layer; 4 096 verifies used 192 of the 1 024 SIMDs).
-// Unit u of a part takes items 4 u .. 4 u + 3; rows past the end redo the last item.
-ELL_HD size_t row_item(size_t group, int row, size_t n) {
-  const size_t i = group * 4 + (size_t)row;
-  return i < n ? i : n - 1;
-}
-struct FnEcdsaPartsR {
-  static constexpr const char* NAME = "ecdsa_parts_r";
-  typedef Work<CvSecp256k1> W;
-  static constexpr int DS_PER_LANE = CoopK256R::E::NW;
-  static constexpr int ROW_BYTES = CoopK256R::ROW_BYTES;
-  size_t n; const u32* u12; const typename W::A* comb; const typename W::VT* tbl; u32* jac;
-  ELL_HD void operator()(size_t unit, const DigitStore& ds, void* row_mem) const {
-    const size_t groups = (n + 3) / 4;
-    const int part = (int)(unit / groups);
-    const size_t g = unit - (size_t)part * groups;
-    u32* out = jac + (size_t)part * 3 * W::NS * n;
-    ELL_FOR_ROWS(row) {
-      const size_t i = row_item(g, row, n);
-      if (part == 2) CoopK256R::ecdsa_fixed(i, n, u12, comb, out);
-      else CoopK256R::ecdsa_half(i, n, part, u12, tbl, ds, out, row_mem);
-    }
-  }
-};
-// in front of them, ONE launch: the first units run the scalar-field prep one item per LANE (the
-// one-lane code: 64 items per wave, one inversion each -- the chain counts), the others build the
-// window tables of the keys four per wave
+// ... one item per row: the first units run the scalar-field prep one item per LANE (the one-lane
+// code: 64 items per wave, one inversion each -- the chain counts), the others build the window
+// tables of the keys four per wave.  (Its prep half is per lane, FnEcdsaPrepTableC's per wave: the
+// two stay apart.)
 struct FnEcdsaPrepTableR {
   static constexpr const char* NAME = "ecdsa_prep_table_r";
   typedef Work<CvSecp256k1> W;
@@ -434,21 +411,28 @@ struct FnEcdsaPrepTableR {
     }
   }
 };
-struct FnMulPartsR {
-  static constexpr const char* NAME = "mul_parts_r";
+template <bool PR>
+struct FnMulPartsK256 {
+  static constexpr const char* NAME = PR ? "mul_parts_r" : "mul_parts_c";
   typedef Work<CvSecp256k1> W;
-  static constexpr int DS_PER_LANE = CoopK256R::E::NW;
-  static constexpr int ROW_BYTES = CoopK256R::ROW_BYTES;
+  typedef CoopK256T<PR> CW;
+  static constexpr int DS_PER_LANE = CW::E::NW;
+  static constexpr int ROW_BYTES = CW::ROW_BYTES;
+  // kg != null: k*P + kg*G -- the units of a third range run the comb of kg
   size_t n; const u8* k; const u8* xy; u32* jac; const u8* kg; const typename W::A* comb;
+  ELL_HD void item(int part, size_t i, const DigitStore& ds, u32* out, void* row_mem) const {
+    if (part == 2) CW::mul_fixed_part(i, n, kg, comb, out);
+    else CW::mul_half(i, n, part, k, xy, ds, out, row_mem);
+  }
   ELL_HD void operator()(size_t unit, const DigitStore& ds, void* row_mem) const {
-    const size_t groups = (n + 3) / 4;
+    const size_t groups = PR ? (n + 3) / 4 : n;              // units per part
     const int part = (int)(unit / groups);
     const size_t g = unit - (size_t)part * groups;
     u32* out = jac + (size_t)part * 3 * W::NS * n;
-    ELL_FOR_ROWS(row) {
-      const size_t i = row_item(g, row, n);
-      if (part == 2) CoopK256R::mul_fixed_part(i, n, kg, comb, out);
-      else CoopK256R::mul_half(i, n, part, k, xy, ds, out, row_mem);
+    if constexpr (PR) {
+      ELL_FOR_ROWS(row) item(part, row_item(g, row, n), ds, out, row_mem);
+    } else {
+      item(part, g, ds, out, row_mem);
     }
   }
 };
@@ -1119,11 +1103,8 @@ class Engine {
     e = getenv("ELLGPU_NORM_K");
     tune_.norm_k = e ? atoi(e) : 0;
   }
-  size_t small_grid() const { return tune_.small_grid; }
   bool split_small_verify() const { return tune_.split_verify; }
-  size_t parted_grid() const { return tune_.parted_grid; }
   size_t coop_grid() const { return CoopK256::AVAILABLE ? tune_.coop_grid : 0; }
-  size_t row_grid() const { return CoopK256::AVAILABLE ? tune_.row_grid : 0; }
   // ... of curve CV: p384 / p521 (the wide layer, coop_wide.h) have a threshold of their own
   // (ELLGPU_WIDE_GRID; default: coop_grid)
   template <class CV>
@@ -1131,9 +1112,37 @@ class Engine {
     if constexpr (!CV::ENDO && CoopConsts<CV>::WIDE) return tune_.wide_grid;
     else return coop_grid();
   }
-  // do the parts of a secp256k1 verify / Point#mul of n items run one item per row?  (else one item per
-  // wave up to coop_grid, one item per lane above)
-  bool rows_for(size_t n) const { return CoopK256::AVAILABLE && n > tune_.row_from && n <= tune_.row_grid; }
+  // The kernel form of a batch of n items on the endomorphism curve (secp256k1): verify, Point#mul
+  // and k1*G + k2*P switch on it (ecdsa_chunk, mul_var_chunk, mul_add_g_chunk).  The one place
+  // where the small-batch thresholds meet:
+  //   FULL        above small_grid: the full-grid tuning, one item per lane
+  //   WIDE        above parted_grid: the register-rich small-grid tuning, one item per lane
+  //   PARTS_*     the parted form: the halves (and the comb) of an item as parts of their own, then a join --
+  //   PARTS_ROW     row_from < n <= row_grid: one item per row of a wave, four items per unit
+  //   PARTS_WAVE    else up to coop_grid: a wave per part
+  //   PARTS_LANE    else a lane per part
+  // Every other curve type is FULL here: the row-layer gates of the NIST curves, sign, mul_fixed,
+  // decompress, recover and EdDSA are their own (coop_grid_of<CV>() / coop_grid() alone).
+  enum class Form { FULL, WIDE, PARTS_LANE, PARTS_ROW, PARTS_WAVE };
+  template <class CV>
+  Form form_for(size_t n) const {
+    if constexpr (CV::ENDO && Work<CV>::L <= 8) {
+      if (n > tune_.small_grid) return Form::FULL;
+      if (n > tune_.parted_grid) return Form::WIDE;
+      if (CoopK256::AVAILABLE && n > tune_.row_from && n <= tune_.row_grid) return Form::PARTS_ROW;
+      return n <= coop_grid() ? Form::PARTS_WAVE : Form::PARTS_LANE;
+    }
+    return Form::FULL;
+  }
+  static bool parted(Form f) { return f != Form::FULL && f != Form::WIDE; }
+  // threads (PARTS_LANE: whole workgroups per part but the last) or units of the launch that runs
+  // `parts` parts of each of n items
+  static size_t part_pad(size_t n) { return (n + 127) & ~(size_t)127; }
+  static size_t part_units(Form form, size_t n, size_t parts) {
+    if (form == Form::PARTS_WAVE) return parts * n;
+    if (form == Form::PARTS_ROW) return parts * ((n + 3) / 4);
+    return (parts - 1) * part_pad(n) + n;
+  }
   // window width of the curve's fixed-base table in use (0 = not built; ellgpu_ctx_comb_bits)
   int comb_bits(int curve) const {
     if (curve < 0 || curve >= CURVE_COUNT || !comb_[curve]) return 0;
@@ -1304,155 +1313,7 @@ class Engine {
   // b any residues.  Registers the curve under an id >= CURVE_CUSTOM0 of this context; Point#mul,
   // mulAdd / jmulAdd and Point#add then run on the device through the generic-a doubling
   // (ShortOps::dbl, A_KIND 1) and a Montgomery field whose modulus is a kernel-time constant.
-  // modulus-dependent constants of a parameter block
-  int rt_field_init(RtField& f, const u8* p_be) {
-    memset(&f, 0, sizeof(f));
-    load_be<8>(f.p, p_be, 32);
-    if (!(f.p[0] & 1u)) return fail(E_ARG, "user-defined curve: the modulus must be odd");
-    bool small = true;
-    for (int i = 1; i < 8; i++) small = small && f.p[i] == 0;
-    if (small && f.p[0] < 5) return fail(E_ARG, "user-defined curve: the modulus must be a prime > 3");
-    u32 inv = 1;                                          // p^-1 mod 2^32 (Newton)
-    for (int i = 0; i < 5; i++) inv *= 2u - f.p[0] * inv;
-    f.n0 = 0u - inv;
-    u32 one[8];
-    bn_zero<8>(one);
-    one[0] = 1;
-    rt_to_mont(f, f.one, one);
-    bn_copy<8>(f.r2, f.one);
-    rt_times_r(f, f.r2);
-    u32 two[8];
-    bn_zero<8>(two);
-    two[0] = 2;
-    bn_sub<8>(f.pm2, f.p, two);
-    return E_OK;
-  }
-  // Red#sqrt's constants of a block's modulus (fp_rt.h) and p.byteLength().  Deterministic: z is
-  // the LEAST quadratic non-residue (Euler's criterion, candidates 2 .. 255), so that the same
-  // parameters always give the same block (register_custom compares blocks).  A modulus without
-  // such a z is no prime; its block gets c = 0 and its roots are outside the documented domain,
-  // like its inverses.
-  static void rt_sqrt_init(RtField& f) {
-    int pb = 256;
-    while (pb > 0 && !((f.p[(pb - 1) >> 5] >> ((pb - 1) & 31)) & 1u)) pb--;
-    f.pbytes = (u32)((pb + 7) / 8);
-    auto shr = [](u32 (&x)[8], int k) {
-      for (int i = 0; i < 8; i++) x[i] = (x[i] >> k) | (i + 1 < 8 ? x[i + 1] << (32 - k) : 0u);
-    };
-    u32 one[8];
-    bn_zero<8>(one);
-    one[0] = 1;
-    bn_copy<8>(f.sqrt_e, f.p);
-    if ((f.p[0] & 3u) == 3u) {
-      f.sqrt_kind = 0;
-      f.sqrt_s = 1;
-      shr(f.sqrt_e, 2);                                   // (p + 1) / 4 = (p >> 2) + 1
-      bn_add<8>(f.sqrt_e, f.sqrt_e, one);
-    } else {
-      f.sqrt_kind = 1;
-      u32 q[8], half[8], pm1[8];
-      bn_sub<8>(pm1, f.p, one);
-      bn_copy<8>(q, pm1);
-      f.sqrt_s = 0;
-      while (!(q[0] & 1u)) { shr(q, 1); f.sqrt_s++; }
-      bn_copy<8>(f.sqrt_e, q);
-      shr(f.sqrt_e, 1);                                   // (q - 1) / 2
-      bn_copy<8>(half, pm1);
-      shr(half, 1);
-      for (u32 z = 2; z < 256; z++) {
-        u32 zz[8], t[8];
-        bn_zero<8>(zz);
-        zz[0] = z;
-        if (bn_geq<8>(zz, f.p)) break;
-        mod_pow(f.p, t, zz, half);
-        if (!bn_eq<8>(t, pm1)) continue;
-        mod_pow(f.p, t, zz, q);
-        mod_to_mont(f.p, f.sqrt_c, t);
-        break;
-      }
-    }
-    int eb = 256;
-    while (eb > 0 && !((f.sqrt_e[(eb - 1) >> 5] >> ((eb - 1) & 31)) & 1u)) eb--;
-    f.sqrt_ebits = (u32)eb;
-  }
-  static void rt_times_r(const RtField& f, u32 (&r)[8]) { mod_times_r(f.p, r); }
-  static void rt_to_mont(const RtField& f, u32 (&out)[8], const u32 (&x)[8]) { mod_to_mont(f.p, out, x); }
-  // host arithmetic modulo any odd m < 2^256, bit by bit (a definition is rare; these are not hot)
-  static void mod_times_r(const u32 (&m)[8], u32 (&r)[8]) {        // r * 2^256 mod m, r < m
-    for (int i = 0; i < 256; i++) {
-      u32 t[8];
-      mod_add<8>(t, r, r, m);
-      bn_copy<8>(r, t);
-    }
-  }
-  // out = x mod m for any x < 2^256
-  static void mod_reduce(const u32 (&m)[8], u32 (&out)[8], const u32 (&x)[8]) {
-    u32 r[8];
-    bn_zero<8>(r);
-    for (int i = 255; i >= 0; i--) {
-      u32 t[8];
-      mod_add<8>(t, r, r, m);
-      bn_copy<8>(r, t);
-      if ((x[i >> 5] >> (i & 31)) & 1u) {
-        u32 o[8];
-        bn_zero<8>(o);
-        o[0] = 1;
-        mod_add<8>(t, r, o, m);
-        bn_copy<8>(r, t);
-      }
-    }
-    bn_copy<8>(out, r);
-  }
-  // out = x * 2^256 mod m for any x < 2^256 (reduced bit by bit first)
-  static void mod_to_mont(const u32 (&m)[8], u32 (&out)[8], const u32 (&x)[8]) {
-    u32 r[8];
-    mod_reduce(m, r, x);
-    mod_times_r(m, r);
-    bn_copy<8>(out, r);
-  }
-  // out = a * b mod m, a and b < m
-  static void mod_mul(const u32 (&m)[8], u32 (&out)[8], const u32 (&a)[8], const u32 (&b)[8]) {
-    u32 r[8];
-    bn_zero<8>(r);
-    for (int i = 255; i >= 0; i--) {
-      u32 t[8];
-      mod_add<8>(t, r, r, m);
-      bn_copy<8>(r, t);
-      if ((b[i >> 5] >> (i & 31)) & 1u) {
-        mod_add<8>(t, r, a, m);
-        bn_copy<8>(r, t);
-      }
-    }
-    bn_copy<8>(out, r);
-  }
-  // out = a^e mod m, a < m
-  static void mod_pow(const u32 (&m)[8], u32 (&out)[8], const u32 (&a)[8], const u32 (&e)[8]) {
-    u32 r[8], o[8];
-    bn_zero<8>(o);
-    o[0] = 1;
-    mod_reduce(m, r, o);
-    for (int i = 255; i >= 0; i--) {
-      mod_mul(m, r, r, r);
-      if ((e[i >> 5] >> (i & 31)) & 1u) mod_mul(m, r, r, a);
-    }
-    bn_copy<8>(out, r);
-  }
-  // the Montgomery constants of a modulus m: -m^-1 mod 2^32, R mod m, R^2 mod m, m - 2
-  static void mont_consts(const u32 (&m)[8], u32& n0, u32 (&one)[8], u32 (&r2)[8], u32 (&mm2)[8]) {
-    u32 inv = 1;                                          // m^-1 mod 2^32 (Newton)
-    for (int i = 0; i < 5; i++) inv *= 2u - m[0] * inv;
-    n0 = 0u - inv;
-    u32 o[8];
-    bn_zero<8>(o);
-    o[0] = 1;
-    mod_to_mont(m, one, o);
-    bn_copy<8>(r2, one);
-    mod_times_r(m, r2);
-    u32 two[8];
-    bn_zero<8>(two);
-    two[0] = 2;
-    bn_sub<8>(mm2, m, two);
-  }
+  // The parameter block is built by rt_define.h (host arithmetic, no engine) and registered here.
   int register_custom(const RtField& f, int* out_curve) {
     for (size_t i = 0; i < custom_.size(); i++)
       if (memcmp(&custom_[i], &f, sizeof(f)) == 0) { *out_curve = CURVE_CUSTOM0 + (int)i; return E_OK; }
@@ -1462,107 +1323,21 @@ class Engine {
     *out_curve = CURVE_CUSTOM0 + (int)custom_.size() - 1;
     return E_OK;
   }
-  // parameter block of a user-defined curve (edwards = 0: short Weierstrass, b; 1: Edwards, d)
-  int build_custom(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be, RtField& f) {
-    if (!p_be || !a_be || !bd_be) return fail(E_ARG, "null pointer");
-    int rc = rt_field_init(f, p_be);
-    if (rc) return rc;
-    u32 a[8], b[8];
-    load_be<8>(a, a_be, 32);
-    load_be<8>(b, bd_be, 32);
-    rt_to_mont(f, f.a_m, a);
-    if (!edwards) {
-      rt_to_mont(f, f.b_m, b);
-      u32 three[8], m3[8];
-      bn_zero<8>(three);
-      three[0] = 3;
-      bn_sub<8>(m3, f.p, three);
-      rt_to_mont(f, m3, m3);
-      f.a_kind = bn_is_zero<8>(f.a_m) ? 0u : (bn_eq<8>(f.a_m, m3) ? 3u : 1u);
-      f.kind = 0;
-      rt_sqrt_init(f);
-    } else {
-      rt_to_mont(f, f.d_m, b);
-      if (bn_is_zero<8>(f.a_m) || bn_is_zero<8>(f.d_m) || bn_eq<8>(f.a_m, f.d_m))
-        return fail(E_ARG, "user-defined Edwards curve: a and d must be non-zero and distinct");
-      f.kind = 1;
-    }
-    return E_OK;
+  // a built block -> its id, a refusal -> fail()
+  int define(const RtStatus& st, const RtField& f, int* out_curve) {
+    return st.code ? fail(st.code, st.msg) : register_custom(f, out_curve);
   }
   int define_short(const u8* p_be, const u8* a_be, const u8* b_be, int* out_curve) {
     if (!out_curve) return fail(E_ARG, "null pointer");
     RtField f;
-    int rc = build_custom(0, p_be, a_be, b_be, f);
-    return rc ? rc : register_custom(f, out_curve);
+    return define(rt_build_custom(0, p_be, a_be, b_be, f), f, out_curve);
   }
-  // An ECDSA domain on a user-defined short curve (ellgpu_curve_define_short_domain): the curve's
-  // block plus the order n and the generator G -- EC#verify, k*G and mulAdd with G on the device.
-  // Refused: n even or < 3, G not on the curve (coordinates >= p included), 4a^3 + 27b^2 = 0.
-  // n's primality is not checked (s^-1 is Fermat's s^(n-2) here).
-  int build_domain(const u8* p_be, const u8* a_be, const u8* b_be, const u8* n_be, const u8* gx_be,
-                   const u8* gy_be, RtField& f) {
-    if (!n_be || !gx_be || !gy_be) return fail(E_ARG, "null pointer");
-    int rc = build_custom(0, p_be, a_be, b_be, f);
-    if (rc) return rc;
-    u32 a[8], b[8], n[8], gx[8], gy[8];
-    load_be<8>(a, a_be, 32);
-    load_be<8>(b, b_be, 32);
-    mod_reduce(f.p, a, a);
-    mod_reduce(f.p, b, b);
-    load_be<8>(n, n_be, 32);
-    load_be<8>(gx, gx_be, 32);
-    load_be<8>(gy, gy_be, 32);
-    bool small = true;
-    for (int i = 1; i < 8; i++) small = small && n[i] == 0;
-    if (!(n[0] & 1u) || (small && n[0] < 3)) return fail(E_ARG, "ECDSA domain: the order must be odd and >= 3");
-    // 4 a^3 + 27 b^2 != 0 (mod p): a curve, not a singular cubic
-    u32 t[8], u[8], k[8];
-    mod_mul(f.p, t, a, a);
-    mod_mul(f.p, t, t, a);
-    bn_zero<8>(k);
-    k[0] = 4;
-    mod_reduce(f.p, k, k);
-    mod_mul(f.p, t, t, k);
-    mod_mul(f.p, u, b, b);
-    bn_zero<8>(k);
-    k[0] = 27;
-    mod_reduce(f.p, k, k);
-    mod_mul(f.p, u, u, k);
-    mod_add<8>(k, t, u, f.p);
-    if (bn_is_zero<8>(k)) return fail(E_ARG, "ECDSA domain: singular curve (4a^3 + 27b^2 = 0 mod p)");
-    // G on the curve: y^2 == x^3 + a x + b, with x, y < p
-    if (bn_geq<8>(gx, f.p) || bn_geq<8>(gy, f.p)) return fail(E_ARG, "ECDSA domain: G is not on the curve");
-    mod_mul(f.p, t, gx, gx);
-    mod_add<8>(t, t, a, f.p);
-    mod_mul(f.p, t, t, gx);
-    mod_add<8>(t, t, b, f.p);
-    mod_mul(f.p, u, gy, gy);
-    if (!bn_eq<8>(t, u)) return fail(E_ARG, "ECDSA domain: G is not on the curve");
-    f.domain = 1;
-    bn_copy<8>(f.n, n);
-    mont_consts(n, f.nn0, f.n_one, f.n_r2, f.nm2);
-    int nb = 256;
-    while (nb > 0 && !((n[(nb - 1) >> 5] >> ((nb - 1) & 31)) & 1u)) nb--;
-    f.nbits = (u32)nb;
-    mod_to_mont(f.p, f.n_p, n);
-    // floor(p / n), as far as 101 (base.js:33-40: the Maxwell trick for <= 100)
-    u32 q = 0, rem[8];
-    bn_copy<8>(rem, f.p);
-    while (q <= 100 && bn_geq<8>(rem, n)) {
-      bn_sub<8>(rem, rem, n);
-      q++;
-    }
-    f.ncand = q <= 100 ? q : RT_NO_MAXWELL;
-    bn_copy<8>(f.gx, gx);
-    bn_copy<8>(f.gy, gy);
-    return E_OK;
-  }
+  // An ECDSA domain on a user-defined short curve: EC#verify, k*G and mulAdd with G on the device
   int define_short_domain(const u8* p_be, const u8* a_be, const u8* b_be, const u8* n_be, const u8* gx_be,
                           const u8* gy_be, int* out_curve) {
     if (!out_curve) return fail(E_ARG, "null pointer");
     RtField f;
-    int rc = build_domain(p_be, a_be, b_be, n_be, gx_be, gy_be, f);
-    return rc ? rc : register_custom(f, out_curve);
+    return define(rt_build_domain(p_be, a_be, b_be, n_be, gx_be, gy_be, f), f, out_curve);
   }
   // `new elliptic.curve.edwards({p, a, c: 1, d})` (edwards.js:11-31) with parameters that are not
   // ed25519's: a x^2 + y^2 = 1 + d x^2 y^2 over an odd prime p < 2^256; Point#mul, mulAdd and
@@ -1570,8 +1345,7 @@ class Engine {
   int define_edwards(const u8* p_be, const u8* a_be, const u8* d_be, int* out_curve) {
     if (!out_curve) return fail(E_ARG, "null pointer");
     RtField f;
-    int rc = build_custom(1, p_be, a_be, d_be, f);
-    return rc ? rc : register_custom(f, out_curve);
+    return define(rt_build_custom(1, p_be, a_be, d_be, f), f, out_curve);
   }
   // the id a definition WOULD get (the existing one for parameters already registered, else the
   // next free one), -1 when the table is full; registers nothing.  Invalid parameters report the
@@ -1580,9 +1354,7 @@ class Engine {
   int custom_slot_for(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be,
                       const u8* const* dom = nullptr) {
     RtField f;
-    std::string keep = err;
-    int rc = dom ? build_domain(p_be, a_be, bd_be, dom[0], dom[1], dom[2], f) : build_custom(edwards, p_be, a_be, bd_be, f);
-    err = keep;
+    const int rc = (dom ? rt_build_domain(p_be, a_be, bd_be, dom[0], dom[1], dom[2], f) : rt_build_custom(edwards, p_be, a_be, bd_be, f)).code;
     if (rc == E_OK)
       for (size_t i = 0; i < custom_.size(); i++)
         if (memcmp(&custom_[i], &f, sizeof(f)) == 0) return CURVE_CUSTOM0 + (int)i;
@@ -1612,6 +1384,38 @@ class Engine {
   // slot of the curve the current call is on (CustomScope)
   template <class CV>
   int comb_idx() const { return CV::RT_ORDER ? custom_curve_ : CV::ID; }
+  template <class CV>
+  const typename Work<CV>::A* comb_of() const { return (const typename Work<CV>::A*)comb_[comb_idx<CV>()]; }
+  // bk.launch of Fn<CV>{n, a...} on n threads -- for a p521 batch with a second wave to pair
+  // (ELL_P521_PAIR_MIN), of the instantiation held to 256 registers, Fn<CV, 2>
+  template <template <class, auto...> class Fn, class CV, class... A>
+  void launch_paired(size_t n, A... a) {
+    if (Work<CV>::L > 12 && n > ELL_P521_PAIR_MIN) {
+      Fn<CV, (Work<CV>::L > 12 ? 2 : 0)> f{n, a...};
+      bk.launch(f, n);
+    } else {
+      Fn<CV> f{n, a...};
+      bk.launch(f, n);
+    }
+  }
+  // the parts of a parted Point#mul (secp256k1) in the kernel of `form`: the two halves of k * P
+  // and, for k * P + kg * G (kg != null), the comb of kg
+  template <class CV>
+  void launch_mul_parts(Form form, size_t n, const u8* k, const u8* xy, typename Work<CV>::VT* tbl, u32* jac,
+                        const u8* kg) {
+    const typename Work<CV>::A* comb = kg ? comb_of<CV>() : nullptr;
+    const size_t units = part_units(form, n, kg ? 3 : 2);
+    if (form == Form::PARTS_WAVE) {           // two or three WAVES per item (coop.h)
+      FnMulPartsK256<false> f{n, k, xy, jac, kg, comb};
+      bk.launch_coop(f, units);
+    } else if (form == Form::PARTS_ROW) {     // one ROW per item and part: four items per wave
+      FnMulPartsK256<true> f{n, k, xy, jac, kg, comb};
+      bk.launch_coop(f, units);
+    } else {                                  // two or three lanes per item
+      FnMulParts<CV> f{n, part_pad(n), k, xy, tbl, jac, kg, comb};
+      launch_fn(f, units);
+    }
+  }
   // Brackets one call on a user-defined curve: takes the device's custom-curve lock, uploads the
   // curve's parameter block (synchronously: every earlier user of the block has finished, see the
   // destructor) and, at the end, waits for the call's device work before the lock is released.
@@ -2717,33 +2521,22 @@ template <class CV>
 int Engine<BK>::mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf,
                   typename Work<CV>::A* raw) {
   typedef Work<CV> W;
+  const Form form = form_for<CV>(n);
   // the window-table scratch is sized by the tuning that is launched (the small-grid tuning's
-  // 5-bit windows take twice the slots per item of the full-grid tuning's)
-  bool wide = false;
-  if constexpr (CV::ENDO && W::L <= 8) wide = n <= small_grid();
-  const size_t slots = wide ? (size_t)W::template stride<true>() : (size_t)W::template stride<false>();
-  // (the parted form: a table and a result per half)
-  const bool parted = wide && n <= parted_grid();
-  typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, (parted ? 2 : 1) * n * slots * sizeof(typename W::VT));
-  u32* jac = (u32*)scratch(S_JAC, (parted ? 2 : 1) * n * 3 * W::NS * 4);
+  // 5-bit windows take twice the slots per item of the full-grid tuning's); the parted form has a
+  // table and a result per half
+  const size_t slots = form != Form::FULL ? (size_t)W::template stride<true>() : (size_t)W::template stride<false>();
+  const size_t halves = parted(form) ? 2 : 1;
+  typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, halves * n * slots * sizeof(typename W::VT));
+  u32* jac = (u32*)scratch(S_JAC, halves * n * 3 * W::NS * 4);
   if (!tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
   bool launched = false;
   if constexpr (CV::ENDO && W::L <= 8) {
-    if (parted) {                           // most SIMDs would idle: two lanes per item, then the join
-      if (!rows_for(n) && n <= coop_grid()) {   // ... or two WAVES per item (coop.h)
-        FnMulPartsC fc{n, k, xy, jac, nullptr, nullptr};
-        bk.launch_coop(fc, 2 * n);
-      } else if (rows_for(n)) {             // ... or one ROW per item and half: four items per wave
-        FnMulPartsR fr{n, k, xy, jac, nullptr, nullptr};
-        bk.launch_coop(fr, 2 * ((n + 3) / 4));
-      } else {
-      const size_t npad = (n + 127) & ~(size_t)127;            // whole workgroups per half
-      FnMulParts<CV> fp{n, npad, k, xy, tbl, jac, nullptr, nullptr};
-      launch_fn(fp, npad + n);
-      }
+    if (parted(form)) {                     // most SIMDs would idle: the halves of every item apart, then the join
+      launch_mul_parts<CV>(form, n, k, xy, tbl, jac, nullptr);
       FnMulJoin<CV> fj{n, jac, false, xy, out_xy, out_inf, raw};   // ... to affine, and the domain test
       return launch_fn(fj, n);
-    } else if (wide) {                      // at most three waves per SIMD: the register-rich tuning
+    } else if (form == Form::WIDE) {        // at most three waves per SIMD: the register-rich tuning
       FnMulVar<CV, 3, true> f{n, k, xy, tbl, jac};
       launch_fn(f, n);
       launched = true;
@@ -2752,20 +2545,13 @@ int Engine<BK>::mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u
   if constexpr (!CV::ENDO && CoopNist<CV>::AVAILABLE) {
     // a handful of items: the ladder of every item on a wave of its own (the row layer); the
     // normalisation and the domain test below are the one-lane kernels'
-    if (!launched && n <= coop_grid_of<CV>() && out_inf) {
+    if (n <= coop_grid_of<CV>() && out_inf) {
       FnMulPartsN<CV> fc{n, k, xy, jac, nullptr, nullptr};
       bk.launch_coop(fc, n);
       launched = true;
     }
   }
-  if (launched) {
-  } else if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnMulVar<CV, (W::L > 12 ? 2 : 0)> f{n, k, xy, tbl, jac};
-    bk.launch(f, n);
-  } else {
-    FnMulVar<CV> f{n, k, xy, tbl, jac};
-    bk.launch(f, n);
-  }
+  if (!launched) launch_paired<FnMulVar, CV>(n, k, xy, tbl, jac);
   int rc = normalize_chunk<CV>(n, jac, out_xy, out_inf, raw);
   if (rc == E_OK && out_inf) {                  // (the comb build has no out_inf: its points are G)
     FnDomainMark<CV> g{n, xy, nullptr, out_xy, out_inf};
@@ -2786,20 +2572,14 @@ int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_inf) 
   if constexpr ((row_k256 || row_nist) && W::NBYTES == W::BYTES) {
     if (n <= coop_grid_of<CV>() && out_inf) {
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
-      FnMulFixedC<CV, CW> fc{n, k, (const typename W::A*)comb_[comb_idx<CV>()], out_xy, out_inf};
+      FnMulFixedC<CV, CW> fc{n, k, comb_of<CV>(), out_xy, out_inf};
       bk.launch_coop(fc, n);
       return E_OK;
     }
   }
   u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
   if (!jac) return fail(E_NOMEM, "scratch allocation failed");
-  if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnMulFixed<CV, (W::L > 12 ? 2 : 0)> f{n, k, (const typename W::A*)comb_[comb_idx<CV>()], jac};
-    bk.launch(f, n);
-  } else {
-    FnMulFixed<CV> f{n, k, (const typename W::A*)comb_[comb_idx<CV>()], jac};
-    bk.launch(f, n);
-  }
+  launch_paired<FnMulFixed, CV>(n, k, comb_of<CV>(), jac);
   return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
 }
 
@@ -2828,23 +2608,13 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
                     u8* out_inf) {
   typedef Work<CV> W;
   if constexpr (CV::ENDO && W::L <= 8) {
-    // (both gates, as in mul_var_chunk / ecdsa_chunk: ELLGPU_SMALL_GRID=0 keeps the call on the
-    // full-grid tuning whatever the parted threshold says)
-    if (n <= small_grid() && n <= parted_grid()) {   // most SIMDs would idle: k2's halves and k1's comb in three waves
+    const Form form = form_for<CV>(n);
+    // (k1*G + k2*P has no WIDE kernel: a wide batch that is not parted runs the ordinary mul_add_g below)
+    if (parted(form)) {                     // most SIMDs would idle: k2's halves and k1's comb apart, then the join
       u32* pj = (u32*)scratch(S_JAC, 3 * n * 3 * W::NS * 4);
       typename W::VT* pt = (typename W::VT*)scratch(S_TBL, 2 * n * (size_t)W::template stride<true>() * sizeof(typename W::VT));
       if (!pt || !pj) return fail(E_NOMEM, "scratch allocation failed");
-      if (!rows_for(n) && n <= coop_grid()) {
-        FnMulPartsC fc{n, k2, xy2, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
-        bk.launch_coop(fc, 3 * n);
-      } else if (rows_for(n)) {
-        FnMulPartsR fr{n, k2, xy2, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
-        bk.launch_coop(fr, 3 * ((n + 3) / 4));
-      } else {
-      const size_t npad = (n + 127) & ~(size_t)127;
-      FnMulParts<CV> fp{n, npad, k2, xy2, pt, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
-      launch_fn(fp, 2 * npad + n);
-      }
+      launch_mul_parts<CV>(form, n, k2, xy2, pt, pj, k1);
       FnMulJoin<CV> fj{n, pj, true, xy2, out_xy, out_inf, nullptr};
       return launch_fn(fj, n);
     }
@@ -2853,7 +2623,7 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
     if (n <= coop_grid_of<CV>()) {                 // the ladder of k2 and the comb of k1 on a wave each, joined on one lane
       u32* pj = (u32*)scratch(S_JAC, 2 * n * 3 * W::NS * 4);
       if (!pj) return fail(E_NOMEM, "scratch allocation failed");
-      FnMulPartsN<CV> fc{n, k2, xy2, pj, k1, (const typename W::A*)comb_[comb_idx<CV>()]};
+      FnMulPartsN<CV> fc{n, k2, xy2, pj, k1, comb_of<CV>()};
       bk.launch_coop(fc, 2 * n);
       FnMulJoin<CV> fj{n, pj, false, xy2, out_xy, out_inf, nullptr};
       return launch_fn(fj, n);
@@ -2862,13 +2632,7 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
   u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
   typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
   if (!tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
-  if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnMulAddG<CV, (W::L > 12 ? 2 : 0)> f{n, k1, k2, xy2, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
-    bk.launch(f, n);
-  } else {
-    FnMulAddG<CV> f{n, k1, k2, xy2, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
-    bk.launch(f, n);
-  }
+  launch_paired<FnMulAddG, CV>(n, k1, k2, xy2, comb_of<CV>(), tbl, jac);
   int rc = normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
   if (rc == E_OK && out_inf) {
     FnDomainMark<CV> g{n, nullptr, xy2, out_xy, out_inf};
@@ -2939,64 +2703,62 @@ template <class CV>
 int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
                 const u8* pub, u8* ok, u8* st) {
   typedef Work<CV> W;
-  bool wide = false;
-  if constexpr (CV::ENDO && W::L <= 8) wide = n <= small_grid();
+  const Form form = form_for<CV>(n);
+  const bool wide = form != Form::FULL;
   const size_t slots = wide ? (size_t)W::template stride<true>() : (size_t)W::template stride<false>();
   typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, n * slots * sizeof(typename W::VT));
   u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
   u32* u12 = (u32*)scratch(S_U12, n * 2 * W::LN * 4);
   u8* valid = (u8*)scratch(S_VALID, n);
   if (!tbl || !pre || !u12 || !valid) return fail(E_NOMEM, "scratch allocation failed");
-  const int K = inv_batch_for(n, INV_BATCH_N);
-  size_t T = (n + K - 1) / K;
-  FnEcdsaPrep<CV> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};
   if constexpr (CV::ENDO && W::L <= 8 && ELL_SPLIT_SMALL_VERIFY) {
     // (the two-kernel form on a FULL grid was measured too, round 4: 8.22 -> 8.37 ms per 2^20 --
     // the table kernel alone takes 0.65 ms where building the table inside ecdsa_main costs
     // 0.5 ms, and there is no latency to hide at four waves per SIMD; small grids only)
+    // (the verify takes the table and parted forms only under split_small_verify(): without it a
+    // wide batch, parted or not, is ecdsa_prep -> the WIDE ecdsa_main below)
     if (wide && split_small_verify()) {
       // latency-bound batch: the window table does not depend on s^-1, so it is built BESIDE
       // ecdsa_prep -- one launch whose first workgroups run the prep and whose others build the
       // tables (FnEcdsaPrepTable); the ladder follows in stream order.  (Round 4 first ran the two
       // as separate kernels on two streams with an event fork / join: 0.6-1.9 % slower than this
       // fused launch, profiles/r04_split_verify_ab.txt.)
-      const int Ks = inv_batch_beside(n, INV_BATCH_N);
-      const size_t Ts = (n + Ks - 1) / Ks;
-      const size_t tpad = (Ts + 127) & ~(size_t)127;          // whole workgroups of either kind
-      const bool rows = n <= parted_grid() && rows_for(n);                           // one item per row
-      if (!rows && n <= parted_grid() && n <= coop_grid()) {
+      if (form == Form::PARTS_WAVE) {
         // a handful of items: the prep on a wave per item, the table on another (row layer), one launch
         FnEcdsaPrepTableC fptc{n, hash, hash_len, shift, r, s, pre, u12, valid, pub, tbl};
         bk.launch_coop(fptc, 2 * n);
-      } else if (rows) {
+      } else if (form == Form::PARTS_ROW) {
         const size_t pu = (n + 63) / 64;
         FnEcdsaPrepTableR fptr{n, pu, hash, hash_len, shift, r, s, pre, u12, valid, pub, tbl};
         bk.launch_coop(fptr, pu + (n + 3) / 4);
       } else {
+        const int Ks = inv_batch_beside(n, INV_BATCH_N);
+        const size_t Ts = (n + Ks - 1) / Ks;
+        const size_t tpad = (Ts + 127) & ~(size_t)127;          // whole workgroups of either kind
         FnEcdsaPrepTable<CV> fpt{{Ts, n, Ks, hash, hash_len, shift, r, s, pre, u12, valid}, tpad, {n, pub, tbl}};
         launch_fn(fpt, tpad + n);
       }
-      if (n <= parted_grid()) {
-        // most SIMDs would idle beside this batch: three lanes per item (FnEcdsaParts), then the join
-        u32* jac = (u32*)scratch(S_JAC, n * 3 * 3 * W::NS * 4);
-        if (!jac) return fail(E_NOMEM, "scratch allocation failed");
-        if (!rows && n <= coop_grid()) {
-          // a handful of items: every part on a wave of its own, lanes-per-item arithmetic
-          FnEcdsaPartsC fc{n, u12, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
-          bk.launch_coop(fc, 3 * n);
-        } else if (rows) {
-          FnEcdsaPartsR fr{n, u12, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
-          bk.launch_coop(fr, 3 * ((n + 3) / 4));
-        } else {
-        const size_t npad = (n + 127) & ~(size_t)127;          // whole workgroups per part
-        FnEcdsaParts<CV> fp{n, npad, u12, (const typename W::A*)comb_[comb_idx<CV>()], tbl, jac};
-        launch_fn(fp, 2 * npad + n);
-        }
-        FnEcdsaJoin<CV> fj{n, valid, r, pub, tbl, jac, ok, st};
-        return launch_fn(fj, n);
+      if (form == Form::WIDE) {
+        FnEcdsaLadder<CV, true> fl{n, u12, valid, r, pub, comb_of<CV>(), tbl, ok, st};
+        return launch_fn(fl, n);
       }
-      FnEcdsaLadder<CV, true> fl{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
-      return launch_fn(fl, n);
+      // most SIMDs would idle beside this batch: the half ladders and the comb of every item as
+      // three parts, then the join
+      u32* jac = (u32*)scratch(S_JAC, n * 3 * 3 * W::NS * 4);
+      if (!jac) return fail(E_NOMEM, "scratch allocation failed");
+      const size_t units = part_units(form, n, 3);
+      if (form == Form::PARTS_WAVE) {         // every part on a wave of its own, lanes-per-item arithmetic
+        FnEcdsaPartsK256<false> fc{n, u12, comb_of<CV>(), tbl, jac};
+        bk.launch_coop(fc, units);
+      } else if (form == Form::PARTS_ROW) {   // one item per row, four per wave
+        FnEcdsaPartsK256<true> fr{n, u12, comb_of<CV>(), tbl, jac};
+        bk.launch_coop(fr, units);
+      } else {                                // three lanes per item
+        FnEcdsaParts<CV> fp{n, part_pad(n), u12, comb_of<CV>(), tbl, jac};
+        launch_fn(fp, units);
+      }
+      FnEcdsaJoin<CV> fj{n, valid, r, pub, tbl, jac, ok, st};
+      return launch_fn(fj, n);
     }
   }
   if constexpr (!CV::ENDO && CoopNist<CV>::AVAILABLE) {
@@ -3012,26 +2774,23 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
       FnEcdsaPrepTableN<CV> fpt{n, hash, hash_len, shift, r, s, pre, u12, valid, pub, gt};
       bk.launch_coop(fpt, 2 * n);
       // ... then the ladder over that table and the comb
-      FnEcdsaPartsN<CV> fc{n, u12, pub, (const typename W::A*)comb_[comb_idx<CV>()], jac, gt};
+      FnEcdsaPartsN<CV> fc{n, u12, pub, comb_of<CV>(), jac, gt};
       bk.launch_coop(fc, 2 * n);
       FnEcdsaJoin2<CV> fj{n, valid, r, pub, jac, ok, st};
       return launch_fn(fj, n);
     }
   }
+  const int K = inv_batch_for(n, INV_BATCH_N);
+  size_t T = (n + K - 1) / K;
+  FnEcdsaPrep<CV> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};
   launch_fn(f1, T);
-  if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnEcdsaMain<CV, (W::L > 12 ? 2 : 0)> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
-    bk.launch(f2, n);
-    return E_OK;
-  }
   if constexpr (CV::ENDO && W::L <= 8) {
     if (wide) {                             // at most three waves per SIMD: the register-rich tuning
-      FnEcdsaMain<CV, 3, true> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
-      return launch_fn(f2, n);
+      FnEcdsaMain<CV, 3, true> f2{n, u12, valid, r, pub, comb_of<CV>(), tbl, ok, st};
+      return launch_fn(f2, n);              // (its own translation unit: engine_extern.h group 7)
     }
   }
-  FnEcdsaMain<CV> f2{n, u12, valid, r, pub, (const typename W::A*)comb_[comb_idx<CV>()], tbl, ok, st};
-  bk.launch(f2, n);
+  launch_paired<FnEcdsaMain, CV>(n, u12, valid, r, pub, comb_of<CV>(), tbl, ok, st);
   return E_OK;
 }
 
@@ -3418,20 +3177,14 @@ int Engine<BK>::sign_chunk(size_t n, const u8* hash, int hash_len, int shift, co
       if (!kinv) return fail(E_NOMEM, "scratch allocation failed");
       u32* pre2 = kinv + n * (W::LN > W::NS ? W::LN : W::NS);
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
-      FnSignPartsC<CV, CW> fc{n, nonces, (const typename W::A*)comb_[comb_idx<CV>()], kg, kg_inf, kinv};
+      FnSignPartsC<CV, CW> fc{n, nonces, comb_of<CV>(), kg, kg_inf, kinv};
       bk.launch_coop(fc, 2 * n);
       FnSignFinish<CV> f2{n, n, 1, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre2,
                           out_r, out_s, out_recid, out_ok, kinv};
       return launch_fn(f2, n);
     }
   }
-  if (W::L > 12 && n > ELL_P521_PAIR_MIN) {
-    FnSignMul<CV, (W::L > 12 ? 2 : 0)> f1{n, nonces, (const typename W::A*)comb_[comb_idx<CV>()], jac};
-    bk.launch(f1, n);
-  } else {
-    FnSignMul<CV> f1{n, nonces, (const typename W::A*)comb_[comb_idx<CV>()], jac};
-    bk.launch(f1, n);
-  }
+  launch_paired<FnSignMul, CV>(n, nonces, comb_of<CV>(), jac);
   int rc = normalize_chunk<CV>(n, jac, kg, kg_inf, nullptr);
   if (rc) return rc;
   u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);

@@ -15,7 +15,7 @@
 // Square root (Red#sqrt, dist/elliptic.js:7177-7232), for ShortCurve#pointFromX and the
 // compressed SEC1 encodings on user-defined curves: the block carries the constants that depend
 // on the modulus alone -- p - 1 = q 2^s, the exponent, c = z^q for a quadratic non-residue z --
-// computed on the host when the curve is defined (Engine::rt_sqrt_init).  p = 3 (mod 4): one
+// computed on the host when the curve is defined (rt_define.h rt_sqrt_init).  p = 3 (mod 4): one
 // exponentiation a^((p+1)/4).  Otherwise Tonelli-Shanks, with the reference's inner search for
 // the order of t replaced by a schedule that s alone fixes: s - 1 rounds, round k squares t
 // k - 1 times and applies the correction under a per-lane select.  Every loop bound is read from

@@ -259,6 +259,16 @@ int hs_rt_field_op(ellgpu_ctx* ctx, int field, int op, size_t n, const u32* a, c
   }
   return 0;
 }
+// the parameter block of ctx's user-defined curve `curve`, byte for byte (what register_custom
+// compares): copies at most cap bytes, returns the block's size (-1: no such curve)
+int hs_rt_block(ellgpu_ctx* ctx, int curve, u8* out, int cap) {
+  if (!ctx) return -1;
+  ELL_LOCK(ctx);
+  const RtField* rt = ctx->eng->custom_block(curve);
+  if (!rt) return -1;
+  memcpy(out, rt, (size_t)cap < sizeof(RtField) ? (size_t)cap : sizeof(RtField));
+  return (int)sizeof(RtField);
+}
 int hs_drbg_draws(int kind, const u8* seed, int nbytes, int ndraws, u8* out) {
   if (kind == 0 && nbytes == 24) { drbg256_draws<6>(seed, ndraws, out); return 0; }
   if (kind == 0 && nbytes == 28) { drbg256_draws<7>(seed, ndraws, out); return 0; }

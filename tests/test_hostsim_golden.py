@@ -406,6 +406,98 @@ def test_verify_golden_secp256k1_both_tunings(hs, monkeypatch):
     c.close()
 
 
+# ---- the form of a small secp256k1 batch, at the thresholds themselves ----------------------------
+# The rule (engine.h Engine::form_for), restated here and never read back from the engine:
+#   wide   = n <= SMALL_GRID                      parted = wide and n <= PARTED_GRID
+#   rows   = parted and ROW_FROM < n <= ROW_GRID  waves  = parted, not rows, n <= COOP_GRID
+#   lanes  = parted, neither rows nor waves       full   = not wide
+# Each configuration lists the batch sizes it is called with and the form each must take.
+_A = dict(ELLGPU_SMALL_GRID="10", ELLGPU_PARTED_GRID="8", ELLGPU_COOP_GRID="3", ELLGPU_ROW_FROM="4", ELLGPU_ROW_GRID="6")
+FORM_CONFIGS = {
+    "a": (_A, {1: "waves", 2: "waves", 3: "waves", 4: "lanes", 5: "rows", 6: "rows", 7: "lanes", 8: "lanes",
+               9: "wide", 10: "wide", 11: "full"}),
+    # overlapping ranges: rows win inside theirs, waves hold on either side of it
+    "b": (dict(ELLGPU_SMALL_GRID="10", ELLGPU_PARTED_GRID="8", ELLGPU_COOP_GRID="6", ELLGPU_ROW_FROM="2", ELLGPU_ROW_GRID="4"),
+          {1: "waves", 2: "waves", 3: "rows", 4: "rows", 5: "waves", 6: "waves", 7: "lanes", 8: "lanes"}),
+    # the small grid gates the parted one: 6 <= PARTED_GRID, yet on the full grid
+    "c": (dict(ELLGPU_SMALL_GRID="5", ELLGPU_PARTED_GRID="8", ELLGPU_COOP_GRID="0", ELLGPU_ROW_GRID="0"),
+          {5: "lanes", 6: "full"}),
+    # ELLGPU_SPLIT_VERIFY=0 takes the verify, and only the verify, off the parted and table forms
+    "d": (dict(_A, ELLGPU_SPLIT_VERIFY="0"), {1: "waves", 2: "waves", 3: "waves", 4: "lanes", 5: "rows", 6: "rows", 7: "lanes",
+                                              8: "lanes", 9: "wide", 10: "wide"}),
+}
+FORM_KERNELS = (b"ecdsa_prep", b"ecdsa_prep_table", b"ecdsa_prep_table_c", b"ecdsa_prep_table_r", b"ecdsa_parts",
+                b"ecdsa_parts_c", b"ecdsa_parts_r", b"ecdsa_join", b"ecdsa_main", b"mul_parts", b"mul_parts_c",
+                b"mul_parts_r", b"mul_join", b"mul_var", b"mul_add_g")
+FORM_LAUNCHES = {
+    "verify": {"waves": {b"ecdsa_prep_table_c", b"ecdsa_parts_c", b"ecdsa_join"},
+               "rows": {b"ecdsa_prep_table_r", b"ecdsa_parts_r", b"ecdsa_join"},
+               "lanes": {b"ecdsa_prep_table", b"ecdsa_parts", b"ecdsa_join"},
+               "wide": {b"ecdsa_prep_table", b"ecdsa_main"},
+               "full": {b"ecdsa_prep", b"ecdsa_main"}},
+    "mul": {"waves": {b"mul_parts_c", b"mul_join"}, "rows": {b"mul_parts_r", b"mul_join"},
+            "lanes": {b"mul_parts", b"mul_join"}, "wide": {b"mul_var"}, "full": {b"mul_var"}},
+    "mul_add_g": {"waves": {b"mul_parts_c", b"mul_join"}, "rows": {b"mul_parts_r", b"mul_join"},
+                  "lanes": {b"mul_parts", b"mul_join"}, "wide": {b"mul_add_g"}, "full": {b"mul_add_g"}},
+}
+
+
+@pytest.fixture(scope="module")
+def form_batch():
+    """eleven secp256k1 items and what Python integers (the oracle's group law) make of them: signatures
+    (every third one over another hash), k2 * Q and k1 * G + k2 * Q.  Computed once; a call takes the
+    first n items."""
+    cur = O.get_curve("secp256k1")
+    n, rng, N = int(cur.n), random.Random(1511), 11
+    z, r, s, q, k1, k2, ok, mul, madd = ([] for _ in range(9))
+    for i in range(N):
+        d, k, zi = rng.randrange(1, n), rng.randrange(1, n), rng.getrandbits(256)
+        Q, R = cur.g.mul(d), cur.g.mul(k)
+        ri = int(R.x) % n
+        si = pow(k, -1, n) * (zi + ri * d) % n
+        if i % 3 == 1:
+            zi ^= 1 << (i * 7)
+        a, b = rng.randrange(1, n), rng.randrange(1, n)
+        z.append(zi), r.append(ri), s.append(si), q.append((int(Q.x), int(Q.y))), k1.append(a), k2.append(b)
+        ok.append(1 if O.ecdsa_verify(cur, zi, 32, ri, si, Q) else 0)
+        P, S = Q.mul(b), cur.g.mul(a).add(Q.mul(b))
+        mul.append((int(P.x), int(P.y))), madd.append((int(S.x), int(S.y)))
+    assert ok == [0 if i % 3 == 1 else 1 for i in range(N)]
+    be = elliptic_amd.ints_to_be
+    pub = np.concatenate([be([x for x, _ in q], 32), be([y for _, y in q], 32)], axis=1)
+    return dict(z=be(z, 32), r=be(r, 32), s=be(s, 32), pub=pub, k1=be(k1, 32), k2=be(k2, 32), ok=ok, mul=mul, madd=madd)
+
+
+@pytest.mark.parametrize("config", sorted(FORM_CONFIGS))
+def test_secp256k1_form_at_the_thresholds(hs, monkeypatch, form_batch, config):
+    """verify, Point#mul and mulAdd with G of n secp256k1 items, one call per n, with every threshold
+    set through its ELLGPU_* variable: the kernels launched are exactly those of the form that the rule
+    above gives n (n == threshold against threshold + 1, and which threshold wins where ranges overlap),
+    and the results are the integers'."""
+    env, forms = FORM_CONFIGS[config]
+    c = _fresh_ctx(hs, monkeypatch, **env)
+    c.mul_fixed("secp256k1", form_batch["k1"][:1])        # (the fixed-base table is built by mul_var launches of its own)
+    fb = form_batch
+
+    def launched(call):
+        hs.hs_launches_reset()
+        out = call()
+        return out, {k for k in FORM_KERNELS if hs.hs_launches(k) > 0}
+
+    for n, form in sorted(forms.items()):
+        ok, got = launched(lambda: c.ecdsa_verify("secp256k1", fb["z"][:n], fb["r"][:n], fb["s"][:n], fb["pub"][:n]))
+        want = FORM_LAUNCHES["verify"]["full" if "ELLGPU_SPLIT_VERIFY" in env else form]
+        assert got == want, (config, n, "verify", sorted(got))
+        assert [int(v) for v in ok] == fb["ok"][:n], (config, n)
+        (xy, inf), got = launched(lambda: c.mul_var("secp256k1", fb["k2"][:n], fb["pub"][:n]))
+        assert got == FORM_LAUNCHES["mul"][form], (config, n, "mul", sorted(got))
+        assert [PC._res_from(xy, inf, i, 32) for i in range(n)] == fb["mul"][:n], (config, n)
+        (xy, inf), got = launched(lambda: c.mul_add2("secp256k1", fb["k1"][:n], None, fb["k2"][:n], fb["pub"][:n]))
+        assert got == FORM_LAUNCHES["mul_add_g"][form], (config, n, "mul_add_g", sorted(got))
+        assert [PC._res_from(xy, inf, i, 32) for i in range(n)] == fb["madd"][:n], (config, n)
+    c.close()
+
+
 @pytest.mark.parametrize("curve", ["p192", "p224", "p256", "p384", "p521"])
 def test_nist_curves_one_lane_and_row_layer(hs, monkeypatch, curve):
     """Small batches on the NIST curves run their ladder and comb on the lanes-per-item layer, one item

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the parted verify (three lanes per item, engine.h FnEcdsaParts; three WAVES per item on
-the row layer, FnEcdsaPartsC) against the one-lane ladder at small batch sizes, on ONE GPU box (developer tool; the override is read when a context
+the row layer, FnEcdsaPartsK256) against the one-lane ladder at small batch sizes, on ONE GPU box (developer tool; the override is read when a context
 is created, so each leg is its own process).
 
     python tools/parted_ab.py [--sizes=1,64,1024,...] [--reps=200]
