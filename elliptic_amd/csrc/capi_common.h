@@ -497,6 +497,20 @@ int ellgpu_custom_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const ui
                                                       der_len, pub_enc, pub_len, out_ok, out_err), true);
 }
 
+// EC#recoverPubKey on a user-defined ECDSA domain (a group: member 0)
+int ellgpu_custom_recover(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                          const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
+                          uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_recover_host(curve, n, hash, hash_len, r, s, recid, out_xy, out_status));
+}
+int ellgpu_custom_recover_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                              const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
+                              uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_recover_dev(curve, n, hash, hash_len, r, s, recid, out_xy, out_status), true);
+}
+
 int ellgpu_ecdsa_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {

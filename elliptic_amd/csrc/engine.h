@@ -747,6 +747,30 @@ struct FnRtDecodePoint {
     if (i < n) W::rt_decode_point(i, enc, len, pl, out_xy, status);
   }
 };
+// EC#recoverPubKey on a user-defined ECDSA domain (Work::rt_recover_*): the scalar-field pass
+// (range checks, one inversion of r per K items, s1 = -e/r, s2 = s/r, the x of R) and the status
+// fold behind the double-scalar multiplication.  pmn = p mod n travels as an argument: the
+// parameter block's bytes are pinned (Engine::register_custom compares them).
+struct RtPmodN { u32 w[8]; };
+struct FnRtRecoverPrep {
+  static constexpr const char* NAME = "rt_recover_prep";
+  typedef Work<CvCustomDomain> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t T, n; int K; RtPmodN pmn; const u8* hash; int hash_len; const u8* r; const u8* s; const u8* recid;
+  u32* pre; u8* xs; u8* odd; u8* s1; u8* s2; u8* status;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) W::rt_recover_prep(t, T, n, K, pmn.w, hash, hash_len, r, s, recid, pre, xs, odd, s1, s2, status);
+  }
+};
+struct FnRtRecoverFinish {
+  static constexpr const char* NAME = "rt_recover_finish";
+  typedef Work<CvCustomDomain> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* dec_st; const u8* inf; u8* out_xy; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_recover_finish(i, dec_st, inf, out_xy, status);
+  }
+};
 template <class CV>
 struct FnPointAdd {
   static constexpr const char* NAME = "point_add";
@@ -1254,6 +1278,11 @@ class Engine {
   template <int U = 0>
   int rt_wire_chunk(int op, size_t n, const u8* a, const u8* b, size_t len, const u32* lens, u8* o1, u8* o2,
                     u8* o3);
+  // EC#recoverPubKey on a user-defined ECDSA domain: rt_recover_prep, the run-time square root
+  // (rt_wire_chunk), s1 * G + s2 * R over the domain's comb, rt_recover_finish
+  template <int U = 0>
+  int rt_recover_chunk(size_t n, const u8* hash, int hash_len, const u8* r, const u8* s, const u8* recid,
+                       u8* out_xy, u8* out_status);
   template <class CV>
   int decompress_chunk(size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_ok);
   template <class CV>
@@ -1320,6 +1349,9 @@ class Engine {
     if ((int)custom_.size() >= CURVE_CUSTOM_MAX)
       return fail(E_UNSUPPORTED, "at most 16 user-defined curves per context");
     custom_.push_back(f);
+    RtPmodN pmn;
+    rt_p_mod_n(f, pmn.w);
+    custom_pmn_.push_back(pmn);
     *out_curve = CURVE_CUSTOM0 + (int)custom_.size() - 1;
     return E_OK;
   }
@@ -2128,6 +2160,45 @@ class Engine {
     });
   }
 
+  // EC#recoverPubKey (ec/index.js:231-259) on a domain: status 0 point / 1 infinity / 2 the
+  // reference throws / 3 r = 0 or r >= n, as ecdsa_recover_dev.  e = new BN(hash) is not
+  // truncated, only reduced mod n; s is not range-checked (the reference reduces it).
+  int check_custom_recover(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                           const u8* recid, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (!custom_is_domain(curve))
+      return fail(E_UNSUPPORTED, "public-key recovery on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
+    return E_OK;
+  }
+  int custom_recover_dev(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                         const u8* recid, u8* out_xy, u8* out_status) {
+    int rc = check_custom_recover(curve, n, hash, hash_len, r, s, recid, out_xy, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    rc = ensure_comb<CvCustomDomain>();
+    if (rc) return rc;
+    const size_t HL = (size_t)hash_len;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_recover_chunk(m, hash + o * HL, hash_len, r + o * 32, s + o * 32, recid + o, out_xy + o * 64,
+                              out_status + o);
+    });
+  }
+  int custom_recover_host(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                          const u8* recid, u8* out_xy, u8* out_status) {
+    int rc = check_custom_recover(curve, n, hash, hash_len, r, s, recid, out_xy, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{hash, (size_t)hash_len}, In{r, 32}, In{s, 32}, In{recid, 1}},
+                  {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      return custom_recover_dev(curve, m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]);
+    });
+  }
+
   // ---- host-buffer wrappers: stage through device buffers --------------------
   // An operand of a host-buffer call: n items of `stride` bytes.  A null host pointer is an absent
   // optional operand (the wrappers have refused the required ones): it gets no device copy, and
@@ -2436,6 +2507,7 @@ class Engine {
   int lane_ = 0;
   Buf staging_[2 * STAGED_MAX];   // the host-buffer calls' device copies: inputs, then outputs (stage())
   std::vector<RtField> custom_;  // user-defined curves of this context (id = CURVE_CUSTOM0 + index)
+  std::vector<RtPmodN> custom_pmn_;  // p mod n of each (zero for a curve without a domain): rt_recover_prep's argument
   bool custom_active_ = false;
   int custom_curve_ = 0;         // the user-defined curve of the call in progress (CustomScope)
   size_t pipe_step_ = pipe_step_default();   // chunks after the first, in quanta
@@ -2659,6 +2731,38 @@ int Engine<BK>::rt_wire_chunk(int op, size_t n, const u8* a, const u8* b, size_t
     FnWireStatus<CvCustom> f{n, a, b, o3, o1, o2};
     bk.launch(f, n);
   }
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_recover_chunk(size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                                 const u8* recid, u8* out_xy, u8* out_status) {
+  typedef Work<CvCustomDomain> W;
+  // the scalars, the x-coordinates and the points R live across the ladder kernels, which use
+  // S_TBL / S_JAC / S_PRE only (as in recover_chunk)
+  u8* buf = (u8*)scratch(S_U12, n * (2 * 32 + 3 * 32));
+  u8* flags = (u8*)scratch(S_VALID, 3 * n);
+  u32* pre = (u32*)scratch(S_PRE, n * W::LN * 4);
+  if (!buf || !flags || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  u8* s1 = buf;
+  u8* s2 = s1 + n * 32;
+  u8* xs = s2 + n * 32;
+  u8* rxy = xs + n * 32;
+  u8* odd = flags;
+  u8* dec_st = flags + n;
+  u8* inf = flags + 2 * n;
+  const int Kr = inv_batch_for(n, INV_BATCH_N);
+  const size_t T = (n + Kr - 1) / Kr;
+  FnRtRecoverPrep f1{T, n, Kr, custom_pmn_[(size_t)(custom_curve_ - CURVE_CUSTOM0)], hash, hash_len, r, s, recid,
+                     pre, xs, odd, s1, s2, out_status};
+  bk.launch(f1, T);
+  int rc = rt_wire_chunk(OP_RT_DECOMPRESS, n, xs, odd, 0, nullptr, rxy, dec_st, nullptr);
+  if (rc) return rc;
+  rc = mul_add_g_chunk<CvCustomDomain>(n, s1, s2, rxy, out_xy, inf);           // s1 * G + s2 * R
+  if (rc) return rc;
+  FnRtRecoverFinish f2{n, dec_st, inf, out_xy, out_status};
+  bk.launch(f2, n);
   return E_OK;
 }
 

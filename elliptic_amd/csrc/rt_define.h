@@ -243,4 +243,13 @@ inline RtStatus rt_build_domain(const u8* p_be, const u8* a_be, const u8* b_be, 
   return {E_OK, nullptr};
 }
 
+// p mod n of a domain's block, for EC#recoverPubKey's second-candidate test (ec/index.js:243:
+// r.cmp(p.umod(n)) >= 0).  A reduction, not p - n: n may exceed p, and p / n may be 8.  Kept beside
+// the block, not in it (the block's bytes are compared when a definition is registered); zero
+// for a curve without a domain.
+inline void rt_p_mod_n(const RtField& f, u32 (&out)[8]) {
+  bn_zero<8>(out);
+  if (f.domain) mod_reduce(f.n, out, f.p);
+}
+
 }  // namespace ell

@@ -918,6 +918,88 @@ struct Work {
     }
   }
 
+  // ---- the same on a user-defined ECDSA domain (run-time p and n, fp_rt.h) -----------------
+  // Nothing ties n to p there: n may exceed p (secp224k1, secp112r1), p / n may be 8 (cofactor
+  // curves), so p mod n is no difference and r + n need not lie below p -- or below 2^256.
+  // pmn = p mod n, computed on the host when the domain is defined (rt_define.h rt_p_mod_n).
+  // The x handed to the square root is what pointFromX has after toRed (short.js:187-190):
+  // r, or r + n for the second candidate, reduced mod p.  Statuses as recover_prep's.
+  ELL_HD static void rt_recover_prep(size_t t, size_t T, size_t n, int K, const u32 (&pmn)[LN], const u8* hash,
+                                     int hash_len, const u8* rs, const u8* ss, const u8* recid, u32* pre,
+                                     u8* xs, u8* odd, u8* s1b, u8* s2b, u8* status) {
+    static_assert(CV::RT_ORDER && L == 8 && LN == 8, "user-defined domains only");
+    u32 nn[LN];
+    order_words(nn);
+    Nl acc = Fn::one();
+    ELL_NOUNROLL
+    for (int j = 0; j < K; j++) {
+      size_t i = t + (size_t)j * T;
+      if (i >= n) break;
+      u32 r[LN];
+      load_be<LN>(r, rs + i * NBYTES, NBYTES);
+      u32 jj = recid[i];
+      bool second = (jj >> 1) != 0;
+      int st = RECOVER_POINT;
+      if (!scalar_in_range(r)) st = RECOVER_DOMAIN;
+      else if (jj > 3 || (second && bn_geq<LN>(r, pmn))) st = RECOVER_THROWS;
+      status[i] = (u8)st;
+      // x = (r + [second] n) mod p: the sum may carry out of 2^256; from_plain reduces its low
+      // words whatever their size, and the carry is worth 2^256, whose Montgomery form is R^2 mod p
+      u32 add[LN], sum[LN];
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) add[l] = (second && st == RECOVER_POINT) ? nn[l] : 0u;
+      const u32 carry = bn_add<LN>(sum, r, add);
+      El top;
+      ELL_UNROLL
+      for (int l = 0; l < L; l++) top.v[l] = carry ? ELL_RT.r2[l] : 0u;
+      store_fe(xs + i * BYTES, F::add(F::from_plain(sum), top));
+      odd[i] = (u8)(jj & 1);
+      Nl rm = fe_select<Fn>(st == RECOVER_POINT, Fn::from_plain(r), Fn::one());
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
+      acc = Fn::mul(acc, rm);
+    }
+    Nl inv = Fn::inv(acc);
+    ELL_NOUNROLL
+    for (int j = K - 1; j >= 0; j--) {
+      size_t i = t + (size_t)j * T;
+      if (i >= n) continue;
+      u32 r[LN], s[LN];
+      load_be<LN>(r, rs + i * NBYTES, NBYTES);
+      load_be<LN>(s, ss + i * NBYTES, NBYTES);
+      bool ok = status[i] == RECOVER_POINT;
+      Nl rm = fe_select<Fn>(ok, Fn::from_plain(r), Fn::one());
+      Nl pr;
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
+      Nl rinv = Fn::mul(inv, pr);
+      inv = Fn::mul(inv, rm);
+      // e = new BN(msg), up to 64 bytes, and s, possibly >= n: both only reduced mod n
+      Nl e = bytes_mod_n(hash + i * (size_t)hash_len, hash_len);
+      Nl s1 = Fn::neg(Fn::mul(e, rinv));
+      Nl s2 = Fn::mul(Fn::from_plain(s), rinv);
+      u32 p1[LN], p2[LN];
+      Fn::to_plain(p1, s1);
+      Fn::to_plain(p2, s2);
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) { p1[l] = ok ? p1[l] : 0u; p2[l] = ok ? p2[l] : 0u; }
+      store_be<LN>(s1b + i * NBYTES, p1, NBYTES);
+      store_be<LN>(s2b + i * NBYTES, p2, NBYTES);
+    }
+  }
+  // the last pass on a domain: dec_st is rt_decompress's status, whose 'invalid point' (2) and
+  // 'Assertion failed' (3) are both the reference throwing
+  ELL_HD static void rt_recover_finish(size_t i, const u8* dec_st, const u8* inf, u8* out_xy, u8* status) {
+    int st = status[i];
+    if (st == RECOVER_POINT && dec_st[i] != DECODE_OK) st = RECOVER_THROWS;
+    else if (st == RECOVER_POINT && inf[i]) st = RECOVER_INF;
+    status[i] = (u8)st;
+    if (st != RECOVER_POINT) {
+      ELL_NOUNROLL
+      for (int b = 0; b < 2 * BYTES; b++) out_xy[i * 2 * BYTES + b] = 0;
+    }
+  }
+
   // ---- EC#sign's own nonces (ec/index.js:136-158): HmacDRBG over the curve's hash
   // (curves.js `hash:`), entropy = the private key, nonce = the truncated message, both
   // n.byteLength() bytes; drbg.generate(n.byteLength()) is repeated while the candidate,

@@ -452,6 +452,30 @@ class Context:
             der.shape[1], der_len.data_ptr(), pubs.data_ptr(), pubs.shape[1], out_ok.data_ptr(),
             out_err.data_ptr() if out_err is not None else None, self._stream()))
 
+    def custom_recover(self, curve, hashes, r, s, recid, out=None):
+        """EC#recoverPubKey per item on a domain id -> (xy, status): 0 point, 1 infinity, 2 the
+        reference throws, 3 r = 0 or r >= n (handed to the reference).  hashes (n, 1..64) are NOT
+        truncated to the order's bit length (the reference does not either): e = BN(hash) mod n"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        r = _u8(r, (n, 32))
+        s = _u8(s, (n, 32))
+        recid = _u8(recid, (n,))
+        xy, st = self._outs(out, [(n, 64), (n,)])
+        self._check(self._lib.ellgpu_custom_recover(self._ctx, self._cid(curve), n, hashes.ctypes.data, hash_len,
+                                                    r.ctypes.data, s.ctypes.data, recid.ctypes.data,
+                                                    xy.ctypes.data, st.ctypes.data))
+        return xy, st
+
+    def custom_recover_dev(self, curve, hashes, r, s, recid, out_xy, out_status):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_recover_dev(self._ctx, self._cid(curve), n, hashes.data_ptr(),
+                                                        hash_len, r.data_ptr(), s.data_ptr(), recid.data_ptr(),
+                                                        out_xy.data_ptr(), out_status.data_ptr(),
+                                                        self._stream()))
+
     def ecdsa_sign(self, curve, hashes, priv, nonces, canonical=False, msg_bits=0):
         """one pass of EC#sign per item for supplied nonces -> (r, s, recid, ok)"""
         NB = ORDER_BYTES[curve]

@@ -43,12 +43,14 @@
  *           customDecodePoints(ctx, curve, enc, encLen) -> {xy, status}
  *           customVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)
  *             -> {ok, err}: the same three on a user-defined short curve / domain (ellgpu_custom_*)
+ *           customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy, status}: EC#recoverPubKey on a
+ *             user-defined domain (ellgpu_custom_recover; 32-byte r, s and coordinates, hashLen 1..64)
  *             offsets: Buffer of n+1 little-endian uint64 byte offsets into msgs
  *           callAsync(op, ctx, curve, hashLen, msgBits, b0, b1, b2, b3) -> Promise
  *             op 0 mulFixed(b0=k) 1 mulVar(k, xy) 2 mulAdd2(k1, p1|null, k2, p2)
  *             3 ecdsaVerify(hash, r, s, pub) 4 x25519(k, x) 5 ecdsaSignDet(hash, priv; i0 = canonical)
  *             6 ecdsaRecover(hash, r, s, recid) 7 ecdsaVerifyWire(hash, der, lens, keys; i0 = der
- *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length) 9 customVerifyWire (as 7);
+ *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length) 9 customVerifyWire (as 7); 10 customRecover (as 6);
  *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
@@ -118,6 +120,8 @@ static struct {
                      const uint32_t*, const uint8_t*, size_t, uint8_t*, uint8_t*);
   int (*custom_decompress)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
   int (*custom_decode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, size_t, uint8_t*, uint8_t*);
+  int (*custom_recover)(ellgpu_ctx*, int, size_t, const uint8_t*, int, const uint8_t*, const uint8_t*,
+                        const uint8_t*, uint8_t*, uint8_t*);
   int (*custom_verify_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, size_t,
                             const uint32_t*, const uint8_t*, size_t, uint8_t*, uint8_t*);
 } L;
@@ -180,6 +184,7 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(custom_decompress, "ellgpu_custom_decompress");
   SYM(custom_decode_points, "ellgpu_custom_decode_points");
   SYM(custom_verify_wire, "ellgpu_custom_verify_wire");
+  SYM(custom_recover, "ellgpu_custom_recover");
   L.h = h;
   napi_value t; CHECK(env, napi_get_boolean(env, 1, &t));
   return t;
@@ -617,8 +622,8 @@ static napi_value fn_sign_det(napi_env env, napi_callback_info info) {
   return o;
 }
 
-/* ecdsaRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy: Buffer(n*2B), status: Buffer(n)} */
-static napi_value fn_recover(napi_env env, napi_callback_info info) {
+/* ecdsaRecover / customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy: Buffer(n*2B), status: Buffer(n)} */
+static napi_value recover_with(napi_env env, napi_callback_info info, int custom) {
   if (!need_lib(env)) return NULL;
   size_t argc = 7; napi_value argv[7];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -637,9 +642,12 @@ static napi_value fn_recover(napi_env env, napi_callback_info info) {
   napi_value bxy, bst; void *dxy, *dst;
   CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
   CHECK(env, result_buffer(env, n, &dst, &bst));
-  if (L.ecdsa_recover(c, curve, n, h, hl, r, sg, j, (uint8_t*)dxy, (uint8_t*)dst) != 0) return lib_error(env);
+  if ((custom ? L.custom_recover : L.ecdsa_recover)(c, curve, n, h, hl, r, sg, j, (uint8_t*)dxy, (uint8_t*)dst) != 0)
+    return lib_error(env);
   return mk_result(env, "xy", bxy, "status", bst);
 }
+static napi_value fn_recover(napi_env env, napi_callback_info info) { return recover_with(env, info, 0); }
+static napi_value fn_custom_recover(napi_env env, napi_callback_info info) { return recover_with(env, info, 1); }
 
 static napi_value decode_points_with(napi_env env, napi_callback_info info, int custom) {
   if (!need_lib(env)) return NULL;
@@ -888,6 +896,8 @@ static void job_execute(napi_env env, void* data) {
     case 9: j->rc = L.custom_verify_wire(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1],
                                          (size_t)j->i0, (const uint32_t*)j->in[2], j->in[3], (size_t)j->i1, j->out0,
                                          j->out1); break;
+    case 10: j->rc = L.custom_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
+                                      j->out0, j->out1); break;
     default: j->rc = L.decode_points(j->ctx, j->curve, j->n, j->in[0], (size_t)j->i0, j->out0, j->out1); break;
   }
   if (j->rc != 0) {               /* last_error is thread-local: read it on this thread */
@@ -901,10 +911,10 @@ static void job_complete(napi_env env, napi_status status, void* data) {
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
     /* result property names per op, in output order */
-    static const char* const names[10][4] = {
+    static const char* const names[11][4] = {
       {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
       {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
-      {"ok", "err", 0, 0}};
+      {"ok", "err", 0, 0}, {"xy", "status", 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -949,7 +959,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
   j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
   j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > 9 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
+  if (op < 0 || op > 10 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
   int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
@@ -973,7 +983,8 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
     case 5: ok = hl > 0 && j->in[0] && j->in[1] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB; break;
-    case 6: ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
+    case 6: case 10:
+            ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB && len[2] == j->n * NB && len[3] == j->n; break;
     case 7: case 9:
@@ -1023,7 +1034,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"decodePoints", fn_decode_points}, {"encodePoints", fn_encode_points}, {"validate", fn_validate},
     {"pointAdd", fn_point_add}, {"sigFromDer", fn_sig_from_der}, {"sigToDer", fn_sig_to_der}, {"ecdsaVerifyWire", fn_verify_wire},
     {"customDecompress", fn_custom_decompress}, {"customDecodePoints", fn_custom_decode_points},
-    {"customVerifyWire", fn_custom_verify_wire},
+    {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -291,6 +291,15 @@ Engine.prototype.customVerifyWireBatch = function customVerifyWireBatch(curve, o
   return this.addon.customVerifyWire(this.ctx, this._id(curve), o.hashes, o.hashLen, o.msgBits | 0,
     p.buf, p.stride, p.lens, o.keys, o.keyLen);
 };
+// customRecoverBatch: EC#recoverPubKey on a domain id; hashes Buffer(n x hashLen), hashLen 1..64 --
+// e = new BN(hash) is NOT truncated to n.bitLength() bits (the reference does not either: a caller
+// with a longer digest truncates it first); r, s Buffer(n x 32), recid Buffer(n) ->
+// { xy: Buffer(n x 64), status: Buffer(n) }; status 0 point, 1 infinity, 2 the reference throws,
+// 3 r = 0 or r >= n (run the reference on those)
+Engine.prototype.customRecoverBatch = function customRecoverBatch(curve, hashes, hashLen, r, s, recid) {
+  this.stats.gpuCalls++; this.stats.gpuItems += recid.length;
+  return this.addon.customRecover(this.ctx, this._id(curve), hashes, hashLen, r, s, recid);
+};
 
 // KeyPair#derive per item (ec/key.js:102-107): priv Buffer(n x B), pub Buffer(n x 2B) ->
 // { x: Buffer(n x B), status: Buffer(n) }; status 0 shared secret, 1 'public point not validated',
@@ -381,6 +390,9 @@ Engine.prototype.ecdsaVerifyWireBatchAsync = function(curve, o) {
 Engine.prototype.customVerifyWireBatchAsync = function(curve, o) {
   var p = packRecords(o.sigs);
   return this._async(9, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
+};
+Engine.prototype.customRecoverBatchAsync = function(curve, hashes, hashLen, r, s, recid) {
+  return this._async(10, curve, hashLen, 0, hashes, r, s, recid);
 };
 Engine.prototype.decodePointBatchAsync = function(curve, enc, encLen) {
   return this._async(8, curve, 0, 0, enc, null, null, null, encLen, 0);

@@ -216,7 +216,7 @@ int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* 
  * Every other preset-named entry point (wire / DER, sign, sign_det, recover, decompress, decode,
  * validate) answers ELLGPU_E_UNSUPPORTED on a domain id; compressed keys, SEC1 encodings and DER
  * signatures on a domain go through ellgpu_custom_decompress / _custom_decode_points /
- * _custom_verify_wire below.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
+ * _custom_verify_wire below, public-key recovery through ellgpu_custom_recover.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
  * without p1 and ecdsa_verify stay ELLGPU_E_UNSUPPORTED. */
 int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                                      const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve);
@@ -261,6 +261,38 @@ int ellgpu_custom_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const ui
                                   int msg_bits, const uint8_t* der, size_t der_stride,
                                   const uint32_t* der_len, const uint8_t* pub_enc, size_t pub_len,
                                   uint8_t* out_ok, uint8_t* out_err, void* stream);
+/* EC#recoverPubKey(msg, {r, s}, j) (lib/elliptic/ec/index.js:231-259) on a DOMAIN id, on the
+ * device: Q = r^-1 (s R - e G) with R = pointFromX(r + (j >> 1) n, j & 1).  An entry point of its
+ * own because ellgpu_ecdsa_recover is documented to refuse user-defined ids (and keeps doing so).
+ * ELLGPU_E_UNSUPPORTED on a plain ellgpu_curve_define_short id or a user-defined Edwards id,
+ * ELLGPU_E_ARG on a preset id -- as ellgpu_custom_verify_wire.  Synchronous like every call on a
+ * user-defined curve; a group runs it on its first member.
+ *   hash   n x hash_len bytes, 1 <= hash_len <= 64.  e = new BN(hash) is NOT TRUNCATED to
+ *          n.bitLength() bits -- recoverPubKey does not call _truncateToN (ec/index.js:236) -- only
+ *          reduced mod n by the arithmetic.  A caller whose digest is longer than n truncates it
+ *          first, as it must for the reference.
+ *   r, s   n x 32 bytes, big-endian;  recid: n bytes (j)
+ *   out_xy n x 64 bytes, x || y; zeroed wherever out_status is not 0
+ *   out_status, the meanings of ellgpu_ecdsa_recover:
+ *     0  Q is finite and written to out_xy
+ *     1  Q is the point at infinity
+ *     2  the reference throws: 'Unable to find sencond key candinate' (j >= 2 and r >= p mod n),
+ *        'invalid point' (x has no y, p = 3 mod 4), 'Assertion failed' (x has no y, p = 1 mod 4:
+ *        bn.js's Tonelli-Shanks loop), 'The recovery param is more than two bits' (j > 3)
+ *     3  r = 0 or r >= n: outside the engine's domain, the item is handed to the reference
+ *        (tested first: such an item is 3 whatever its j)
+ *   s is not range-checked: the reference reduces it mod n, and s = 0 is legal.
+ * Nothing ties n to p on a domain.  p mod n is computed when the domain is defined (not p - n);
+ * the x handed to pointFromX is reduced mod p as toRed does: where n > p (secp224k1, secp112r1)
+ * an r in [p, n) stands for x = r - p and r + n may need two subtractions of p; on a cofactor
+ * curve (p / n = 8) r + n lies below p, and most valid signatures recover a point outside the
+ * subgroup or none -- in the reference too. */
+int ellgpu_custom_recover(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                          const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
+                          uint8_t* out_status);
+int ellgpu_custom_recover_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                              const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
+                              uint8_t* out_status, void* stream);
 /* User-defined (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) over an odd prime
  * p < 2^256 -- `new elliptic.curve.edwards({p, a, c: 1, d, ...})` (lib/elliptic/curve/edwards.js:
  * 11-31) with parameters that are not ed25519's.  Same id space, widths (32 bytes) and entry

@@ -15,7 +15,16 @@ custom_verify_wire_dev, next to the raw-form ecdsa_verify_dev over the decoded r
 on brainpoolP256r1 (square root: one exponentiation) and secp224k1 (Tonelli-Shanks, p - 1 = q 2^2);
 and the key decoding alone (custom_decode_points_dev), which is where the square root is.
 
-    python tools/bench_custom_ecdsa.py --wire [log2 n ...]                     (default: 18)"""
+    python tools/bench_custom_ecdsa.py --wire [log2 n ...]                     (default: 18)
+
+--recover: public-key recovery (custom_recover_dev) next to the raw-form ecdsa_verify_dev on the
+same domain, same r and s, in one run -- on brainpoolP256r1 and secp224k1.  r is the x of a point
+k G (so every item has its square root and runs the whole recovery; status 0 is asserted), s is
+random, the verify's keys are random points.  Recovery is one square root and one batched
+inversion more than a verify; "kernels_ms" are the launches of one recovery call
+(ellgpu_ctx_set_timing).
+
+    python tools/bench_custom_ecdsa.py --recover [log2 n ...]                  (default: 16 18)"""
 import json
 import os
 import sys
@@ -123,6 +132,56 @@ def run_wire(ctx, spec, n):
     return out
 
 
+def run_recover(ctx, spec, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_domain_checks as CD
+    cid = CD.define(ctx, spec)
+    nn = CD.I(spec["n"])
+    keep = nn.bit_length() - 1                      # scalars below 2^(bitLength(n) - 1) < n
+    def below_n(tag):
+        a = bench.xof("custom-recover:%s:%s" % (spec["name"], tag), n * 32).reshape(n, 32).copy()
+        a[:, :32 - (keep + 7) // 8] = 0
+        if keep % 8:
+            a[:, 32 - (keep + 7) // 8] &= (1 << (keep % 8)) - 1
+        a[:, 31] |= 1
+        return a
+    d, k, s = below_n("d"), below_n("k"), below_n("s")
+    q, inf = ctx.mul_fixed(cid, d)
+    kg, inf2 = ctx.mul_fixed(cid, k)
+    assert not inf.any() and not inf2.any()
+    # r = x(k G) where that is below n (else r = 1: counted, and excluded from the status check)
+    r = kg[:, :32].copy()
+    big = np.array([int.from_bytes(bytes(x), "big") >= nn for x in r])
+    r[big] = 0
+    r[big, 31] = 1
+    recid = (kg[:, 63] & 1).astype(np.uint8)
+    h = bench.xof("custom-recover:h", n * 32).reshape(n, 32).copy()
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    dh, dr, ds, dq, dj = t(h), t(r), t(s), t(q), t(recid)
+    ok = torch.zeros(n, dtype=torch.uint8, device=dev)
+    dxy = torch.zeros(n, 64, dtype=torch.uint8, device=dev)
+    dst = torch.full((n,), 9, dtype=torch.uint8, device=dev)
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": spec["name"], "n": n,
+           "r_not_x": int(big.sum())}
+    for name, fn in (("raw_verify", lambda: ctx.ecdsa_verify_dev(cid, dh, dr, ds, dq, ok)),
+                     ("recover", lambda: ctx.custom_recover_dev(cid, dh, dr, ds, dj, dxy, dst))):
+        ms = timed(fn)
+        out[name + "_ms"] = round(ms, 3)
+        out[name + "_M_per_s"] = round(n / ms / 1e3, 2)
+    st = dst.cpu().numpy()
+    assert (st[~big] == 0).all(), np.unique(st, return_counts=True)
+    out["recover_over_verify"] = round(out["recover_ms"] / out["raw_verify_ms"], 4)
+    ctx.set_timing(True)
+    ctx.custom_recover_dev(cid, dh, dr, ds, dj, dxy, dst)
+    torch.cuda.synchronize()
+    out["kernels_ms"] = {name: round(ms, 4) for name, (cnt, ms) in ctx.get_timing().items()}
+    ctx.set_timing(False)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
@@ -135,6 +194,17 @@ def main():
                 spec = next(c for c in CD.curves() if c["name"] == name)
                 for lg in [int(a) for a in sys.argv[2:]] or [18]:
                     print(json.dumps(run_wire(ctx, spec, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
+    if sys.argv[1:2] == ["--recover"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            for name in ("brainpoolP256r1", "secp224k1"):
+                spec = next(c for c in CD.curves() if c["name"] == name)
+                for lg in [int(a) for a in sys.argv[2:]] or [16, 18]:
+                    print(json.dumps(run_recover(ctx, spec, 1 << lg)), flush=True)
         finally:
             ctx.close()
         return
