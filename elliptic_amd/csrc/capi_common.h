@@ -511,6 +511,37 @@ int ellgpu_custom_recover_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_
   return finish(ctx, ctx->eng->custom_recover_dev(curve, n, hash, hash_len, r, s, recid, out_xy, out_status), true);
 }
 
+// EC#sign on a user-defined ECDSA domain (a group: member 0): supplied nonces, or HmacDRBG over drbg_hash
+static_assert(ELLGPU_CUSTOM_SIGN_MAX_DRAWS == ell::CUSTOM_SIGN_MAX_DRAWS, "the header's draw cap is the engine's");
+int ellgpu_custom_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_sign_host(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
+                                                out_r, out_s, out_recid, out_ok));
+}
+int ellgpu_custom_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                           const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                           uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
+                                               out_r, out_s, out_recid, out_ok), true);
+}
+int ellgpu_custom_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                           const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r, uint8_t* out_s,
+                           uint8_t* out_recid, uint8_t* out_ok) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_sign_host(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
+                                                canonical, out_r, out_s, out_recid, out_ok));
+}
+int ellgpu_custom_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                               int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
+                               uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
+                                               canonical, out_r, out_s, out_recid, out_ok), true);
+}
+
 int ellgpu_ecdsa_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {

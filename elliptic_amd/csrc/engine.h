@@ -771,6 +771,45 @@ struct FnRtRecoverFinish {
     if (i < n) W::rt_recover_finish(i, dec_st, inf, out_xy, status);
   }
 };
+// EC#sign on a user-defined ECDSA domain (Work::rt_sign_*): the nonce draw (HmacDRBG over the
+// caller's hash H, run-time n.byteLength() and n.bitLength()), k*G over the domain's comb, and the
+// scalar-field pass over the run-time n behind the affine conversion.  Everything per-domain they
+// need is in the parameter block already (n, nbits).
+// candidates per item before ellgpu_custom_sign_det gives up (ELLGPU_CUSTOM_SIGN_MAX_DRAWS): where n lies
+// just above a power of two half of all candidates are rejected, so the presets' 16 would not do
+constexpr int CUSTOM_SIGN_MAX_DRAWS = 64;
+template <class H>
+struct FnRtSignNonce {
+  static constexpr const char* NAME = "rt_sign_nonce";
+  typedef Work<CvCustomDomain> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* hash; int hash_len; int shift; const u8* priv; int draws; u8* nonces;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::template rt_sign_nonce<H>(i, hash, hash_len, shift, priv, draws, nonces);
+  }
+};
+struct FnRtSignMul {
+  static constexpr const char* NAME = "rt_sign_mul";
+  typedef Work<CvCustomDomain> W;
+  static constexpr int MIN_WAVES = ELL_FIXED_MIN_WAVES;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* nonces; const W::A* comb; u32* jac;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_sign_mul(i, n, nonces, comb, jac);
+  }
+};
+struct FnRtSignFinish {
+  static constexpr const char* NAME = "rt_sign_finish";
+  typedef Work<CvCustomDomain> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u8* hash; int hash_len; int shift; const u8* priv;
+  const u8* nonces; const u8* kg_xy; const u8* kg_inf; int canonical; u32* pre;
+  u8* out_r; u8* out_s; u8* out_recid; u8* out_ok;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) W::rt_sign_finish(t, T, n, K, hash, hash_len, shift, priv, nonces, kg_xy, kg_inf, canonical,
+                                 pre, out_r, out_s, out_recid, out_ok);
+  }
+};
 template <class CV>
 struct FnPointAdd {
   static constexpr const char* NAME = "point_add";
@@ -1283,6 +1322,11 @@ class Engine {
   template <int U = 0>
   int rt_recover_chunk(size_t n, const u8* hash, int hash_len, const u8* r, const u8* s, const u8* recid,
                        u8* out_xy, u8* out_status);
+  // EC#sign on a user-defined ECDSA domain: rt_sign_nonce (nonces == null: drawn over drbg_hash),
+  // rt_sign_mul, normalize, rt_sign_finish
+  template <int U = 0>
+  int rt_sign_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv, const u8* nonces,
+                    int drbg_hash, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok);
   template <class CV>
   int decompress_chunk(size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_ok);
   template <class CV>
@@ -2199,6 +2243,60 @@ class Engine {
     });
   }
 
+  // EC#sign (ec/index.js:110-186) on a domain: one pass of its loop for supplied nonces
+  // (nonces != null), or with the reference's own HmacDRBG over drbg_hash (nonces == null)
+  int check_custom_sign(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                        const u8* nonces, bool det, int drbg_hash, u8* out_r, u8* out_s, u8* out_recid,
+                        u8* out_ok, int& shift) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (!custom_is_domain(curve))
+      return fail(E_UNSUPPORTED, "ECDSA sign on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (n && (!hash || !priv || (!det && !nonces) || !out_r || !out_s || !out_recid || !out_ok))
+      return fail(E_ARG, "null pointer");
+    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
+    if (det && (drbg_hash < 0 || drbg_hash > 2)) return fail(E_ARG, "drbg_hash must be ELLGPU_HASH_SHA256, _SHA384 or _SHA512");
+    const int nbits = (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits;
+    rc = truncate_shift(hash_len, msg_bits, nbits, 8, shift);
+    if (rc) return rc;
+    // hmac-drbg's constructor: entropy of n.byteLength() bytes against hmacStrength = 192 bits
+    if (det && (nbits + 7) / 8 < 24)
+      return fail(E_UNSUPPORTED, "EC#sign throws on this domain: 'Not enough entropy. Minimum is: 192 bits' (n.byteLength() < 24)");
+    return E_OK;
+  }
+  int custom_sign_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                      const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                      u8* out_recid, u8* out_ok) {
+    int shift;
+    int rc = check_custom_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
+                               out_recid, out_ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    rc = ensure_comb<CvCustomDomain>();
+    if (rc) return rc;
+    const size_t HL = (size_t)hash_len;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_sign_chunk(m, hash + o * HL, hash_len, shift, priv + o * 32, det ? nullptr : nonces + o * 32,
+                           drbg_hash, canonical, out_r + o * 32, out_s + o * 32, out_recid + o, out_ok + o);
+    });
+  }
+  int custom_sign_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                       const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                       u8* out_recid, u8* out_ok) {
+    int shift;
+    int rc = check_custom_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
+                               out_recid, out_ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{hash, (size_t)hash_len}, In{priv, 32}, In{det ? nullptr : nonces, 32}},
+                  {Out{out_r, 32}, Out{out_s, 32}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto o) {
+      return custom_sign_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], det, drbg_hash, canonical, o[0], o[1],
+                             o[2], o[3]);
+    });
+  }
+
   // ---- host-buffer wrappers: stage through device buffers --------------------
   // An operand of a host-buffer call: n items of `stride` bytes.  A null host pointer is an absent
   // optional operand (the wrappers have refused the required ones): it gets no device copy, and
@@ -2763,6 +2861,45 @@ int Engine<BK>::rt_recover_chunk(size_t n, const u8* hash, int hash_len, const u
   if (rc) return rc;
   FnRtRecoverFinish f2{n, dec_st, inf, out_xy, out_status};
   bk.launch(f2, n);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_sign_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv,
+                              const u8* nonces, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                              u8* out_recid, u8* out_ok) {
+  typedef Work<CvCustomDomain> W;
+  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
+  u8* kg = (u8*)scratch(S_U12, n * (2 * W::BYTES + 1));          // k*G affine + infinity flags
+  if (!jac || !kg) return fail(E_NOMEM, "scratch allocation failed");
+  u8* kg_inf = kg + n * 2 * W::BYTES;
+  if (!nonces) {
+    u8* drawn = (u8*)scratch(S_TBL, n * W::NBYTES);       // the passes below use S_JAC / S_U12 / S_PRE
+    if (!drawn) return fail(E_NOMEM, "scratch allocation failed");
+    if (drbg_hash == 0) {
+      FnRtSignNonce<Sha256> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
+      bk.launch(f, n);
+    } else if (drbg_hash == 1) {
+      FnRtSignNonce<Sha384> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
+      bk.launch(f, n);
+    } else {
+      FnRtSignNonce<Sha512> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
+      bk.launch(f, n);
+    }
+    nonces = drawn;
+  }
+  FnRtSignMul f1{n, nonces, comb_of<CvCustomDomain>(), jac};
+  bk.launch(f1, n);
+  int rc = normalize_chunk<CvCustomDomain>(n, jac, kg, kg_inf, nullptr);
+  if (rc) return rc;
+  u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
+  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
+  const int Kf = inv_batch_for(n, INV_BATCH_N);
+  const size_t T = (n + Kf - 1) / Kf;
+  FnRtSignFinish f2{T, n, Kf, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre,
+                    out_r, out_s, out_recid, out_ok};
+  bk.launch(f2, T);
   return E_OK;
 }
 

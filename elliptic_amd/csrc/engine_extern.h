@@ -82,7 +82,7 @@ namespace ell {
                                                    const u8*, const u8*, const u8*, u8*, u8*);       \
   KW template int Engine<HipBackend>::rt_wire_chunk<0>(int, size_t, const u8*, const u8*, size_t,    \
                                                        const u32*, u8*, u8*, u8*);
-// user-defined ECDSA domains (CvCustomDomain): verify, recovery, k*G and k1*G + k2*Q -- their own translation
+// user-defined ECDSA domains (CvCustomDomain): verify, recovery, sign, k*G and k1*G + k2*Q -- their own translation
 // unit (group 17, with its own parameter block); the window ladder of the comb build is CvCustom's
 #define ELL_DECL_DOMAIN(KW)                                                                          \
   KW template int Engine<HipBackend>::ensure_comb<CvCustomDomain>();                                 \
@@ -95,7 +95,9 @@ namespace ell {
                                                                   const u8*, const u8*, const u8*,   \
                                                                   u8*, u8*);                         \
   KW template int Engine<HipBackend>::rt_recover_chunk<0>(size_t, const u8*, int, const u8*,         \
-                                                          const u8*, const u8*, u8*, u8*);
+                                                          const u8*, const u8*, u8*, u8*);           \
+  KW template int Engine<HipBackend>::rt_sign_chunk<0>(size_t, const u8*, int, int, const u8*,       \
+                                                       const u8*, int, int, u8*, u8*, u8*, u8*);
 #define ELL_DECL_ED2(KW)                                                                            \
   KW template int Engine<HipBackend>::ed_decompress_chunk<0>(size_t, const u8*, const u8*, u8*, u8*); \
   KW template int Engine<HipBackend>::ed_codec_chunk<0>(int, size_t, const u8*, int, const u8*, u8*, u8*); \

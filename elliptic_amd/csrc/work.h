@@ -1263,6 +1263,175 @@ struct Work {
     }
   }
 
+  // ---- EC#sign on a user-defined ECDSA domain (run-time p and n, fp_rt.h) ---------------------
+  // Three of the presets' shortcuts do not hold there, so nothing above is reused:
+  //   * the nonce's shift (_truncateToN(k, true), k a BN: 8 * byteLength(value) - n.bitLength()
+  //     when positive) depends on the VALUE: on secp224k1 (225-bit n in 29 bytes) a 29-byte value
+  //     shifts by 7, one with a zero top byte does not, a supplied 32-byte value shifts by 31;
+  //   * r = x mod n is a general reduction: n may exceed p (no subtraction), p / n may be 8;
+  //   * the recovery parameter's second bit is x != r, whatever floor(p / n) is.
+  // n.bitLength() is the block's nbits, n.byteLength() follows from it.
+  ELL_HD static int rt_order_bytes() { return ((int)ELL_RT.nbits + 7) >> 3; }
+  // v (a 32-byte big-endian integer) -> k = v >> max(0, 8 * byteLength(v) - n.bitLength()), by selects
+  ELL_HD static void rt_truncate_nonce(u32 (&k)[LN], const u32 (&v)[LN]) {
+    static_assert(CV::RT_ORDER && LN == 8, "user-defined domains only");
+    int bl = 0;
+    ELL_UNROLL
+    for (int b = 0; b < 4 * LN; b++) bl = ((v[b >> 2] >> (8 * (b & 3))) & 0xffu) ? b + 1 : bl;
+    int sh = 8 * bl - (int)ELL_RT.nbits;
+    sh = sh > 0 ? sh : 0;
+    const int ws = sh >> 5, bs = sh & 31;
+    u32 w[LN + 1];
+    ELL_UNROLL
+    for (int i = 0; i <= LN; i++) {                 // w = v >> 32 ws, one word of zeros above
+      u32 x = 0;
+      ELL_UNROLL
+      for (int j = 0; j < LN; j++) x = (j == i + ws) ? v[j] : x;
+      w[i] = x;
+    }
+    ELL_UNROLL
+    for (int i = 0; i < LN; i++) k[i] = bs ? ((w[i] >> bs) | (w[i + 1] << ((32 - bs) & 31))) : w[i];
+  }
+  ELL_HD static void rt_load_nonce(u32 (&k)[LN], const u8* kb) {
+    u32 v[LN];
+    load_be<LN>(v, kb, NBYTES);
+    rt_truncate_nonce(k, v);
+  }
+  ELL_HD static bool rt_nonce_ok(const u32 (&k)[LN]) {          // 1 < k < n - 1 (ec/index.js:158)
+    u32 nn[LN], nm1[LN], one1[LN];
+    order_words(nn);
+    ELL_UNROLL
+    for (int l = 0; l < LN; l++) one1[l] = l == 0 ? 1u : 0u;
+    bn_sub<LN>(nm1, nn, one1);
+    return !bn_is_zero<LN>(k) && !bn_eq<LN>(k, one1) && !bn_geq<LN>(k, nm1);
+  }
+  // msg = _truncateToN(hash, false, msg_bits): the shift is the host's, then ONE subtraction of n
+  ELL_HD static void rt_load_msg(u32 (&e)[LN], const u8* h, int hash_len, int shift) {
+    u32 nn[LN], t[LN];
+    order_words(nn);
+    load_hash(e, h, hash_len, shift);
+    u32 br = bn_sub<LN>(t, e, nn);
+    bn_select<LN>(e, br == 0, t, e);
+  }
+  // EC#sign's own nonce (ec/index.js:141-159) for item i: HmacDRBG over H, entropy = priv mod n and
+  // nonce = msg as n.byteLength() bytes each, generate(n.byteLength()) per candidate with the
+  // reseed in front of every further one, at most `draws` candidates.  Writes the accepted
+  // candidate as a 32-byte integer (what the supplied-nonce passes below take: its byte length,
+  // and so its shift, is the draw's), zeros where none was accepted.
+  template <class H>
+  ELL_HD static void rt_sign_nonce(size_t i, const u8* hash, int hash_len, int shift, const u8* priv, int draws,
+                                   u8* nonce_out) {
+    static_assert(CV::RT_ORDER && LN == 8, "user-defined domains only");
+    const int nb = rt_order_bytes();
+    alignas(4) u8 eb[NBYTES], pb[NBYTES], kb[NBYTES];
+    {
+      u32 e[LN], d[LN];
+      rt_load_msg(e, hash + i * (size_t)hash_len, hash_len, shift);
+      store_be<LN>(eb, e, NBYTES);
+      load_priv_mod_n(d, priv, i);
+      store_be<LN>(pb, d, NBYTES);
+    }
+    HmacDrbg<H> g;
+    g.init(pb + (NBYTES - nb), nb, eb + (NBYTES - nb), nb);
+    u32 v[LN];
+    bool done = false;
+    ELL_NOUNROLL
+    for (int it = 0; it < draws && !done; it++) {
+      if (it) g.reseed();
+      ELL_NOUNROLL
+      for (int b = 0; b < NBYTES - nb; b++) kb[b] = 0;
+      g.draw(kb + (NBYTES - nb), nb);
+      u32 k[LN];
+      load_be<LN>(v, kb, NBYTES);
+      rt_truncate_nonce(k, v);
+      done = rt_nonce_ok(k);
+    }
+    ELL_UNROLL
+    for (int l = 0; l < LN; l++) v[l] = done ? v[l] : 0u;
+    store_be<LN>(nonce_out + i * NBYTES, v, NBYTES);
+  }
+  // k*G over the domain's comb for every nonce -> Jacobian scratch (then normalize -> affine)
+  ELL_HD static void rt_sign_mul(size_t i, size_t n, const u8* nonces, const A* comb, u32* jac) {
+    u32 k[LN];
+    rt_load_nonce(k, nonces + i * NBYTES);
+    J r = LD::template comb_mul<L, COMB_W, COMB_BITS, COMB_SIGNED>(k, comb);
+    store_jac(jac, n, i, r);
+  }
+  // the scalar-field pass: thread t finishes items t, t+T, ... with one inversion per K items.
+  // ok = 0 (r, s, recid zeroed) exactly where the reference goes on to its next nonce: k <= 1,
+  // k >= n - 1, k*G = O, r = 0, s = 0.
+  ELL_HD static void rt_sign_finish(size_t t, size_t T, size_t n, int K, const u8* hash, int hash_len,
+                                    int shift, const u8* priv, const u8* nonces, const u8* kg_xy,
+                                    const u8* kg_inf, int canonical, u32* pre, u8* out_r, u8* out_s,
+                                    u8* out_recid, u8* out_ok) {
+    static_assert(CV::RT_ORDER && L == 8 && LN == 8, "user-defined domains only");
+    u32 nn[LN];
+    order_words(nn);
+    Nl acc = Fn::one();
+    ELL_NOUNROLL
+    for (int j = 0; j < K; j++) {
+      size_t i = t + (size_t)j * T;
+      if (i >= n) break;
+      u32 k[LN];
+      rt_load_nonce(k, nonces + i * NBYTES);
+      bool ok = rt_nonce_ok(k) && kg_inf[i] == 0;
+      out_ok[i] = ok ? 1 : 0;
+      Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
+      acc = Fn::mul(acc, km);
+    }
+    Nl inv = Fn::inv(acc);
+    ELL_NOUNROLL
+    for (int j = K - 1; j >= 0; j--) {
+      size_t i = t + (size_t)j * T;
+      if (i >= n) continue;
+      u32 k[LN], e[LN], d[LN], x[L], y[L];
+      rt_load_nonce(k, nonces + i * NBYTES);
+      rt_load_msg(e, hash + i * (size_t)hash_len, hash_len, shift);
+      load_be<LN>(d, priv + i * NBYTES, NBYTES);
+      load_be<L>(x, kg_xy + i * 2 * BYTES, BYTES);
+      load_be<L>(y, kg_xy + i * 2 * BYTES + BYTES, BYTES);
+      bool ok = out_ok[i] != 0;
+      Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
+      Nl pr;
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
+      Nl kinv = Fn::mul(inv, pr);
+      inv = Fn::mul(inv, km);
+      // r = x mod n, a general reduction (x < p < 2^256, n anything): into the order field and out
+      u32 r[LN];
+      Fn::to_plain(r, Fn::from_plain(x));
+      const bool wrapped = !bn_eq<LN>(r, x);
+      // s = k^-1 (msg + r d): (r) * (d R) / R = r d as a plain residue, msg joins it reduced (the
+      // one subtraction leaves it below n only while msg_bits does not exceed the digest's own
+      // bits), and (msg + r d) * (k^-1 R) / R is s, plain.  d is any 32-byte value: d R mod n.
+      Nl rp, ep;
+      bn_copy<LN>(rp.v, r);
+      Fn::to_plain(ep.v, Fn::from_plain(e));
+      Nl sm = Fn::mul(Fn::add(Fn::mul(rp, Fn::from_plain(d)), ep), kinv);
+      u32 sp[LN];
+      bn_copy<LN>(sp, sm.v);
+      ok = ok && !bn_is_zero<LN>(r) && !bn_is_zero<LN>(sp);
+      u32 recid = (y[0] & 1u) | (wrapped ? 2u : 0u);
+      // low-s form: s > n >> 1  ->  s = n - s, recid ^= 1
+      u32 nh[LN], ns[LN];
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) nh[l] = (nn[l] >> 1) | (l + 1 < LN ? nn[l + 1] << 31 : 0u);
+      bool high = canonical && !bn_geq<LN>(nh, sp);
+      bn_sub<LN>(ns, nn, sp);
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) sp[l] = high ? ns[l] : sp[l];
+      recid ^= high ? 1u : 0u;
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) { r[l] = ok ? r[l] : 0u; sp[l] = ok ? sp[l] : 0u; }
+      store_be<LN>(out_r + i * NBYTES, r, NBYTES);
+      store_be<LN>(out_s + i * NBYTES, sp, NBYTES);
+      out_recid[i] = (u8)(ok ? recid : 0u);
+      out_ok[i] = ok ? 1 : 0;
+    }
+  }
+
   // JPoint#eqXToP (short.js:908-925): X == r*Z^2, retry with r+n while < p.
   // (for every preset p < 2n, so one retry at most)
   ELL_HD static bool eq_x_to_p(const J& p, const u32 (&r)[LN]) {

@@ -27,6 +27,9 @@ ORDER_BYTES = dict(FIELD_BYTES)
 # operand is not on the curve -- outside the engine's domain, reported instead of guessed (the
 # reference computes with such points, and its answer depends on the order of its own operations)
 STATUS_OFF_CURVE = 2
+# Context.custom_sign_det's drbg_hash (include/ellgpu.h ELLGPU_HASH_*) and its cap on candidates per item
+HASH_SHA256, HASH_SHA384, HASH_SHA512 = 0, 1, 2
+CUSTOM_SIGN_MAX_DRAWS = 64
 # user-defined short curves (Context.define_short) are addressed by the integer id the library
 # hands out; their scalars and coordinates are 32 bytes wide whatever the prime's size
 CURVE_CUSTOM0 = 16
@@ -475,6 +478,58 @@ class Context:
                                                         hash_len, r.data_ptr(), s.data_ptr(), recid.data_ptr(),
                                                         out_xy.data_ptr(), out_status.data_ptr(),
                                                         self._stream()))
+
+    def custom_sign(self, curve, hashes, priv, nonces, canonical=False, msg_bits=0, out=None):
+        """one pass of EC#sign per item on a domain id for supplied nonces -> (r, s, recid, ok).
+        hashes (n, 1..64); priv, nonces (n, 32) big-endian: priv is reduced mod n, a nonce v stands
+        for k = v >> max(0, 8 byteLength(v) - n.bitLength()) as options.k's BN does; ok = 0 (r, s,
+        recid zeroed) where the reference goes on to its next nonce"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        priv = _u8(priv, (n, 32))
+        nonces = _u8(nonces, (n, 32))
+        r, s, rec, ok = self._outs(out, [(n, 32), (n, 32), (n,), (n,)])
+        self._check(self._lib.ellgpu_custom_sign(self._ctx, self._cid(curve), n, hashes.ctypes.data, hash_len,
+                                                 int(msg_bits), priv.ctypes.data, nonces.ctypes.data,
+                                                 1 if canonical else 0, r.ctypes.data, s.ctypes.data,
+                                                 rec.ctypes.data, ok.ctypes.data))
+        return r, s, rec, ok
+
+    def custom_sign_dev(self, curve, hashes, priv, nonces, out_r, out_s, out_recid, out_ok, canonical=False,
+                        msg_bits=0):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_sign_dev(self._ctx, self._cid(curve), n, hashes.data_ptr(), hash_len,
+                                                     int(msg_bits), priv.data_ptr(), nonces.data_ptr(),
+                                                     1 if canonical else 0, out_r.data_ptr(), out_s.data_ptr(),
+                                                     out_recid.data_ptr(), out_ok.data_ptr(), self._stream()))
+
+    def custom_sign_det(self, curve, hashes, priv, drbg_hash=HASH_SHA256, canonical=False, msg_bits=0, out=None):
+        """EC#sign per item on a domain id with the reference's own HmacDRBG nonces over drbg_hash
+        (HASH_SHA256 / HASH_SHA384 / HASH_SHA512: the caller's options.hash) -> (r, s, recid, ok);
+        at most CUSTOM_SIGN_MAX_DRAWS candidates per item.  Unsupported where n.byteLength() < 24
+        (the reference throws 'Not enough entropy')"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        priv = _u8(priv, (n, 32))
+        r, s, rec, ok = self._outs(out, [(n, 32), (n, 32), (n,), (n,)])
+        self._check(self._lib.ellgpu_custom_sign_det(self._ctx, self._cid(curve), n, hashes.ctypes.data, hash_len,
+                                                     int(msg_bits), priv.ctypes.data, int(drbg_hash),
+                                                     1 if canonical else 0, r.ctypes.data, s.ctypes.data,
+                                                     rec.ctypes.data, ok.ctypes.data))
+        return r, s, rec, ok
+
+    def custom_sign_det_dev(self, curve, hashes, priv, out_r, out_s, out_recid, out_ok, drbg_hash=HASH_SHA256,
+                            canonical=False, msg_bits=0):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_sign_det_dev(self._ctx, self._cid(curve), n, hashes.data_ptr(),
+                                                         hash_len, int(msg_bits), priv.data_ptr(), int(drbg_hash),
+                                                         1 if canonical else 0, out_r.data_ptr(),
+                                                         out_s.data_ptr(), out_recid.data_ptr(),
+                                                         out_ok.data_ptr(), self._stream()))
 
     def ecdsa_sign(self, curve, hashes, priv, nonces, canonical=False, msg_bits=0):
         """one pass of EC#sign per item for supplied nonces -> (r, s, recid, ok)"""

@@ -45,12 +45,18 @@
  *             -> {ok, err}: the same three on a user-defined short curve / domain (ellgpu_custom_*)
  *           customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy, status}: EC#recoverPubKey on a
  *             user-defined domain (ellgpu_custom_recover; 32-byte r, s and coordinates, hashLen 1..64)
+ *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
+ *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
+ *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
+ *             nonces, r and s; drbgHash 0 sha256, 1 sha384, 2 sha512)
  *             offsets: Buffer of n+1 little-endian uint64 byte offsets into msgs
  *           callAsync(op, ctx, curve, hashLen, msgBits, b0, b1, b2, b3) -> Promise
  *             op 0 mulFixed(b0=k) 1 mulVar(k, xy) 2 mulAdd2(k1, p1|null, k2, p2)
  *             3 ecdsaVerify(hash, r, s, pub) 4 x25519(k, x) 5 ecdsaSignDet(hash, priv; i0 = canonical)
  *             6 ecdsaRecover(hash, r, s, recid) 7 ecdsaVerifyWire(hash, der, lens, keys; i0 = der
  *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length) 9 customVerifyWire (as 7); 10 customRecover (as 6);
+ *             11 customSign(hash, priv, nonces; i0 = canonical) 12 customSignDet(hash, priv; i0 = canonical,
+ *             i1 = drbgHash);
  *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
@@ -122,6 +128,10 @@ static struct {
   int (*custom_decode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, size_t, uint8_t*, uint8_t*);
   int (*custom_recover)(ellgpu_ctx*, int, size_t, const uint8_t*, int, const uint8_t*, const uint8_t*,
                         const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_sign)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*, int,
+                     uint8_t*, uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_sign_det)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, int, int,
+                         uint8_t*, uint8_t*, uint8_t*, uint8_t*);
   int (*custom_verify_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, size_t,
                             const uint32_t*, const uint8_t*, size_t, uint8_t*, uint8_t*);
 } L;
@@ -185,6 +195,8 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(custom_decode_points, "ellgpu_custom_decode_points");
   SYM(custom_verify_wire, "ellgpu_custom_verify_wire");
   SYM(custom_recover, "ellgpu_custom_recover");
+  SYM(custom_sign, "ellgpu_custom_sign");
+  SYM(custom_sign_det, "ellgpu_custom_sign_det");
   L.h = h;
   napi_value t; CHECK(env, napi_get_boolean(env, 1, &t));
   return t;
@@ -622,6 +634,46 @@ static napi_value fn_sign_det(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) and
+ * customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok} */
+static napi_value custom_sign_with(napi_env env, napi_callback_info info, int det) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 8; napi_value argv[8];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  int32_t curve, hl, mb, dh = 0; bool canon = 0;
+  if (argc < 8 || napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
+      napi_get_value_int32(env, argv[4], &mb) != napi_ok || (det && napi_get_value_int32(env, argv[6], &dh) != napi_ok))
+    THROW(env, det ? "customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical)"
+                   : "customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical)");
+  napi_get_value_bool(env, argv[7], &canon);
+  if (hl <= 0) THROW(env, "bad hashLen");
+  const uint8_t *h, *d, *k = NULL; size_t lh, ld, lk = 0;
+  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &d, &ld, 0)) return NULL;
+  if (!det && !get_buf(env, argv[6], &k, &lk, 0)) return NULL;
+  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
+  size_t n = lh / (size_t)hl;
+  if (ld != n * 32 || (!det && lk != ld)) THROW(env, "buffer length mismatch");
+  napi_value br, bs, brec, bok, o; void *dr, *dsg, *drec, *dok;
+  CHECK(env, result_buffer(env, n * 32, &dr, &br));
+  CHECK(env, result_buffer(env, n * 32, &dsg, &bs));
+  CHECK(env, result_buffer(env, n, &drec, &brec));
+  CHECK(env, result_buffer(env, n, &dok, &bok));
+  int rc = det ? L.custom_sign_det(c, curve, n, h, hl, mb, d, dh, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg,
+                                   (uint8_t*)drec, (uint8_t*)dok)
+               : L.custom_sign(c, curve, n, h, hl, mb, d, k, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg, (uint8_t*)drec,
+                               (uint8_t*)dok);
+  if (rc != 0) return lib_error(env);
+  CHECK(env, napi_create_object(env, &o));
+  CHECK(env, napi_set_named_property(env, o, "r", br));
+  CHECK(env, napi_set_named_property(env, o, "s", bs));
+  CHECK(env, napi_set_named_property(env, o, "recid", brec));
+  CHECK(env, napi_set_named_property(env, o, "ok", bok));
+  return o;
+}
+static napi_value fn_custom_sign(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 0); }
+static napi_value fn_custom_sign_det(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 1); }
+
 /* ecdsaRecover / customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy: Buffer(n*2B), status: Buffer(n)} */
 static napi_value recover_with(napi_env env, napi_callback_info info, int custom) {
   if (!need_lib(env)) return NULL;
@@ -898,6 +950,10 @@ static void job_execute(napi_env env, void* data) {
                                          j->out1); break;
     case 10: j->rc = L.custom_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
                                       j->out0, j->out1); break;
+    case 11: j->rc = L.custom_sign(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2], j->i0,
+                                   j->out0, j->out1, j->out2, j->out3); break;
+    case 12: j->rc = L.custom_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1, j->i0,
+                                       j->out0, j->out1, j->out2, j->out3); break;
     default: j->rc = L.decode_points(j->ctx, j->curve, j->n, j->in[0], (size_t)j->i0, j->out0, j->out1); break;
   }
   if (j->rc != 0) {               /* last_error is thread-local: read it on this thread */
@@ -911,10 +967,10 @@ static void job_complete(napi_env env, napi_status status, void* data) {
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
     /* result property names per op, in output order */
-    static const char* const names[11][4] = {
+    static const char* const names[13][4] = {
       {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
       {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
-      {"ok", "err", 0, 0}, {"xy", "status", 0, 0}};
+      {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -959,7 +1015,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
   j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
   j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > 10 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
+  if (op < 0 || op > 12 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
   int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
@@ -983,6 +1039,10 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
     case 5: ok = hl > 0 && j->in[0] && j->in[1] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB; break;
+    case 11: case 12:
+            ok = hl > 0 && j->in[0] && j->in[1] && (op == 12 || j->in[2]) && len[0] % (size_t)hl == 0;
+            j->n = ok ? len[0] / (size_t)hl : 0;
+            ok = ok && len[1] == j->n * NB && (op == 12 || len[2] == j->n * NB); break;
     case 6: case 10:
             ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
@@ -1000,10 +1060,10 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
     free(j);
     THROW(env, "callAsync: buffer length mismatch");
   }
-  j->out0_len = op == 3 || op == 7 || op == 9 ? j->n : op == 4 ? j->n * 32 : op == 5 ? j->n * NB : j->n * 2 * B;
-  j->out1_len = op == 5 ? j->n * NB : j->n;
-  j->out2_len = op == 5 ? j->n : 0;
-  j->out3_len = op == 5 ? j->n : 0;
+  j->out0_len = op == 3 || op == 7 || op == 9 ? j->n : op == 4 ? j->n * 32 : op == 5 || op >= 11 ? j->n * NB : j->n * 2 * B;
+  j->out1_len = op == 5 || op >= 11 ? j->n * NB : j->n;
+  j->out2_len = op == 5 || op >= 11 ? j->n : 0;
+  j->out3_len = op == 5 || op >= 11 ? j->n : 0;
   j->out0 = (uint8_t*)malloc(j->out0_len ? j->out0_len : 1);
   j->out1 = (uint8_t*)malloc(j->out1_len ? j->out1_len : 1);
   j->out2 = (uint8_t*)malloc(j->out2_len ? j->out2_len : 1);
@@ -1035,6 +1095,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"pointAdd", fn_point_add}, {"sigFromDer", fn_sig_from_der}, {"sigToDer", fn_sig_to_der}, {"ecdsaVerifyWire", fn_verify_wire},
     {"customDecompress", fn_custom_decompress}, {"customDecodePoints", fn_custom_decode_points},
     {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
+    {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -300,6 +300,24 @@ Engine.prototype.customRecoverBatch = function customRecoverBatch(curve, hashes,
   this.stats.gpuCalls++; this.stats.gpuItems += recid.length;
   return this.addon.customRecover(this.ctx, this._id(curve), hashes, hashLen, r, s, recid);
 };
+// customSignBatch: one pass of EC#sign per item on a domain id for supplied nonces; hashes
+// Buffer(n x hashLen), hashLen 1..64, msgBits = options.msgBitLength or 0; priv, nonces Buffer(n x 32)
+// big-endian -- priv is reduced mod n, a nonce v stands for k = v >> max(0, 8 byteLength(v) -
+// n.bitLength()) as a BN from options.k does -> { r, s: Buffer(n x 32), recid, ok: Buffer(n) };
+// ok = 0 (r, s, recid zeroed) where the reference goes on to its next nonce
+Engine.prototype.customSignBatch = function customSignBatch(curve, hashes, hashLen, msgBits, priv, nonces, canonical) {
+  this.stats.gpuCalls++; this.stats.gpuItems += priv.length / 32;
+  return this.addon.customSign(this.ctx, this._id(curve), hashes, hashLen, msgBits | 0, priv, nonces, !!canonical);
+};
+// customSignDetBatch: EC#sign per item with the reference's own HmacDRBG nonces over drbgHash
+// ('sha256' | 'sha384' | 'sha512' or 0 | 1 | 2: the caller's options.hash); throws where
+// n.byteLength() < 24, as EC#sign does ('Not enough entropy')
+var DRBG_HASH = { sha256: 0, sha384: 1, sha512: 2 };
+function drbgHashId(h) { return typeof h === 'string' && h in DRBG_HASH ? DRBG_HASH[h] : h | 0; }
+Engine.prototype.customSignDetBatch = function customSignDetBatch(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
+  this.stats.gpuCalls++; this.stats.gpuItems += priv.length / 32;
+  return this.addon.customSignDet(this.ctx, this._id(curve), hashes, hashLen, msgBits | 0, priv, drbgHashId(drbgHash), !!canonical);
+};
 
 // KeyPair#derive per item (ec/key.js:102-107): priv Buffer(n x B), pub Buffer(n x 2B) ->
 // { x: Buffer(n x B), status: Buffer(n) }; status 0 shared secret, 1 'public point not validated',
@@ -393,6 +411,12 @@ Engine.prototype.customVerifyWireBatchAsync = function(curve, o) {
 };
 Engine.prototype.customRecoverBatchAsync = function(curve, hashes, hashLen, r, s, recid) {
   return this._async(10, curve, hashLen, 0, hashes, r, s, recid);
+};
+Engine.prototype.customSignBatchAsync = function(curve, hashes, hashLen, msgBits, priv, nonces, canonical) {
+  return this._async(11, curve, hashLen, msgBits | 0, hashes, priv, nonces, null, canonical ? 1 : 0, 0);
+};
+Engine.prototype.customSignDetBatchAsync = function(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
+  return this._async(12, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
 };
 Engine.prototype.decodePointBatchAsync = function(curve, enc, encLen) {
   return this._async(8, curve, 0, 0, enc, null, null, null, encLen, 0);

@@ -216,7 +216,8 @@ int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* 
  * Every other preset-named entry point (wire / DER, sign, sign_det, recover, decompress, decode,
  * validate) answers ELLGPU_E_UNSUPPORTED on a domain id; compressed keys, SEC1 encodings and DER
  * signatures on a domain go through ellgpu_custom_decompress / _custom_decode_points /
- * _custom_verify_wire below, public-key recovery through ellgpu_custom_recover.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
+ * _custom_verify_wire below, public-key recovery through ellgpu_custom_recover, signing through
+ * ellgpu_custom_sign / _custom_sign_det.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
  * without p1 and ecdsa_verify stay ELLGPU_E_UNSUPPORTED. */
 int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                                      const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve);
@@ -293,6 +294,61 @@ int ellgpu_custom_recover(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* h
 int ellgpu_custom_recover_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                               const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
                               uint8_t* out_status, void* stream);
+/* EC#sign(msg, key, options) (lib/elliptic/ec/index.js:110-186) on a DOMAIN id, on the device.
+ * Entry points of their own because ellgpu_ecdsa_sign / _sign_det are documented to refuse
+ * user-defined ids (and keep doing so).  ELLGPU_E_UNSUPPORTED on a plain ellgpu_curve_define_short
+ * id or a user-defined Edwards id, ELLGPU_E_ARG on a preset id -- as ellgpu_custom_recover.
+ * Synchronous like every call on a user-defined curve; a group runs them on its first member.
+ *   hash     n x hash_len bytes, 1 <= hash_len <= 64; hash_len and msg_bits (options.msgBitLength,
+ *            0 = 8 hash_len) as for ellgpu_ecdsa_verify on a domain:
+ *            msg = _truncateToN(hash, false, msg_bits) = hash >> max(0, bits - n.bitLength()), then ONE
+ *            conditional subtraction of n
+ *   priv     n x 32 bytes big-endian, any value: reduced mod n (KeyPair#_importPrivate)
+ *   nonces   (ellgpu_custom_sign) n x 32 bytes big-endian, what options.k(iter) returns as a BN
+ *   out_r, out_s  n x 32 bytes big-endian;  out_recid, out_ok: n bytes; out_ok is strictly 0 / 1
+ * ellgpu_custom_sign is ONE pass of the reference's loop per item.  Three things differ from the presets:
+ *   - k = _truncateToN(v, true) of a BN v is v >> max(0, 8 byteLength(v) - n.bitLength()): the shift
+ *     depends on the VALUE's own byte length.  On secp224k1 (225-bit n in 29 bytes) a 29-byte value
+ *     with a non-zero top byte shifts by 7, one with a zero top byte does not shift, and a supplied
+ *     value wider than n.byteLength() shifts by more.
+ *   - r = x(k G) mod n is a general reduction: nothing ties n to p.  Where n > p nothing is
+ *     subtracted, on a cofactor-8 curve n may be subtracted several times.
+ *   - recid = (y odd) | (x != r ? 2 : 0): one bit however large floor(p / n) is.
+ * s = k^-1 (msg + r priv) mod n; with canonical != 0 and s > n >> 1: s = n - s, recid ^= 1.
+ * out_ok = 0 (r, s, recid zeroed) exactly where the reference goes on to its next nonce:
+ * k <= 1, k >= n - 1, k G at infinity, r = 0, s = 0.
+ *
+ * ellgpu_custom_sign_det draws the nonces itself: HmacDRBG (hmac-drbg 1.0.1, no pers) over drbg_hash --
+ * a user-defined curve's hash is the caller's options.hash, hence an argument; any other value is
+ * ELLGPU_E_ARG -- with entropy = priv mod n and nonce = msg as n.byteLength() bytes each, and
+ * generate(n.byteLength()) per candidate.  A candidate outside 1 < k < n - 1 is followed by the next, up to
+ * ELLGPU_CUSTOM_SIGN_MAX_DRAWS per item (the presets' 16 would be too few: where n lies just above a
+ * power of two -- secp224k1, the 253-bit n of a cofactor-8 curve -- half of all candidates are
+ * rejected); an item that exhausts them, or whose accepted candidate gives k G at infinity, r = 0 or
+ * s = 0 (as likely as guessing a key), is out_ok = 0.
+ * On a domain with n.byteLength() < 24 ellgpu_custom_sign_det answers ELLGPU_E_UNSUPPORTED: the
+ * reference's EC#sign throws there ('Not enough entropy. Minimum is: 192 bits' -- hmacStrength is 192
+ * for all three hashes and the DRBG is constructed before the loop, whatever options.k is), so EC#sign
+ * itself is undefined on such a domain.  ellgpu_custom_sign stays usable there, as the arithmetic of
+ * one pass of the loop.  The same holds for a msg_bits that leaves msg wider than n.byteLength()
+ * bytes: the reference throws in BN#toArray; here s is computed with msg reduced mod n, and the
+ * DRBG is seeded with msg's low n.byteLength() bytes. */
+#define ELLGPU_HASH_SHA256 0
+#define ELLGPU_HASH_SHA384 1
+#define ELLGPU_HASH_SHA512 2
+#define ELLGPU_CUSTOM_SIGN_MAX_DRAWS 64
+int ellgpu_custom_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok);
+int ellgpu_custom_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                           const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                           uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream);
+int ellgpu_custom_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                           const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r, uint8_t* out_s,
+                           uint8_t* out_recid, uint8_t* out_ok);
+int ellgpu_custom_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                               int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
+                               uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream);
 /* User-defined (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) over an odd prime
  * p < 2^256 -- `new elliptic.curve.edwards({p, a, c: 1, d, ...})` (lib/elliptic/curve/edwards.js:
  * 11-31) with parameters that are not ed25519's.  Same id space, widths (32 bytes) and entry

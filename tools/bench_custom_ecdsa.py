@@ -24,7 +24,16 @@ random, the verify's keys are random points.  Recovery is one square root and on
 inversion more than a verify; "kernels_ms" are the launches of one recovery call
 (ellgpu_ctx_set_timing).
 
-    python tools/bench_custom_ecdsa.py --recover [log2 n ...]                  (default: 16 18)"""
+    python tools/bench_custom_ecdsa.py --recover [log2 n ...]                  (default: 16 18)
+
+--sign: signing on the domain (brainpoolP256r1) -- custom_sign_dev over supplied nonces and
+custom_sign_det_dev with its own HmacDRBG (SHA-256) nonces -- beside the verify, the recovery and
+k*G (mul_fixed_dev) of the same domain in the same run.  k*G is the floor no signature can beat
+("sign_over_mul_fixed"); "sign_det_over_sign" is what the DRBG costs.  Every signature is
+asserted accepted, the signatures of the deterministic call are then verified and their keys
+recovered; "kernels_ms" are the launches of one custom_sign_det call.
+
+    python tools/bench_custom_ecdsa.py --sign [log2 n ...]                     (default: 18 20)"""
 import json
 import os
 import sys
@@ -182,6 +191,57 @@ def run_recover(ctx, spec, n):
     return out
 
 
+def run_sign(ctx, spec, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_domain_checks as CD
+    cid = CD.define(ctx, spec)
+    nn = CD.I(spec["n"])
+    keep = nn.bit_length() - 1                      # scalars below 2^(bitLength(n) - 1) < n
+    def below_n(tag):
+        a = bench.xof("custom-sign:%s:%s" % (spec["name"], tag), n * 32).reshape(n, 32).copy()
+        a[:, :32 - (keep + 7) // 8] = 0
+        if keep % 8:
+            a[:, 32 - (keep + 7) // 8] &= (1 << (keep % 8)) - 1
+        a[:, 31] |= 3                               # 1 < k
+        return a
+    d, k = below_n("d"), below_n("k")
+    h = bench.xof("custom-sign:h", n * 32).reshape(n, 32).copy()
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    z = lambda *sh: torch.zeros(*sh, dtype=torch.uint8, device=dev)
+    dh, dd, dk = t(h), t(d), t(k)
+    r1, s1, j1, ok1 = z(n, 32), z(n, 32), z(n), z(n)
+    r2, s2, j2, ok2 = z(n, 32), z(n, 32), z(n), z(n)
+    dq, dinf, dxy, dst, ver = z(n, 64), z(n), z(n, 64), z(n), z(n)
+    ctx.mul_fixed_dev(cid, dd, dq, dinf)
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": spec["name"], "n": n}
+    for name, fn in (("mul_fixed", lambda: ctx.mul_fixed_dev(cid, dd, dxy, dinf)),
+                     ("sign", lambda: ctx.custom_sign_dev(cid, dh, dd, dk, r1, s1, j1, ok1, canonical=True)),
+                     ("sign_det", lambda: ctx.custom_sign_det_dev(cid, dh, dd, r2, s2, j2, ok2, drbg_hash=0,
+                                                                  canonical=True)),
+                     ("verify", lambda: ctx.ecdsa_verify_dev(cid, dh, r2, s2, dq, ver)),
+                     ("recover", lambda: ctx.custom_recover_dev(cid, dh, r2, s2, j2, dxy, dst))):
+        ms = timed(fn)
+        out[name + "_ms"] = round(ms, 3)
+        out[name + "_M_per_s"] = round(n / ms / 1e3, 2)
+    # every item signed; the deterministic signatures verify and give their keys back (32-byte
+    # digests on a 256-bit n: recovery sees the digest the signature was made over)
+    assert bool((ok1 == 1).all()) and bool((ok2 == 1).all()) and bool((ver == 1).all())
+    if nn.bit_length() == 256:
+        assert not dst.any().item() and torch.equal(dxy, dq)
+    out["sign_over_mul_fixed"] = round(out["sign_ms"] / out["mul_fixed_ms"], 4)
+    out["sign_det_over_mul_fixed"] = round(out["sign_det_ms"] / out["mul_fixed_ms"], 4)
+    out["sign_det_over_sign"] = round(out["sign_det_ms"] / out["sign_ms"], 4)
+    ctx.set_timing(True)
+    ctx.custom_sign_det_dev(cid, dh, dd, r2, s2, j2, ok2, drbg_hash=0, canonical=True)
+    torch.cuda.synchronize()
+    out["kernels_ms"] = {name: round(ms, 4) for name, (cnt, ms) in ctx.get_timing().items()}
+    ctx.set_timing(False)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
@@ -194,6 +254,16 @@ def main():
                 spec = next(c for c in CD.curves() if c["name"] == name)
                 for lg in [int(a) for a in sys.argv[2:]] or [18]:
                     print(json.dumps(run_wire(ctx, spec, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
+    if sys.argv[1:2] == ["--sign"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            spec = next(c for c in CD.curves() if c["name"] == "brainpoolP256r1")
+            for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
+                print(json.dumps(run_sign(ctx, spec, 1 << lg)), flush=True)
         finally:
             ctx.close()
         return
