@@ -542,6 +542,50 @@ int ellgpu_custom_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8
                                                canonical, out_r, out_s, out_recid, out_ok), true);
 }
 
+// KeyPair#derive, KeyPair#validate and BasePoint#encode on a user-defined short curve (a group: member 0)
+int ellgpu_custom_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                         uint8_t* out_x, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_derive_host(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr));
+}
+int ellgpu_custom_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                             uint8_t* out_x, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_derive_dev(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr), true);
+}
+int ellgpu_custom_derive_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                              size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_derive_host(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err));
+}
+int ellgpu_custom_derive_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                                  size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err,
+                                  void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_derive_dev(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err),
+                true);
+}
+int ellgpu_custom_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
+                           int check_order, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_validate_host(curve, n, xy, inf, check_order, out_status));
+}
+int ellgpu_custom_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
+                               int check_order, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_validate_dev(curve, n, xy, inf, check_order, out_status), true);
+}
+int ellgpu_custom_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                uint8_t* out_enc) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_encode_points_host(curve, n, xy, compact, out_enc));
+}
+int ellgpu_custom_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                    uint8_t* out_enc, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_encode_points_dev(curve, n, xy, compact, out_enc), true);
+}
+
 int ellgpu_ecdsa_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {

@@ -747,6 +747,46 @@ struct FnRtDecodePoint {
     if (i < n) W::rt_decode_point(i, enc, len, pl, out_xy, status);
   }
 };
+// KeyPair#derive, KeyPair#validate and BasePoint#encode on a user-defined short curve
+// (Work::rt_ecdh_front / rt_derive_finish / rt_validate_fold / rt_encode_point): the passes in
+// front of and behind the variable-base ladder (FnMulVar<CvCustom>, as Point#mul runs it)
+struct FnRtEcdhFront {
+  static constexpr const char* NAME = "rt_ecdh_front";
+  typedef Work<CvCustom> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* pub; size_t len; int pl; u8* pts; u8* dec_st; u8* valid; u8* scal;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_ecdh_front(i, pub, len, pl, pts, dec_st, valid, scal);
+  }
+};
+struct FnRtDeriveFinish {
+  static constexpr const char* NAME = "rt_derive_finish";
+  typedef Work<CvCustom> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u32* jac; const u8* dec_st; const u8* valid; u32* pre; u8* out_x; u8* status;
+  u8* err;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) W::rt_derive_finish(t, T, n, K, jac, dec_st, valid, pre, out_x, status, err);
+  }
+};
+struct FnRtValidateFold {
+  static constexpr const char* NAME = "rt_validate_fold";
+  typedef Work<CvCustom> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* inf; const u8* valid; const u32* jac; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_validate_fold(i, n, inf, valid, jac, status);
+  }
+};
+struct FnRtEncodePoint {
+  static constexpr const char* NAME = "rt_encode_point";
+  typedef Work<CvCustom> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* xy; int compact; int pl; u8* out;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::rt_encode_point(i, xy, compact, pl, out);
+  }
+};
 // EC#recoverPubKey on a user-defined ECDSA domain (Work::rt_recover_*): the scalar-field pass
 // (range checks, one inversion of r per K items, s1 = -e/r, s2 = s/r, the x of R) and the status
 // fold behind the double-scalar multiplication.  pmn = p mod n travels as an argument: the
@@ -1317,6 +1357,23 @@ class Engine {
   template <int U = 0>
   int rt_wire_chunk(int op, size_t n, const u8* a, const u8* b, size_t len, const u32* lens, u8* o1, u8* o2,
                     u8* o3);
+  // KeyPair#derive and #validate on user-defined short curves: rt_ecdh_front, the variable-base
+  // ladder of mul_var_chunk (FnMulVar<CvCustom>; none for a validate without the order test), then
+  // rt_derive_finish or rt_validate_fold -- the same code object.
+  //   derive:   k = the private keys, pub = raw x || y (len == 0) or SEC1 encodings of len bytes,
+  //             err may be null
+  //   validate: pub = raw x || y, inf may be null
+  template <int U = 0>
+  int rt_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len, u8* out_x, u8* status, u8* err);
+  template <int U = 0>
+  int rt_validate_chunk(size_t n, const u8* xy, const u8* inf, bool check_order, u8* status);
+  // BasePoint#encode at the curve's own width
+  template <int U = 0>
+  int rt_encode_chunk(size_t n, const u8* xy, int compact, u8* out_enc);
+  // the front pass and the ladder shared by the two above: flags (valid, then the decoder's
+  // status) and, with `ladder`, the Jacobian results; the scalars are k, or the order (k == null)
+  template <int U = 0>
+  int rt_ecdh_ladder(size_t n, const u8* k, const u8* pub, size_t len, bool ladder, u8*& flags, u32*& jac);
   // EC#recoverPubKey on a user-defined ECDSA domain: rt_recover_prep, the run-time square root
   // (rt_wire_chunk), s1 * G + s2 * R over the domain's comb, rt_recover_finish
   template <int U = 0>
@@ -2297,6 +2354,96 @@ class Engine {
     });
   }
 
+  // ---- the key side on user-defined short curves: ECDH, validation, SEC1 encoding ---------------
+  // KeyPair#derive (ec/key.js:101-107), KeyPair#validate (key.js:40-51) and BasePoint#encode
+  // (base.js:295-311).  derive and encode need neither n nor G: a plain define_short id will do;
+  // validate's order test needs the domain's n.
+  int custom_pbytes() const { return (int)custom_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].pbytes; }
+  // pub_len == 0: pub is n x 64 raw coordinates (ellgpu_custom_derive); else n SEC1 encodings of
+  // pub_len bytes (ellgpu_custom_derive_wire) -- a length that is neither 1 + pbytes nor
+  // 1 + 2 pbytes is no error of the call: every item is then 'Unknown point format'
+  int check_custom_derive(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len,
+                          u8* out_x, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!priv || !pub || !out_x || !out_status)) return fail(E_ARG, "null pointer");
+    if (wire && pub_len == 0) return fail(E_ARG, "pub_len must be positive");
+    return E_OK;
+  }
+  int custom_derive_dev(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                        u8* out_status, u8* out_err) {
+    int rc = check_custom_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t PS = wire ? pub_len : 64;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_derive_chunk(m, priv + o * 32, pub + o * PS, wire ? pub_len : 0, out_x + o * 32, out_status + o,
+                             out_err ? out_err + o : nullptr);
+    });
+  }
+  int custom_derive_host(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                         u8* out_status, u8* out_err) {
+    int rc = check_custom_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{priv, 32}, In{pub, wire ? pub_len : 64}}, {Out{out_x, 32}, Out{out_status, 1}, Out{out_err, 1}},
+                  [&](size_t m, auto d, auto o) {
+      return custom_derive_dev(curve, m, d[0], d[1], wire, pub_len, o[0], o[1], o[2]);
+    });
+  }
+  // statuses as validate_dev's; check_order on a plain id: it has no n
+  int check_custom_validate(int curve, size_t n, const u8* xy, int check_order, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (check_order && !custom_is_domain(curve))
+      return fail(E_UNSUPPORTED, "the order test on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
+    return E_OK;
+  }
+  int custom_validate_dev(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
+    int rc = check_custom_validate(curve, n, xy, check_order, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_validate_chunk(m, xy + o * 64, inf ? inf + o : nullptr, check_order != 0, out_status + o);
+    });
+  }
+  int custom_validate_host(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
+    int rc = check_custom_validate(curve, n, xy, check_order, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{xy, 64}, In{inf, 1}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      return custom_validate_dev(curve, m, d[0], d[1], check_order, o[0]);
+    });
+  }
+  // rows of 1 + pbytes (compact) or 1 + 2 pbytes bytes
+  int custom_encode_points_dev(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_pbytes();
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return rt_encode_chunk(m, xy + o * 64, compact, out_enc + o * EL);
+    });
+  }
+  int custom_encode_points_host(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_pbytes();
+    return staged(n, {In{xy, 64}}, {Out{out_enc, EL}}, [&](size_t m, auto d, auto o) {
+      return custom_encode_points_dev(curve, m, d[0], compact, o[0]);
+    });
+  }
+
   // ---- host-buffer wrappers: stage through device buffers --------------------
   // An operand of a host-buffer call: n items of `stride` bytes.  A null host pointer is an absent
   // optional operand (the wrappers have refused the required ones): it gets no device copy, and
@@ -2829,6 +2976,68 @@ int Engine<BK>::rt_wire_chunk(int op, size_t n, const u8* a, const u8* b, size_t
     FnWireStatus<CvCustom> f{n, a, b, o3, o1, o2};
     bk.launch(f, n);
   }
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_encode_chunk(size_t n, const u8* xy, int compact, u8* out_enc) {
+  FnRtEncodePoint f{n, xy, compact, custom_pbytes(), out_enc};
+  bk.launch(f, n);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_ecdh_ladder(size_t n, const u8* k, const u8* pub, size_t len, bool ladder, u8*& flags, u32*& jac) {
+  typedef Work<CvCustom> W;
+  // the points, the order as scalars and the flags live across the ladder kernel, which uses
+  // S_TBL / S_JAC only (as in rt_recover_chunk)
+  flags = (u8*)scratch(S_VALID, 2 * n);
+  if (!flags) return fail(E_NOMEM, "scratch allocation failed");
+  u8* pts = nullptr;
+  u8* scal = nullptr;
+  typename W::VT* tbl = nullptr;
+  jac = nullptr;
+  if (ladder) {
+    pts = (u8*)scratch(S_U12, n * (size_t)(k ? 64 : 96));
+    tbl = (typename W::VT*)scratch(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
+    jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
+    if (!pts || !tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
+    if (!k) scal = pts + n * 64;
+  }
+  FnRtEcdhFront f0{n, pub, len, custom_pbytes(), pts, flags + n, flags, scal};
+  bk.launch(f0, n);
+  if (ladder) launch_paired<FnMulVar, CvCustom>(n, k ? k : (const u8*)scal, (const u8*)pts, tbl, jac);   // form_for<CvCustom>: FULL
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len, u8* out_x, u8* status, u8* err) {
+  typedef Work<CvCustom> W;
+  u8* flags;
+  u32* jac;
+  int rc = rt_ecdh_ladder(n, k, pub, len, true, flags, jac);
+  if (rc) return rc;
+  u32* pre = (u32*)scratch(S_PRE, n * W::NS * 4);
+  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
+  const int K = norm_batch_for(n);
+  const size_t T = (n + K - 1) / K;
+  FnRtDeriveFinish f1{T, n, K, jac, flags + n, flags, pre, out_x, status, err};
+  bk.launch(f1, T);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::rt_validate_chunk(size_t n, const u8* xy, const u8* inf, bool check_order, u8* status) {
+  u8* flags;
+  u32* jac;
+  int rc = rt_ecdh_ladder(n, nullptr, xy, 0, check_order, flags, jac);
+  if (rc) return rc;
+  FnRtValidateFold f2{n, inf, flags, jac, status};
+  bk.launch(f2, n);
   return E_OK;
 }
 

@@ -68,7 +68,8 @@ namespace ell {
   KW template int Engine<HipBackend>::launch_fn<FnMulJoin<CvSecp256k1>>(                             \
       const FnMulJoin<CvSecp256k1>&, size_t);
 // user-defined short curves (CvCustom): scalar multiplication, point addition and the wire
-// formats (pointFromX, decodePoint, the DER parser, the wire verify's status)
+// formats (pointFromX, decodePoint, the DER parser, the wire verify's status), ECDH, key validation
+// and SEC1 encoding
 #define ELL_DECL_CUSTOM(KW)                                                                          \
   KW template int Engine<HipBackend>::mul_var_chunk<CvCustom>(size_t, const u8*, const u8*, u8*, u8*, \
                                                               Work<CvCustom>::A*);                   \
@@ -81,7 +82,13 @@ namespace ell {
   KW template int Engine<HipBackend>::edc_chunk<0>(int, size_t, const u8*, const u8*, const u8*,     \
                                                    const u8*, const u8*, const u8*, u8*, u8*);       \
   KW template int Engine<HipBackend>::rt_wire_chunk<0>(int, size_t, const u8*, const u8*, size_t,    \
-                                                       const u32*, u8*, u8*, u8*);
+                                                       const u32*, u8*, u8*, u8*);                   \
+  KW template int Engine<HipBackend>::rt_ecdh_ladder<0>(size_t, const u8*, const u8*, size_t, bool,  \
+                                                        u8*&, u32*&);                                \
+  KW template int Engine<HipBackend>::rt_derive_chunk<0>(size_t, const u8*, const u8*, size_t, u8*,  \
+                                                         u8*, u8*);                                  \
+  KW template int Engine<HipBackend>::rt_validate_chunk<0>(size_t, const u8*, const u8*, bool, u8*); \
+  KW template int Engine<HipBackend>::rt_encode_chunk<0>(size_t, const u8*, int, u8*);
 // user-defined ECDSA domains (CvCustomDomain): verify, recovery, sign, k*G and k1*G + k2*Q -- their own translation
 // unit (group 17, with its own parameter block); the window ladder of the comb build is CvCustom's
 #define ELL_DECL_DOMAIN(KW)                                                                          \

@@ -488,9 +488,17 @@ struct Work {
   // 1 + pl (02/03) or 1 + 2 pl (04/06/07) bytes, coordinates out BYTES wide.  status as
   // decode_point's, with rt_no_root() for a compressed x without a y.
   ELL_HD static void rt_decode_point(size_t i, const u8* enc, size_t len, int pl, u8* out_xy, u8* status) {
-    const u8* e = enc + i * len;
+    El x, y;
+    const u32 st = rt_decode(enc + i * len, len, pl, x, y);
+    store_fe(out_xy + i * 2 * BYTES, x);
+    store_fe(out_xy + i * 2 * BYTES + BYTES, y);
+    status[i] = (u8)st;
+  }
+  // one encoding -> its status and the point in registers (zero unless the status is 0)
+  ELL_HD static u32 rt_decode(const u8* e, size_t len, int pl, El& x, El& y) {
     const u32 tag = len ? e[0] : 0u;
-    El x = F::zero(), y = F::zero();
+    x = F::zero();
+    y = F::zero();
     u32 st = DECODE_FORMAT;
     if ((tag == 4 || tag == 6 || tag == 7) && len == 1 + 2 * (size_t)pl) {
       const u32 last = e[len - 1] & 1u;
@@ -505,9 +513,113 @@ struct Work {
       st = lift_x(y, x, tag == 3) ? (u32)DECODE_OK : rt_no_root();
       if (st != DECODE_OK) { x = F::zero(); y = F::zero(); }
     }
-    store_fe(out_xy + i * 2 * BYTES, x);
-    store_fe(out_xy + i * 2 * BYTES + BYTES, y);
+    return st;
+  }
+  // ---- KeyPair#derive / KeyPair#validate / BasePoint#encode on a user-defined curve -------------
+  // (ec/key.js:101-107, 40-51; base.js:295-311.)  The front pass of derive and validate, one item
+  // per lane: the peer's point from raw x || y (len == 0; each coordinate reduced mod p as toRed
+  // does) or from a SEC1 encoding of len bytes (rt_decode, with its square root), then
+  // ShortCurve#validate (short.js:205-216).  pts gets the reduced point the ladder runs on -- zero
+  // for an item that did not decode or is not on the curve: the formulas are complete, and the
+  // finish passes do not read such an item's result.  scal (validate with the order test): the
+  // order n as the item's scalar, read from the block (zero on a plain curve, which the host refuses).
+  ELL_HD static void rt_ecdh_front(size_t i, const u8* pub, size_t len, int pl, u8* pts, u8* dec_st, u8* valid,
+                                   u8* scal) {
+    El x, y;
+    u32 st = DECODE_OK;
+    if (len) {
+      st = rt_decode(pub + i * len, len, pl, x, y);
+    } else {
+      x = load_fe(pub + i * 2 * BYTES);
+      y = load_fe(pub + i * 2 * BYTES + BYTES);
+    }
+    const bool on = st == DECODE_OK && F::eq(F::sqr(y), curve_rhs(x));
+    if (pts) {
+      store_fe(pts + i * 2 * BYTES, fe_select<F>(on, x, F::zero()));
+      store_fe(pts + i * 2 * BYTES + BYTES, fe_select<F>(on, y, F::zero()));
+    }
+    if (dec_st) dec_st[i] = (u8)st;
+    valid[i] = on ? 1 : 0;
+    if (scal) {
+      u32 nn[L];
+      ELL_UNROLL
+      for (int l = 0; l < L; l++) nn[l] = ELL_RT.n[l];
+      store_be<L>(scal + i * BYTES, nn, BYTES);
+    }
+  }
+  // derive's last pass: the x of priv * pub with one inversion per K items (thread t: items t,
+  // t + T, ...), and the status fold -- 3 the key did not decode, 1 'public point not validated',
+  // 2 the product is the point at infinity (getX throws), else 0.  An item that is not 0 enters
+  // the shared product as one and gets a zeroed x.  err (may be null): the decoder's own status.
+  enum { DERIVE_OK = 0, DERIVE_NOT_VALIDATED = 1, DERIVE_INF = 2, DERIVE_UNDECODED = 3 };
+  ELL_HD static void rt_derive_finish(size_t t, size_t T, size_t n, int K, const u32* jac, const u8* dec_st,
+                                      const u8* valid, u32* pre, u8* out_x, u8* status, u8* err) {
+    auto load_z = [&](size_t i) {
+      El z;
+      ELL_UNROLL
+      for (int l = 0; l < NS; l++) z.v[l] = jac[(size_t)(2 * NS + l) * n + i];
+      return z;
+    };
+    int cnt = 0;
+    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
+    if (cnt > K) cnt = K;
+    El acc = F::one();
+    ELL_NOUNROLL
+    for (int j = 0; j < cnt; j++) {
+      size_t i = t + (size_t)j * T;
+      El z = load_z(i);
+      int st = DERIVE_OK;
+      if (dec_st[i] != DECODE_OK) st = DERIVE_UNDECODED;
+      else if (!valid[i]) st = DERIVE_NOT_VALIDATED;
+      else if (F::is_zero(z)) st = DERIVE_INF;
+      status[i] = (u8)st;
+      if (err) err[i] = dec_st[i];
+      z = fe_select<F>(st == DERIVE_OK, z, F::one());
+      ELL_UNROLL
+      for (int l = 0; l < NS; l++) pre[(size_t)l * n + i] = acc.v[l];
+      acc = F::mul(acc, z);
+    }
+    El inv = F::inv(acc);
+    ELL_NOUNROLL
+    for (int j = cnt - 1; j >= 0; j--) {
+      size_t i = t + (size_t)j * T;
+      const bool ok = status[i] == DERIVE_OK;
+      El z = fe_select<F>(ok, load_z(i), F::one());
+      El pr, X;
+      ELL_UNROLL
+      for (int l = 0; l < NS; l++) { pr.v[l] = pre[(size_t)l * n + i]; X.v[l] = jac[(size_t)l * n + i]; }
+      El zinv = F::mul(inv, pr);
+      inv = F::mul(inv, z);
+      El x = F::mul(X, F::sqr(zinv));
+      store_fe(out_x + i * BYTES, fe_select<F>(ok, x, F::zero()));
+    }
+  }
+  // validate's last pass, KeyPair#validate's tests in its order: 1 'Invalid public key' (inf[i]
+  // set; inf may be null), 2 'Public key is not a point', 3 'Public key * N != O' (jac, the
+  // ladder's n * P: only with the order test), else 0
+  ELL_HD static void rt_validate_fold(size_t i, size_t n, const u8* inf, const u8* valid, const u32* jac,
+                                      u8* status) {
+    int st = VALIDATE_OK;
+    if (inf && inf[i]) st = VALIDATE_INF;
+    else if (!valid[i]) st = VALIDATE_NOT_POINT;
+    else if (jac) {
+      El z;
+      ELL_UNROLL
+      for (int l = 0; l < NS; l++) z.v[l] = jac[(size_t)(2 * NS + l) * n + i];
+      if (!F::is_zero(z)) st = VALIDATE_ORDER;
+    }
     status[i] = (u8)st;
+  }
+  // BasePoint#_encode (base.js:299-307) at the curve's own width pl = p.byteLength(): rows of
+  // 1 + pl (02/03 || x) or 1 + 2 pl (04 || x || y) bytes, coordinates reduced mod p first
+  ELL_HD static void rt_encode_point(size_t i, const u8* xy, int compact, int pl, u8* out) {
+    u32 xp[L], yp[L];
+    F::to_plain(xp, load_fe(xy + i * 2 * BYTES));
+    F::to_plain(yp, load_fe(xy + i * 2 * BYTES + BYTES));
+    u8* o = out + i * (compact ? 1 + (size_t)pl : 1 + 2 * (size_t)pl);
+    o[0] = compact ? (u8)(2u + (yp[0] & 1u)) : (u8)4;
+    store_be<L>(o + 1, xp, pl);                          // (rows of odd length: byte stores)
+    if (!compact) store_be<L>(o + 1 + pl, yp, pl);
   }
   // BasePoint#_encode (base.js:299-307): 02/03 || x  or  04 || x || y, coordinates reduced
   ELL_HD static void encode_point(size_t i, const u8* xy, int compact, u8* out) {

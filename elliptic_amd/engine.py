@@ -81,6 +81,7 @@ class Context:
         self.devices = list(devices) if devices is not None else [device]
         self._own = None                  # torch view of the context's own stream (see _stream)
         self._pending_default = None
+        self._pbytes = {}                 # p.byteLength() of the user-defined short curves (custom_encode_points)
 
     def group_size(self):
         return self._lib.ellgpu_group_size(self._ctx)
@@ -117,6 +118,7 @@ class Context:
         cid = ctypes.c_int(-1)
         enc = [int(v % p if i else v).to_bytes(32, "big") for i, v in enumerate((int(p), int(a), int(b)))]
         self._check(self._lib.ellgpu_curve_define_short(self._ctx, enc[0], enc[1], enc[2], ctypes.byref(cid)))
+        self._pbytes[cid.value] = (int(p).bit_length() + 7) // 8
         return cid.value
 
     def define_short_domain(self, p, a, b, n, gx, gy):
@@ -129,6 +131,7 @@ class Context:
         p = int(p)
         enc = [int(v).to_bytes(32, "big") for v in (p, int(a) % p, int(b) % p, int(n), int(gx), int(gy))]
         self._check(self._lib.ellgpu_curve_define_short_domain(self._ctx, *enc, ctypes.byref(cid)))
+        self._pbytes[cid.value] = (p.bit_length() + 7) // 8
         return cid.value
 
     def define_edwards(self, p, a, d):
@@ -530,6 +533,95 @@ class Context:
                                                          1 if canonical else 0, out_r.data_ptr(),
                                                          out_s.data_ptr(), out_recid.data_ptr(),
                                                          out_ok.data_ptr(), self._stream()))
+
+    # ---- the key side on user-defined short curves: ECDH, validation, SEC1 encoding -------------
+
+    def custom_derive(self, curve, priv, pub_xy, out=None):
+        """KeyPair#derive per item on a domain id or a plain define_short id -> (x, status): 0 x is
+        pub.mul(priv).getX(), 1 'public point not validated', 2 the product is the point at
+        infinity.  priv (n, 32) is used as it stands (not reduced mod n); pub_xy (n, 64), each
+        coordinate reduced mod p"""
+        priv = _u8(priv, (-1, 32))
+        n = priv.shape[0]
+        pub_xy = _u8(pub_xy, (n, 64))
+        x, st = self._outs(out, [(n, 32), (n,)])
+        self._check(self._lib.ellgpu_custom_derive(self._ctx, self._cid(curve), n, priv.ctypes.data,
+                                                   pub_xy.ctypes.data, x.ctypes.data, st.ctypes.data))
+        return x, st
+
+    def custom_derive_dev(self, curve, priv, pub_xy, out_x, out_status):
+        n = priv.shape[0]
+        self._check(self._lib.ellgpu_custom_derive_dev(self._ctx, self._cid(curve), n, priv.data_ptr(),
+                                                       pub_xy.data_ptr(), out_x.data_ptr(), out_status.data_ptr(),
+                                                       self._stream()))
+
+    def custom_derive_wire(self, curve, priv, pubs, out=None, want_err=True):
+        """KeyPair#derive with the peer keys as SEC1 encodings, rows of `pubs` (n, pub_len) ->
+        (x, status, err): status as custom_derive plus 3 = the key did not decode; err the
+        statuses of custom_decode_points.  want_err=False passes no err array -> (x, status, None);
+        out= is then (x, status)"""
+        priv = _u8(priv, (-1, 32))
+        n = priv.shape[0]
+        pubs = _u8(pubs)
+        if pubs.ndim != 2 or pubs.shape[0] != n:
+            raise ValueError("pubs must be (n, pub_len)")
+        if want_err:
+            x, st, err = self._outs(out, [(n, 32), (n,), (n,)])
+        else:
+            (x, st), err = self._outs(out, [(n, 32), (n,)]), None
+        self._check(self._lib.ellgpu_custom_derive_wire(self._ctx, self._cid(curve), n, priv.ctypes.data,
+                                                        pubs.ctypes.data, pubs.shape[1], x.ctypes.data,
+                                                        st.ctypes.data, err.ctypes.data if want_err else None))
+        return x, st, err
+
+    def custom_derive_wire_dev(self, curve, priv, pubs, out_x, out_status, out_err=None):
+        n, pub_len = pubs.shape
+        self._check(self._lib.ellgpu_custom_derive_wire_dev(
+            self._ctx, self._cid(curve), n, priv.data_ptr(), pubs.data_ptr(), pub_len, out_x.data_ptr(),
+            out_status.data_ptr(), out_err.data_ptr() if out_err is not None else None, self._stream()))
+
+    def custom_validate(self, curve, xy, inf=None, check_order=True, out=None):
+        """KeyPair#validate per item -> status: 0 ok, 1 'Invalid public key' (inf[i] set), 2 'Public
+        key is not a point', 3 'Public key * N != O' (check_order: needs a domain id)"""
+        xy = _u8(xy, (-1, 64))
+        n = xy.shape[0]
+        inf = _u8(inf, (n,)) if inf is not None else None
+        st, = self._outs(out, [(n,)])
+        self._check(self._lib.ellgpu_custom_validate(self._ctx, self._cid(curve), n, xy.ctypes.data,
+                                                     inf.ctypes.data if inf is not None else None,
+                                                     1 if check_order else 0, st.ctypes.data))
+        return st
+
+    def custom_validate_dev(self, curve, xy, inf, check_order, out_status):
+        n = xy.shape[0]
+        self._check(self._lib.ellgpu_custom_validate_dev(self._ctx, self._cid(curve), n, xy.data_ptr(),
+                                                         inf.data_ptr() if inf is not None else None,
+                                                         1 if check_order else 0, out_status.data_ptr(),
+                                                         self._stream()))
+
+    def custom_encode_points(self, curve, xy, compact=False, out=None):
+        """BasePoint#encode per item at the curve's own width -> (n, 1 + PL) for compact, else
+        (n, 1 + 2 PL), PL = coord_bytes(curve); coordinates are reduced mod p first"""
+        xy = _u8(xy, (-1, 64))
+        n = xy.shape[0]
+        pl = self._pbytes.get(self._cid(curve))
+        if pl is None:
+            # not a short curve defined on this context: the library's own refusal (preset, unknown
+            # or Edwards id), asked for with no items so that no width has to be guessed
+            self._check(self._lib.ellgpu_custom_encode_points(self._ctx, self._cid(curve), 0, None, 0, None))
+            raise ValueError("custom_encode_points: curve %r was not defined on this context" % (curve,))
+        enc, = self._outs(out, [(n, 1 + pl if compact else 1 + 2 * pl)])
+        self._check(self._lib.ellgpu_custom_encode_points(self._ctx, self._cid(curve), n, xy.ctypes.data,
+                                                          1 if compact else 0, enc.ctypes.data))
+        return enc
+
+    def custom_encode_points_dev(self, curve, xy, compact, out_enc):
+        """the _dev form: like every _dev call it trusts the caller's buffers -- out_enc must hold
+        n rows of 1 + PL (compact) or 1 + 2 PL bytes, PL = p.byteLength() of the curve"""
+        n = xy.shape[0]
+        self._check(self._lib.ellgpu_custom_encode_points_dev(self._ctx, self._cid(curve), n, xy.data_ptr(),
+                                                              1 if compact else 0, out_enc.data_ptr(),
+                                                              self._stream()))
 
     def ecdsa_sign(self, curve, hashes, priv, nonces, canonical=False, msg_bits=0):
         """one pass of EC#sign per item for supplied nonces -> (r, s, recid, ok)"""

@@ -45,6 +45,9 @@
  *             -> {ok, err}: the same three on a user-defined short curve / domain (ellgpu_custom_*)
  *           customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy, status}: EC#recoverPubKey on a
  *             user-defined domain (ellgpu_custom_recover; 32-byte r, s and coordinates, hashLen 1..64)
+ *           customEcdh(ctx, op, curve, b0, b1, i0, i1): the key side on a user-defined short curve, the ops
+ *             13..16 of callAsync below -- KeyPair#derive, #validate and BasePoint#encode
+ *             (ellgpu_custom_derive / _custom_derive_wire / _custom_validate / _custom_encode_points)
  *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
  *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
  *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
@@ -55,6 +58,9 @@
  *             3 ecdsaVerify(hash, r, s, pub) 4 x25519(k, x) 5 ecdsaSignDet(hash, priv; i0 = canonical)
  *             6 ecdsaRecover(hash, r, s, recid) 7 ecdsaVerifyWire(hash, der, lens, keys; i0 = der
  *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length) 9 customVerifyWire (as 7); 10 customRecover (as 6);
+ *             13 customDerive(priv, pubXY) -> {x, status}  14 customDeriveWire(priv, enc; i0 = key length) ->
+ *             {x, status, err}  15 customValidate(xy, inf or null; i0 = checkOrder) -> {status}
+ *             16 customEncodePoints(xy; i0 = compact, i1 = p.byteLength()) -> {enc};
  *             11 customSign(hash, priv, nonces; i0 = canonical) 12 customSignDet(hash, priv; i0 = canonical,
  *             i1 = drbgHash);
  *             runs on a libuv worker
@@ -128,6 +134,11 @@ static struct {
   int (*custom_decode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, size_t, uint8_t*, uint8_t*);
   int (*custom_recover)(ellgpu_ctx*, int, size_t, const uint8_t*, int, const uint8_t*, const uint8_t*,
                         const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_derive)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_derive_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, uint8_t*,
+                            uint8_t*);
+  int (*custom_validate)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, int, uint8_t*);
+  int (*custom_encode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, int, uint8_t*);
   int (*custom_sign)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*, int,
                      uint8_t*, uint8_t*, uint8_t*, uint8_t*);
   int (*custom_sign_det)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, int, int,
@@ -195,6 +206,10 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(custom_decode_points, "ellgpu_custom_decode_points");
   SYM(custom_verify_wire, "ellgpu_custom_verify_wire");
   SYM(custom_recover, "ellgpu_custom_recover");
+  SYM(custom_derive, "ellgpu_custom_derive");
+  SYM(custom_derive_wire, "ellgpu_custom_derive_wire");
+  SYM(custom_validate, "ellgpu_custom_validate");
+  SYM(custom_encode_points, "ellgpu_custom_encode_points");
   SYM(custom_sign, "ellgpu_custom_sign");
   SYM(custom_sign_det, "ellgpu_custom_sign_det");
   L.h = h;
@@ -911,6 +926,79 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
   return mk_result(env, "sig", bsig, "pub", bpub);
 }
 
+/* ---- the key side on user-defined short curves: KeyPair#derive / #validate, BasePoint#encode ----
+ * ops 13 derive(priv, pubXY)  14 deriveWire(priv, enc; i0 = key length)  15 validate(xy, inf or
+ * null; i0 = checkOrder)  16 encodePoints(xy; i0 = compact, i1 = p.byteLength()).  Scalars and
+ * coordinates are 32 bytes.  ecdh_shape: the item count and the result lengths from the input
+ * lengths (0 = mismatch); ecdh_call: the C ABI call.  Shared by customEcdh and callAsync.
+ * The library writes encodePoints' rows at the CURVE's width, which this addon cannot ask it for
+ * (index.js records it when the curve is defined and refuses another): so the call never gets the
+ * caller-sized result buffer.  It writes into n rows of ECDH_ENC_MAX bytes -- the widest a curve
+ * below 2^256 has -- and the result is cut from those: a wrong i1 gives wrong bytes, never a write
+ * past the end. */
+#define ECDH_ENC_MAX 65
+static const char* const ECDH_NAMES[4][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0}};
+static int ecdh_shape(int op, const uint8_t* const in[2], const size_t len[2], int i0, int i1, size_t* n, size_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!in[0]) return 0;
+  if (op == 13 || op == 14) {
+    if (!in[1] || len[0] % 32 || (op == 14 && i0 <= 0)) return 0;
+    *n = len[0] / 32;
+    if (len[1] != *n * (op == 13 ? 64 : (size_t)i0)) return 0;
+    out[0] = *n * 32; out[1] = *n; out[2] = op == 14 ? *n : 0;
+  } else if (op == 15 || op == 16) {
+    if (len[0] % 64) return 0;
+    *n = len[0] / 64;
+    if (op == 15) { if (in[1] && len[1] != *n) return 0; out[0] = *n; }
+    else { if (i1 <= 0 || i1 > 32) return 0; out[0] = *n * (1 + (i0 ? 1 : 2) * (size_t)i1); }
+  } else return 0;
+  return 1;
+}
+static int ecdh_call(int op, ellgpu_ctx* c, int curve, size_t n, const uint8_t* const in[2], int i0, uint8_t* const out[3]) {
+  switch (op) {
+    case 13: return L.custom_derive(c, curve, n, in[0], in[1], out[0], out[1]);
+    case 14: return L.custom_derive_wire(c, curve, n, in[0], in[1], (size_t)i0, out[0], out[1], out[2]);
+    case 15: return L.custom_validate(c, curve, n, in[0], in[1], i0, out[0]);
+    default: return L.custom_encode_points(c, curve, n, in[0], i0, out[0]);
+  }
+}
+/* customEcdh(ctx, op, curve, b0, b1, i0, i1) -> the op's result object */
+static napi_value fn_custom_ecdh(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 7; napi_value argv[7];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) THROW(env, "customEcdh(ctx, op, curve, b0, b1, i0, i1)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  int32_t op, curve, i0, i1;
+  if (napi_get_value_int32(env, argv[1], &op) != napi_ok || napi_get_value_int32(env, argv[2], &curve) != napi_ok ||
+      napi_get_value_int32(env, argv[5], &i0) != napi_ok || napi_get_value_int32(env, argv[6], &i1) != napi_ok)
+    THROW(env, "customEcdh(ctx, op, curve, b0, b1, i0, i1)");
+  const uint8_t* in[2]; size_t len[2], n = 0, ol[3];
+  if (!get_buf(env, argv[3], &in[0], &len[0], 0) || !get_buf(env, argv[4], &in[1], &len[1], 1)) return NULL;
+  if (op == 16) {                        /* the row width is the curve's: not a caller's choice to get wrong silently */
+    if (i1 <= 0 || i1 > 32) THROW(env, "customEncodePoints: coordBytes must be 1..32");
+  }
+  if (!ecdh_shape(op, in, len, i0, i1, &n, ol)) THROW(env, "buffer length mismatch");
+  napi_value b[3] = {NULL, NULL, NULL}; void* d[3] = {NULL, NULL, NULL};
+  for (int k = 0; k < 3 && ECDH_NAMES[op - 13][k]; k++) CHECK(env, result_buffer(env, ol[k], &d[k], &b[k]));
+  uint8_t* out[3] = {(uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2]};
+  uint8_t* wide = NULL;
+  if (op == 16) {
+    wide = (uint8_t*)malloc(n * ECDH_ENC_MAX + 1);
+    if (!wide) THROW(env, "customEcdh: out of memory");
+    out[0] = wide;
+  }
+  int rc = ecdh_call(op, c, curve, n, in, i0, out);
+  if (wide) {
+    if (rc == 0) memcpy(d[0], wide, ol[0]);
+    free(wide);
+  }
+  if (rc != 0) return lib_error(env);
+  napi_value o; CHECK(env, napi_create_object(env, &o));
+  for (int k = 0; k < 3 && ECDH_NAMES[op - 13][k]; k++) CHECK(env, napi_set_named_property(env, o, ECDH_NAMES[op - 13][k], b[k]));
+  return o;
+}
+
 /* ---- asynchronous form: napi_async_work + Promise ---------------------------------- */
 typedef struct {
   napi_async_work work;
@@ -954,6 +1042,11 @@ static void job_execute(napi_env env, void* data) {
                                    j->out0, j->out1, j->out2, j->out3); break;
     case 12: j->rc = L.custom_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1, j->i0,
                                        j->out0, j->out1, j->out2, j->out3); break;
+    case 13: case 14: case 15: case 16: {
+      const uint8_t* in[2] = {j->in[0], j->in[1]};
+      uint8_t* out[3] = {j->out0, j->out1, j->out2};
+      j->rc = ecdh_call(j->op, j->ctx, j->curve, j->n, in, j->i0, out); break;
+    }
     default: j->rc = L.decode_points(j->ctx, j->curve, j->n, j->in[0], (size_t)j->i0, j->out0, j->out1); break;
   }
   if (j->rc != 0) {               /* last_error is thread-local: read it on this thread */
@@ -967,10 +1060,11 @@ static void job_complete(napi_env env, napi_status status, void* data) {
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
     /* result property names per op, in output order */
-    static const char* const names[13][4] = {
+    static const char* const names[17][4] = {
       {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
       {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
-      {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"}};
+      {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
+      {"x", "status", 0, 0}, {"x", "status", "err", 0}, {"status", 0, 0, 0}, {"enc", 0, 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1015,7 +1109,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
   j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
   j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > 12 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
+  if (op < 0 || op > 16 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
   int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
@@ -1027,7 +1121,12 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   }
   size_t B = (size_t)j->B, NB = (size_t)j->NB;
   int ok = 1;
+  size_t ecdh_out[3] = {0, 0, 0};
   switch (op) {
+    case 13: case 14: case 15: case 16: {
+      const uint8_t* in2[2] = {j->in[0], j->in[1]};
+      ok = ecdh_shape(op, in2, len, i0, i1, &j->n, ecdh_out); break;
+    }
     case 0: j->n = len[0] / B; ok = j->in[0] && len[0] % B == 0; break;
     case 1: j->n = len[0] / B; ok = j->in[0] && j->in[1] && len[0] % B == 0 && len[1] == j->n * 2 * B; break;
     case 2: j->n = len[0] / B; ok = j->in[0] && j->in[2] && j->in[3] && len[0] % B == 0 && len[2] == len[0] &&
@@ -1064,7 +1163,9 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   j->out1_len = op == 5 || op >= 11 ? j->n * NB : j->n;
   j->out2_len = op == 5 || op >= 11 ? j->n : 0;
   j->out3_len = op == 5 || op >= 11 ? j->n : 0;
-  j->out0 = (uint8_t*)malloc(j->out0_len ? j->out0_len : 1);
+  if (op >= 13) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
+  /* (op 16: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
+  j->out0 = (uint8_t*)malloc(op == 16 ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
   j->out1 = (uint8_t*)malloc(j->out1_len ? j->out1_len : 1);
   j->out2 = (uint8_t*)malloc(j->out2_len ? j->out2_len : 1);
   j->out3 = (uint8_t*)malloc(j->out3_len ? j->out3_len : 1);
@@ -1095,7 +1196,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"pointAdd", fn_point_add}, {"sigFromDer", fn_sig_from_der}, {"sigToDer", fn_sig_to_der}, {"ecdsaVerifyWire", fn_verify_wire},
     {"customDecompress", fn_custom_decompress}, {"customDecodePoints", fn_custom_decode_points},
     {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
-    {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
+    {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det}, {"customEcdh", fn_custom_ecdh},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

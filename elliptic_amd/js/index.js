@@ -45,6 +45,7 @@ function Engine(options) {
     options.devices.map(function(d) { return d | 0; }) : null;
   this.ctx = this.addon.createContext(this.devices || (options.device | 0));
   this.stats = { gpuCalls: 0, gpuItems: 0, passthrough: 0, offCurve: 0 };
+  this._coordBytes = {};       // p.byteLength() of the short curves defined here, by id (customEncodePointBatch)
 }
 
 // The context owns the device's memory for this engine (fixed-base tables: 1.6 GB for secp256k1 at
@@ -74,11 +75,19 @@ Engine.prototype.combBits = function combBits(curve) {
 // (`new elliptic.curve.short({p, a, b})`, lib/elliptic/curve/short.js:11-24) and return its curve
 // id: usable with mulBatch (points given), mulAddBatch (both points given) and pointAddBatch, with
 // 32-byte scalars and coordinates.  p, a, b: BN-like (toArray) or 32-byte Buffers.
+// p.byteLength() of a 32-byte big-endian prime: the width of a SEC1 coordinate on its curve
+function byteLength(p32) {
+  var i = 0;
+  while (i < p32.length - 1 && p32[i] === 0) i++;
+  return p32.length - i;
+}
 Engine.prototype.defineShort = function defineShort(p, a, b) {
   function buf(v) {
     return Buffer.isBuffer(v) ? v : Buffer.from(v.toArray('be', 32));
   }
-  return this.addon.defineShort(this.ctx, buf(p), buf(a), buf(b));
+  var id = this.addon.defineShort(this.ctx, buf(p), buf(a), buf(b));
+  this._coordBytes[id] = byteLength(buf(p));
+  return id;
 };
 // An ECDSA domain on such a curve: the curve plus its order n and generator G = (gx, gy)
 // (ellgpu_curve_define_short_domain).  Its id takes what a defineShort id takes, and also
@@ -88,7 +97,9 @@ Engine.prototype.defineShortDomain = function defineShortDomain(p, a, b, n, gx, 
   function buf(v) {
     return Buffer.isBuffer(v) ? v : Buffer.from(v.toArray('be', 32));
   }
-  return this.addon.defineShortDomain(this.ctx, buf(p), buf(a), buf(b), buf(n), buf(gx), buf(gy));
+  var id = this.addon.defineShortDomain(this.ctx, buf(p), buf(a), buf(b), buf(n), buf(gx), buf(gy));
+  this._coordBytes[id] = byteLength(buf(p));
+  return id;
 };
 // The same for a (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) that is not ed25519
 // (`new elliptic.curve.edwards({p, a, c: 1, d})`, lib/elliptic/curve/edwards.js:11-31)
@@ -365,6 +376,49 @@ Engine.prototype.eddsaSignBatch = function eddsaSignBatch(msgs, secrets) {
   return this.addon.eddsaSign(this.ctx, Buffer.concat(msgs), off, 0, secrets);
 };
 
+// The key side on a user-defined short curve (an id from defineShort / defineShortDomain), on the
+// device.  Scalars and coordinates are 32 bytes; a SEC1 coordinate is p.byteLength() bytes.
+// install() does not route KeyPair#derive / #validate / getPublic to these: they are for callers
+// that batch.
+// customDeriveBatch: KeyPair#derive; privs Buffer(n x 32) used as they stand (Point#mul does not
+// reduce them mod n), pubs Buffer(n x 64) x || y, each coordinate reduced mod p ->
+// { x: Buffer(n x 32), status: Buffer(n) }; status 0 shared secret, 1 'public point not validated',
+// 2 the product is the point at infinity (getX throws)
+Engine.prototype.customDeriveBatch = function customDeriveBatch(curve, privs, pubs) {
+  this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
+  return this.addon.customEcdh(this.ctx, 13, this._id(curve), privs, pubs, 0, 0);
+};
+// customDeriveWireBatch: the same with the peer keys as SEC1 encodings of pubLen bytes each
+// (keyFromPublic -> decodePoint) -> { x, status, err }; status 3 = the key did not decode, err the
+// statuses of customDecodePointBatch
+Engine.prototype.customDeriveWireBatch = function customDeriveWireBatch(curve, privs, pubs, pubLen) {
+  this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
+  return this.addon.customEcdh(this.ctx, 14, this._id(curve), privs, pubs, pubLen | 0, 0);
+};
+// customValidateBatch: KeyPair#validate; xy Buffer(n x 64), inf Buffer(n) or null -> { status }:
+// 0 ok, 1 'Invalid public key', 2 'Public key is not a point', 3 'Public key * N != O' (checkOrder:
+// a domain id only)
+Engine.prototype.customValidateBatch = function customValidateBatch(curve, xy, inf, checkOrder) {
+  this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
+  return this.addon.customEcdh(this.ctx, 15, this._id(curve), xy, inf || null, checkOrder === false ? 0 : 1, 0);
+};
+// customEncodePointBatch: BasePoint#encode at the curve's own width PL = p.byteLength() ->
+// { enc: Buffer(n x (1 + PL)) } for compact, else n x (1 + 2 PL).  PL is what defineShort /
+// defineShortDomain recorded for the id: the library writes rows of that width whatever the caller
+// believes, so an id this engine did not define, or a coordBytes (optional) that is not the
+// curve's, throws before anything runs.
+Engine.prototype._encodeWidth = function _encodeWidth(curve, coordBytes) {
+  var pl = this._coordBytes[this._id(curve)];
+  if (pl === undefined) throw new Error('customEncodePointBatch: not a short curve defined on this engine');
+  if (coordBytes !== undefined && coordBytes !== null && coordBytes !== pl)
+    throw new Error('customEncodePointBatch: coordBytes ' + coordBytes + ' is not the curve\'s p.byteLength() = ' + pl);
+  return pl;
+};
+Engine.prototype.customEncodePointBatch = function customEncodePointBatch(curve, xy, compact, coordBytes) {
+  var pl = this._encodeWidth(curve, coordBytes);
+  this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
+  return this.addon.customEcdh(this.ctx, 16, this._id(curve), xy, null, compact ? 1 : 0, pl);
+};
 // ---- asynchronous batch API: same arguments, returns a Promise; the work runs on a
 // libuv worker thread (napi_async_work), so the JS thread stays responsive during a large
 // batch.  A context processes one call at a time, so calls are chained.
@@ -417,6 +471,20 @@ Engine.prototype.customSignBatchAsync = function(curve, hashes, hashLen, msgBits
 };
 Engine.prototype.customSignDetBatchAsync = function(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
   return this._async(12, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
+};
+Engine.prototype.customDeriveBatchAsync = function(curve, privs, pubs) {
+  return this._async(13, curve, 0, 0, privs, pubs, null, null, 0, 0);
+};
+Engine.prototype.customDeriveWireBatchAsync = function(curve, privs, pubs, pubLen) {
+  return this._async(14, curve, 0, 0, privs, pubs, null, null, pubLen | 0, 0);
+};
+Engine.prototype.customValidateBatchAsync = function(curve, xy, inf, checkOrder) {
+  return this._async(15, curve, 0, 0, xy, inf || null, null, null, checkOrder === false ? 0 : 1, 0);
+};
+Engine.prototype.customEncodePointBatchAsync = function(curve, xy, compact, coordBytes) {
+  var pl;
+  try { pl = this._encodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
+  return this._async(16, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
 };
 Engine.prototype.decodePointBatchAsync = function(curve, enc, encLen) {
   return this._async(8, curve, 0, 0, enc, null, null, null, encLen, 0);

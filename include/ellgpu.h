@@ -217,7 +217,8 @@ int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* 
  * validate) answers ELLGPU_E_UNSUPPORTED on a domain id; compressed keys, SEC1 encodings and DER
  * signatures on a domain go through ellgpu_custom_decompress / _custom_decode_points /
  * _custom_verify_wire below, public-key recovery through ellgpu_custom_recover, signing through
- * ellgpu_custom_sign / _custom_sign_det.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
+ * ellgpu_custom_sign / _custom_sign_det, ECDH, key validation and SEC1 encoding through
+ * ellgpu_custom_derive / _custom_derive_wire / _custom_validate / _custom_encode_points.  On a plain ellgpu_curve_define_short id, mul_fixed, mul_add2
  * without p1 and ecdsa_verify stay ELLGPU_E_UNSUPPORTED. */
 int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                                      const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve);
@@ -349,6 +350,61 @@ int ellgpu_custom_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* 
 int ellgpu_custom_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                                int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
                                uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream);
+/* The key side on user-defined short curves, on the device: ECDH, key validation and SEC1
+ * encoding.  Entry points of their own because ellgpu_validate, ellgpu_encode_points and the other
+ * preset-named ones are documented to refuse user-defined ids (and keep doing so).  ELLGPU_E_ARG on a
+ * preset id or an unknown id, ELLGPU_E_UNSUPPORTED on a user-defined Edwards id.  Synchronous like
+ * every call on a user-defined curve; a group runs them on its first member.  Scalars and
+ * coordinates in and out of the engine are 32 bytes big-endian; a SEC1 coordinate is
+ * PL = p.byteLength() bytes.
+ * ellgpu_custom_derive: KeyPair#derive(pub) (lib/elliptic/ec/key.js:101-107) per item, on a domain
+ *   id or a plain ellgpu_curve_define_short id (derive needs neither n nor G).
+ *   priv    n x 32 bytes, used as it stands, as Point#mul uses it (short.js:422-432): NOT reduced
+ *           mod n -- the reference's _importPrivate (key.js:76-82) did that earlier
+ *   pub_xy  n x 64 bytes, x || y; each coordinate is reduced mod p as toRed does (short.js:261-264):
+ *           a coordinate >= p is legal input
+ *   out_x   n x 32 bytes: pub.mul(priv).getX(); zeroed unless out_status is 0
+ *   out_status
+ *     0  out_x is the shared secret
+ *     1  'public point not validated': ShortCurve#validate (short.js:205-216) found
+ *        y^2 != x^3 + a x + b
+ *     2  the product is the point at infinity (priv = 0, a multiple of the point's order): getX
+ *        throws in the reference
+ * ellgpu_custom_derive_wire: the same with the peer key as a SEC1 encoding -- keyFromPublic ->
+ *   BaseCurve#decodePoint (base.js:270-293).  One pub_len per call: 1 + PL (02 / 03) or 1 + 2 PL
+ *   (04 / 06 / 07); any other pub_len > 0 leaves every item undecoded, pub_len = 0 is ELLGPU_E_ARG.
+ *   out_err (may be NULL) carries exactly the statuses of ellgpu_custom_decode_points (0 / 1 / 2 / 3; a
+ *   compressed x without a y is 3 where p = 1 mod 4).  An item whose key does not decode has
+ *   out_status 3 and a zeroed out_x.  An uncompressed key is not tested by the decoder, as in the
+ *   reference: the derive's own validation answers 1 for it.  Decoding, the root, validation, the
+ *   ladder and the x all run on the device within this one call.
+ * ellgpu_custom_validate: KeyPair#validate (key.js:40-51) with the statuses of ellgpu_validate,
+ *   tested in the reference's order: 0 {result: true}; 1 'Invalid public key' (inf[i] != 0; inf
+ *   may be NULL); 2 'Public key is not a point'; 3 'Public key * N != O'.  With check_order != 0
+ *   one n * P per item through the variable-base ladder, the domain's n as the scalar;
+ *   check_order != 0 on a plain id is ELLGPU_E_UNSUPPORTED (it has no n).  xy: n x 64 bytes,
+ *   reduced mod p.
+ * ellgpu_custom_encode_points: BasePoint#encode (base.js:295-311) at the curve's own width:
+ *   compact == 0 gives 04 || x || y, 1 + 2 PL bytes per item; compact != 0 gives 02/03 || x,
+ *   1 + PL bytes.  Coordinates are reduced mod p first.  With ellgpu_mul_fixed on a domain this is
+ *   KeyPair#getPublic(compact, enc) (key.js:53-67). */
+int ellgpu_custom_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                         uint8_t* out_x, uint8_t* out_status);
+int ellgpu_custom_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                             uint8_t* out_x, uint8_t* out_status, void* stream);
+int ellgpu_custom_derive_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                              size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err);
+int ellgpu_custom_derive_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                                  size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err,
+                                  void* stream);
+int ellgpu_custom_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
+                           int check_order, uint8_t* out_status);
+int ellgpu_custom_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
+                               int check_order, uint8_t* out_status, void* stream);
+int ellgpu_custom_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                uint8_t* out_enc);
+int ellgpu_custom_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                    uint8_t* out_enc, void* stream);
 /* User-defined (twisted) Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 (c = 1) over an odd prime
  * p < 2^256 -- `new elliptic.curve.edwards({p, a, c: 1, d, ...})` (lib/elliptic/curve/edwards.js:
  * 11-31) with parameters that are not ed25519's.  Same id space, widths (32 bytes) and entry

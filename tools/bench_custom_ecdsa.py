@@ -33,7 +33,16 @@ k*G (mul_fixed_dev) of the same domain in the same run.  k*G is the floor no sig
 asserted accepted, the signatures of the deterministic call are then verified and their keys
 recovered; "kernels_ms" are the launches of one custom_sign_det call.
 
-    python tools/bench_custom_ecdsa.py --sign [log2 n ...]                     (default: 18 20)"""
+    python tools/bench_custom_ecdsa.py --sign [log2 n ...]                     (default: 18 20)
+
+--ecdh: the key side on the domain (brainpoolP256r1), in one run: custom_derive_dev over raw peer
+keys, custom_derive_wire_dev over the same keys compressed (02 / 03 || x: the square root on top),
+mul_var_dev on the same scalars and points as the yardstick -- the raw derive adds one equation test
+in front and drops the y behind ("derive_over_mul_var") -- and custom_validate_dev with the order
+test (one n * P per item).  Every item is asserted status 0, the two derives equal to mul_var's x;
+"kernels_ms" are the launches of one custom_derive_wire call.
+
+    python tools/bench_custom_ecdsa.py --ecdh [log2 n ...]                     (default: 18 20)"""
 import json
 import os
 import sys
@@ -242,6 +251,52 @@ def run_sign(ctx, spec, n):
     return out
 
 
+def run_ecdh(ctx, spec, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_domain_checks as CD
+    cid = CD.define(ctx, spec)
+    nn = CD.I(spec["n"])
+    pl = (CD.I(spec["p"]).bit_length() + 7) // 8
+    keep = nn.bit_length() - 1                      # scalars below 2^(bitLength(n) - 1) < n
+    def below_n(tag):
+        a = bench.xof("custom-ecdh:%s:%s" % (spec["name"], tag), n * 32).reshape(n, 32).copy()
+        a[:, :32 - (keep + 7) // 8] = 0
+        if keep % 8:
+            a[:, 32 - (keep + 7) // 8] &= (1 << (keep % 8)) - 1
+        a[:, 31] |= 1
+        return a
+    d, k = below_n("d"), below_n("k")
+    q, inf = ctx.mul_fixed(cid, d)                  # the peers' keys
+    assert not inf.any()
+    keys = np.concatenate([(2 + (q[:, 63] & 1))[:, None], q[:, 32 - pl:32]], axis=1).astype(np.uint8)
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    z = lambda *sh: torch.full(sh, 9, dtype=torch.uint8, device=dev)
+    dk, dq, dkeys = t(k), t(q), t(keys)
+    x1, st1, x2, st2, err2, vst, mxy, minf = z(n, 32), z(n), z(n, 32), z(n), z(n), z(n), z(n, 64), z(n)
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": spec["name"], "n": n}
+    for name, fn in (("mul_var", lambda: ctx.mul_var_dev(cid, dk, dq, mxy, minf)),
+                     ("derive", lambda: ctx.custom_derive_dev(cid, dk, dq, x1, st1)),
+                     ("derive_wire", lambda: ctx.custom_derive_wire_dev(cid, dk, dkeys, x2, st2, err2)),
+                     ("validate_order", lambda: ctx.custom_validate_dev(cid, dq, None, True, vst))):
+        ms = timed(fn)
+        out[name + "_ms"] = round(ms, 3)
+        out[name + "_M_per_s"] = round(n / ms / 1e3, 2)
+    assert not st1.any().item() and not st2.any().item() and not err2.any().item() and not vst.any().item()
+    assert not minf.any().item() and torch.equal(x1, mxy[:, :32]) and torch.equal(x2, x1)
+    out["derive_over_mul_var"] = round(out["derive_ms"] / out["mul_var_ms"], 4)
+    out["derive_wire_over_derive"] = round(out["derive_wire_ms"] / out["derive_ms"], 4)
+    out["validate_over_mul_var"] = round(out["validate_order_ms"] / out["mul_var_ms"], 4)
+    ctx.set_timing(True)
+    ctx.custom_derive_wire_dev(cid, dk, dkeys, x2, st2, err2)
+    torch.cuda.synchronize()
+    out["kernels_ms"] = {name: round(ms, 4) for name, (cnt, ms) in ctx.get_timing().items()}
+    ctx.set_timing(False)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
@@ -264,6 +319,16 @@ def main():
             spec = next(c for c in CD.curves() if c["name"] == "brainpoolP256r1")
             for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
                 print(json.dumps(run_sign(ctx, spec, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
+    if sys.argv[1:2] == ["--ecdh"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            spec = next(c for c in CD.curves() if c["name"] == "brainpoolP256r1")
+            for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
+                print(json.dumps(run_ecdh(ctx, spec, 1 << lg)), flush=True)
         finally:
             ctx.close()
         return
