@@ -217,7 +217,7 @@ int ellgpu_ctx_comb_bits(ellgpu_ctx* ctx, int curve) {
   return ctx->eng->comb_bits(curve);
 }
 
-// dom: n, gx, gy of an ECDSA domain (edwards = 0), else null
+// edwards: 0 short, 1 Edwards, 2 Montgomery (b unused); dom: n, gx, gy of an ECDSA domain (edwards = 0), else null
 static int define_custom(ellgpu_ctx* ctx, int edwards, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                          int* out_curve, const uint8_t* const* dom = nullptr) {
   if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
@@ -244,6 +244,7 @@ static int define_custom(ellgpu_ctx* ctx, int edwards, const uint8_t* p, const u
   }
   ctx->eng->err.clear();
   int rc = dom ? ctx->eng->define_short_domain(p, a, b, dom[0], dom[1], dom[2], out_curve)
+               : edwards == 2 ? ctx->eng->define_mont(p, a, out_curve)
                : edwards ? ctx->eng->define_edwards(p, a, b, out_curve) : ctx->eng->define_short(p, a, b, out_curve);
   if (rc) g_last_error = ctx->eng->err.empty() ? "ellgpu error" : ctx->eng->err;
   return rc;
@@ -255,6 +256,9 @@ int ellgpu_curve_define_short(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* 
 int ellgpu_curve_define_edwards(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* d,
                                 int* out_curve) {
   return define_custom(ctx, 1, p, a, d, out_curve);
+}
+int ellgpu_curve_define_mont(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, int* out_curve) {
+  return define_custom(ctx, 2, p, a, nullptr, out_curve);
 }
 int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                                      const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve) {
@@ -584,6 +588,37 @@ int ellgpu_custom_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const 
                                     uint8_t* out_enc, void* stream) {
   ELL_ENTER_DEV(ctx, stream);
   return finish(ctx, ctx->eng->custom_encode_points_dev(curve, n, xy, compact, out_enc), true);
+}
+
+// Point#mul + getX, MontCurve#validate and KeyPair#derive on a user-defined Montgomery curve (a group: member 0)
+int ellgpu_custom_mont_ladder(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
+                              uint8_t* out_x, uint8_t* out_inf) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_mont_host(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_LADDER, n, k, in_x, out_x, out_inf));
+}
+int ellgpu_custom_mont_ladder_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
+                                  uint8_t* out_x, uint8_t* out_inf, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_mont_dev(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_LADDER, n, k, in_x, out_x, out_inf), true);
+}
+int ellgpu_custom_mont_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* in_x, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_mont_host(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_VALIDATE, n, nullptr, in_x, nullptr, out_status));
+}
+int ellgpu_custom_mont_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* in_x, uint8_t* out_status,
+                                    void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_mont_dev(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_VALIDATE, n, nullptr, in_x, nullptr, out_status), true);
+}
+int ellgpu_custom_mont_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
+                              uint8_t* out_x, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_mont_host(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_DERIVE, n, priv, pub_x, out_x, out_status));
+}
+int ellgpu_custom_mont_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
+                                  uint8_t* out_x, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_mont_dev(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_DERIVE, n, priv, pub_x, out_x, out_status), true);
 }
 
 int ellgpu_ecdsa_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,

@@ -22,6 +22,7 @@
 
 #include "edwards.h"
 #include "edcustom.h"
+#include "montcustom.h"
 #include "mont.h"
 #include "rt_define.h"
 #include "work.h"
@@ -1105,6 +1106,32 @@ struct FnEdcNormalize {
   }
 };
 
+// user-defined Montgomery curves (montcustom.h)
+struct FnMontcLadder {
+  static constexpr const char* NAME = "montc_ladder";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* k; const u8* x; u32* xz;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) MontcWork::ladder(i, n, k, x, xz);
+  }
+};
+struct FnMontcValidate {
+  static constexpr const char* NAME = "montc_validate";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* x; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) MontcWork::validate(i, x, status);
+  }
+};
+struct FnMontcNormalize {
+  static constexpr const char* NAME = "montc_normalize";
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u32* xz; u32* pre; const u8* vst; u8* out_x; u8* out_flag;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) MontcWork::normalize(t, T, n, K, xz, pre, vst, out_x, out_flag);
+  }
+};
+
 // ---- curve metadata ----------------------------------------------------------
 struct CurveInfo {
   const char* name;
@@ -1352,6 +1379,10 @@ class Engine {
   template <int U = 0>
   int edc_chunk(int op, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                 const u8* a, const u8* b, u8* out_xy, u8* out_inf);
+  // user-defined Montgomery curves: op 0 = Point#mul + getX (flag: Z == 0), 1 = MontCurve#validate
+  // (k, out_x unused), 2 = KeyPair#derive (validate, ladder, getX; flag: the derive status)
+  template <int U = 0>
+  int montc_chunk(int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag);
   // wire formats on user-defined short curves (OP_RT_*): pointFromX, decodePoint, the DER parser
   // and the wire verify's status fold -- the kernels of one code object (inst.hip group 16)
   template <int U = 0>
@@ -1480,10 +1511,19 @@ class Engine {
     RtField f;
     return define(rt_build_custom(1, p_be, a_be, d_be, f), f, out_curve);
   }
+  // `new elliptic.curve.mont({p, a, b})` (mont.js:11-21) with parameters that are not curve25519's:
+  // b y^2 = x^3 + a x^2 + x over an odd prime p < 2^256, x-only; Point#mul + getX,
+  // MontCurve#validate and KeyPair#derive run on the device (montcustom.h).  No b: no formula reads it.
+  int define_mont(const u8* p_be, const u8* a_be, int* out_curve) {
+    if (!out_curve) return fail(E_ARG, "null pointer");
+    RtField f;
+    return define(rt_build_custom(2, p_be, a_be, nullptr, f), f, out_curve);
+  }
   // the id a definition WOULD get (the existing one for parameters already registered, else the
   // next free one), -1 when the table is full; registers nothing.  Invalid parameters report the
   // next free id: the definition itself then fails with its own message, on the first member.
-  // dom: n, gx, gy of an ECDSA domain (edwards = 0), else null
+  // edwards: 0 short, 1 Edwards, 2 Montgomery (bd_be unused); dom: n, gx, gy of an ECDSA domain
+  // (edwards = 0), else null
   int custom_slot_for(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be,
                       const u8* const* dom = nullptr) {
     RtField f;
@@ -1502,6 +1542,10 @@ class Engine {
   bool custom_is_edwards(int curve) const {
     size_t slot = (size_t)(curve - CURVE_CUSTOM0);
     return is_custom(curve) && slot < custom_.size() && custom_[slot].kind == 1;
+  }
+  bool custom_is_mont(int curve) const {
+    size_t slot = (size_t)(curve - CURVE_CUSTOM0);
+    return is_custom(curve) && slot < custom_.size() && custom_[slot].kind == 2;
   }
   bool custom_is_domain(int curve) const {
     size_t slot = (size_t)(curve - CURVE_CUSTOM0);
@@ -1557,10 +1601,16 @@ class Engine {
     Engine* e;
     bool owner = false;
     int rc = E_OK;
-    CustomScope(Engine* eng, int curve) : e(eng) {
+    // mont: the call is one of the Montgomery entry points (custom_mont_*); every other call
+    // refuses a Montgomery id here, before anything is uploaded
+    CustomScope(Engine* eng, int curve, bool mont = false) : e(eng) {
       if (!is_custom(curve) || e->custom_active_) return;
       size_t slot = (size_t)(curve - CURVE_CUSTOM0);
       if (slot >= e->custom_.size()) { rc = e->fail(E_ARG, "unknown curve id"); return; }
+      if (!mont && e->custom_[slot].kind == 2) {
+        rc = e->fail(E_UNSUPPORTED, "not available on user-defined Montgomery curves (x-only: ellgpu_custom_mont_ladder, _validate, _derive)");
+        return;
+      }
       custom_mutex(e->bk.device_index()).lock();
       owner = true;
       e->custom_active_ = true;
@@ -2165,6 +2215,7 @@ class Engine {
                                : fail(E_ARG, "unknown curve id");
     const RtField* f = custom_block(curve);
     if (!f) return fail(E_ARG, "unknown curve id");
+    if (f->kind == 2) return fail(E_UNSUPPORTED, "not available on user-defined Montgomery curves (x-only: ellgpu_custom_mont_ladder, _validate, _derive)");
     if (f->kind != 0) return fail(E_UNSUPPORTED, "not available on user-defined Edwards curves");
     if (need_domain && !f->domain)
       return fail(E_UNSUPPORTED, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
@@ -2710,6 +2761,44 @@ class Engine {
       return ecdsa_verify_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], d[3], o[0], o[1]);
     });
   }
+  // ---- user-defined Montgomery curves (ellgpu_custom_mont_*) --------------------------------
+  // op as montc_chunk's.  A preset or unknown id is an argument error, a short or Edwards
+  // user-defined id is unsupported.
+  enum { OP_MONTC_LADDER = 0, OP_MONTC_VALIDATE = 1, OP_MONTC_DERIVE = 2 };
+  int check_custom_mont(int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
+    if (!is_custom(curve))
+      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (curve25519 has ellgpu_x25519_ladder and ellgpu_x25519_derive)")
+                               : fail(E_ARG, "unknown curve id");
+    const RtField* f = custom_block(curve);
+    if (!f) return fail(E_ARG, "unknown curve id");
+    if (f->kind != 2) return fail(E_UNSUPPORTED, "not a user-defined Montgomery curve (ellgpu_curve_define_mont)");
+    if (n && (!x || !out_flag || (op != OP_MONTC_VALIDATE && (!k || !out_x)))) return fail(E_ARG, "null pointer");
+    return E_OK;
+  }
+  int custom_mont_dev(int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
+    int rc = check_custom_mont(curve, op, n, k, x, out_x, out_flag);
+    if (rc) return rc;
+    CustomScope sc(this, curve, true);
+    if (sc.rc) return sc.rc;
+    const bool v = op == OP_MONTC_VALIDATE;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return montc_chunk(op, m, v ? nullptr : k + o * 32, x + o * 32, v ? nullptr : out_x + o * 32, out_flag + o);
+    });
+  }
+  int custom_mont_host(int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
+    int rc = check_custom_mont(curve, op, n, k, x, out_x, out_flag);
+    if (rc) return rc;
+    CustomScope sc(this, curve, true);
+    if (sc.rc) return sc.rc;
+    if (op == OP_MONTC_VALIDATE)
+      return staged(n, {In{x, 32}}, {Out{out_flag, 1}}, [&](size_t m, auto d, auto r) {
+        return custom_mont_dev(curve, op, m, nullptr, d[0], nullptr, r[0]);
+      });
+    return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_flag, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_mont_dev(curve, op, m, d[0], d[1], r[0], r[1]);
+    });
+  }
+
   int x25519_host(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
     if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
     return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_inf, 1}, Out{out_bad, 1}},
@@ -3138,6 +3227,31 @@ int Engine<BK>::edc_chunk(int op, size_t n, const u8* k1, const u8* xy1, const u
     FnEdcDomainMark h{n, xy1, op == 1 ? xy2 : nullptr, out_xy, out_inf};
     bk.launch(h, n);
   }
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::montc_chunk(int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
+  if (op == OP_MONTC_VALIDATE) {
+    FnMontcValidate fv{n, x, out_flag};
+    bk.launch(fv, n);
+    return E_OK;
+  }
+  u32* xz = (u32*)scratch(S_JAC, n * 2 * 8 * 4);
+  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
+  u8* vst = op == OP_MONTC_DERIVE ? (u8*)scratch(S_VALID, n) : nullptr;
+  if (!xz || !pre || (op == OP_MONTC_DERIVE && !vst)) return fail(E_NOMEM, "scratch allocation failed");
+  if (vst) {
+    FnMontcValidate fv{n, x, vst};
+    bk.launch(fv, n);
+  }
+  FnMontcLadder f{n, k, x, xz};
+  bk.launch(f, n);
+  const int K = norm_batch_for(n);
+  const size_t T = (n + K - 1) / K;
+  FnMontcNormalize g{T, n, K, xz, pre, vst, out_x, out_flag};
+  bk.launch(g, T);
   return E_OK;
 }
 

@@ -39,7 +39,19 @@ struct RtField {
   u32 b_m[8];      // curve coefficient b, Montgomery form
   u32 a_kind;      // 0: a == 0, 3: a == p - 3, 1: anything else
   u32 d_m[8];      // Edwards curves (edcustom.h): coefficient d, Montgomery form; a_m holds a
-  u32 kind;        // 0: short Weierstrass (a_m, b_m), 1: (twisted) Edwards with c = 1 (a_m, d_m)
+  u32 kind;        // 0: short Weierstrass (a_m, b_m), 1: (twisted) Edwards with c = 1 (a_m, d_m),
+                   // 2: Montgomery (montcustom.h), which REUSES fields of the other kinds -- the
+                   //    block's size and layout are pinned, and a Montgomery curve needs neither a
+                   //    Weierstrass b nor a square root:
+                   //      a_m         the curve's a, Montgomery form
+                   //      b_m         a24 = (a + 2) / 4 mod p, Montgomery form (the curve's own b
+                   //                  enters no formula of the reference and is not stored)
+                   //      sqrt_e      (p - 1) / 2: Euler's criterion through pow_sqrt_e
+                   //      sqrt_ebits  its bit length
+                   //      sqrt_kind   0: p = 3 (mod 4), 1: p = 1 (mod 4) -- what MontCurve#validate
+                   //                  answers on a non-residue (false / 'Assertion failed')
+                   //      pbytes      p.byteLength()
+                   //    a_kind, d_m, sqrt_s, sqrt_c and the domain fields stay zero
   // ECDSA domain (ellgpu_curve_define_short_domain): the order n and the generator G.  Zero for a
   // plain curve, so that a domain and the plain curve with the same (p, a, b) are different blocks.
   u32 domain;      // 1: the fields below are set

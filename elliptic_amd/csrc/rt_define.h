@@ -1,5 +1,6 @@
 // ellgpu -- definition of a user-defined curve: host arithmetic modulo any odd m < 2^256 and the
-// parameter block (fp_rt.h RtField) of a short curve, an ECDSA domain on it or an Edwards curve.
+// parameter block (fp_rt.h RtField) of a short curve, an ECDSA domain on it, an Edwards curve or a
+// Montgomery curve.
 // Host only, no engine: Engine::define_* forward a refusal to fail() and register the block.
 // Engine::register_custom compares blocks byte for byte (same parameters, same id): every builder
 // starts from a zeroed block and writes each member as a function of the parameters alone.
@@ -153,11 +154,41 @@ inline void rt_sqrt_init(RtField& f) {
   f.sqrt_ebits = (u32)bit_length(f.sqrt_e);
 }
 
-// parameter block of a user-defined curve (edwards = 0: short Weierstrass, b; 1: Edwards, d):
-// p an odd prime < 2^256 (primality is the caller's business, as it is the reference's), a and
-// b / d any residues
+// The block of a Montgomery curve (kind 2; fp_rt.h documents the fields it reuses): a24 =
+// (a + 2) / 4 where the short curve's b sits, (p - 1) / 2 and p mod 4 where Red#sqrt's constants sit
+inline void rt_mont_init(RtField& f, const u32 (&a_m)[8]) {
+  u32 two[8], t[8];
+  bn_zero<8>(two);
+  two[0] = 2;
+  mod_to_mont(f.p, two, two);
+  mod_add<8>(t, a_m, two, f.p);
+  for (int h = 0; h < 2; h++) {                         // t / 2 mod p, twice: (t + p) / 2 for an odd t
+    u32 c = 0;
+    if (t[0] & 1u) c = bn_add<8>(t, t, f.p);
+    for (int i = 0; i < 8; i++) t[i] = (t[i] >> 1) | ((i + 1 < 8 ? t[i + 1] : c) << 31);
+  }
+  bn_copy<8>(f.b_m, t);
+  bn_copy<8>(f.sqrt_e, f.p);
+  for (int i = 0; i < 8; i++) f.sqrt_e[i] = (f.p[i] >> 1) | (i + 1 < 8 ? f.p[i + 1] << 31 : 0u);   // (p - 1) / 2
+  f.sqrt_ebits = (u32)bit_length(f.sqrt_e);
+  f.sqrt_kind = (f.p[0] & 3u) == 1u ? 1u : 0u;
+  f.pbytes = (u32)((bit_length(f.p) + 7) / 8);
+  f.kind = 2;
+}
+// parameter block of a user-defined curve (edwards = 0: short Weierstrass, b; 1: Edwards, d; 2:
+// Montgomery, bd_be unused): p an odd prime < 2^256 (primality is the caller's business, as it is
+// the reference's), a and b / d any residues
 inline RtStatus rt_build_custom(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be, RtField& f) {
-  if (!p_be || !a_be || !bd_be) return {E_ARG, "null pointer"};
+  if (!p_be || !a_be || (!bd_be && edwards != 2)) return {E_ARG, "null pointer"};
+  if (edwards == 2) {
+    const RtStatus st = rt_field_init(f, p_be);
+    if (st.code) return st;
+    u32 a[8];
+    load_be<8>(a, a_be, 32);
+    mod_to_mont(f.p, f.a_m, a);
+    rt_mont_init(f, f.a_m);
+    return {E_OK, nullptr};
+  }
   const RtStatus st = rt_field_init(f, p_be);
   if (st.code) return st;
   u32 a[8], b[8];

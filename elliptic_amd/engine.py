@@ -142,6 +142,17 @@ class Context:
         self._check(self._lib.ellgpu_curve_define_edwards(self._ctx, enc[0], enc[1], enc[2], ctypes.byref(cid)))
         return cid.value
 
+    def define_mont(self, p, a):
+        """Register the Montgomery curve b y^2 = x^3 + a x^2 + x over the odd prime p < 2^256 (`new
+        curve.mont({p, a, b})` with parameters that are not curve25519's) and return its curve id.
+        There is no b: no formula of the reference's x-only model reads it.  Such an id is valid for
+        custom_mont_ladder / custom_mont_validate / custom_mont_derive and their _dev forms only."""
+        cid = ctypes.c_int(-1)
+        p = int(p)
+        self._check(self._lib.ellgpu_curve_define_mont(self._ctx, p.to_bytes(32, "big"), (int(a) % p if p else int(a)).to_bytes(32, "big"),
+                                                       ctypes.byref(cid)))
+        return cid.value
+
     def reserve(self, curve, n):
         self._check(self._lib.ellgpu_ctx_reserve(self._ctx, self._cid(curve), int(n)))
 
@@ -598,6 +609,58 @@ class Context:
                                                          inf.data_ptr() if inf is not None else None,
                                                          1 if check_order else 0, out_status.data_ptr(),
                                                          self._stream()))
+
+    # ---- user-defined Montgomery curves (define_mont): x-only ladder, validate, ECDH ---------------
+
+    def custom_mont_ladder(self, curve, k, x, out=None):
+        """Point#mul(k) + getX() per item on a define_mont id -> (x, inf): k (n, 32) as it stands
+        (neither reduced nor clamped), x (n, 32) reduced mod p; inf = 1 where Z = 0 (the reference's
+        getX() returns 0 there), with x zeroed -- the contract of x25519()"""
+        k = _u8(k, (-1, 32))
+        n = k.shape[0]
+        x = _u8(x, (n, 32))
+        ox, inf = self._outs(out, [(n, 32), (n,)])
+        self._check(self._lib.ellgpu_custom_mont_ladder(self._ctx, self._cid(curve), n, k.ctypes.data, x.ctypes.data,
+                                                        ox.ctypes.data, inf.ctypes.data))
+        return ox, inf
+
+    def custom_mont_ladder_dev(self, curve, k, x, out_x, out_inf):
+        n = k.shape[0]
+        self._check(self._lib.ellgpu_custom_mont_ladder_dev(self._ctx, self._cid(curve), n, k.data_ptr(), x.data_ptr(),
+                                                            out_x.data_ptr(), out_inf.data_ptr(), self._stream()))
+
+    def custom_mont_validate(self, curve, x, out=None):
+        """MontCurve#validate per item -> status: 0 true, 1 false (a non-residue, p = 3 mod 4),
+        3 'Assertion failed' (a non-residue, p = 1 mod 4: bn.js's Tonelli-Shanks loop throws)"""
+        x = _u8(x, (-1, 32))
+        n = x.shape[0]
+        st, = self._outs(out, [(n,)])
+        self._check(self._lib.ellgpu_custom_mont_validate(self._ctx, self._cid(curve), n, x.ctypes.data, st.ctypes.data))
+        return st
+
+    def custom_mont_validate_dev(self, curve, x, out_status):
+        n = x.shape[0]
+        self._check(self._lib.ellgpu_custom_mont_validate_dev(self._ctx, self._cid(curve), n, x.data_ptr(),
+                                                              out_status.data_ptr(), self._stream()))
+
+    def custom_mont_derive(self, curve, priv, pub_x, out=None):
+        """KeyPair#derive per item on a define_mont id -> (x, status): 0 x is pub.mul(priv).getX(),
+        1 'public point not validated', 3 'Assertion failed' (validate threw), 2 Z = 0 (the reference
+        returns 0).  Validation is tested first; priv (n, 32) is used as it stands; x is zeroed
+        unless the status is 0"""
+        priv = _u8(priv, (-1, 32))
+        n = priv.shape[0]
+        pub_x = _u8(pub_x, (n, 32))
+        x, st = self._outs(out, [(n, 32), (n,)])
+        self._check(self._lib.ellgpu_custom_mont_derive(self._ctx, self._cid(curve), n, priv.ctypes.data,
+                                                        pub_x.ctypes.data, x.ctypes.data, st.ctypes.data))
+        return x, st
+
+    def custom_mont_derive_dev(self, curve, priv, pub_x, out_x, out_status):
+        n = priv.shape[0]
+        self._check(self._lib.ellgpu_custom_mont_derive_dev(self._ctx, self._cid(curve), n, priv.data_ptr(),
+                                                            pub_x.data_ptr(), out_x.data_ptr(), out_status.data_ptr(),
+                                                            self._stream()))
 
     def custom_encode_points(self, curve, xy, compact=False, out=None):
         """BasePoint#encode per item at the curve's own width -> (n, 1 + PL) for compact, else

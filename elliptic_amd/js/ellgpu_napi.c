@@ -48,6 +48,8 @@
  *           customEcdh(ctx, op, curve, b0, b1, i0, i1): the key side on a user-defined short curve, the ops
  *             13..16 of callAsync below -- KeyPair#derive, #validate and BasePoint#encode
  *             (ellgpu_custom_derive / _custom_derive_wire / _custom_validate / _custom_encode_points)
+ *             and, on a user-defined Montgomery curve (defineMont(ctx, p, a); ellgpu_custom_mont_ladder /
+ *             _validate / _derive), the ops 17..19: Point#mul + getX, MontCurve#validate, KeyPair#derive
  *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
  *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
  *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
@@ -61,6 +63,8 @@
  *             13 customDerive(priv, pubXY) -> {x, status}  14 customDeriveWire(priv, enc; i0 = key length) ->
  *             {x, status, err}  15 customValidate(xy, inf or null; i0 = checkOrder) -> {status}
  *             16 customEncodePoints(xy; i0 = compact, i1 = p.byteLength()) -> {enc};
+ *             17 customMontLadder(k, x) -> {x, inf}  18 customMontValidate(x) -> {status}
+ *             19 customMontDerive(priv, x) -> {x, status};
  *             11 customSign(hash, priv, nonces; i0 = canonical) 12 customSignDet(hash, priv; i0 = canonical,
  *             i1 = drbgHash);
  *             runs on a libuv worker
@@ -98,6 +102,10 @@ static struct {
   int (*group_size)(const ellgpu_ctx*);
   int (*define_short)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, int*);
   int (*define_edwards)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, int*);
+  int (*define_mont)(ellgpu_ctx*, const uint8_t*, const uint8_t*, int*);
+  int (*custom_mont_ladder)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_mont_validate)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*);
+  int (*custom_mont_derive)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
   int (*define_short_domain)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
                              const uint8_t*, const uint8_t*, int*);
   void (*ctx_destroy)(ellgpu_ctx*);
@@ -185,6 +193,10 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(group_create, "ellgpu_group_create"); SYM(group_size, "ellgpu_group_size");
   SYM(define_short, "ellgpu_curve_define_short");
   SYM(define_edwards, "ellgpu_curve_define_edwards");
+  SYM(define_mont, "ellgpu_curve_define_mont");
+  SYM(custom_mont_ladder, "ellgpu_custom_mont_ladder");
+  SYM(custom_mont_validate, "ellgpu_custom_mont_validate");
+  SYM(custom_mont_derive, "ellgpu_custom_mont_derive");
   SYM(define_short_domain, "ellgpu_curve_define_short_domain");
   SYM(ctx_destroy, "ellgpu_ctx_destroy"); SYM(mul_fixed, "ellgpu_mul_fixed"); SYM(mul_var, "ellgpu_mul_var");
   SYM(mul_add2, "ellgpu_mul_add2"); SYM(ecdsa_verify, "ellgpu_ecdsa_verify"); SYM(x25519, "ellgpu_x25519_ladder");
@@ -398,6 +410,23 @@ static napi_value define_common(napi_env env, napi_callback_info info, int edwar
 }
 static napi_value fn_define_short(napi_env e, napi_callback_info i) { return define_common(e, i, 0); }
 static napi_value fn_define_edwards(napi_env e, napi_callback_info i) { return define_common(e, i, 1); }
+/* defineMont(ctx, p, a) -> curve id: 32-byte big-endian Buffers (ellgpu_curve_define_mont; no b) */
+static napi_value fn_define_mont(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 3; napi_value argv[3];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) THROW(env, "defineMont(ctx, p, a)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  const uint8_t* b[2]; size_t l[2];
+  for (int i = 0; i < 2; i++) {
+    if (!get_buf(env, argv[1 + i], &b[i], &l[i], 0)) return NULL;
+    if (l[i] != 32) THROW(env, "defineMont: p, a are 32-byte big-endian Buffers");
+  }
+  int id = -1;
+  if (L.define_mont(c, b[0], b[1], &id) != 0) THROW(env, L.last_error());
+  napi_value v; CHECK(env, napi_create_int32(env, id, &v));
+  return v;
+}
 /* defineShortDomain(ctx, p, a, b, n, gx, gy) -> curve id: 32-byte big-endian Buffers
  * (ellgpu_curve_define_short_domain) */
 static napi_value fn_define_short_domain(napi_env env, napi_callback_info info) {
@@ -937,7 +966,9 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
  * below 2^256 has -- and the result is cut from those: a wrong i1 gives wrong bytes, never a write
  * past the end. */
 #define ECDH_ENC_MAX 65
-static const char* const ECDH_NAMES[4][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0}};
+#define ECDH_OP_LAST 19                 /* 17 montLadder(k, x)  18 montValidate(x)  19 montDerive(priv, x): 32-byte rows */
+static const char* const ECDH_NAMES[7][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
+                                             {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0}};
 static int ecdh_shape(int op, const uint8_t* const in[2], const size_t len[2], int i0, int i1, size_t* n, size_t out[3]) {
   out[0] = out[1] = out[2] = 0;
   if (!in[0]) return 0;
@@ -951,6 +982,11 @@ static int ecdh_shape(int op, const uint8_t* const in[2], const size_t len[2], i
     *n = len[0] / 64;
     if (op == 15) { if (in[1] && len[1] != *n) return 0; out[0] = *n; }
     else { if (i1 <= 0 || i1 > 32) return 0; out[0] = *n * (1 + (i0 ? 1 : 2) * (size_t)i1); }
+  } else if (op == 17 || op == 18 || op == 19) {
+    if (len[0] % 32) return 0;
+    *n = len[0] / 32;
+    if (op == 18) { if (in[1]) return 0; out[0] = *n; }
+    else { if (!in[1] || len[1] != len[0]) return 0; out[0] = *n * 32; out[1] = *n; }
   } else return 0;
   return 1;
 }
@@ -959,6 +995,9 @@ static int ecdh_call(int op, ellgpu_ctx* c, int curve, size_t n, const uint8_t* 
     case 13: return L.custom_derive(c, curve, n, in[0], in[1], out[0], out[1]);
     case 14: return L.custom_derive_wire(c, curve, n, in[0], in[1], (size_t)i0, out[0], out[1], out[2]);
     case 15: return L.custom_validate(c, curve, n, in[0], in[1], i0, out[0]);
+    case 17: return L.custom_mont_ladder(c, curve, n, in[0], in[1], out[0], out[1]);
+    case 18: return L.custom_mont_validate(c, curve, n, in[0], out[0]);
+    case 19: return L.custom_mont_derive(c, curve, n, in[0], in[1], out[0], out[1]);
     default: return L.custom_encode_points(c, curve, n, in[0], i0, out[0]);
   }
 }
@@ -978,6 +1017,7 @@ static napi_value fn_custom_ecdh(napi_env env, napi_callback_info info) {
   if (op == 16) {                        /* the row width is the curve's: not a caller's choice to get wrong silently */
     if (i1 <= 0 || i1 > 32) THROW(env, "customEncodePoints: coordBytes must be 1..32");
   }
+  if (op < 13 || op > ECDH_OP_LAST) THROW(env, "customEcdh: bad op");
   if (!ecdh_shape(op, in, len, i0, i1, &n, ol)) THROW(env, "buffer length mismatch");
   napi_value b[3] = {NULL, NULL, NULL}; void* d[3] = {NULL, NULL, NULL};
   for (int k = 0; k < 3 && ECDH_NAMES[op - 13][k]; k++) CHECK(env, result_buffer(env, ol[k], &d[k], &b[k]));
@@ -1042,7 +1082,7 @@ static void job_execute(napi_env env, void* data) {
                                    j->out0, j->out1, j->out2, j->out3); break;
     case 12: j->rc = L.custom_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1, j->i0,
                                        j->out0, j->out1, j->out2, j->out3); break;
-    case 13: case 14: case 15: case 16: {
+    case 13: case 14: case 15: case 16: case 17: case 18: case 19: {
       const uint8_t* in[2] = {j->in[0], j->in[1]};
       uint8_t* out[3] = {j->out0, j->out1, j->out2};
       j->rc = ecdh_call(j->op, j->ctx, j->curve, j->n, in, j->i0, out); break;
@@ -1060,11 +1100,12 @@ static void job_complete(napi_env env, napi_status status, void* data) {
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
     /* result property names per op, in output order */
-    static const char* const names[17][4] = {
+    static const char* const names[ECDH_OP_LAST + 1][4] = {
       {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
       {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
       {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
-      {"x", "status", 0, 0}, {"x", "status", "err", 0}, {"status", 0, 0, 0}, {"enc", 0, 0, 0}};
+      {"x", "status", 0, 0}, {"x", "status", "err", 0}, {"status", 0, 0, 0}, {"enc", 0, 0, 0},
+      {"x", "inf", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1109,7 +1150,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
   j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
   j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > 16 || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
+  if (op < 0 || op > ECDH_OP_LAST || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
   int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
@@ -1123,7 +1164,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   int ok = 1;
   size_t ecdh_out[3] = {0, 0, 0};
   switch (op) {
-    case 13: case 14: case 15: case 16: {
+    case 13: case 14: case 15: case 16: case 17: case 18: case 19: {
       const uint8_t* in2[2] = {j->in[0], j->in[1]};
       ok = ecdh_shape(op, in2, len, i0, i1, &j->n, ecdh_out); break;
     }
@@ -1188,7 +1229,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"open", fn_open}, {"createContext", fn_create}, {"destroyContext", fn_destroy},
     {"defer", fn_defer}, {"collect", fn_collect}, {"combBits", fn_comb_bits},
     {"curveId", fn_curve_id}, {"fieldBytes", fn_field_bytes}, {"orderBytes", fn_order_bytes},
-    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"defineShortDomain", fn_define_short_domain}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
+    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"defineMont", fn_define_mont}, {"defineShortDomain", fn_define_short_domain}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
     {"mulAdd2", fn_mul_add2}, {"ecdsaVerify", fn_verify}, {"x25519", fn_x25519}, {"x25519Derive", fn_x25519_derive},
     {"callAsync", fn_call_async}, {"decompress", fn_decompress},
     {"eddsaVerify", fn_eddsa_verify}, {"eddsaSign", fn_eddsa_sign}, {"ecdsaSign", fn_sign}, {"ecdsaRecover", fn_recover}, {"ecdsaSignDet", fn_sign_det},

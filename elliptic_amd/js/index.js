@@ -109,6 +109,16 @@ Engine.prototype.defineEdwards = function defineEdwards(p, a, d) {
   }
   return this.addon.defineEdwards(this.ctx, buf(p), buf(a), buf(d));
 };
+// The same for a Montgomery curve b y^2 = x^3 + a x^2 + x that is not curve25519 (`new
+// elliptic.curve.mont({p, a, b})`, lib/elliptic/curve/mont.js:11-21).  No b: no formula of the
+// reference's x-only model reads it.  Such an id takes customMontLadderBatch / customMontValidateBatch
+// / customMontDeriveBatch (and their Async forms) only; every other call refuses it.
+Engine.prototype.defineMont = function defineMont(p, a) {
+  function buf(v) {
+    return Buffer.isBuffer(v) ? v : Buffer.from(v.toArray('be', 32));
+  }
+  return this.addon.defineMont(this.ctx, buf(p), buf(a));
+};
 
 // ---- batch API on flat Buffers (fixed-width big-endian, item-major) ----------
 // scalars: n x B bytes; points: n x 2B bytes (x||y) or null for the generator.
@@ -402,6 +412,28 @@ Engine.prototype.customValidateBatch = function customValidateBatch(curve, xy, i
   this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
   return this.addon.customEcdh(this.ctx, 15, this._id(curve), xy, inf || null, checkOrder === false ? 0 : 1, 0);
 };
+// User-defined Montgomery curves (an id from defineMont), x-only, on the device.  install() does
+// not route Point#mul / validate / KeyPair#derive of such a curve to these (ladderDomain() answers
+// null for it): they are for callers that batch.
+// customMontLadderBatch: Point#mul(k) + getX(); ks Buffer(n x 32) used as they stand (neither reduced
+// nor clamped), xs Buffer(n x 32) reduced mod p -> { x: Buffer(n x 32), inf: Buffer(n) }; inf 1 where
+// Z = 0 -- the reference's getX() returns 0 there (redInvm of 0 is 0), the engine flags it; x zeroed
+Engine.prototype.customMontLadderBatch = function customMontLadderBatch(curve, ks, xs) {
+  this.stats.gpuCalls++; this.stats.gpuItems += ks.length / 32;
+  return this.addon.customEcdh(this.ctx, 17, this._id(curve), ks, xs, 0, 0);
+};
+// customMontValidateBatch: MontCurve#validate -> { status }: 0 true, 1 false (a non-residue where
+// p = 3 mod 4), 3 'Assertion failed' (a non-residue where p = 1 mod 4: bn.js's Tonelli-Shanks loop)
+Engine.prototype.customMontValidateBatch = function customMontValidateBatch(curve, xs) {
+  this.stats.gpuCalls++; this.stats.gpuItems += xs.length / 32;
+  return this.addon.customEcdh(this.ctx, 18, this._id(curve), xs, null, 0, 0);
+};
+// customMontDeriveBatch: KeyPair#derive -> { x, status }: 0 shared secret, 1 'public point not
+// validated', 3 'Assertion failed', 2 Z = 0; validation first (x = 0 is valid: 2); x zeroed unless 0
+Engine.prototype.customMontDeriveBatch = function customMontDeriveBatch(curve, privs, xs) {
+  this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
+  return this.addon.customEcdh(this.ctx, 19, this._id(curve), privs, xs, 0, 0);
+};
 // customEncodePointBatch: BasePoint#encode at the curve's own width PL = p.byteLength() ->
 // { enc: Buffer(n x (1 + PL)) } for compact, else n x (1 + 2 PL).  PL is what defineShort /
 // defineShortDomain recorded for the id: the library writes rows of that width whatever the caller
@@ -485,6 +517,15 @@ Engine.prototype.customEncodePointBatchAsync = function(curve, xy, compact, coor
   var pl;
   try { pl = this._encodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
   return this._async(16, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
+};
+Engine.prototype.customMontLadderBatchAsync = function(curve, ks, xs) {
+  return this._async(17, curve, 0, 0, ks, xs, null, null, 0, 0);
+};
+Engine.prototype.customMontValidateBatchAsync = function(curve, xs) {
+  return this._async(18, curve, 0, 0, xs, null, null, null, 0, 0);
+};
+Engine.prototype.customMontDeriveBatchAsync = function(curve, privs, xs) {
+  return this._async(19, curve, 0, 0, privs, xs, null, null, 0, 0);
 };
 Engine.prototype.decodePointBatchAsync = function(curve, enc, encLen) {
   return this._async(8, curve, 0, 0, enc, null, null, null, encLen, 0);

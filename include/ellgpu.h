@@ -417,6 +417,58 @@ int ellgpu_custom_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const 
  * as (0, 0)). */
 int ellgpu_curve_define_edwards(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* d,
                                 int* out_curve);
+/* User-defined Montgomery curve b y^2 = x^3 + a x^2 + x over an odd prime p < 2^256 --
+ * `new elliptic.curve.mont({p, a, b})` (lib/elliptic/curve/mont.js:11-21) with parameters that are
+ * not curve25519's: M-221, a Montgomery curve over a brainpool prime, curve25519 written out by
+ * hand.  p and a are 32 bytes big-endian, a is reduced mod p.  There is NO b: the reference stores
+ * it and no formula of its x-only model reads it (a24 = (a + 2) / 4 is all Point#dbl needs), so
+ * two curves that differ in b alone are the same curve here.  Same id space
+ * (ELLGPU_CURVE_CUSTOM0 + i, at most 16 per context), the same group semantics and the same
+ * synchronous calls as ellgpu_curve_define_short; the same (p, a) twice returns the same id, and a
+ * Montgomery curve never shares an id with a short or Edwards curve over the same numbers.
+ * ELLGPU_E_ARG for p even or <= 3; p is not tested for primality.
+ * The model is x-only, so a Montgomery id has entry points of its own, and EVERY other entry point
+ * (ellgpu_mul_var, _mul_add2, _point_add, _mul_fixed, the short-curve ellgpu_custom_* calls, all
+ * preset-named ones) answers ELLGPU_E_UNSUPPORTED on it.  The calls below answer ELLGPU_E_ARG on a
+ * preset id or an unknown id and ELLGPU_E_UNSUPPORTED on a short or Edwards user-defined id.
+ * ellgpu_x25519_ladder / _derive stay the preset's.  A group runs them on its first member.
+ * ellgpu_custom_mont_ladder: Point#mul(k) + getX() (mont.js:130-178), the contract of
+ *   ellgpu_x25519_ladder.
+ *   k       n x 32 bytes big-endian, used as it stands: neither reduced nor clamped
+ *   in_x    n x 32 bytes big-endian, the point (x : 1); reduced mod p as toRed does (decodePoint,
+ *           mont.js:59-61), so a value >= p is legal input
+ *   out_x   n x 32 bytes: X / Z; zeroed where out_inf is set
+ *   out_inf 1 where the result has Z = 0.  The reference's getX() does NOT throw there on such a
+ *           curve (redInvm of 0 is 0 in bn.js's generic Mont context): it returns 0, which is
+ *           also a legal abscissa -- the engine flags the case instead.  k = 0 gives Z = 0; so does
+ *           x = 0 for every k (each diffAdd multiplies Z by the difference's x), and a low-order
+ *           point such as x = 1 on curve25519 written as a user-defined curve.
+ * ellgpu_custom_mont_validate: MontCurve#validate (mont.js:23-32) per item: is rhs = x^3 + a x^2 + x
+ *   a square?  By Euler's criterion, rhs^((p-1)/2).  out_status, numbered as
+ *   ellgpu_custom_decompress:
+ *     0  true (rhs = 0 included, so x = 0 is valid)
+ *     1  false: a non-residue where p = 3 (mod 4)
+ *     3  'Assertion failed': a non-residue where p = 1 (mod 4) -- the reference takes
+ *        rhs.redSqrt() and bn.js's Tonelli-Shanks loop throws before validate can compare
+ * ellgpu_custom_mont_derive: KeyPair#derive(pub) (lib/elliptic/ec/key.js:101-107): validate, ladder
+ *   and getX in one call.  priv is used as it stands.  out_status:
+ *     0  out_x is the shared secret
+ *     1  'public point not validated' (validate answered false)
+ *     3  'Assertion failed' (validate threw)
+ *     2  Z = 0 (the reference returns 0)
+ *   Validation is tested first: x = 0 is valid, so it is 2, not 1.  out_x is zeroed unless 0. */
+int ellgpu_curve_define_mont(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, int* out_curve);
+int ellgpu_custom_mont_ladder(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
+                              uint8_t* out_x, uint8_t* out_inf);
+int ellgpu_custom_mont_ladder_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
+                                  uint8_t* out_x, uint8_t* out_inf, void* stream);
+int ellgpu_custom_mont_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* in_x, uint8_t* out_status);
+int ellgpu_custom_mont_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* in_x,
+                                    uint8_t* out_status, void* stream);
+int ellgpu_custom_mont_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
+                              uint8_t* out_x, uint8_t* out_status);
+int ellgpu_custom_mont_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
+                                  uint8_t* out_x, uint8_t* out_status, void* stream);
 
 /* ---- host-buffer entry points (what the N-API addon binds) -------------- */
 

@@ -42,7 +42,18 @@ in front and drops the y behind ("derive_over_mul_var") -- and custom_validate_d
 test (one n * P per item).  Every item is asserted status 0, the two derives equal to mul_var's x;
 "kernels_ms" are the launches of one custom_derive_wire call.
 
-    python tools/bench_custom_ecdsa.py --ecdh [log2 n ...]                     (default: 18 20)"""
+    python tools/bench_custom_ecdsa.py --ecdh [log2 n ...]                     (default: 18 20)
+
+--mont: user-defined Montgomery curves, on curve25519 written out by hand (c25519_user of
+tests/golden/custom_mont.json), in one run: custom_mont_ladder_dev and custom_mont_derive_dev beside
+the preset's x25519_ladder_dev on the same rows (one-limb a24, special-form prime) and beside
+mul_var_dev on w25519_like, the same curve in short Weierstrass form through the run-time field
+(the short custom ladder).  Device-resident buffers, HIP-event timing; the four calls alternate
+over three rounds and each figure is the median round.  The custom ladder is asserted equal to the
+preset's item for item and every derive status 0; "kernels_ms" are the launches of one
+custom_mont_derive call.
+
+    python tools/bench_custom_ecdsa.py --mont [log2 n ...]                     (default: 18 20)"""
 import json
 import os
 import sys
@@ -297,6 +308,59 @@ def run_ecdh(ctx, spec, n):
     return out
 
 
+def run_mont(ctx, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_domain_checks as CD
+    import custom_ecdh_checks as CE
+    import custom_mont_checks as CM
+    spec = CM.spec_of("c25519_user")
+    cid = CM.define(ctx, spec)
+    wspec = CE.spec_of("w25519_like")
+    wid = CD.define(ctx, wspec)
+    rnd = lambda tag: bench.xof("custom-mont:%s" % tag, n * 32).reshape(n, 32).copy()
+    k, d = rnd("k"), rnd("d")
+    d[:, 0] &= 0x0F                                  # the peers' keys: below the subgroup order of either form
+    d[:, 31] |= 1
+    base = np.zeros((n, 32), np.uint8)
+    base[:, 31] = 9
+    x, inf = ctx.custom_mont_ladder(cid, d, base)    # abscissae of the curve: x(d G)
+    assert not inf.any()
+    q, qinf = ctx.mul_fixed(wid, d)                  # the same keys on the short form
+    assert not qinf.any()
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    z = lambda *sh: torch.full(sh, 9, dtype=torch.uint8, device=dev)
+    dk, dx, dq = t(k), t(x), t(q)
+    px, pinf, lx, linf, sx, sst, mxy, minf = z(n, 32), z(n), z(n, 32), z(n), z(n, 32), z(n), z(n, 64), z(n)
+    calls = (("x25519_ladder", lambda: ctx.x25519_dev(dk, dx, px, pinf)),
+             ("custom_mont_ladder", lambda: ctx.custom_mont_ladder_dev(cid, dk, dx, lx, linf)),
+             ("custom_mont_derive", lambda: ctx.custom_mont_derive_dev(cid, dk, dx, sx, sst)),
+             ("mul_var_w25519_like", lambda: ctx.mul_var_dev(wid, dk, dq, mxy, minf)))
+    rounds = {name: [] for name, _ in calls}
+    for _ in range(3):
+        for name, fn in calls:
+            rounds[name].append(timed(fn))
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": spec["name"], "n": n}
+    for name, _ in calls:
+        ms = sorted(rounds[name])[1]
+        out[name + "_ms"] = round(ms, 3)
+        out[name + "_ms_rounds"] = [round(v, 3) for v in rounds[name]]
+        out[name + "_M_per_s"] = round(n / ms / 1e3, 2)
+    assert torch.equal(lx, px) and torch.equal(linf, pinf) and not linf.any().item()
+    assert not sst.any().item() and torch.equal(sx, lx) and not minf.any().item()
+    out["custom_ladder_over_preset"] = round(out["custom_mont_ladder_ms"] / out["x25519_ladder_ms"], 4)
+    out["custom_derive_over_custom_ladder"] = round(out["custom_mont_derive_ms"] / out["custom_mont_ladder_ms"], 4)
+    out["short_mul_var_over_custom_ladder"] = round(out["mul_var_w25519_like_ms"] / out["custom_mont_ladder_ms"], 4)
+    ctx.set_timing(True)
+    ctx.custom_mont_derive_dev(cid, dk, dx, sx, sst)
+    torch.cuda.synchronize()
+    out["kernels_ms"] = {name: round(ms, 4) for name, (cnt, ms) in ctx.get_timing().items()}
+    ctx.set_timing(False)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
@@ -319,6 +383,15 @@ def main():
             spec = next(c for c in CD.curves() if c["name"] == "brainpoolP256r1")
             for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
                 print(json.dumps(run_sign(ctx, spec, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
+    if sys.argv[1:2] == ["--mont"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
+                print(json.dumps(run_mont(ctx, 1 << lg)), flush=True)
         finally:
             ctx.close()
         return
