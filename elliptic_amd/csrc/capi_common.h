@@ -590,6 +590,71 @@ int ellgpu_custom_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const 
   return finish(ctx, ctx->eng->custom_encode_points_dev(curve, n, xy, compact, out_enc), true);
 }
 
+// pointFromX / pointFromY, decodePoint, KeyPair#validate, KeyPair#derive and BasePoint#encode on a
+// user-defined Edwards curve (a group: member 0)
+int ellgpu_custom_ed_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
+                                int from_y, uint8_t* out_xy, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_decompress_host(curve, n, v, odd, from_y, out_xy, out_status));
+}
+int ellgpu_custom_ed_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
+                                    int from_y, uint8_t* out_xy, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_decompress_dev(curve, n, v, odd, from_y, out_xy, out_status), true);
+}
+int ellgpu_custom_ed_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                   uint8_t* out_xy, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_decode_points_host(curve, n, enc, enc_len, out_xy, out_status));
+}
+int ellgpu_custom_ed_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                       uint8_t* out_xy, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_decode_points_dev(curve, n, enc, enc_len, out_xy, out_status), true);
+}
+int ellgpu_custom_ed_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* order_host,
+                              uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_validate_host(curve, n, xy, order_host, out_status));
+}
+int ellgpu_custom_ed_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* order_host,
+                                  uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_validate_dev(curve, n, xy, order_host, out_status), true);
+}
+int ellgpu_custom_ed_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                            uint8_t* out_x, uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_derive_host(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr));
+}
+int ellgpu_custom_ed_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                                uint8_t* out_x, uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_derive_dev(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr), true);
+}
+int ellgpu_custom_ed_derive_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                                 size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_derive_host(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err));
+}
+int ellgpu_custom_ed_derive_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                                     size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err,
+                                     void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_derive_dev(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err),
+                true);
+}
+int ellgpu_custom_ed_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                   uint8_t* out_enc) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_encode_points_host(curve, n, xy, compact, out_enc));
+}
+int ellgpu_custom_ed_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                       uint8_t* out_enc, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_encode_points_dev(curve, n, xy, compact, out_enc), true);
+}
+
 // Point#mul + getX, MontCurve#validate and KeyPair#derive on a user-defined Montgomery curve (a group: member 0)
 int ellgpu_custom_mont_ladder(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
                               uint8_t* out_x, uint8_t* out_inf) {

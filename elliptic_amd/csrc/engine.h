@@ -22,6 +22,7 @@
 
 #include "edwards.h"
 #include "edcustom.h"
+#include "edckey.h"
 #include "montcustom.h"
 #include "mont.h"
 #include "rt_define.h"
@@ -1106,6 +1107,66 @@ struct FnEdcNormalize {
   }
 };
 
+// the key side of user-defined Edwards curves (edckey.h): the passes in front of and behind the
+// ladder (FnEdcMulVar, as Point#mul runs it)
+struct FnEdcKeyFrontCoord {
+  static constexpr const char* NAME = "edc_key_front_coord";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* v; const u8* odd; int from_y; u8* pts; u8* st; u8* need; u32* nd;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcKey::front_coord(i, n, v, odd, from_y, pts, st, need, nd);
+  }
+};
+struct FnEdcKeyFrontEnc {
+  static constexpr const char* NAME = "edc_key_front_enc";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* enc; size_t len; int pl; u8* pts; u8* st; u8* need; u32* nd;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcKey::front_enc(i, n, enc, len, pl, pts, st, need, nd);
+  }
+};
+struct FnEdcKeyFrontXy {
+  static constexpr const char* NAME = "edc_key_front_xy";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* xy; u8* pts; u8* valid; u8* inf; u8* scal; EdcKey::Scalar order;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcKey::front_xy(i, xy, pts, valid, inf, scal, order);
+  }
+};
+struct FnEdcKeyQuotient {
+  static constexpr const char* NAME = "edc_key_quotient";
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; u32* nd; u32* pre;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) EdcKey::quotient(t, T, n, K, nd, pre);
+  }
+};
+struct FnEdcKeyRoot {
+  static constexpr const char* NAME = "edc_key_root";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u32* nd; const u8* pts; const u8* st; const u8* need; u8* out_xy; u8* out_st; u8* valid;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcKey::root(i, n, nd, pts, st, need, out_xy, out_st, valid);
+  }
+};
+struct FnEdcKeyDeriveFinish {
+  static constexpr const char* NAME = "edc_key_derive_finish";
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u32* proj; const u8* dec_st; const u8* valid; u32* pre; u8* out_x; u8* status;
+  u8* err;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) EdcKey::derive_finish(t, T, n, K, proj, dec_st, valid, pre, out_x, status, err);
+  }
+};
+struct FnEdcKeyValidateFold {
+  static constexpr const char* NAME = "edc_key_validate_fold";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* inf; const u8* valid; const u32* proj; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcKey::validate_fold(i, n, inf, valid, proj, status);
+  }
+};
+
 // user-defined Montgomery curves (montcustom.h)
 struct FnMontcLadder {
   static constexpr const char* NAME = "montc_ladder";
@@ -1379,6 +1440,19 @@ class Engine {
   template <int U = 0>
   int edc_chunk(int op, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                 const u8* a, const u8* b, u8* out_xy, u8* out_inf);
+  // the key side of user-defined Edwards curves (edckey.h).  edk_point_chunk: pointFromX / pointFromY
+  // (len == 0: a = the coordinates, b = the parities) or decodePoint (a = encodings of len bytes)
+  // through front, quotient and root; with `valid` the point goes to the ladder's operand buffer.
+  // edk_derive_chunk: KeyPair#derive of raw (len == 0) or SEC1 keys; edk_validate_chunk:
+  // KeyPair#validate, order == null without the order test.
+  template <int U = 0>
+  int edk_point_chunk(size_t n, const u8* a, const u8* b, int from_y, size_t len, u8* out_xy, u8* out_st, u8* valid);
+  template <int U = 0>
+  int edk_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len, u8* out_x, u8* status, u8* err);
+  template <int U = 0>
+  int edk_validate_chunk(size_t n, const u8* xy, const u8* order, u8* status);
+  template <int U = 0>
+  int edk_encode_chunk(size_t n, const u8* xy, int compact, u8* out_enc);
   // user-defined Montgomery curves: op 0 = Point#mul + getX (flag: Z == 0), 1 = MontCurve#validate
   // (k, out_x unused), 2 = KeyPair#derive (validate, ladder, getX; flag: the derive status)
   template <int U = 0>
@@ -1484,6 +1558,11 @@ class Engine {
     RtPmodN pmn;
     rt_p_mod_n(f, pmn.w);
     custom_pmn_.push_back(pmn);
+    // an Edwards block carries neither Red#sqrt's constants nor p.byteLength() (its bytes are
+    // pinned): the key-side calls (custom_ed_*) upload this copy, which has them, in its place
+    RtField aug = f;
+    if (f.kind == 1) rt_sqrt_init(aug);
+    custom_aug_.push_back(aug);
     *out_curve = CURVE_CUSTOM0 + (int)custom_.size() - 1;
     return E_OK;
   }
@@ -1602,8 +1681,9 @@ class Engine {
     bool owner = false;
     int rc = E_OK;
     // mont: the call is one of the Montgomery entry points (custom_mont_*); every other call
-    // refuses a Montgomery id here, before anything is uploaded
-    CustomScope(Engine* eng, int curve, bool mont = false) : e(eng) {
+    // refuses a Montgomery id here, before anything is uploaded.  ed_key: the call is one of the
+    // Edwards key-side entry points (custom_ed_*), which run on the curve's augmented block.
+    CustomScope(Engine* eng, int curve, bool mont = false, bool ed_key = false) : e(eng) {
       if (!is_custom(curve) || e->custom_active_) return;
       size_t slot = (size_t)(curve - CURVE_CUSTOM0);
       if (slot >= e->custom_.size()) { rc = e->fail(E_ARG, "unknown curve id"); return; }
@@ -1615,7 +1695,7 @@ class Engine {
       owner = true;
       e->custom_active_ = true;
       e->custom_curve_ = curve;
-      e->bk.rt_upload(e->custom_[slot]);
+      e->bk.rt_upload(ed_key ? e->custom_aug_[slot] : e->custom_[slot]);
     }
     ~CustomScope() {
       if (!owner) return;
@@ -2799,6 +2879,141 @@ class Engine {
     });
   }
 
+  // ---- the key side of user-defined Edwards curves (ellgpu_custom_ed_*) --------------------------
+  // pointFromX / pointFromY, decodePoint, KeyPair#validate, KeyPair#derive and BasePoint#encode on a
+  // define_edwards id (edckey.h).  A preset or unknown id is an argument error, a short or
+  // Montgomery user-defined id is unsupported.  Every call runs under CustomScope's ed_key form: on
+  // the curve's augmented block, which the other calls never see.
+  // p.byteLength() of the Edwards curve of the call in progress: from the augmented copy (the registered block's is zero)
+  int custom_ed_pbytes() const { return (int)custom_aug_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].pbytes; }
+  int check_custom_ed(int curve) {
+    if (!is_custom(curve))
+      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (ed25519 has ellgpu_decompress, ellgpu_decode_points, ellgpu_validate and ellgpu_ecdh_derive)")
+                               : fail(E_ARG, "unknown curve id");
+    const RtField* f = custom_block(curve);
+    if (!f) return fail(E_ARG, "unknown curve id");
+    if (f->kind != 1) return fail(E_UNSUPPORTED, "not a user-defined Edwards curve (ellgpu_curve_define_edwards)");
+    return E_OK;
+  }
+  int custom_ed_decompress_dev(int curve, size_t n, const u8* v, const u8* odd, int from_y, u8* out_xy, u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!v || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edk_point_chunk(m, v + o * 32, odd + o, from_y ? 1 : 0, 0, out_xy + o * 64, out_status + o, nullptr);
+    });
+  }
+  int custom_ed_decompress_host(int curve, size_t n, const u8* v, const u8* odd, int from_y, u8* out_xy, u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!v || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{v, 32}, In{odd, 1}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_ed_decompress_dev(curve, m, d[0], d[1], from_y, r[0], r[1]);
+    });
+  }
+  // enc_len other than 1 + PL and 1 + 2 PL is no error of the call: every item is then 'Unknown point format'
+  int custom_ed_decode_points_dev(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edk_point_chunk(m, enc + o * enc_len, nullptr, 0, enc_len, out_xy + o * 64, out_status + o, nullptr);
+    });
+  }
+  int custom_ed_decode_points_host(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{enc, enc_len}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_ed_decode_points_dev(curve, m, d[0], enc_len, r[0], r[1]);
+    });
+  }
+  // order: 32 bytes in HOST memory in both forms (a parameter of the call, not a batch operand), or null
+  int custom_ed_validate_dev(int curve, size_t n, const u8* xy, const u8* order_host, u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edk_validate_chunk(m, xy + o * 64, order_host, out_status + o);
+    });
+  }
+  int custom_ed_validate_host(int curve, size_t n, const u8* xy, const u8* order, u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{xy, 64}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return custom_ed_validate_dev(curve, m, d[0], order, r[0]);
+    });
+  }
+  // wire: pub is n SEC1 encodings of pub_len bytes (ellgpu_custom_ed_derive_wire), else n x 64 raw coordinates
+  int check_custom_ed_derive(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                             u8* out_status) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!priv || !pub || !out_x || !out_status)) return fail(E_ARG, "null pointer");
+    if (wire && pub_len == 0) return fail(E_ARG, "pub_len must be positive");
+    return E_OK;
+  }
+  int custom_ed_derive_dev(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                           u8* out_status, u8* out_err) {
+    int rc = check_custom_ed_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    const size_t PS = wire ? pub_len : 64;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edk_derive_chunk(m, priv + o * 32, pub + o * PS, wire ? pub_len : 0, out_x + o * 32, out_status + o,
+                              out_err ? out_err + o : nullptr);
+    });
+  }
+  int custom_ed_derive_host(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                            u8* out_status, u8* out_err) {
+    int rc = check_custom_ed_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{priv, 32}, In{pub, wire ? pub_len : 64}}, {Out{out_x, 32}, Out{out_status, 1}, Out{out_err, 1}},
+                  [&](size_t m, auto d, auto o) {
+      return custom_ed_derive_dev(curve, m, d[0], d[1], wire, pub_len, o[0], o[1], o[2]);
+    });
+  }
+  // rows of 1 + PL (compact) or 1 + 2 PL bytes: the short curve's row writer (Work::rt_encode_point)
+  int custom_ed_encode_points_dev(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_ed_pbytes();
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edk_encode_chunk(m, xy + o * 64, compact, out_enc + o * EL);
+    });
+  }
+  int custom_ed_encode_points_host(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+    int rc = check_custom_ed(curve);
+    if (rc) return rc;
+    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve, false, true);
+    if (sc.rc) return sc.rc;
+    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_ed_pbytes();
+    return staged(n, {In{xy, 64}}, {Out{out_enc, EL}}, [&](size_t m, auto d, auto o) {
+      return custom_ed_encode_points_dev(curve, m, d[0], compact, o[0]);
+    });
+  }
   int x25519_host(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
     if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
     return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_inf, 1}, Out{out_bad, 1}},
@@ -2842,6 +3057,7 @@ class Engine {
   Buf staging_[2 * STAGED_MAX];   // the host-buffer calls' device copies: inputs, then outputs (stage())
   std::vector<RtField> custom_;  // user-defined curves of this context (id = CURVE_CUSTOM0 + index)
   std::vector<RtPmodN> custom_pmn_;  // p mod n of each (zero for a curve without a domain): rt_recover_prep's argument
+  std::vector<RtField> custom_aug_;  // an Edwards curve's block with Red#sqrt's constants and pbytes (else a plain copy)
   bool custom_active_ = false;
   int custom_curve_ = 0;         // the user-defined curve of the call in progress (CustomScope)
   size_t pipe_step_ = pipe_step_default();   // chunks after the first, in quanta
@@ -3252,6 +3468,99 @@ int Engine<BK>::montc_chunk(int op, size_t n, const u8* k, const u8* x, u8* out_
   const size_t T = (n + K - 1) / K;
   FnMontcNormalize g{T, n, K, xz, pre, vst, out_x, out_flag};
   bk.launch(g, T);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edk_point_chunk(size_t n, const u8* a, const u8* b, int from_y, size_t len, u8* out_xy, u8* out_st,
+                                u8* valid) {
+  // the point under construction, the decoder's status and what the root pass owes each item live
+  // across the three passes; out_xy == null: the finished point stays in S_U12 for the ladder
+  u8* pts = (u8*)scratch(S_U12, n * 64);
+  u8* flags = (u8*)scratch(S_VALID, 3 * n);
+  u32* nd = (u32*)scratch(S_PRE, n * 24 * 4);                    // numerator, denominator, prefix products
+  if (!pts || !flags || !nd) return fail(E_NOMEM, "scratch allocation failed");
+  u8* st = flags;
+  u8* need = flags + n;
+  u32* pre = nd + n * 16;
+  if (len) {
+    FnEdcKeyFrontEnc f{n, a, len, custom_ed_pbytes(), pts, st, need, nd};
+    bk.launch(f, n);
+  } else {
+    FnEdcKeyFrontCoord f{n, a, b, from_y, pts, st, need, nd};
+    bk.launch(f, n);
+  }
+  const int K = norm_batch_for(n);
+  const size_t T = (n + K - 1) / K;
+  FnEdcKeyQuotient q{T, n, K, nd, pre};
+  bk.launch(q, T);
+  FnEdcKeyRoot r{n, nd, pts, st, need, out_xy ? out_xy : pts, out_st, valid};
+  bk.launch(r, n);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edk_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len, u8* out_x, u8* status, u8* err) {
+  u8* pts = (u8*)scratch(S_U12, n * 64);
+  u8* flags = (u8*)scratch(S_VALID, 3 * n);
+  u32* pre = (u32*)scratch(S_PRE, n * 24 * 4);
+  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
+  EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, n * 8 * sizeof(EdcWork::P));
+  if (!pts || !flags || !pre || !proj || !tbl) return fail(E_NOMEM, "scratch allocation failed");
+  u8* dec_st = flags;
+  u8* valid = flags + 2 * n;
+  if (len) {
+    int rc = edk_point_chunk(n, pub, nullptr, 0, len, nullptr, dec_st, valid);   // the same buffers, already sized
+    if (rc) return rc;
+  } else {
+    FnEdcKeyFrontXy f0{n, pub, pts, valid, nullptr, nullptr, EdcKey::Scalar{}};
+    bk.launch(f0, n);
+  }
+  FnEdcMulVar lad{n, k, pts, tbl, proj};
+  bk.launch(lad, n);
+  const int K = norm_batch_for(n);
+  const size_t T = (n + K - 1) / K;
+  FnEdcKeyDeriveFinish f1{T, n, K, proj, len ? dec_st : nullptr, valid, pre, out_x, status, err};
+  bk.launch(f1, T);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edk_encode_chunk(size_t n, const u8* xy, int compact, u8* out_enc) {
+  FnRtEncodePoint f{n, xy, compact, custom_ed_pbytes(), out_enc};        // the short curve's row writer
+  bk.launch(f, n);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edk_validate_chunk(size_t n, const u8* xy, const u8* order, u8* status) {
+  u8* flags = (u8*)scratch(S_VALID, 3 * n);
+  if (!flags) return fail(E_NOMEM, "scratch allocation failed");
+  u8* pts = nullptr;
+  u8* scal = nullptr;
+  u32* proj = nullptr;
+  EdcWork::P* tbl = nullptr;
+  EdcKey::Scalar ord{};
+  if (order) {
+    pts = (u8*)scratch(S_U12, n * 96);                           // the points, then `order` once per item
+    proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
+    tbl = (EdcWork::P*)scratch(S_TBL, n * 8 * sizeof(EdcWork::P));
+    if (!pts || !proj || !tbl) return fail(E_NOMEM, "scratch allocation failed");
+    scal = pts + n * 64;
+    memcpy(ord.b, order, 32);
+  }
+  FnEdcKeyFrontXy f0{n, xy, pts, flags + 2 * n, flags, scal, ord};
+  bk.launch(f0, n);
+  if (order) {
+    FnEdcMulVar lad{n, scal, pts, tbl, proj};                     // the ladder of Point#mul, one scalar for all
+    bk.launch(lad, n);
+  }
+  FnEdcKeyValidateFold f2{n, flags, flags + 2 * n, proj, status};
+  bk.launch(f2, n);
   return E_OK;
 }
 

@@ -69,7 +69,7 @@ namespace ell {
       const FnMulJoin<CvSecp256k1>&, size_t);
 // user-defined short curves (CvCustom): scalar multiplication, point addition and the wire
 // formats (pointFromX, decodePoint, the DER parser, the wire verify's status), ECDH, key validation
-// and SEC1 encoding; user-defined Edwards (edc_chunk) and Montgomery (montc_chunk) curves
+// and SEC1 encoding; user-defined Edwards (edc_chunk; the key side: edk_*_chunk) and Montgomery (montc_chunk) curves
 #define ELL_DECL_CUSTOM(KW)                                                                          \
   KW template int Engine<HipBackend>::mul_var_chunk<CvCustom>(size_t, const u8*, const u8*, u8*, u8*, \
                                                               Work<CvCustom>::A*);                   \
@@ -82,6 +82,12 @@ namespace ell {
   KW template int Engine<HipBackend>::edc_chunk<0>(int, size_t, const u8*, const u8*, const u8*,     \
                                                    const u8*, const u8*, const u8*, u8*, u8*);       \
   KW template int Engine<HipBackend>::montc_chunk<0>(int, size_t, const u8*, const u8*, u8*, u8*);   \
+  KW template int Engine<HipBackend>::edk_point_chunk<0>(size_t, const u8*, const u8*, int, size_t,  \
+                                                         u8*, u8*, u8*);                             \
+  KW template int Engine<HipBackend>::edk_derive_chunk<0>(size_t, const u8*, const u8*, size_t, u8*, \
+                                                          u8*, u8*);                                 \
+  KW template int Engine<HipBackend>::edk_validate_chunk<0>(size_t, const u8*, const u8*, u8*);      \
+  KW template int Engine<HipBackend>::edk_encode_chunk<0>(size_t, const u8*, int, u8*);              \
   KW template int Engine<HipBackend>::rt_wire_chunk<0>(int, size_t, const u8*, const u8*, size_t,    \
                                                        const u32*, u8*, u8*, u8*);                   \
   KW template int Engine<HipBackend>::rt_ecdh_ladder<0>(size_t, const u8*, const u8*, size_t, bool,  \

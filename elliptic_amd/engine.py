@@ -82,6 +82,7 @@ class Context:
         self._own = None                  # torch view of the context's own stream (see _stream)
         self._pending_default = None
         self._pbytes = {}                 # p.byteLength() of the user-defined short curves (custom_encode_points)
+        self._ed_pbytes = {}              # ... and of the user-defined Edwards curves (custom_ed_encode_points)
 
     def group_size(self):
         return self._lib.ellgpu_group_size(self._ctx)
@@ -140,6 +141,7 @@ class Context:
         cid = ctypes.c_int(-1)
         enc = [int(v % p if i else v).to_bytes(32, "big") for i, v in enumerate((int(p), int(a), int(d)))]
         self._check(self._lib.ellgpu_curve_define_edwards(self._ctx, enc[0], enc[1], enc[2], ctypes.byref(cid)))
+        self._ed_pbytes[cid.value] = (int(p).bit_length() + 7) // 8
         return cid.value
 
     def define_mont(self, p, a):
@@ -661,6 +663,134 @@ class Context:
         self._check(self._lib.ellgpu_custom_mont_derive_dev(self._ctx, self._cid(curve), n, priv.data_ptr(),
                                                             pub_x.data_ptr(), out_x.data_ptr(), out_status.data_ptr(),
                                                             self._stream()))
+
+    # ---- the key side of user-defined Edwards curves (define_edwards) ------------------------------
+
+    def custom_ed_decompress(self, curve, v, odd, from_y=False, out=None):
+        """EdwardsCurve#pointFromX (from_y=False) or #pointFromY per item on a define_edwards id ->
+        (xy, status): 0 a point, 2 'invalid point', 3 'Assertion failed' (a non-residue where
+        p = 1 mod 4).  odd (n,) is the reference's boolean.  A zero denominator gives a zero square
+        (redInvm(0) = 0): pointFromX then returns (x, 0) with status 0; pointFromY with x^2 = 0
+        returns (0, y) for an even request and 'invalid point' for an odd one"""
+        v = _u8(v, (-1, 32))
+        n = v.shape[0]
+        odd = _u8(odd, (n,))
+        xy, st = self._outs(out, [(n, 64), (n,)])
+        self._check(self._lib.ellgpu_custom_ed_decompress(self._ctx, self._cid(curve), n, v.ctypes.data, odd.ctypes.data,
+                                                          1 if from_y else 0, xy.ctypes.data, st.ctypes.data))
+        return xy, st
+
+    def custom_ed_decompress_dev(self, curve, v, odd, from_y, out_xy, out_status):
+        n = v.shape[0]
+        self._check(self._lib.ellgpu_custom_ed_decompress_dev(self._ctx, self._cid(curve), n, v.data_ptr(), odd.data_ptr(),
+                                                              1 if from_y else 0, out_xy.data_ptr(),
+                                                              out_status.data_ptr(), self._stream()))
+
+    def custom_ed_decode_points(self, curve, enc, out=None):
+        """BaseCurve#decodePoint per row of `enc` (n, enc_len) on a define_edwards id -> (xy, status)
+        as custom_decode_points; 04 / 06 / 07 points are not tested against the curve"""
+        enc = _u8(enc)
+        if enc.ndim != 2:
+            raise ValueError("enc must be (n, enc_len)")
+        n, enc_len = enc.shape
+        xy, st = self._outs(out, [(n, 64), (n,)])
+        self._check(self._lib.ellgpu_custom_ed_decode_points(self._ctx, self._cid(curve), n, enc.ctypes.data, enc_len,
+                                                             xy.ctypes.data, st.ctypes.data))
+        return xy, st
+
+    def custom_ed_decode_points_dev(self, curve, enc, out_xy, out_status):
+        n, enc_len = enc.shape
+        self._check(self._lib.ellgpu_custom_ed_decode_points_dev(self._ctx, self._cid(curve), n, enc.data_ptr(), enc_len,
+                                                                 out_xy.data_ptr(), out_status.data_ptr(),
+                                                                 self._stream()))
+
+    @staticmethod
+    def _order_bytes(order):
+        return None if order is None else int(order).to_bytes(32, "big")
+
+    def custom_ed_validate(self, curve, xy, order=None, out=None):
+        """KeyPair#validate per item -> status: 0 ok, 1 'Invalid public key' (the point is (0, 1)),
+        2 'Public key is not a point', 3 'Public key * N != O'.  order: the integer N (an Edwards
+        definition carries none), or None to skip the order test"""
+        xy = _u8(xy, (-1, 64))
+        n = xy.shape[0]
+        st, = self._outs(out, [(n,)])
+        self._check(self._lib.ellgpu_custom_ed_validate(self._ctx, self._cid(curve), n, xy.ctypes.data,
+                                                        self._order_bytes(order), st.ctypes.data))
+        return st
+
+    def custom_ed_validate_dev(self, curve, xy, order, out_status):
+        """order is an integer or None here too: it travels as a parameter, not as a device buffer"""
+        n = xy.shape[0]
+        self._check(self._lib.ellgpu_custom_ed_validate_dev(self._ctx, self._cid(curve), n, xy.data_ptr(),
+                                                            self._order_bytes(order), out_status.data_ptr(),
+                                                            self._stream()))
+
+    def custom_ed_derive(self, curve, priv, pub_xy, out=None):
+        """KeyPair#derive per item on a define_edwards id -> (x, status): 0 x is
+        pub.mul(priv).getX(), 1 'public point not validated', 2 the product has Z = 0 (incomplete
+        addition laws only).  priv (n, 32) is used as it stands; priv = 0 or the peer (0, 1) gives
+        status 0 with x = 0"""
+        priv = _u8(priv, (-1, 32))
+        n = priv.shape[0]
+        pub_xy = _u8(pub_xy, (n, 64))
+        x, st = self._outs(out, [(n, 32), (n,)])
+        self._check(self._lib.ellgpu_custom_ed_derive(self._ctx, self._cid(curve), n, priv.ctypes.data,
+                                                      pub_xy.ctypes.data, x.ctypes.data, st.ctypes.data))
+        return x, st
+
+    def custom_ed_derive_dev(self, curve, priv, pub_xy, out_x, out_status):
+        n = priv.shape[0]
+        self._check(self._lib.ellgpu_custom_ed_derive_dev(self._ctx, self._cid(curve), n, priv.data_ptr(),
+                                                          pub_xy.data_ptr(), out_x.data_ptr(), out_status.data_ptr(),
+                                                          self._stream()))
+
+    def custom_ed_derive_wire(self, curve, priv, pubs, out=None, want_err=True):
+        """custom_ed_derive with the peer keys as SEC1 encodings, rows of `pubs` (n, pub_len) ->
+        (x, status, err): status 3 = the key did not decode; err the statuses of
+        custom_ed_decode_points.  want_err=False passes no err array -> (x, status, None)"""
+        priv = _u8(priv, (-1, 32))
+        n = priv.shape[0]
+        pubs = _u8(pubs)
+        if pubs.ndim != 2 or pubs.shape[0] != n:
+            raise ValueError("pubs must be (n, pub_len)")
+        if want_err:
+            x, st, err = self._outs(out, [(n, 32), (n,), (n,)])
+        else:
+            (x, st), err = self._outs(out, [(n, 32), (n,)]), None
+        self._check(self._lib.ellgpu_custom_ed_derive_wire(self._ctx, self._cid(curve), n, priv.ctypes.data,
+                                                           pubs.ctypes.data, pubs.shape[1], x.ctypes.data,
+                                                           st.ctypes.data, err.ctypes.data if want_err else None))
+        return x, st, err
+
+    def custom_ed_derive_wire_dev(self, curve, priv, pubs, out_x, out_status, out_err=None):
+        n, pub_len = pubs.shape
+        self._check(self._lib.ellgpu_custom_ed_derive_wire_dev(
+            self._ctx, self._cid(curve), n, priv.data_ptr(), pubs.data_ptr(), pub_len, out_x.data_ptr(),
+            out_status.data_ptr(), out_err.data_ptr() if out_err is not None else None, self._stream()))
+
+    def custom_ed_encode_points(self, curve, xy, compact=False, out=None):
+        """BasePoint#encode per item at the curve's own width -> (n, 1 + PL) for compact, else
+        (n, 1 + 2 PL), PL = p.byteLength() as recorded by define_edwards"""
+        xy = _u8(xy, (-1, 64))
+        n = xy.shape[0]
+        pl = self._ed_pbytes.get(self._cid(curve))
+        if pl is None:
+            # not an Edwards curve defined on this context: the library's own refusal, asked for with
+            # no items so that no width has to be guessed
+            self._check(self._lib.ellgpu_custom_ed_encode_points(self._ctx, self._cid(curve), 0, None, 0, None))
+            raise ValueError("custom_ed_encode_points: curve %r was not defined on this context" % (curve,))
+        enc, = self._outs(out, [(n, 1 + pl if compact else 1 + 2 * pl)])
+        self._check(self._lib.ellgpu_custom_ed_encode_points(self._ctx, self._cid(curve), n, xy.ctypes.data,
+                                                             1 if compact else 0, enc.ctypes.data))
+        return enc
+
+    def custom_ed_encode_points_dev(self, curve, xy, compact, out_enc):
+        """out_enc must hold n rows of 1 + PL (compact) or 1 + 2 PL bytes"""
+        n = xy.shape[0]
+        self._check(self._lib.ellgpu_custom_ed_encode_points_dev(self._ctx, self._cid(curve), n, xy.data_ptr(),
+                                                                 1 if compact else 0, out_enc.data_ptr(),
+                                                                 self._stream()))
 
     def custom_encode_points(self, curve, xy, compact=False, out=None):
         """BasePoint#encode per item at the curve's own width -> (n, 1 + PL) for compact, else

@@ -65,6 +65,11 @@
  *             16 customEncodePoints(xy; i0 = compact, i1 = p.byteLength()) -> {enc};
  *             17 customMontLadder(k, x) -> {x, inf}  18 customMontValidate(x) -> {status}
  *             19 customMontDerive(priv, x) -> {x, status};
+ *             20 customEdDecompress(v, odd; i0 = fromY) -> {xy, status}  21 customEdDecodePoints(enc; i0 = row
+ *             length) -> {xy, status}  22 customEdValidate(xy, order or null) -> {status}  23 customEdDerive(priv,
+ *             pubXY) -> {x, status}  24 customEdDeriveWire(priv, enc; i0 = key length) -> {x, status, err}
+ *             25 customEdEncodePoints(xy; i0 = compact, i1 = p.byteLength()) -> {enc}
+ *             (ellgpu_custom_ed_*: the key side of a user-defined Edwards curve);
  *             11 customSign(hash, priv, nonces; i0 = canonical) 12 customSignDet(hash, priv; i0 = canonical,
  *             i1 = drbgHash);
  *             runs on a libuv worker
@@ -106,6 +111,13 @@ static struct {
   int (*custom_mont_ladder)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
   int (*custom_mont_validate)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*);
   int (*custom_mont_derive)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_ed_decompress)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, int, uint8_t*, uint8_t*);
+  int (*custom_ed_decode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, size_t, uint8_t*, uint8_t*);
+  int (*custom_ed_validate)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*);
+  int (*custom_ed_derive)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_ed_derive_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, size_t, uint8_t*, uint8_t*,
+                               uint8_t*);
+  int (*custom_ed_encode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, int, uint8_t*);
   int (*define_short_domain)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
                              const uint8_t*, const uint8_t*, int*);
   void (*ctx_destroy)(ellgpu_ctx*);
@@ -197,6 +209,12 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(custom_mont_ladder, "ellgpu_custom_mont_ladder");
   SYM(custom_mont_validate, "ellgpu_custom_mont_validate");
   SYM(custom_mont_derive, "ellgpu_custom_mont_derive");
+  SYM(custom_ed_decompress, "ellgpu_custom_ed_decompress");
+  SYM(custom_ed_decode_points, "ellgpu_custom_ed_decode_points");
+  SYM(custom_ed_validate, "ellgpu_custom_ed_validate");
+  SYM(custom_ed_derive, "ellgpu_custom_ed_derive");
+  SYM(custom_ed_derive_wire, "ellgpu_custom_ed_derive_wire");
+  SYM(custom_ed_encode_points, "ellgpu_custom_ed_encode_points");
   SYM(define_short_domain, "ellgpu_curve_define_short_domain");
   SYM(ctx_destroy, "ellgpu_ctx_destroy"); SYM(mul_fixed, "ellgpu_mul_fixed"); SYM(mul_var, "ellgpu_mul_var");
   SYM(mul_add2, "ellgpu_mul_add2"); SYM(ecdsa_verify, "ellgpu_ecdsa_verify"); SYM(x25519, "ellgpu_x25519_ladder");
@@ -966,22 +984,40 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
  * below 2^256 has -- and the result is cut from those: a wrong i1 gives wrong bytes, never a write
  * past the end. */
 #define ECDH_ENC_MAX 65
-#define ECDH_OP_LAST 19                 /* 17 montLadder(k, x)  18 montValidate(x)  19 montDerive(priv, x): 32-byte rows */
-static const char* const ECDH_NAMES[7][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
-                                             {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0}};
+/* 17 montLadder(k, x)  18 montValidate(x)  19 montDerive(priv, x): 32-byte rows.
+ * The key side of a user-defined Edwards curve (ellgpu_custom_ed_*): 20 edDecompress(v, odd; i0 = fromY)
+ * 21 edDecodePoints(enc; i0 = row length)  22 edValidate(xy, order: 32 bytes or null)  23 edDerive(priv, pubXY)
+ * 24 edDeriveWire(priv, enc; i0 = key length)  25 edEncodePoints(xy; i0 = compact, i1 = p.byteLength(); as 16) */
+#define ECDH_OP_LAST 25
+#define ECDH_ENC_OP(op) ((op) == 16 || (op) == 25)
+static const char* const ECDH_NAMES[13][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
+                                              {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0},
+                                              {"xy", "status", 0}, {"xy", "status", 0}, {"status", 0, 0}, {"x", "status", 0},
+                                              {"x", "status", "err"}, {"enc", 0, 0}};
 static int ecdh_shape(int op, const uint8_t* const in[2], const size_t len[2], int i0, int i1, size_t* n, size_t out[3]) {
   out[0] = out[1] = out[2] = 0;
   if (!in[0]) return 0;
-  if (op == 13 || op == 14) {
-    if (!in[1] || len[0] % 32 || (op == 14 && i0 <= 0)) return 0;
+  if (op == 13 || op == 14 || op == 23 || op == 24) {
+    const int wire = op == 14 || op == 24;
+    if (!in[1] || len[0] % 32 || (wire && i0 <= 0)) return 0;
     *n = len[0] / 32;
-    if (len[1] != *n * (op == 13 ? 64 : (size_t)i0)) return 0;
-    out[0] = *n * 32; out[1] = *n; out[2] = op == 14 ? *n : 0;
-  } else if (op == 15 || op == 16) {
+    if (len[1] != *n * (wire ? (size_t)i0 : 64)) return 0;
+    out[0] = *n * 32; out[1] = *n; out[2] = wire ? *n : 0;
+  } else if (op == 15 || op == 16 || op == 22 || op == 25) {
     if (len[0] % 64) return 0;
     *n = len[0] / 64;
     if (op == 15) { if (in[1] && len[1] != *n) return 0; out[0] = *n; }
+    else if (op == 22) { if (in[1] && len[1] != 32) return 0; out[0] = *n; }
     else { if (i1 <= 0 || i1 > 32) return 0; out[0] = *n * (1 + (i0 ? 1 : 2) * (size_t)i1); }
+  } else if (op == 20) {
+    if (!in[1] || len[0] % 32) return 0;
+    *n = len[0] / 32;
+    if (len[1] != *n) return 0;
+    out[0] = *n * 64; out[1] = *n;
+  } else if (op == 21) {
+    if (in[1] || i0 <= 0 || len[0] % (size_t)i0) return 0;
+    *n = len[0] / (size_t)i0;
+    out[0] = *n * 64; out[1] = *n;
   } else if (op == 17 || op == 18 || op == 19) {
     if (len[0] % 32) return 0;
     *n = len[0] / 32;
@@ -998,6 +1034,12 @@ static int ecdh_call(int op, ellgpu_ctx* c, int curve, size_t n, const uint8_t* 
     case 17: return L.custom_mont_ladder(c, curve, n, in[0], in[1], out[0], out[1]);
     case 18: return L.custom_mont_validate(c, curve, n, in[0], out[0]);
     case 19: return L.custom_mont_derive(c, curve, n, in[0], in[1], out[0], out[1]);
+    case 20: return L.custom_ed_decompress(c, curve, n, in[0], in[1], i0, out[0], out[1]);
+    case 21: return L.custom_ed_decode_points(c, curve, n, in[0], (size_t)i0, out[0], out[1]);
+    case 22: return L.custom_ed_validate(c, curve, n, in[0], in[1], out[0]);
+    case 23: return L.custom_ed_derive(c, curve, n, in[0], in[1], out[0], out[1]);
+    case 24: return L.custom_ed_derive_wire(c, curve, n, in[0], in[1], (size_t)i0, out[0], out[1], out[2]);
+    case 25: return L.custom_ed_encode_points(c, curve, n, in[0], i0, out[0]);
     default: return L.custom_encode_points(c, curve, n, in[0], i0, out[0]);
   }
 }
@@ -1014,7 +1056,7 @@ static napi_value fn_custom_ecdh(napi_env env, napi_callback_info info) {
     THROW(env, "customEcdh(ctx, op, curve, b0, b1, i0, i1)");
   const uint8_t* in[2]; size_t len[2], n = 0, ol[3];
   if (!get_buf(env, argv[3], &in[0], &len[0], 0) || !get_buf(env, argv[4], &in[1], &len[1], 1)) return NULL;
-  if (op == 16) {                        /* the row width is the curve's: not a caller's choice to get wrong silently */
+  if (ECDH_ENC_OP(op)) {                 /* the row width is the curve's: not a caller's choice to get wrong silently */
     if (i1 <= 0 || i1 > 32) THROW(env, "customEncodePoints: coordBytes must be 1..32");
   }
   if (op < 13 || op > ECDH_OP_LAST) THROW(env, "customEcdh: bad op");
@@ -1023,7 +1065,7 @@ static napi_value fn_custom_ecdh(napi_env env, napi_callback_info info) {
   for (int k = 0; k < 3 && ECDH_NAMES[op - 13][k]; k++) CHECK(env, result_buffer(env, ol[k], &d[k], &b[k]));
   uint8_t* out[3] = {(uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2]};
   uint8_t* wide = NULL;
-  if (op == 16) {
+  if (ECDH_ENC_OP(op)) {
     wide = (uint8_t*)malloc(n * ECDH_ENC_MAX + 1);
     if (!wide) THROW(env, "customEcdh: out of memory");
     out[0] = wide;
@@ -1082,7 +1124,7 @@ static void job_execute(napi_env env, void* data) {
                                    j->out0, j->out1, j->out2, j->out3); break;
     case 12: j->rc = L.custom_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1, j->i0,
                                        j->out0, j->out1, j->out2, j->out3); break;
-    case 13: case 14: case 15: case 16: case 17: case 18: case 19: {
+    case 13: case 14: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: {
       const uint8_t* in[2] = {j->in[0], j->in[1]};
       uint8_t* out[3] = {j->out0, j->out1, j->out2};
       j->rc = ecdh_call(j->op, j->ctx, j->curve, j->n, in, j->i0, out); break;
@@ -1105,7 +1147,9 @@ static void job_complete(napi_env env, napi_status status, void* data) {
       {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
       {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
       {"x", "status", 0, 0}, {"x", "status", "err", 0}, {"status", 0, 0, 0}, {"enc", 0, 0, 0},
-      {"x", "inf", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0}};
+      {"x", "inf", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
+      {"xy", "status", 0, 0}, {"xy", "status", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
+      {"x", "status", "err", 0}, {"enc", 0, 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1164,7 +1208,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   int ok = 1;
   size_t ecdh_out[3] = {0, 0, 0};
   switch (op) {
-    case 13: case 14: case 15: case 16: case 17: case 18: case 19: {
+    case 13: case 14: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: {
       const uint8_t* in2[2] = {j->in[0], j->in[1]};
       ok = ecdh_shape(op, in2, len, i0, i1, &j->n, ecdh_out); break;
     }
@@ -1205,8 +1249,8 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   j->out2_len = op == 5 || op >= 11 ? j->n : 0;
   j->out3_len = op == 5 || op >= 11 ? j->n : 0;
   if (op >= 13) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
-  /* (op 16: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
-  j->out0 = (uint8_t*)malloc(op == 16 ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
+  /* (ops 16, 25: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
+  j->out0 = (uint8_t*)malloc(ECDH_ENC_OP(op) ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
   j->out1 = (uint8_t*)malloc(j->out1_len ? j->out1_len : 1);
   j->out2 = (uint8_t*)malloc(j->out2_len ? j->out2_len : 1);
   j->out3 = (uint8_t*)malloc(j->out3_len ? j->out3_len : 1);

@@ -46,6 +46,7 @@ function Engine(options) {
   this.ctx = this.addon.createContext(this.devices || (options.device | 0));
   this.stats = { gpuCalls: 0, gpuItems: 0, passthrough: 0, offCurve: 0 };
   this._coordBytes = {};       // p.byteLength() of the short curves defined here, by id (customEncodePointBatch)
+  this._edCoordBytes = {};   // p.byteLength() of the Edwards curves defined here (customEdEncodePointBatch)
 }
 
 // The context owns the device's memory for this engine (fixed-base tables: 1.6 GB for secp256k1 at
@@ -107,7 +108,9 @@ Engine.prototype.defineEdwards = function defineEdwards(p, a, d) {
   function buf(v) {
     return Buffer.isBuffer(v) ? v : Buffer.from(v.toArray('be', 32));
   }
-  return this.addon.defineEdwards(this.ctx, buf(p), buf(a), buf(d));
+  var id = this.addon.defineEdwards(this.ctx, buf(p), buf(a), buf(d));
+  this._edCoordBytes[id] = byteLength(buf(p));
+  return id;
 };
 // The same for a Montgomery curve b y^2 = x^3 + a x^2 + x that is not curve25519 (`new
 // elliptic.curve.mont({p, a, b})`, lib/elliptic/curve/mont.js:11-21).  No b: no formula of the
@@ -451,6 +454,60 @@ Engine.prototype.customEncodePointBatch = function customEncodePointBatch(curve,
   this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
   return this.addon.customEcdh(this.ctx, 16, this._id(curve), xy, null, compact ? 1 : 0, pl);
 };
+// The key side of a user-defined Edwards curve (an id from defineEdwards), on the device
+// (ellgpu_custom_ed_*).  install() does not route pointFromX / pointFromY / decodePoint /
+// KeyPair#validate / #derive / Point#encode of such a curve to these: they are for callers that batch.
+// customEdDecompressBatch: pointFromX (fromY falsy) or pointFromY; vs Buffer(n x 32) reduced mod p,
+// odds Buffer(n), the reference's boolean (non-zero: the odd root) -> { xy: Buffer(n x 64), status }:
+// 0 point, 2 'invalid point', 3 'Assertion failed' (a non-residue where p = 1 mod 4).  A zero
+// denominator gives a zero square (redInvm(0) = 0): pointFromX returns (x, 0) with status 0;
+// pointFromY with x^2 = 0 returns (0, y) for an even request, 'invalid point' for an odd one
+Engine.prototype.customEdDecompressBatch = function customEdDecompressBatch(curve, vs, odds, fromY) {
+  this.stats.gpuCalls++; this.stats.gpuItems += vs.length / 32;
+  return this.addon.customEcdh(this.ctx, 20, this._id(curve), vs, odds, fromY ? 1 : 0, 0);
+};
+// customEdDecodePointBatch: decodePoint per row of encLen bytes -> { xy, status } as customDecodePointBatch
+Engine.prototype.customEdDecodePointBatch = function customEdDecodePointBatch(curve, enc, encLen) {
+  this.stats.gpuCalls++; this.stats.gpuItems += encLen > 0 ? enc.length / encLen : 0;
+  return this.addon.customEcdh(this.ctx, 21, this._id(curve), enc, null, encLen, 0);
+};
+// customEdValidateBatch: KeyPair#validate -> { status }: 0 ok, 1 'Invalid public key' ((0, 1)),
+// 2 'Public key is not a point', 3 'Public key * N != O'; order a 32-byte Buffer or a BN-like, or
+// null / undefined to skip the order test (an Edwards definition carries no n)
+function orderBuf(order) {
+  if (order === undefined || order === null) return null;
+  return Buffer.isBuffer(order) ? order : Buffer.from(order.toArray('be', 32));
+}
+Engine.prototype.customEdValidateBatch = function customEdValidateBatch(curve, xy, order) {
+  this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
+  return this.addon.customEcdh(this.ctx, 22, this._id(curve), xy, orderBuf(order), 0, 0);
+};
+// customEdDeriveBatch: KeyPair#derive -> { x, status }: 0 shared secret (the identity is a legal peer and
+// result: x = 0), 1 'public point not validated', 2 Z = 0 (incomplete addition laws only); privs as they stand
+Engine.prototype.customEdDeriveBatch = function customEdDeriveBatch(curve, privs, pubXY) {
+  this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
+  return this.addon.customEcdh(this.ctx, 23, this._id(curve), privs, pubXY, 0, 0);
+};
+// customEdDeriveWireBatch: the same with SEC1 keys of keyLen bytes -> { x, status, err }: status 3 the key
+// did not decode, err the statuses of customEdDecodePointBatch
+Engine.prototype.customEdDeriveWireBatch = function customEdDeriveWireBatch(curve, privs, enc, keyLen) {
+  this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
+  return this.addon.customEcdh(this.ctx, 24, this._id(curve), privs, enc, keyLen, 0);
+};
+// customEdEncodePointBatch: Point#encode at PL = p.byteLength(), recorded by defineEdwards; the
+// contract of customEncodePointBatch
+Engine.prototype._edEncodeWidth = function _edEncodeWidth(curve, coordBytes) {
+  var pl = this._edCoordBytes[this._id(curve)];
+  if (pl === undefined) throw new Error('customEdEncodePointBatch: not an Edwards curve defined on this engine');
+  if (coordBytes !== undefined && coordBytes !== null && coordBytes !== pl)
+    throw new Error('customEdEncodePointBatch: coordBytes ' + coordBytes + ' is not the curve\'s p.byteLength() = ' + pl);
+  return pl;
+};
+Engine.prototype.customEdEncodePointBatch = function customEdEncodePointBatch(curve, xy, compact, coordBytes) {
+  var pl = this._edEncodeWidth(curve, coordBytes);
+  this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
+  return this.addon.customEcdh(this.ctx, 25, this._id(curve), xy, null, compact ? 1 : 0, pl);
+};
 // ---- asynchronous batch API: same arguments, returns a Promise; the work runs on a
 // libuv worker thread (napi_async_work), so the JS thread stays responsive during a large
 // batch.  A context processes one call at a time, so calls are chained.
@@ -517,6 +574,26 @@ Engine.prototype.customEncodePointBatchAsync = function(curve, xy, compact, coor
   var pl;
   try { pl = this._encodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
   return this._async(16, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
+};
+Engine.prototype.customEdDecompressBatchAsync = function(curve, vs, odds, fromY) {
+  return this._async(20, curve, 0, 0, vs, odds, null, null, fromY ? 1 : 0, 0);
+};
+Engine.prototype.customEdDecodePointBatchAsync = function(curve, enc, encLen) {
+  return this._async(21, curve, 0, 0, enc, null, null, null, encLen, 0);
+};
+Engine.prototype.customEdValidateBatchAsync = function(curve, xy, order) {
+  return this._async(22, curve, 0, 0, xy, orderBuf(order), null, null, 0, 0);
+};
+Engine.prototype.customEdDeriveBatchAsync = function(curve, privs, pubXY) {
+  return this._async(23, curve, 0, 0, privs, pubXY, null, null, 0, 0);
+};
+Engine.prototype.customEdDeriveWireBatchAsync = function(curve, privs, enc, keyLen) {
+  return this._async(24, curve, 0, 0, privs, enc, null, null, keyLen, 0);
+};
+Engine.prototype.customEdEncodePointBatchAsync = function(curve, xy, compact, coordBytes) {
+  var pl;
+  try { pl = this._edEncodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
+  return this._async(25, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
 };
 Engine.prototype.customMontLadderBatchAsync = function(curve, ks, xs) {
   return this._async(17, curve, 0, 0, ks, xs, null, null, 0, 0);

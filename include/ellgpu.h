@@ -469,6 +469,78 @@ int ellgpu_custom_mont_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_
                               uint8_t* out_x, uint8_t* out_status);
 int ellgpu_custom_mont_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
                                   uint8_t* out_x, uint8_t* out_status, void* stream);
+/* The key side of a user-defined Edwards curve (an id from ellgpu_curve_define_edwards):
+ * EdwardsCurve#pointFromX / #pointFromY (lib/elliptic/curve/edwards.js:50-97), BaseCurve#decodePoint
+ * (base.js:270-293), KeyPair#validate and KeyPair#derive (ec/key.js:40-51, 101-107) and
+ * BasePoint#encode (base.js:298-306), batched on the device.  Conventions of ellgpu_custom_mont_*:
+ * synchronous; a group runs them on its first member; ELLGPU_E_ARG on a preset id or an unknown id,
+ * ELLGPU_E_UNSUPPORTED on a short or Montgomery user-defined id.  The short-curve ellgpu_custom_*
+ * calls, the Montgomery ones and the preset-named ones keep refusing an Edwards id.  Scalars and
+ * coordinates are 32 bytes big-endian, coordinates reduced mod p on input as toRed does (a value
+ * >= p is legal input); a SEC1 coordinate is PL = p.byteLength() bytes.
+ * The field-only calls (decompress, decode_points, validate without order, encode_points) are exact
+ * on every curve the definition accepts; the ladder-based ones (derive, validate's order test) are
+ * exact where the addition law is complete (a a square, d not), as ellgpu_mul_var is.
+ * ellgpu_custom_ed_decompress: from_y == 0 is pointFromX(v, odd): y^2 = (1 - a x^2) / (1 - d x^2);
+ *   from_y != 0 is pointFromY(v, odd): x^2 = (y^2 - 1) / (d y^2 - a).
+ *   v          n x 32 bytes, the known coordinate
+ *   odd        n bytes, the reference's boolean: non-zero asks for the odd root
+ *   out_xy     n x 64 bytes x || y; zeroed unless the status is 0
+ *   out_status 0 a point; 2 'invalid point'; 3 'Assertion failed' (a non-residue where p = 1 mod 4:
+ *              bn.js's Tonelli-Shanks loop throws; where p = 3 mod 4 a non-residue is 2)
+ *   As in the reference: redInvm(0) is 0, so a zero denominator gives a zero square, and pointFromX
+ *   then RETURNS (x, 0) for either parity -- status 0, although that point is not on the curve.
+ *   pointFromY with x^2 = 0 (y = +-1, or a zero denominator) returns (0, y) for odd == 0 and answers
+ *   'invalid point' for odd != 0, before any root is taken.  A root of the wrong parity is negated;
+ *   the root 0 is returned for both parities.
+ * ellgpu_custom_ed_decode_points: decodePoint with pointFromX for 02 / 03; enc is n rows of enc_len
+ *   bytes.  out_status as ellgpu_custom_decode_points: 0 a point, 1 'Unknown point format' (prefix or
+ *   length; an enc_len that is neither 1 + PL nor 1 + 2 PL makes every item 1), 2 'invalid point',
+ *   3 'Assertion failed' (a hybrid 06 / 07 prefix contradicting y's last bit, or a compressed x
+ *   without a root where p = 1 mod 4).  04 / 06 / 07 points are NOT tested against the curve.
+ * ellgpu_custom_ed_validate: KeyPair#validate in its order.  out_status: 0 {result: true};
+ *   1 'Invalid public key' (the point is (0, 1) after reduction); 2 'Public key is not a point'
+ *   (a x^2 + y^2 != 1 + d x^2 y^2); 3 'Public key * N != O'.  order_host: 32 bytes big-endian in HOST
+ *   memory in both forms (a parameter of the call, read before it returns), or NULL to skip the
+ *   order test -- an Edwards definition carries no n.  It is used as it stands, through the ladder of
+ *   ellgpu_mul_var; the product is the identity when X = 0 and Y = Z.
+ * ellgpu_custom_ed_derive: KeyPair#derive(pub).  out_status: 0 out_x is pub.mul(priv).getX();
+ *   1 'public point not validated'; 2 the product has Z = 0 (only where the addition law is
+ *   incomplete; the reference's getX() returns 0 there, the engine flags it).  priv is used as it
+ *   stands.  The identity is a legal peer and a legal result: priv = 0 or the peer (0, 1) gives
+ *   status 0 with x = 0 (getX() does not throw on this model).  out_x is zeroed unless the status is 0.
+ * ellgpu_custom_ed_derive_wire: the same with the peer's key as a SEC1 encoding of pub_len bytes --
+ *   decoding, root, validation, ladder and x in one call, under the contract of
+ *   ellgpu_custom_derive_wire: status 3 for a key that did not decode, out_err (may be NULL) the
+ *   decoder's own status.
+ * ellgpu_custom_ed_encode_points: BasePoint#encode at rows of 1 + PL (compact: 02 / 03 || x) or
+ *   1 + 2 PL (04 || x || y) bytes, coordinates reduced mod p first; the contract of
+ *   ellgpu_custom_encode_points. */
+int ellgpu_custom_ed_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
+                                int from_y, uint8_t* out_xy, uint8_t* out_status);
+int ellgpu_custom_ed_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
+                                    int from_y, uint8_t* out_xy, uint8_t* out_status, void* stream);
+int ellgpu_custom_ed_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                   uint8_t* out_xy, uint8_t* out_status);
+int ellgpu_custom_ed_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
+                                       uint8_t* out_xy, uint8_t* out_status, void* stream);
+int ellgpu_custom_ed_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* order_host,
+                              uint8_t* out_status);
+int ellgpu_custom_ed_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* order_host,
+                                  uint8_t* out_status, void* stream);
+int ellgpu_custom_ed_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                            uint8_t* out_x, uint8_t* out_status);
+int ellgpu_custom_ed_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
+                                uint8_t* out_x, uint8_t* out_status, void* stream);
+int ellgpu_custom_ed_derive_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
+                                 size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err);
+int ellgpu_custom_ed_derive_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv,
+                                     const uint8_t* pub_enc, size_t pub_len, uint8_t* out_x, uint8_t* out_status,
+                                     uint8_t* out_err, void* stream);
+int ellgpu_custom_ed_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                   uint8_t* out_enc);
+int ellgpu_custom_ed_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
+                                       uint8_t* out_enc, void* stream);
 
 /* ---- host-buffer entry points (what the N-API addon binds) -------------- */
 

@@ -53,7 +53,16 @@ over three rounds and each figure is the median round.  The custom ladder is ass
 preset's item for item and every derive status 0; "kernels_ms" are the launches of one
 custom_mont_derive call.
 
-    python tools/bench_custom_ecdsa.py --mont [log2 n ...]                     (default: 18 20)"""
+    python tools/bench_custom_ecdsa.py --mont [log2 n ...]                     (default: 18 20)
+
+--edwards: the key side of user-defined Edwards curves, on Curve1174 and on twisted_a4 (2^255 - 19)
+of tests/golden/custom_ed.json, in one run: custom_ed_decompress_dev (pointFromY), custom_ed_validate_dev
+without and with the order test, custom_ed_derive_dev and custom_ed_derive_wire_dev (compressed
+keys) beside mul_var_dev on the same id and rows.  Device-resident buffers, HIP-event timing; the calls
+alternate over three rounds and each figure is the median round.  Every status is asserted 0 and
+the two derives equal to mul_var's x; "kernels_ms" are the launches of one custom_ed_derive_wire call.
+
+    python tools/bench_custom_ecdsa.py --edwards [log2 n ...]                  (default: 18 20)"""
 import json
 import os
 import sys
@@ -361,6 +370,58 @@ def run_mont(ctx, n):
     return out
 
 
+def run_edwards(ctx, name, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_ed_checks as CK
+    spec = CK.spec_of(name)
+    cid = CK.define(ctx, spec)
+    m = CK.model_of(spec)
+    rnd = lambda tag: bench.xof("custom-ed:%s:%s" % (name, tag), n * 32).reshape(n, 32).copy()
+    k, s = rnd("k"), rnd("s")
+    y0 = next(y for y in range(2, 1000) if m.from_y(y, 0)[1] == 0 and m.from_y(y, 0)[0][0])
+    g, st = ctx.custom_ed_decompress(cid, CK.rows([y0] * n), np.zeros(n, np.uint8), True)
+    assert not st.any()
+    pub, inf = ctx.mul_var(cid, s, g)                  # the peers' keys: s G
+    assert not inf.any()
+    enc = ctx.custom_ed_encode_points(cid, pub, True)
+    order = (1 << 256) - 1
+    dev = torch.device("cuda", 0)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    z = lambda *sh: torch.full(sh, 9, dtype=torch.uint8, device=dev)
+    dk, dpub, denc, dy, dodd = t(k), t(pub), t(enc), t(pub[:, 32:]), t(pub[:, 31] & 1)
+    oxy, ost, v0, v1, dx, dst, wx, wst, mxy, minf = z(n, 64), z(n), z(n), z(n), z(n, 32), z(n), z(n, 32), z(n), z(n, 64), z(n)
+    calls = (("mul_var", lambda: ctx.mul_var_dev(cid, dk, dpub, mxy, minf)),
+             ("custom_ed_decompress", lambda: ctx.custom_ed_decompress_dev(cid, dy, dodd, True, oxy, ost)),
+             ("custom_ed_validate", lambda: ctx.custom_ed_validate_dev(cid, dpub, None, v0)),
+             ("custom_ed_validate_order", lambda: ctx.custom_ed_validate_dev(cid, dpub, order, v1)),
+             ("custom_ed_derive", lambda: ctx.custom_ed_derive_dev(cid, dk, dpub, dx, dst)),
+             ("custom_ed_derive_wire", lambda: ctx.custom_ed_derive_wire_dev(cid, dk, denc, wx, wst)))
+    rounds = {nm: [] for nm, _ in calls}
+    for _ in range(3):
+        for nm, fn in calls:
+            rounds[nm].append(timed(fn))
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": name, "n": n}
+    for nm, _ in calls:
+        ms = sorted(rounds[nm])[1]
+        out[nm + "_ms"] = round(ms, 3)
+        out[nm + "_ms_rounds"] = [round(v, 3) for v in rounds[nm]]
+        out[nm + "_M_per_s"] = round(n / ms / 1e3, 2)
+    assert not ost.any().item() and torch.equal(oxy, dpub) and not v0.any().item() and not minf.any().item()
+    assert set(v1.unique().tolist()) <= {0, 3}          # an arbitrary scalar as the order: the ladder runs, the answer is its own
+    assert not dst.any().item() and not wst.any().item() and torch.equal(dx, mxy[:, :32]) and torch.equal(wx, dx)
+    out["derive_over_mul_var_plus_decompress"] = round(
+        out["custom_ed_derive_ms"] / (out["mul_var_ms"] + out["custom_ed_decompress_ms"]), 4)
+    out["derive_over_mul_var"] = round(out["custom_ed_derive_ms"] / out["mul_var_ms"], 4)
+    ctx.set_timing(True)
+    ctx.custom_ed_derive_wire_dev(cid, dk, denc, wx, wst)
+    torch.cuda.synchronize()
+    out["kernels_ms"] = {nm: round(ms, 4) for nm, (cnt, ms) in ctx.get_timing().items()}
+    ctx.set_timing(False)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
@@ -383,6 +444,16 @@ def main():
             spec = next(c for c in CD.curves() if c["name"] == "brainpoolP256r1")
             for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
                 print(json.dumps(run_sign(ctx, spec, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
+    if sys.argv[1:2] == ["--edwards"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            for lg in [int(a) for a in sys.argv[2:]] or [18, 20]:
+                for name in ("curve1174", "twisted_a4"):
+                    print(json.dumps(run_edwards(ctx, name, 1 << lg)), flush=True)
         finally:
             ctx.close()
         return
