@@ -236,6 +236,103 @@ static void run_field_op(HipBackend& bk, int op, size_t n, const u32* a, const u
   hipLaunchKernelGGL(k_field_op<F>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, bk.cur, op, n, a, b, r);
 }
 
+// ---- white-box probe: one field operation per WAVE (or per row) on the lanes-per-item fields
+// (coop.h / coop_mont.h / coop_wide.h / coop_ed.h; tests/test_gpu_coop_field.py).  One wave per
+// block and one item per block; FpK256R (PER_ROW) holds four items per block, row threadIdx.x >> 4
+// its own.  All 64 lanes run to the end -- the DPP / permlane moves read the lanes beside them --,
+// the rows of a last wave that have no item compute on zeros and store nothing.  Operands enter by
+// from_plain and results leave by to_plain (a Montgomery form cancels).
+template <class F, class = void>
+struct ell_coop_per_row { static constexpr bool value = false; };
+template <class F>
+struct ell_coop_per_row<F, std::enable_if_t<F::PER_ROW>> { static constexpr bool value = true; };
+template <class F, class = void>
+struct ell_coop_pack4 { static constexpr bool value = false; };                 // (FpMontC / FpFoldC pack two or three rows only)
+template <class F>
+struct ell_coop_pack4<F, std::void_t<decltype(&F::pack4)>> { static constexpr bool value = true; };
+template <class F>
+struct ell_coop_k256 { static constexpr bool value = false; };
+template <bool PR>
+struct ell_coop_k256<FpK256CT<PR>> { static constexpr bool value = true; };
+template <class F>
+__global__ void __launch_bounds__(64) k_coop_field_op(int op, size_t n, const u32* a, const u32* b, u32* r) {
+  typedef typename F::El El;
+  constexpr int L = F::L;
+  constexpr bool PR = ell_coop_per_row<F>::value;
+  const size_t item = PR ? (size_t)blockIdx.x * 4 + (threadIdx.x >> 4) : (size_t)blockIdx.x;
+  const bool live = item < n;
+  u32 ta[L], tb[L], tr[L];
+  for (int l = 0; l < L; l++) { ta[l] = live ? a[item * L + l] : 0u; tb[l] = live ? b[item * L + l] : 0u; }
+  const El x = F::from_plain(ta), y = F::from_plain(tb);
+  El z = x;
+  switch (op) {
+    case 0: z = F::add(x, y); break;
+    case 1: z = F::sub(x, y); break;
+    case 2: z = F::mul(x, y); break;
+    case 3: z = F::sqr(x); break;
+    case 5: z = F::neg(x); break;
+    case 6: z = F::template mul_pow2<1>(x); break;
+    case 7: z = F::template mul_pow2<2>(x); break;
+    case 8: z = F::template mul_pow2<3>(x); break;
+    default: break;
+  }
+  if constexpr (ell_coop_k256<F>::value) {
+    // the lazy forms and the row layer's own corners, as tests/hostsim hs_field_op computes them
+    if (op == 11) z = F::mul2(x, y, F::template neg_l<4>(x), F::template sub_l<4>(x, y));
+    if (op == 12) { const El q = F::sqr(x); z = F::norm(F::add_l(q, F::half_l(q))); }
+    if (op == 14) { z = F::mul(x, y); z = F::is_zero_w(z) == F::is_zero(z) ? z : F::one(); }
+    if (op == 15) z = F::mul(F::template sub_l<4>(x, y), F::add_l(x, y));
+    if (op == 16) z = F::norm(F::template cneg_l<2>(F::load_words(ta), (tb[0] & 1u) != 0));
+  } else {
+    if (op == 4) z = F::inv(x);
+  }
+  if constexpr (has_quad<F>::value) {                    // (short.h: FpFoldW has no QUAD member, FpK256R's is false)
+    // four (two, three) products in one instruction stream, one per row of the wave, each row read
+    // back through the class's own unpack: x y, y (x + y), (x + y)(x - y), (x - y) x
+    if (op >= 20 && op <= 28) {
+      const El s = F::add(x, y), d = F::sub(x, y);
+      if constexpr (ell_coop_pack4<F>::value) {
+        if (op <= 23) {
+          El q0, q1, q2, q3;
+          F::unpack4(F::mulq(F::pack4(x, y, s, d), F::pack4(y, s, d, x)), q0, q1, q2, q3);
+          z = op == 20 ? q0 : op == 21 ? q1 : op == 22 ? q2 : q3;
+        }
+      }
+      if (op == 24 || op == 26) {
+        El q0, q1;
+        F::unpack2(F::mulq(F::pack2(x, y), F::pack2(y, s)), q0, q1);
+        // 24: row 0, a wrong value if row 1 is not the lone product (26 hands row 1 out)
+        z = op == 26 ? q1 : F::eq(q1, F::mul(y, s)) ? q0 : F::add(q0, F::one());
+      }
+      if (op == 25 || op == 27 || op == 28) {
+        El q0, q1, q2;
+        F::unpack3(F::mulq(F::pack3(x, y, s), F::pack3(y, s, d)), q0, q1, q2);
+        const bool same = F::eq(q1, F::mul(y, s)) && F::eq(q2, F::mul(s, d));
+        z = op == 27 ? q1 : op == 28 ? q2 : same ? q0 : F::add(q0, F::one());
+      }
+    }
+  }
+  F::to_plain(tr, z);
+  if (live && (threadIdx.x & 15u) == 0 && (PR || threadIdx.x == 0))
+    for (int l = 0; l < L; l++) r[item * L + l] = tr[l];
+}
+template <class F>
+static void run_coop_field_op(HipBackend& bk, int op, size_t n, const u32* a, const u32* b, u32* r) {
+  const size_t blocks = ell_coop_per_row<F>::value ? (n + 3) / 4 : n;
+  hipLaunchKernelGGL(k_coop_field_op<F>, dim3((unsigned)blocks), dim3(64), 0, bk.cur, op, n, a, b, r);
+}
+// which ops a lanes-per-item field id takes (ellgpu_debug_field_op)
+static bool coop_field_takes(int field, int op) {
+  const bool k256 = field == 3 || field == 4;
+  const bool quad = field == 3 || field == 5 || (field >= 31 && field <= 33);
+  if ((op >= 0 && op <= 3) || (op >= 5 && op <= 9)) return true;
+  if (op == 4) return !k256;
+  if (op == 11 || op == 12 || (op >= 14 && op <= 16)) return k256;
+  if (op >= 20 && op <= 23) return field == 3 || field == 5;
+  if (op >= 24 && op <= 28) return quad;
+  return false;
+}
+
 }  // namespace ell
 
 #define ELL_BACKEND ell::HipBackend
@@ -408,12 +505,24 @@ extern "C" int ellgpu_ctx_get_timing(ellgpu_ctx* ctx, char* buf, size_t cap) {
 // (26 = ed25519 order); 100+s the run-time field FpMontRT over the modulus p of this context's
 // user-defined curve 16+s, 200+s FpMontRTn over the order n of that curve (an ECDSA domain),
 // 8 limbs, operands any value < 2^256, ops 0..8 only (ELLGPU_E_ARG otherwise).  op: 0 add, 1 sub,
-// 2 mul, 3 sqr, 4 inv, 5 neg, 6 / 7 / 8 multiply by 2 / 4 / 8.
+// 2 mul, 3 sqr, 4 inv, 5 neg, 6 / 7 / 8 multiply by 2 / 4 / 8, 9 identity.
+// The lanes-per-item fields (k_coop_field_op: one item per wave, operands any value of `limbs` words,
+// below 2^528 on 35): 3 FpK256C, 4 FpK256R (four items per wave, one per row), 5 Fp25519C (8 limbs
+// each); 31 / 32 / 33 the row fields of p192 / p224 / p256 (6 / 7 / 8 limbs), 34 / 35 the wave-wide
+// fields of p384 / p521 (12 / 17).  They take ops 0..3 and 5..9; 4 except on 3 and 4; on 3 and 4 also
+// 11 x y + (4p - x)(x - y + 4p) by mul2, 12 3/2 x^2, 14 x y with is_zero_w checked against is_zero,
+// 15 (x - y)(x + y) on lazy operands, 16 load_words of a, negated lazily if b is odd.  With s = x + y
+// and d = x - y: 20..23 rows 0..3 of mulq(pack4(x, y, s, d), pack4(y, s, d, x)) through unpack4 (3
+// and 5 only: the fields of 31..33 have no pack4); 24 row 0 of mulq(pack2(x, y), pack2(y, s)) through
+// unpack2 -- x y, or x y + 1 where row 1 is not y s --, 26 its row 1; 25 row 0 of mulq(pack3(x, y, s),
+// pack3(y, s, d)) through unpack3, rows 1 and 2 checked likewise, 27 / 28 its rows 1 / 2 (3, 5, 31..33;
+// 4, 34 and 35 hold no four products).  Any other op on these ids: ELLGPU_E_ARG.
 extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t n, const uint32_t* a,
                                      const uint32_t* b, uint32_t* r) {
   using namespace ell;
   ELL_ENTER(ctx, nullptr);
   int L = 0;
+  bool coop = false;
   const RtField* rt = nullptr;
   switch (field) {
     case 0: case 1: case 2: case 10: case 13: case 20: case 23: case 26: L = 8; break;
@@ -421,6 +530,11 @@ extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t 
     case 12: case 22: L = 7; break;
     case 14: case 24: L = 12; break;
     case 15: case 25: L = 17; break;
+    case 3: case 4: case 5: case 33: L = 8; coop = true; break;
+    case 31: L = 6; coop = true; break;
+    case 32: L = 7; coop = true; break;
+    case 34: L = 12; coop = true; break;
+    case 35: L = 17; coop = true; break;
     default:
       if (field >= 100 && field < 100 + CURVE_CUSTOM_MAX) rt = ctx->eng->custom_block(CURVE_CUSTOM0 + field - 100);
       else if (field >= 200 && field < 200 + CURVE_CUSTOM_MAX) rt = ctx->eng->custom_block(CURVE_CUSTOM0 + field - 200);
@@ -431,6 +545,8 @@ extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t 
       L = 8;
       break;
   }
+  if (coop && !coop_field_takes(field, op)) return set_err(ELLGPU_E_ARG, "field probe: this lanes-per-item field does not take this op");
+  if (coop && n > 0x7FFFFFFFu) return set_err(ELLGPU_E_ARG, "field probe: too many items (one block per item)");
   HipBackend& bk = ctx->eng->bk;
   // the run-time fields read the probe's own block: one per device, so such a probe holds the device's
   // custom-curve lock from the (synchronous) upload to the end of its kernel
@@ -457,6 +573,14 @@ extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t 
     case 0: run_field_op<FpK256>(bk, op, n, da, db, dr); break;
     case 1: run_field_op<Fp25519>(bk, op, n, da, db, dr); break;
     case 2: run_field_op<FpK256L>(bk, op, n, da, db, dr); break;      // the 9 x 29-bit field (op 11: mul2, op 12: half)
+    case 3: run_coop_field_op<FpK256C>(bk, op, n, da, db, dr); break;
+    case 4: run_coop_field_op<FpK256R>(bk, op, n, da, db, dr); break;
+    case 5: run_coop_field_op<Fp25519C>(bk, op, n, da, db, dr); break;
+    case 31: run_coop_field_op<CoopNist<CvP192>::F>(bk, op, n, da, db, dr); break;
+    case 32: run_coop_field_op<CoopNist<CvP224>::F>(bk, op, n, da, db, dr); break;
+    case 33: run_coop_field_op<CoopNist<CvP256>::F>(bk, op, n, da, db, dr); break;
+    case 34: run_coop_field_op<CoopNist<CvP384>::F>(bk, op, n, da, db, dr); break;
+    case 35: run_coop_field_op<CoopNist<CvP521>::F>(bk, op, n, da, db, dr); break;
     case 10: run_field_op<FpMont<consts::SECP256K1_P>>(bk, op, n, da, db, dr); break;
     case 11: run_field_op<CvP192::F>(bk, op, n, da, db, dr); break;
     case 12: run_field_op<CvP224::F>(bk, op, n, da, db, dr); break;

@@ -810,7 +810,18 @@ int ellgpu_probe_valu(ellgpu_ctx* ctx, int kind, int blocks, int iters, double* 
  * < 2^256, ops 0..8; ELLGPU_E_ARG for an id that is not defined, for 200+s on a curve that is
  * no ECDSA domain, and for any other op); op: 0 add 1 sub 2 mul 3 sqr 4 inv 5 neg, 6 / 7 / 8
  * multiply by 2 / 4 / 8, 9 identity (reduce the input), 10 (field 1 only) multiply by the
- * one-limb constant b[0]. */
+ * one-limb constant b[0].
+ * The lanes-per-item fields, one item per wavefront (operands any value of `L` limbs, below 2^528
+ * on 35): 3 / 4 secp256k1 p over a 16-lane row, one item per wave / four items per wave (one per
+ * row); 5 2^255-19 over a row (8 limbs each); 31 / 32 / 33 p192 / p224 / p256 over a row (6 / 7 /
+ * 8 limbs); 34 / 35 p384 / p521 over the wave (12 / 17 limbs).  Their ops: 0..3, 5..9; 4 except
+ * on 3 and 4; on 3 and 4 also 11 (x y + (4p - x)(x - y + 4p) in one reduction), 12 (3/2 x^2),
+ * 14 (x y, the two zero tests compared), 15 ((x - y)(x + y) on lazy operands), 16 (a read from
+ * the table format, negated if b is odd).  Four products at once, s = x + y, d = x - y: 20..23
+ * (3 and 5 only) x y, y s, s d, d x from the four rows of one product of four; 24 / 26 x y / y s
+ * from a product of two (3, 5, 31..33), 25 / 27 / 28 x y / y s / s d from a product of three; 24
+ * and 25 return x y + 1 if the other rows are not what a lone product gives.  ELLGPU_E_ARG for
+ * any other op on these ids. */
 int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t n, const uint32_t* a,
                           const uint32_t* b, uint32_t* r);
 

@@ -105,6 +105,25 @@ template <class F, class = void>
 struct has_wide_probe { static constexpr bool value = false; };
 template <class RR>
 struct has_wide_probe<FpSolinas<RR>, void> { static constexpr bool value = true; };
+// the lanes-per-item fields (ids 3, 4, 5, 31..35), as csrc/capi.hip k_coop_field_op tells them apart
+template <class F>
+struct is_k256_row { static constexpr bool value = false; };
+template <bool PR>
+struct is_k256_row<FpK256CT<PR>> { static constexpr bool value = true; };
+template <class F, class = void>
+struct has_pack4 { static constexpr bool value = false; };
+template <class F>
+struct has_pack4<F, std::void_t<decltype(&F::pack4)>> { static constexpr bool value = true; };
+static bool coop_field_takes(int field, int op) {
+  const bool k256 = field == 3 || field == 4;
+  const bool quad = field == 3 || field == 5 || (field >= 31 && field <= 33);
+  if ((op >= 0 && op <= 3) || (op >= 5 && op <= 9)) return true;
+  if (op == 4) return !k256;
+  if (op == 11 || op == 12 || (op >= 14 && op <= 16)) return k256;
+  if (op >= 20 && op <= 23) return field == 3 || field == 5;
+  if (op >= 24 && op <= 28) return quad;
+  return false;
+}
 template <class F>
 static void field_op(int op, const u32* a, const u32* b, u32* r) {
   typename F::El x, y, z;
@@ -117,7 +136,7 @@ static void field_op(int op, const u32* a, const u32* b, u32* r) {
     case 1: z = F::sub(x, y); break;
     case 2: z = F::mul(x, y); break;
     case 3: z = F::sqr(x); break;
-    case 4: if constexpr (!std::is_same<F, FpK256C>::value) z = F::inv(x); else z = x; break;
+    case 4: if constexpr (!is_k256_row<F>::value) z = F::inv(x); else z = x; break;
     case 5: z = F::neg(x); break;
     case 6: z = F::template mul_pow2<1>(x); break;
     case 7: z = F::template mul_pow2<2>(x); break;
@@ -137,16 +156,41 @@ static void field_op(int op, const u32* a, const u32* b, u32* r) {
     if (op == 17) z = F::mul_sub_mul(x, y, F::sub(y, x), F::add(x, y));        // x y - (y - x)(x + y)
     if (op == 18) z = F::mul_sub_sqr8(x, y, F::sub(x, y));                      // x y - 8 (x - y)^2
   }
-  if constexpr (std::is_same<F, FpK256L>::value || std::is_same<F, FpK256C>::value) {
+  if constexpr (std::is_same<F, FpK256L>::value || is_k256_row<F>::value) {
     if (op == 11) z = F::mul2(x, y, F::template neg_l<4>(x), F::template sub_l<4>(x, y));
     if (op == 12) { typename F::El a = F::sqr(x); z = F::norm(F::add_l(a, F::half_l(a))); }
   }
-  if constexpr (std::is_same<F, FpK256C>::value) {
+  if constexpr (is_k256_row<F>::value) {
     // the row layer's own corners: the exact zero test of a product, a lazy difference through a
     // product, an entry read from the one-lane tables' memory format
     if (op == 14) { z = F::mul(x, y); z = F::is_zero_w(z) == F::is_zero(z) ? z : F::one(); }
     if (op == 15) z = F::mul(F::template sub_l<4>(x, y), F::add_l(x, y));
     if (op == 16) z = F::norm(F::template cneg_l<2>(F::load_words(ta), (tb[0] & 1u) != 0));
+  }
+  if constexpr (ell::has_quad<F>::value) {
+    // four (two, three) products side by side, one per row of the wave, read back through the class's
+    // own unpack (k_coop_field_op's ops 20..28): x y, y (x + y), (x + y)(x - y), (x - y) x
+    if (op >= 20 && op <= 28) {
+      const typename F::El s = F::add(x, y), d = F::sub(x, y);
+      if constexpr (has_pack4<F>::value) {
+        if (op <= 23) {
+          typename F::El q[4];
+          F::unpack4(F::mulq(F::pack4(x, y, s, d), F::pack4(y, s, d, x)), q[0], q[1], q[2], q[3]);
+          z = q[op - 20];
+        }
+      }
+      if (op == 24 || op == 26) {
+        typename F::El q0, q1;
+        F::unpack2(F::mulq(F::pack2(x, y), F::pack2(y, s)), q0, q1);
+        z = op == 26 ? q1 : F::eq(q1, F::mul(y, s)) ? q0 : F::add(q0, F::one());
+      }
+      if (op == 25 || op == 27 || op == 28) {
+        typename F::El q0, q1, q2;
+        F::unpack3(F::mulq(F::pack3(x, y, s), F::pack3(y, s, d)), q0, q1, q2);
+        const bool same = F::eq(q1, F::mul(y, s)) && F::eq(q2, F::mul(s, d));
+        z = op == 27 ? q1 : op == 28 ? q2 : same ? q0 : F::add(q0, F::one());
+      }
+    }
   }
   F::to_plain(tr, z);
   for (int i = 0; i < F::L; i++) r[i] = tr[i];
@@ -194,7 +238,7 @@ int hs_launches(const char* name) {
 // field: 0 k256, 1 25519, 2.. mont(curve p): 10+curve -> base field, 20+curve -> order field
 int hs_field_limbs(int field) {
   switch (field) {
-    case 0: case 1: case 2: case 3: return 8;
+    case 0: case 1: case 2: case 3: case 4: case 5: return 8;
     case 10: return 8; case 11: return 6; case 12: return 7; case 13: return 8; case 14: return 12; case 15: return 17;
     case 31: return 6; case 32: return 7; case 33: return 8; case 34: return 12; case 35: return 17;
     case 20: return 8; case 21: return 6; case 22: return 7; case 23: return 8; case 24: return 12; case 25: return 17;
@@ -203,10 +247,14 @@ int hs_field_limbs(int field) {
   return -1;
 }
 int hs_field_op(int field, int op, const u32* a, const u32* b, u32* r) {
+  // (the lanes-per-item ids refuse what ellgpu_debug_field_op refuses for them)
+  if ((field == 3 || field == 4 || field == 5 || (field >= 31 && field <= 35)) && !coop_field_takes(field, op)) return -1;
   switch (field) {
     case 0: field_op<FpK256>(op, a, b, r); break;
     case 2: field_op<FpK256L>(op, a, b, r); break;
     case 3: field_op<FpK256C>(op, a, b, r); break;
+    case 4: field_op<FpK256R>(op, a, b, r); break;      // one item per row: a row of the host simulation is one item
+    case 5: field_op<Fp25519C>(op, a, b, r); break;     // 2^255 - 19 over a row (csrc/coop_ed.h)
     // the row layer's Montgomery fields (csrc/coop_mont.h), host simulation of the row
     case 31: field_op<CoopNist<CvP192>::F>(op, a, b, r); break;
     case 32: field_op<CoopNist<CvP224>::F>(op, a, b, r); break;
