@@ -217,7 +217,7 @@ int ellgpu_ctx_comb_bits(ellgpu_ctx* ctx, int curve) {
   return ctx->eng->comb_bits(curve);
 }
 
-// edwards: 0 short, 1 Edwards, 2 Montgomery (b unused); dom: n, gx, gy of an ECDSA domain (edwards = 0), else null
+// edwards: 0 short, 1 Edwards, 2 Montgomery (b unused); dom: n, gx, gy of an ECDSA domain (edwards = 0 or 1), else null
 static int define_custom(ellgpu_ctx* ctx, int edwards, const uint8_t* p, const uint8_t* a, const uint8_t* b,
                          int* out_curve, const uint8_t* const* dom = nullptr) {
   if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
@@ -243,7 +243,8 @@ static int define_custom(ellgpu_ctx* ctx, int edwards, const uint8_t* p, const u
     return ELLGPU_OK;
   }
   ctx->eng->err.clear();
-  int rc = dom ? ctx->eng->define_short_domain(p, a, b, dom[0], dom[1], dom[2], out_curve)
+  int rc = dom ? (edwards ? ctx->eng->define_edwards_domain(p, a, b, dom[0], dom[1], dom[2], out_curve)
+                          : ctx->eng->define_short_domain(p, a, b, dom[0], dom[1], dom[2], out_curve))
                : edwards == 2 ? ctx->eng->define_mont(p, a, out_curve)
                : edwards ? ctx->eng->define_edwards(p, a, b, out_curve) : ctx->eng->define_short(p, a, b, out_curve);
   if (rc) g_last_error = ctx->eng->err.empty() ? "ellgpu error" : ctx->eng->err;
@@ -265,6 +266,12 @@ int ellgpu_curve_define_short_domain(ellgpu_ctx* ctx, const uint8_t* p, const ui
   const uint8_t* dom[3] = {n, gx, gy};
   if (!n || !gx || !gy) return set_err(ELLGPU_E_ARG, "null pointer");
   return define_custom(ctx, 0, p, a, b, out_curve, dom);
+}
+int ellgpu_curve_define_edwards_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* d,
+                                       const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve) {
+  const uint8_t* dom[3] = {n, gx, gy};
+  if (!n || !gx || !gy) return set_err(ELLGPU_E_ARG, "null pointer");
+  return define_custom(ctx, 1, p, a, d, out_curve, dom);
 }
 
 #define ELL_ENTER(ctx, stream)                                      \
@@ -653,6 +660,49 @@ int ellgpu_custom_ed_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, con
                                        uint8_t* out_enc, void* stream) {
   ELL_ENTER_DEV(ctx, stream);
   return finish(ctx, ctx->eng->custom_ed_encode_points_dev(curve, n, xy, compact, out_enc), true);
+}
+
+// EC#verify and EC#sign on a user-defined Edwards domain (a group: member 0)
+int ellgpu_custom_ed_verify(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                            const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_ok,
+                            uint8_t* out_status) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_verify_host(curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status));
+}
+int ellgpu_custom_ed_verify_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                                const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_ok,
+                                uint8_t* out_status, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_verify_dev(curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status),
+                true);
+}
+int ellgpu_custom_ed_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                          const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                          uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_sign_host(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
+                                                   out_r, out_s, out_recid, out_ok));
+}
+int ellgpu_custom_ed_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                              const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                              uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
+                                                  out_r, out_s, out_recid, out_ok), true);
+}
+int ellgpu_custom_ed_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                              const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r, uint8_t* out_s,
+                              uint8_t* out_recid, uint8_t* out_ok) {
+  ELL_ENTER(ctx, nullptr);
+  return finish(ctx, ctx->eng->custom_ed_sign_host(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
+                                                   canonical, out_r, out_s, out_recid, out_ok));
+}
+int ellgpu_custom_ed_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                                  int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
+                                  uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
+  ELL_ENTER_DEV(ctx, stream);
+  return finish(ctx, ctx->eng->custom_ed_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
+                                                  canonical, out_r, out_s, out_recid, out_ok), true);
 }
 
 // Point#mul + getX, MontCurve#validate and KeyPair#derive on a user-defined Montgomery curve (a group: member 0)

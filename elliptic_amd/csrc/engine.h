@@ -27,6 +27,7 @@
 #include "mont.h"
 #include "rt_define.h"
 #include "work.h"
+#include "edcecdsa.h"
 #include "coop_ed.h"
 
 #ifndef ELL_INV_BATCH
@@ -1167,6 +1168,67 @@ struct FnEdcKeyValidateFold {
   }
 };
 
+// ECDSA on a user-defined Edwards domain (edcecdsa.h).  The ladders read G's table through
+// STAGE_WORDS / stage_src(): the device backend copies that many words into LDS once per workgroup
+// and calls the three-argument form with the copy; a backend without LDS calls the two-argument
+// form, which reads the table where it lives.
+struct FnEdcEcdsaGTable {
+  static constexpr const char* NAME = "edc_ecdsa_gtable";
+  static constexpr int DS_PER_LANE = 0;
+  u32* gt;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i == 0) EdcEcdsa::g_table(gt);
+  }
+};
+struct FnEdcEcdsaLadder {
+  static constexpr const char* NAME = "edc_ecdsa_ladder";
+  static constexpr int DS_PER_LANE = EdcWork::NWIN * 2;
+  static constexpr int MIN_WAVES = 3;
+  static constexpr int STAGE_WORDS = EdcEcdsa::GT_WORDS;
+  size_t n; const u32* u12; const u8* pub; const u32* gt; EdcWork::P* tbl; u32* proj; u8* on_curve;
+  ELL_HD const u32* stage_src() const { return gt; }
+  ELL_HD void operator()(size_t i, const DigitStore& ds, const u32* staged) const {
+    if (i < n) EdcEcdsa::verify_ladder(i, n, u12, pub, staged, tbl, ds, proj, on_curve);
+  }
+  ELL_HD void operator()(size_t i, const DigitStore& ds) const { (*this)(i, ds, gt); }
+};
+struct FnEdcEcdsaEq {
+  static constexpr const char* NAME = "edc_ecdsa_eq";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u32* proj; const u8* valid; const u8* on_curve; const u8* r; u8* ok; u8* st;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcEcdsa::eq_maxwell(i, n, proj, valid, on_curve, r, ok, st);
+  }
+};
+struct FnEdcEcdsaEqAffine {
+  static constexpr const char* NAME = "edc_ecdsa_eq_affine";
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u32* proj; const u8* valid; const u8* on_curve; const u8* r; u32* pre; u8* ok; u8* st;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) EdcEcdsa::eq_affine(t, T, n, K, proj, valid, on_curve, r, pre, ok, st);
+  }
+};
+struct FnEdcSignMul {
+  static constexpr const char* NAME = "edc_sign_mul";
+  static constexpr int DS_PER_LANE = EdcWork::NWIN;
+  static constexpr int MIN_WAVES = 3;
+  static constexpr int STAGE_WORDS = EdcEcdsa::GT_WORDS;
+  size_t n; const u8* nonces; const u32* gt; u32* proj;
+  ELL_HD const u32* stage_src() const { return gt; }
+  ELL_HD void operator()(size_t i, const DigitStore& ds, const u32* staged) const {
+    if (i < n) EdcEcdsa::sign_mul(i, n, nonces, staged, ds, proj);
+  }
+  ELL_HD void operator()(size_t i, const DigitStore& ds) const { (*this)(i, ds, gt); }
+};
+struct FnEdcSignNorm {
+  static constexpr const char* NAME = "edc_sign_norm";
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u32* proj; u32* pre; u8* kg_xy; u8* kg_inf;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) EdcEcdsa::sign_norm(t, T, n, K, proj, pre, kg_xy, kg_inf);
+  }
+};
+
 // user-defined Montgomery curves (montcustom.h)
 struct FnMontcLadder {
   static constexpr const char* NAME = "montc_ladder";
@@ -1489,6 +1551,18 @@ class Engine {
   template <int U = 0>
   int rt_sign_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv, const u8* nonces,
                     int drbg_hash, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok);
+  // ECDSA on a user-defined Edwards domain (edcecdsa.h; inst.hip group 18).  verify: the short
+  // domain's ecdsa_prep, edc_ecdsa_ladder, then edc_ecdsa_eq (eqXToP) or edc_ecdsa_eq_affine
+  // (no _maxwellTrick).  sign: the short domain's rt_sign_nonce and rt_sign_finish around
+  // edc_sign_mul and edc_sign_norm.  ensure_ed_gtable: G's table of the call's domain, once.
+  template <int U = 0>
+  int ensure_ed_gtable();
+  template <int U = 0>
+  int edc_verify_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s, const u8* pub,
+                       u8* ok, u8* st);
+  template <int U = 0>
+  int edc_sign_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv, const u8* nonces,
+                     int drbg_hash, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok);
   template <class CV>
   int decompress_chunk(size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_ok);
   template <class CV>
@@ -1590,6 +1664,14 @@ class Engine {
     RtField f;
     return define(rt_build_custom(1, p_be, a_be, d_be, f), f, out_curve);
   }
+  // An ECDSA domain on a user-defined Edwards curve: EC#verify and EC#sign on the device
+  // (custom_ed_verify_*, custom_ed_sign_*), and everything a plain define_edwards id can do
+  int define_edwards_domain(const u8* p_be, const u8* a_be, const u8* d_be, const u8* n_be, const u8* gx_be,
+                            const u8* gy_be, int* out_curve) {
+    if (!out_curve) return fail(E_ARG, "null pointer");
+    RtField f;
+    return define(rt_build_edwards_domain(p_be, a_be, d_be, n_be, gx_be, gy_be, f), f, out_curve);
+  }
   // `new elliptic.curve.mont({p, a, b})` (mont.js:11-21) with parameters that are not curve25519's:
   // b y^2 = x^3 + a x^2 + x over an odd prime p < 2^256, x-only; Point#mul + getX,
   // MontCurve#validate and KeyPair#derive run on the device (montcustom.h).  No b: no formula reads it.
@@ -1606,7 +1688,9 @@ class Engine {
   int custom_slot_for(int edwards, const u8* p_be, const u8* a_be, const u8* bd_be,
                       const u8* const* dom = nullptr) {
     RtField f;
-    const int rc = (dom ? rt_build_domain(p_be, a_be, bd_be, dom[0], dom[1], dom[2], f) : rt_build_custom(edwards, p_be, a_be, bd_be, f)).code;
+    const int rc = (dom ? (edwards ? rt_build_edwards_domain(p_be, a_be, bd_be, dom[0], dom[1], dom[2], f)
+                                   : rt_build_domain(p_be, a_be, bd_be, dom[0], dom[1], dom[2], f))
+                        : rt_build_custom(edwards, p_be, a_be, bd_be, f)).code;
     if (rc == E_OK)
       for (size_t i = 0; i < custom_.size(); i++)
         if (memcmp(&custom_[i], &f, sizeof(f)) == 0) return CURVE_CUSTOM0 + (int)i;
@@ -1626,9 +1710,12 @@ class Engine {
     size_t slot = (size_t)(curve - CURVE_CUSTOM0);
     return is_custom(curve) && slot < custom_.size() && custom_[slot].kind == 2;
   }
+  // an ECDSA domain on a SHORT curve: what the comb, ecdsa_verify, mul_fixed and mul_add2 without p1
+  // ask for.  An Edwards domain (kind 1, domain 1) is none: those calls treat it as the plain
+  // Edwards curve it also is.
   bool custom_is_domain(int curve) const {
     size_t slot = (size_t)(curve - CURVE_CUSTOM0);
-    return is_custom(curve) && slot < custom_.size() && custom_[slot].domain == 1;
+    return is_custom(curve) && slot < custom_.size() && custom_[slot].kind == 0 && custom_[slot].domain == 1;
   }
   // the parameter block of a user-defined curve, null for an id that is none of this context's
   // (the white-box field probes read it: ellgpu_debug_field_op, tests/hostsim)
@@ -3014,6 +3101,104 @@ class Engine {
       return custom_ed_encode_points_dev(curve, m, d[0], compact, o[0]);
     });
   }
+
+  // ---- ECDSA on user-defined Edwards domains (ellgpu_custom_ed_verify, _sign, _sign_det) --------
+  // EC#verify and EC#sign over a define_edwards_domain id (edcecdsa.h).  A preset or unknown id is
+  // an argument error; a short id, a Montgomery id and an Edwards id without a domain are unsupported.
+  int check_custom_ed_domain(int curve) {
+    if (!is_custom(curve))
+      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (the presets have ellgpu_ecdsa_verify and ellgpu_ecdsa_sign)")
+                               : fail(E_ARG, "unknown curve id");
+    const RtField* f = custom_block(curve);
+    if (!f) return fail(E_ARG, "unknown curve id");
+    if (f->kind != 1 || !f->domain)
+      return fail(E_UNSUPPORTED, "ECDSA on a user-defined Edwards curve needs its domain (ellgpu_curve_define_edwards_domain)");
+    return E_OK;
+  }
+  int check_custom_ed_verify(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
+                             const u8* s, const u8* pub, u8* ok, int& shift) {
+    int rc = check_custom_ed_domain(curve);
+    if (rc) return rc;
+    if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
+    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
+    return truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift);
+  }
+  int custom_ed_verify_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
+                           const u8* s, const u8* pub, u8* ok, u8* st) {
+    int shift;
+    int rc = check_custom_ed_verify(curve, n, hash, hash_len, msg_bits, r, s, pub, ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    rc = ensure_ed_gtable();
+    if (rc) return rc;
+    const size_t HL = (size_t)hash_len;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edc_verify_chunk(m, hash + o * HL, hash_len, shift, r + o * 32, s + o * 32, pub + o * 64, ok + o,
+                              st ? st + o : nullptr);
+    });
+  }
+  int custom_ed_verify_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
+                            const u8* s, const u8* pub, u8* ok, u8* st) {
+    int shift;
+    int rc = check_custom_ed_verify(curve, n, hash, hash_len, msg_bits, r, s, pub, ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{hash, (size_t)hash_len}, In{r, 32}, In{s, 32}, In{pub, 64}}, {Out{ok, 1}, Out{st, 1}},
+                  [&](size_t m, auto d, auto o) {
+      return custom_ed_verify_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], d[3], o[0], o[1]);
+    });
+  }
+  // the argument lists and semantics of check_custom_sign / custom_sign_* on a short domain
+  int check_custom_ed_sign(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                           const u8* nonces, bool det, int drbg_hash, u8* out_r, u8* out_s, u8* out_recid,
+                           u8* out_ok, int& shift) {
+    int rc = check_custom_ed_domain(curve);
+    if (rc) return rc;
+    if (n && (!hash || !priv || (!det && !nonces) || !out_r || !out_s || !out_recid || !out_ok))
+      return fail(E_ARG, "null pointer");
+    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
+    if (det && (drbg_hash < 0 || drbg_hash > 2)) return fail(E_ARG, "drbg_hash must be ELLGPU_HASH_SHA256, _SHA384 or _SHA512");
+    const int nbits = (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits;
+    rc = truncate_shift(hash_len, msg_bits, nbits, 8, shift);
+    if (rc) return rc;
+    if (det && (nbits + 7) / 8 < 24)
+      return fail(E_UNSUPPORTED, "EC#sign throws on this domain: 'Not enough entropy. Minimum is: 192 bits' (n.byteLength() < 24)");
+    return E_OK;
+  }
+  int custom_ed_sign_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                         const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                         u8* out_recid, u8* out_ok) {
+    int shift;
+    int rc = check_custom_ed_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
+                                  out_recid, out_ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    rc = ensure_ed_gtable();
+    if (rc) return rc;
+    const size_t HL = (size_t)hash_len;
+    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+      return edc_sign_chunk(m, hash + o * HL, hash_len, shift, priv + o * 32, det ? nullptr : nonces + o * 32,
+                            drbg_hash, canonical, out_r + o * 32, out_s + o * 32, out_recid + o, out_ok + o);
+    });
+  }
+  int custom_ed_sign_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                          const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                          u8* out_recid, u8* out_ok) {
+    int shift;
+    int rc = check_custom_ed_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
+                                  out_recid, out_ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return staged(n, {In{hash, (size_t)hash_len}, In{priv, 32}, In{det ? nullptr : nonces, 32}},
+                  {Out{out_r, 32}, Out{out_s, 32}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto o) {
+      return custom_ed_sign_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], det, drbg_hash, canonical, o[0], o[1],
+                                o[2], o[3]);
+    });
+  }
   int x25519_host(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
     if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
     return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_inf, 1}, Out{out_bad, 1}},
@@ -3561,6 +3746,99 @@ int Engine<BK>::edk_validate_chunk(size_t n, const u8* xy, const u8* order, u8* 
   }
   FnEdcKeyValidateFold f2{n, flags, flags + 2 * n, proj, status};
   bk.launch(f2, n);
+  return E_OK;
+}
+
+// G .. 8G of the Edwards domain of the call in progress, in the slot a short domain's comb would
+// take (comb_idx): built on the device on first use.  Its 512 bytes are NOT counted against
+// ELLGPU_COMB_MAX_BYTES: that limit makes a comb fall back to a narrower one, and this table has no
+// narrower form -- under the limit the calls would only fail.  comb_bits_ stays 0: the slot holds no comb.
+template <class BK>
+template <int U>
+int Engine<BK>::ensure_ed_gtable() {
+  const int idx = custom_curve_;
+  if (comb_[idx]) return E_OK;
+  u32* gt = (u32*)bk.alloc(EdcEcdsa::GT_WORDS * sizeof(u32));
+  if (!gt) return fail(E_NOMEM, "generator table allocation failed");
+  FnEdcEcdsaGTable f{gt};
+  bk.launch(f, 1);
+  const int src = bk.sync();
+  if (src != E_OK) {
+    bk.free_(gt);
+    return fail(src, "building the generator table failed on the device");
+  }
+  comb_[idx] = gt;
+  comb_base_[idx] = gt;
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edc_verify_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
+                                 const u8* pub, u8* ok, u8* st) {
+  EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, n * 8 * sizeof(EdcWork::P));
+  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
+  u32* u12 = (u32*)scratch(S_U12, n * 2 * 8 * 4);
+  u8* flags = (u8*)scratch(S_VALID, 2 * n);
+  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
+  if (!tbl || !pre || !u12 || !flags || !proj) return fail(E_NOMEM, "scratch allocation failed");
+  u8* valid = flags;
+  u8* onc = flags + n;
+  const u32* gt = (const u32*)comb_[custom_curve_];
+  const int K = inv_batch_for(n, INV_BATCH_N);
+  const size_t T = (n + K - 1) / K;
+  FnEcdsaPrep<CvCustomDomain> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};   // the short domain's: n alone
+  launch_fn(f1, T);
+  FnEdcEcdsaLadder f2{n, u12, pub, gt, tbl, proj, onc};
+  bk.launch(f2, n);
+  if (custom_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].ncand != RT_NO_MAXWELL) {
+    FnEdcEcdsaEq f3{n, proj, valid, onc, r, ok, st};
+    bk.launch(f3, n);
+  } else {
+    const int Kn = norm_batch_for(n);
+    const size_t Tn = (n + Kn - 1) / Kn;
+    FnEdcEcdsaEqAffine f3{Tn, n, Kn, proj, valid, onc, r, pre, ok, st};
+    bk.launch(f3, Tn);
+  }
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edc_sign_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv, const u8* nonces,
+                               int drbg_hash, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
+  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
+  u8* kg = (u8*)scratch(S_U12, n * (64 + 1));                    // k*G affine + infinity flags
+  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
+  if (!proj || !kg || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  u8* kg_inf = kg + n * 64;
+  const u32* gt = (const u32*)comb_[custom_curve_];
+  if (!nonces) {
+    u8* drawn = (u8*)scratch(S_TBL, n * 32);
+    if (!drawn) return fail(E_NOMEM, "scratch allocation failed");
+    if (drbg_hash == 0) {
+      FnRtSignNonce<Sha256> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
+      launch_fn(f, n);
+    } else if (drbg_hash == 1) {
+      FnRtSignNonce<Sha384> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
+      launch_fn(f, n);
+    } else {
+      FnRtSignNonce<Sha512> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
+      launch_fn(f, n);
+    }
+    nonces = drawn;
+  }
+  FnEdcSignMul f1{n, nonces, gt, proj};
+  bk.launch(f1, n);
+  const int Kn = norm_batch_for(n);
+  const size_t Tn = (n + Kn - 1) / Kn;
+  FnEdcSignNorm f2{Tn, n, Kn, proj, pre, kg, kg_inf};
+  bk.launch(f2, Tn);
+  const int Kf = inv_batch_for(n, INV_BATCH_N);
+  const size_t T = (n + Kf - 1) / Kf;
+  FnRtSignFinish f3{T, n, Kf, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre,
+                    out_r, out_s, out_recid, out_ok};
+  launch_fn(f3, T);
   return E_OK;
 }
 

@@ -111,7 +111,23 @@ namespace ell {
   KW template int Engine<HipBackend>::rt_recover_chunk<0>(size_t, const u8*, int, const u8*,         \
                                                           const u8*, const u8*, u8*, u8*);           \
   KW template int Engine<HipBackend>::rt_sign_chunk<0>(size_t, const u8*, int, int, const u8*,       \
-                                                       const u8*, int, int, u8*, u8*, u8*, u8*);
+                                                       const u8*, int, int, u8*, u8*, u8*, u8*);     \
+  KW template int Engine<HipBackend>::launch_fn<FnEcdsaPrep<CvCustomDomain>>(                        \
+      const FnEcdsaPrep<CvCustomDomain>&, size_t);                                                   \
+  KW template int Engine<HipBackend>::launch_fn<FnRtSignNonce<Sha256>>(const FnRtSignNonce<Sha256>&, size_t); \
+  KW template int Engine<HipBackend>::launch_fn<FnRtSignNonce<Sha384>>(const FnRtSignNonce<Sha384>&, size_t); \
+  KW template int Engine<HipBackend>::launch_fn<FnRtSignNonce<Sha512>>(const FnRtSignNonce<Sha512>&, size_t); \
+  KW template int Engine<HipBackend>::launch_fn<FnRtSignFinish>(const FnRtSignFinish&, size_t);
+// ECDSA on user-defined Edwards domains (edcecdsa.h): G's table, the verify ladder and its two
+// comparisons, k*G and its normalisation -- their own translation unit (group 18, with its own
+// parameter block).  The scalar-field passes around them are the short domain's kernels, launched
+// through the launch_fn instantiations of group 17 above: they read n from that unit's block.
+#define ELL_DECL_EDDOMAIN(KW)                                                                        \
+  KW template int Engine<HipBackend>::ensure_ed_gtable<0>();                                         \
+  KW template int Engine<HipBackend>::edc_verify_chunk<0>(size_t, const u8*, int, int, const u8*,    \
+                                                          const u8*, const u8*, u8*, u8*);           \
+  KW template int Engine<HipBackend>::edc_sign_chunk<0>(size_t, const u8*, int, int, const u8*,      \
+                                                        const u8*, int, int, u8*, u8*, u8*, u8*);
 #define ELL_DECL_ED2(KW)                                                                            \
   KW template int Engine<HipBackend>::ed_decompress_chunk<0>(size_t, const u8*, const u8*, u8*, u8*); \
   KW template int Engine<HipBackend>::ed_codec_chunk<0>(int, size_t, const u8*, int, const u8*, u8*, u8*); \
@@ -150,6 +166,7 @@ ELL_DECL_ED3(extern)
 ELL_DECL_ED4(extern)
 ELL_DECL_CUSTOM(extern)
 ELL_DECL_DOMAIN(extern)
+ELL_DECL_EDDOMAIN(extern)
 ELL_DECL_G7(extern)
 ELL_DECL_G8(extern)
 

@@ -47,13 +47,30 @@ struct MinWaves<Fn, decltype((void)Fn::MIN_WAVES)> { static constexpr int value 
 // CONTRACT for every functor: f(tid, ds) must be IDEMPOTENT per item and free of side effects
 // other than its own item's outputs (no atomics, no counters) -- fill_lane makes the idle lanes of
 // the launch's last wave repeat the last item's work instead of sitting masked off.
+// Fn::STAGE_WORDS (optional): a table of that many 32-bit words at f.stage_src() that every item
+// of the launch reads (the window table of a domain's generator).  The workgroup copies it into
+// LDS before any of its waves leaves, and the functor's three-argument form reads the copy.
+template <class Fn, class = void>
+struct StageWords { static constexpr int value = 0; };
+template <class Fn>
+struct StageWords<Fn, decltype((void)Fn::STAGE_WORDS)> { static constexpr int value = Fn::STAGE_WORDS; };
+
 template <class Fn>
 __global__ void __launch_bounds__(BLOCK, MinWaves<Fn>::value) k_run(const Fn f, size_t nthreads) {
   __shared__ signed char lds_digits[(Fn::DS_PER_LANE > 0 ? Fn::DS_PER_LANE : 1) * BLOCK];
   size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   DigitStore ds{lds_digits + threadIdx.x, BLOCK};
-  if (!fill_lane(tid, nthreads)) return;       // the launch's last wave works with all its lanes
-  f(tid, ds);
+  if constexpr (StageWords<Fn>::value > 0) {
+    __shared__ u32 lds_stage[StageWords<Fn>::value];
+    const u32* src = f.stage_src();
+    for (int w = (int)threadIdx.x; w < StageWords<Fn>::value; w += (int)blockDim.x) lds_stage[w] = src[w];
+    __syncthreads();                             // AHEAD of the early return below: every wave of the workgroup stages and arrives
+    if (!fill_lane(tid, nthreads)) return;
+    f(tid, ds, (const u32*)lds_stage);
+  } else {
+    if (!fill_lane(tid, nthreads)) return;       // the launch's last wave works with all its lanes
+    f(tid, ds);
+  }
 }
 
 // The lanes-per-item layer (coop.h): ONE unit per workgroup of one wave.  A field element is one
@@ -81,6 +98,7 @@ struct TimedLaunch {
 // user-defined curve's parameter block into the current device's constant memory
 int rt_upload_device(const RtField* f);
 int rt_upload_device_dom(const RtField* f);      // the same block for the ECDSA-domain kernels (group 17)
+int rt_upload_device_ed(const RtField* f);       // ... and for the Edwards-domain kernels (group 18)
 
 struct HipBackend {
   int device = 0;
@@ -177,9 +195,12 @@ struct HipBackend {
   void* own_stream() const { return (void*)own; }
   // (the ECDSA-domain kernels' block only for a domain: a plain user-defined curve's calls never
   // launch them, and pay one blocking copy as before)
+  // (an Edwards domain's calls launch kernels of all three units: the curve's own, the short
+  // domain's scalar-field passes, the Edwards ladders)
   void rt_upload(const RtField& f) {
     note((hipError_t)rt_upload_device(&f));
     if (f.domain) note((hipError_t)rt_upload_device_dom(&f));
+    if (f.domain && f.kind == 1) note((hipError_t)rt_upload_device_ed(&f));
   }
   void note(hipError_t e) {
     if (e != hipSuccess && !last) last = (int)e;

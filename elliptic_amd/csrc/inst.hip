@@ -3,6 +3,8 @@
 //   hipcc -c inst.hip -DELL_INST_CURVE=CvP384 -DELL_INST_GROUP=4   (see build.py)
 #if ELL_INST_GROUP == 17
 #define ELL_RT_SYMBOL g_rt_dom      // this code object's own parameter block (fp_rt.h)
+#elif ELL_INST_GROUP == 18
+#define ELL_RT_SYMBOL g_rt_ed
 #endif
 #include "engine_extern.h"
 
@@ -52,6 +54,13 @@ int rt_upload_device_dom(const RtField* f) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rt_dom), f, sizeof(RtField), 0, hipMemcpyHostToDevice);
 }
 ELL_DECL_DOMAIN(ELL_NOKW)
+#elif ELL_INST_GROUP == 18
+// ECDSA on user-defined Edwards domains, with a parameter block of their own
+__constant__ RtField g_rt_ed;
+int rt_upload_device_ed(const RtField* f) {
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rt_ed), f, sizeof(RtField), 0, hipMemcpyHostToDevice);
+}
+ELL_DECL_EDDOMAIN(ELL_NOKW)
 #else
 #error "unknown ELL_INST_GROUP"
 #endif

@@ -213,6 +213,30 @@ inline RtStatus rt_build_custom(int edwards, const u8* p_be, const u8* a_be, con
   }
   return {E_OK, nullptr};
 }
+// the domain fields of a block whose curve is built: the order n (odd, >= 3) and the generator
+// (coordinates < p), the same for a short and an Edwards domain
+inline bool rt_order_ok(const u32 (&n)[8]) {
+  bool small = true;
+  for (int i = 1; i < 8; i++) small = small && n[i] == 0;
+  return (n[0] & 1u) && !(small && n[0] < 3);
+}
+inline void rt_fill_domain(RtField& f, const u32 (&n)[8], const u32 (&gx)[8], const u32 (&gy)[8]) {
+  f.domain = 1;
+  bn_copy<8>(f.n, n);
+  mont_consts(n, f.nn0, f.n_one, f.n_r2, f.nm2);
+  f.nbits = (u32)bit_length(n);
+  mod_to_mont(f.p, f.n_p, n);
+  // floor(p / n), as far as 101 (base.js:33-40: the Maxwell trick for <= 100)
+  u32 q = 0, rem[8];
+  bn_copy<8>(rem, f.p);
+  while (q <= 100 && bn_geq<8>(rem, n)) {
+    bn_sub<8>(rem, rem, n);
+    q++;
+  }
+  f.ncand = q <= 100 ? q : RT_NO_MAXWELL;
+  bn_copy<8>(f.gx, gx);
+  bn_copy<8>(f.gy, gy);
+}
 // An ECDSA domain on a user-defined short curve (ellgpu_curve_define_short_domain): the curve's
 // block plus the order n and the generator G -- EC#verify, k*G and mulAdd with G on the device.
 // Refused: n even or < 3, G not on the curve (coordinates >= p included), 4a^3 + 27b^2 = 0.
@@ -230,9 +254,7 @@ inline RtStatus rt_build_domain(const u8* p_be, const u8* a_be, const u8* b_be, 
   load_be<8>(n, n_be, 32);
   load_be<8>(gx, gx_be, 32);
   load_be<8>(gy, gy_be, 32);
-  bool small = true;
-  for (int i = 1; i < 8; i++) small = small && n[i] == 0;
-  if (!(n[0] & 1u) || (small && n[0] < 3)) return {E_ARG, "ECDSA domain: the order must be odd and >= 3"};
+  if (!rt_order_ok(n)) return {E_ARG, "ECDSA domain: the order must be odd and >= 3"};
   // 4 a^3 + 27 b^2 != 0 (mod p): a curve, not a singular cubic
   u32 t[8], u[8], k[8];
   mod_mul(f.p, t, a, a);
@@ -256,21 +278,41 @@ inline RtStatus rt_build_domain(const u8* p_be, const u8* a_be, const u8* b_be, 
   mod_add<8>(t, t, b, f.p);
   mod_mul(f.p, u, gy, gy);
   if (!bn_eq<8>(t, u)) return {E_ARG, "ECDSA domain: G is not on the curve"};
-  f.domain = 1;
-  bn_copy<8>(f.n, n);
-  mont_consts(n, f.nn0, f.n_one, f.n_r2, f.nm2);
-  f.nbits = (u32)bit_length(n);
-  mod_to_mont(f.p, f.n_p, n);
-  // floor(p / n), as far as 101 (base.js:33-40: the Maxwell trick for <= 100)
-  u32 q = 0, rem[8];
-  bn_copy<8>(rem, f.p);
-  while (q <= 100 && bn_geq<8>(rem, n)) {
-    bn_sub<8>(rem, rem, n);
-    q++;
-  }
-  f.ncand = q <= 100 ? q : RT_NO_MAXWELL;
-  bn_copy<8>(f.gx, gx);
-  bn_copy<8>(f.gy, gy);
+  rt_fill_domain(f, n, gx, gy);
+  return {E_OK, nullptr};
+}
+// An ECDSA domain on a user-defined Edwards curve (ellgpu_curve_define_edwards_domain): the curve's
+// block (rt_build_custom(1, ...)) plus the same domain fields.  Refused: n even or < 3, a
+// coordinate of G >= p, G off the curve a x^2 + y^2 = 1 + d x^2 y^2, G = (0, 1).  Neither p nor n
+// is tested for primality and n * G = O is not tested, as on a short domain.
+inline RtStatus rt_build_edwards_domain(const u8* p_be, const u8* a_be, const u8* d_be, const u8* n_be,
+                                        const u8* gx_be, const u8* gy_be, RtField& f) {
+  if (!n_be || !gx_be || !gy_be) return {E_ARG, "null pointer"};
+  const RtStatus st = rt_build_custom(1, p_be, a_be, d_be, f);
+  if (st.code) return st;
+  u32 a[8], d[8], n[8], gx[8], gy[8];
+  load_be<8>(a, a_be, 32);
+  load_be<8>(d, d_be, 32);
+  mod_reduce(f.p, a, a);
+  mod_reduce(f.p, d, d);
+  load_be<8>(n, n_be, 32);
+  load_be<8>(gx, gx_be, 32);
+  load_be<8>(gy, gy_be, 32);
+  if (!rt_order_ok(n)) return {E_ARG, "ECDSA domain: the order must be odd and >= 3"};
+  if (bn_geq<8>(gx, f.p) || bn_geq<8>(gy, f.p)) return {E_ARG, "ECDSA domain: G is not on the curve"};
+  u32 x2[8], y2[8], l[8], r[8], one[8];
+  bn_zero<8>(one);
+  one[0] = 1;
+  mod_mul(f.p, x2, gx, gx);
+  mod_mul(f.p, y2, gy, gy);
+  mod_mul(f.p, l, a, x2);
+  mod_add<8>(l, l, y2, f.p);
+  mod_mul(f.p, r, d, x2);
+  mod_mul(f.p, r, r, y2);
+  mod_add<8>(r, r, one, f.p);
+  if (!bn_eq<8>(l, r)) return {E_ARG, "ECDSA domain: G is not on the curve"};
+  if (bn_is_zero<8>(gx) && bn_eq<8>(gy, one)) return {E_ARG, "ECDSA domain: G is the identity (0, 1)"};
+  rt_fill_domain(f, n, gx, gy);
   return {E_OK, nullptr};
 }
 

@@ -144,6 +144,20 @@ class Context:
         self._ed_pbytes[cid.value] = (int(p).bit_length() + 7) // 8
         return cid.value
 
+    def define_edwards_domain(self, p, a, d, n, gx, gy):
+        """Register an ECDSA domain on an Edwards curve: the curve of define_edwards plus its order n
+        and generator G = (gx, gy) (`new elliptic.ec(new curves.PresetCurve({type: 'edwards', p, a,
+        c: '1', d, n, g}))`), and return its curve id.  Beside everything a define_edwards id allows,
+        custom_ed_verify, custom_ed_sign and custom_ed_sign_det (and their _dev forms) take it.
+        Raises EllgpuError (ELLGPU_E_ARG) for n even or < 3, G off the curve, a coordinate of G >= p
+        or G = (0, 1); n and p are not tested for primality, n * G = O is not tested."""
+        cid = ctypes.c_int(-1)
+        p = int(p)
+        enc = [int(v).to_bytes(32, "big") for v in (p, int(a) % p, int(d) % p, int(n), int(gx), int(gy))]
+        self._check(self._lib.ellgpu_curve_define_edwards_domain(self._ctx, *enc, ctypes.byref(cid)))
+        self._ed_pbytes[cid.value] = (p.bit_length() + 7) // 8
+        return cid.value
+
     def define_mont(self, p, a):
         """Register the Montgomery curve b y^2 = x^3 + a x^2 + x over the odd prime p < 2^256 (`new
         curve.mont({p, a, b})` with parameters that are not curve25519's) and return its curve id.
@@ -791,6 +805,82 @@ class Context:
         self._check(self._lib.ellgpu_custom_ed_encode_points_dev(self._ctx, self._cid(curve), n, xy.data_ptr(),
                                                                  1 if compact else 0, out_enc.data_ptr(),
                                                                  self._stream()))
+
+    # ---- ECDSA on user-defined Edwards domains (ellgpu_custom_ed_verify / _sign / _sign_det) -------
+    # curve: an id from define_edwards_domain
+
+    def custom_ed_verify(self, curve, hashes, r, s, pub, msg_bits=0, status=False, out=None):
+        """EC#verify per item on an Edwards domain id -> ok, a mask of strictly 0 / 1; hashes
+        (n, 1..64), r, s (n, 32), pub (n, 64) affine.  status=True -> (ok, st): st[i] = 2 where r and
+        s are in range but pub[i] is not on the curve (ok[i] is 0 there), else 0.  out= the result
+        arrays to write into: (ok,) or, with status, (ok, st)"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        r = _u8(r, (n, 32))
+        s = _u8(s, (n, 32))
+        pub = _u8(pub, (n, 64))
+        res = self._outs(out, [(n,), (n,)] if status else [(n,)])
+        self._check(self._lib.ellgpu_custom_ed_verify(self._ctx, self._cid(curve), n, hashes.ctypes.data, hash_len,
+                                                      int(msg_bits), r.ctypes.data, s.ctypes.data, pub.ctypes.data,
+                                                      res[0].ctypes.data, res[1].ctypes.data if status else None))
+        return (res[0], res[1]) if status else res[0]
+
+    def custom_ed_verify_dev(self, curve, hashes, r, s, pub, out_ok, out_status=None, msg_bits=0):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_ed_verify_dev(
+            self._ctx, self._cid(curve), n, hashes.data_ptr(), hash_len, int(msg_bits), r.data_ptr(), s.data_ptr(),
+            pub.data_ptr(), out_ok.data_ptr(), out_status.data_ptr() if out_status is not None else None,
+            self._stream()))
+
+    def custom_ed_sign(self, curve, hashes, priv, nonces, canonical=False, msg_bits=0, out=None):
+        """one pass of EC#sign per item on an Edwards domain id for supplied nonces -> (r, s, recid,
+        ok); arguments and results as custom_sign"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        priv = _u8(priv, (n, 32))
+        nonces = _u8(nonces, (n, 32))
+        r, s, rec, ok = self._outs(out, [(n, 32), (n, 32), (n,), (n,)])
+        self._check(self._lib.ellgpu_custom_ed_sign(self._ctx, self._cid(curve), n, hashes.ctypes.data, hash_len,
+                                                    int(msg_bits), priv.ctypes.data, nonces.ctypes.data,
+                                                    1 if canonical else 0, r.ctypes.data, s.ctypes.data,
+                                                    rec.ctypes.data, ok.ctypes.data))
+        return r, s, rec, ok
+
+    def custom_ed_sign_dev(self, curve, hashes, priv, nonces, out_r, out_s, out_recid, out_ok, canonical=False,
+                           msg_bits=0):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_ed_sign_dev(self._ctx, self._cid(curve), n, hashes.data_ptr(), hash_len,
+                                                        int(msg_bits), priv.data_ptr(), nonces.data_ptr(),
+                                                        1 if canonical else 0, out_r.data_ptr(), out_s.data_ptr(),
+                                                        out_recid.data_ptr(), out_ok.data_ptr(), self._stream()))
+
+    def custom_ed_sign_det(self, curve, hashes, priv, drbg_hash=HASH_SHA256, canonical=False, msg_bits=0, out=None):
+        """EC#sign per item on an Edwards domain id with the reference's own HmacDRBG nonces over
+        drbg_hash -> (r, s, recid, ok); arguments and results as custom_sign_det"""
+        hashes = _u8(hashes)
+        if hashes.ndim != 2:
+            raise ValueError("hashes must be (n, hash_len)")
+        n, hash_len = hashes.shape
+        priv = _u8(priv, (n, 32))
+        r, s, rec, ok = self._outs(out, [(n, 32), (n, 32), (n,), (n,)])
+        self._check(self._lib.ellgpu_custom_ed_sign_det(self._ctx, self._cid(curve), n, hashes.ctypes.data, hash_len,
+                                                        int(msg_bits), priv.ctypes.data, int(drbg_hash),
+                                                        1 if canonical else 0, r.ctypes.data, s.ctypes.data,
+                                                        rec.ctypes.data, ok.ctypes.data))
+        return r, s, rec, ok
+
+    def custom_ed_sign_det_dev(self, curve, hashes, priv, out_r, out_s, out_recid, out_ok, drbg_hash=HASH_SHA256,
+                               canonical=False, msg_bits=0):
+        n, hash_len = hashes.shape
+        self._check(self._lib.ellgpu_custom_ed_sign_det_dev(self._ctx, self._cid(curve), n, hashes.data_ptr(),
+                                                            hash_len, int(msg_bits), priv.data_ptr(), int(drbg_hash),
+                                                            1 if canonical else 0, out_r.data_ptr(),
+                                                            out_s.data_ptr(), out_recid.data_ptr(),
+                                                            out_ok.data_ptr(), self._stream()))
 
     def custom_encode_points(self, curve, xy, compact=False, out=None):
         """BasePoint#encode per item at the curve's own width -> (n, 1 + PL) for compact, else

@@ -72,6 +72,9 @@
  *             (ellgpu_custom_ed_*: the key side of a user-defined Edwards curve);
  *             11 customSign(hash, priv, nonces; i0 = canonical) 12 customSignDet(hash, priv; i0 = canonical,
  *             i1 = drbgHash);
+ *             26 customEdVerify(hash, r, s, pub) -> {ok, status}  27 customEdSign (as 11)  28 customEdSignDet (as 12)
+ *             (ellgpu_custom_ed_verify / _sign / _sign_det: ECDSA on a user-defined Edwards domain,
+ *             defineEdwardsDomain(ctx, p, a, d, n, gx, gy); sync forms customEdVerify, customEdSign, customEdSignDet);
  *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
@@ -161,6 +164,14 @@ static struct {
   int (*custom_encode_points)(ellgpu_ctx*, int, size_t, const uint8_t*, int, uint8_t*);
   int (*custom_sign)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*, int,
                      uint8_t*, uint8_t*, uint8_t*, uint8_t*);
+  int (*define_edwards_domain)(ellgpu_ctx*, const uint8_t*, const uint8_t*, const uint8_t*, const uint8_t*,
+                               const uint8_t*, const uint8_t*, int*);
+  int (*custom_ed_verify)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*,
+                          const uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_ed_sign)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*, int,
+                        uint8_t*, uint8_t*, uint8_t*, uint8_t*);
+  int (*custom_ed_sign_det)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, int, int,
+                            uint8_t*, uint8_t*, uint8_t*, uint8_t*);
   int (*custom_sign_det)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, int, int,
                          uint8_t*, uint8_t*, uint8_t*, uint8_t*);
   int (*custom_verify_wire)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, size_t,
@@ -242,6 +253,10 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(custom_encode_points, "ellgpu_custom_encode_points");
   SYM(custom_sign, "ellgpu_custom_sign");
   SYM(custom_sign_det, "ellgpu_custom_sign_det");
+  SYM(define_edwards_domain, "ellgpu_curve_define_edwards_domain");
+  SYM(custom_ed_verify, "ellgpu_custom_ed_verify");
+  SYM(custom_ed_sign, "ellgpu_custom_ed_sign");
+  SYM(custom_ed_sign_det, "ellgpu_custom_ed_sign_det");
   L.h = h;
   napi_value t; CHECK(env, napi_get_boolean(env, 1, &t));
   return t;
@@ -447,22 +462,26 @@ static napi_value fn_define_mont(napi_env env, napi_callback_info info) {
 }
 /* defineShortDomain(ctx, p, a, b, n, gx, gy) -> curve id: 32-byte big-endian Buffers
  * (ellgpu_curve_define_short_domain) */
-static napi_value fn_define_short_domain(napi_env env, napi_callback_info info) {
+static napi_value define_domain_with(napi_env env, napi_callback_info info, int edwards) {
   if (!need_lib(env)) return NULL;
   size_t argc = 7; napi_value argv[7];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 7) THROW(env, "defineShortDomain(ctx, p, a, b, n, gx, gy)");
+  if (argc < 7) THROW(env, edwards ? "defineEdwardsDomain(ctx, p, a, d, n, gx, gy)" : "defineShortDomain(ctx, p, a, b, n, gx, gy)");
   ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
   const uint8_t* b[6]; size_t l[6];
   for (int i = 0; i < 6; i++) {
     if (!get_buf(env, argv[1 + i], &b[i], &l[i], 0)) return NULL;
-    if (l[i] != 32) THROW(env, "defineShortDomain: p, a, b, n, gx, gy are 32-byte big-endian Buffers");
+    if (l[i] != 32) THROW(env, "defineShortDomain / defineEdwardsDomain: the six parameters are 32-byte big-endian Buffers");
   }
   int id = -1;
-  if (L.define_short_domain(c, b[0], b[1], b[2], b[3], b[4], b[5], &id) != 0) THROW(env, L.last_error());
+  if ((edwards ? L.define_edwards_domain : L.define_short_domain)(c, b[0], b[1], b[2], b[3], b[4], b[5], &id) != 0)
+    THROW(env, L.last_error());
   napi_value v; CHECK(env, napi_create_int32(env, id, &v));
   return v;
 }
+static napi_value fn_define_short_domain(napi_env env, napi_callback_info info) { return define_domain_with(env, info, 0); }
+/* defineEdwardsDomain(ctx, p, a, d, n, gx, gy) -> curve id (ellgpu_curve_define_edwards_domain) */
+static napi_value fn_define_edwards_domain(napi_env env, napi_callback_info info) { return define_domain_with(env, info, 1); }
 /* destroyContext(ctx): releases the context's device memory and streams (ellgpu_ctx_destroy) and the
  * addon's pin on the external; any later call with that external throws.  Refused while Promise-form
  * batches are in flight (a worker thread is inside the context). */
@@ -555,7 +574,7 @@ static napi_value fn_mul_fixed(napi_env e, napi_callback_info i) { return mul_co
 static napi_value fn_mul_var(napi_env e, napi_callback_info i) { return mul_common(e, i, 1); }
 static napi_value fn_mul_add2(napi_env e, napi_callback_info i) { return mul_common(e, i, 2); }
 
-static napi_value fn_verify(napi_env env, napi_callback_info info) {
+static napi_value verify_with(napi_env env, napi_callback_info info, int ed) {
   if (!need_lib(env)) return NULL;
   size_t argc = 8; napi_value argv[8];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -574,9 +593,12 @@ static napi_value fn_verify(napi_env env, napi_callback_info info) {
   napi_value bok, bst; void *dok, *dst;
   CHECK(env, result_buffer(env, n, &dok, &bok));
   CHECK(env, result_buffer(env, n, &dst, &bst));
-  if (L.ecdsa_verify(c, curve, n, h, hl, mb, r, s, q, (uint8_t*)dok, (uint8_t*)dst) != 0) return lib_error(env);
+  if ((ed ? L.custom_ed_verify : L.ecdsa_verify)(c, curve, n, h, hl, mb, r, s, q, (uint8_t*)dok, (uint8_t*)dst) != 0) return lib_error(env);
   return mk_result(env, "ok", bok, "status", bst);
 }
+static napi_value fn_verify(napi_env env, napi_callback_info info) { return verify_with(env, info, 0); }
+/* customEdVerify(ctx, curve, hash, hashLen, msgBits, r, s, pub) -> {ok, status} (ellgpu_custom_ed_verify) */
+static napi_value fn_custom_ed_verify(napi_env env, napi_callback_info info) { return verify_with(env, info, 1); }
 static napi_value fn_x25519(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
   size_t argc = 3; napi_value argv[3];
@@ -698,7 +720,7 @@ static napi_value fn_sign_det(napi_env env, napi_callback_info info) {
 
 /* customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) and
  * customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok} */
-static napi_value custom_sign_with(napi_env env, napi_callback_info info, int det) {
+static napi_value custom_sign_with(napi_env env, napi_callback_info info, int det, int ed) {
   if (!need_lib(env)) return NULL;
   size_t argc = 8; napi_value argv[8];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -721,10 +743,10 @@ static napi_value custom_sign_with(napi_env env, napi_callback_info info, int de
   CHECK(env, result_buffer(env, n * 32, &dsg, &bs));
   CHECK(env, result_buffer(env, n, &drec, &brec));
   CHECK(env, result_buffer(env, n, &dok, &bok));
-  int rc = det ? L.custom_sign_det(c, curve, n, h, hl, mb, d, dh, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg,
-                                   (uint8_t*)drec, (uint8_t*)dok)
-               : L.custom_sign(c, curve, n, h, hl, mb, d, k, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg, (uint8_t*)drec,
-                               (uint8_t*)dok);
+  int rc = det ? (ed ? L.custom_ed_sign_det : L.custom_sign_det)(c, curve, n, h, hl, mb, d, dh, canon ? 1 : 0, (uint8_t*)dr,
+                                                                 (uint8_t*)dsg, (uint8_t*)drec, (uint8_t*)dok)
+               : (ed ? L.custom_ed_sign : L.custom_sign)(c, curve, n, h, hl, mb, d, k, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg,
+                                                         (uint8_t*)drec, (uint8_t*)dok);
   if (rc != 0) return lib_error(env);
   CHECK(env, napi_create_object(env, &o));
   CHECK(env, napi_set_named_property(env, o, "r", br));
@@ -733,8 +755,11 @@ static napi_value custom_sign_with(napi_env env, napi_callback_info info, int de
   CHECK(env, napi_set_named_property(env, o, "ok", bok));
   return o;
 }
-static napi_value fn_custom_sign(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 0); }
-static napi_value fn_custom_sign_det(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 1); }
+static napi_value fn_custom_sign(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 0, 0); }
+static napi_value fn_custom_sign_det(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 1, 0); }
+/* customEdSign / customEdSignDet: the same argument lists on a user-defined Edwards domain (ellgpu_custom_ed_sign / _sign_det) */
+static napi_value fn_custom_ed_sign(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 0, 1); }
+static napi_value fn_custom_ed_sign_det(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 1, 1); }
 
 /* ecdsaRecover / customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy: Buffer(n*2B), status: Buffer(n)} */
 static napi_value recover_with(napi_env env, napi_callback_info info, int custom) {
@@ -989,6 +1014,10 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
  * 21 edDecodePoints(enc; i0 = row length)  22 edValidate(xy, order: 32 bytes or null)  23 edDerive(priv, pubXY)
  * 24 edDeriveWire(priv, enc; i0 = key length)  25 edEncodePoints(xy; i0 = compact, i1 = p.byteLength(); as 16) */
 #define ECDH_OP_LAST 25
+#define ED_OP_VERIFY 26          /* ECDSA on a user-defined Edwards domain: verify (as op 3), sign (as 11), sign_det (as 12) */
+#define ED_OP_SIGN 27
+#define ED_OP_SIGN_DET 28
+#define OP_LAST 28
 #define ECDH_ENC_OP(op) ((op) == 16 || (op) == 25)
 static const char* const ECDH_NAMES[13][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
                                               {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0},
@@ -1124,6 +1153,12 @@ static void job_execute(napi_env env, void* data) {
                                    j->out0, j->out1, j->out2, j->out3); break;
     case 12: j->rc = L.custom_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1, j->i0,
                                        j->out0, j->out1, j->out2, j->out3); break;
+    case ED_OP_VERIFY: j->rc = L.custom_ed_verify(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2],
+                                                  j->in[3], j->out0, j->out1); break;
+    case ED_OP_SIGN: j->rc = L.custom_ed_sign(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2], j->i0,
+                                              j->out0, j->out1, j->out2, j->out3); break;
+    case ED_OP_SIGN_DET: j->rc = L.custom_ed_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1,
+                                                      j->i0, j->out0, j->out1, j->out2, j->out3); break;
     case 13: case 14: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: {
       const uint8_t* in[2] = {j->in[0], j->in[1]};
       uint8_t* out[3] = {j->out0, j->out1, j->out2};
@@ -1142,14 +1177,15 @@ static void job_complete(napi_env env, napi_status status, void* data) {
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
     /* result property names per op, in output order */
-    static const char* const names[ECDH_OP_LAST + 1][4] = {
+    static const char* const names[OP_LAST + 1][4] = {
       {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
       {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
       {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
       {"x", "status", 0, 0}, {"x", "status", "err", 0}, {"status", 0, 0, 0}, {"enc", 0, 0, 0},
       {"x", "inf", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
       {"xy", "status", 0, 0}, {"xy", "status", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
-      {"x", "status", "err", 0}, {"enc", 0, 0, 0}};
+      {"x", "status", "err", 0}, {"enc", 0, 0, 0},
+      {"ok", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1194,7 +1230,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
   j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
   j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > ECDH_OP_LAST || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
+  if (op < 0 || op > OP_LAST || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
   int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
@@ -1216,17 +1252,20 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
     case 1: j->n = len[0] / B; ok = j->in[0] && j->in[1] && len[0] % B == 0 && len[1] == j->n * 2 * B; break;
     case 2: j->n = len[0] / B; ok = j->in[0] && j->in[2] && j->in[3] && len[0] % B == 0 && len[2] == len[0] &&
                                      len[3] == j->n * 2 * B && (!j->in[1] || len[1] == j->n * 2 * B); break;
-    case 3: ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
+    case 3: case ED_OP_VERIFY:
+            ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB && len[2] == j->n * NB && len[3] == j->n * 2 * B; break;
     case 4: j->n = len[0] / 32; ok = j->in[0] && j->in[1] && len[0] % 32 == 0 && len[1] == len[0]; break;
     case 5: ok = hl > 0 && j->in[0] && j->in[1] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB; break;
-    case 11: case 12:
-            ok = hl > 0 && j->in[0] && j->in[1] && (op == 12 || j->in[2]) && len[0] % (size_t)hl == 0;
+    case 11: case 12: case ED_OP_SIGN: case ED_OP_SIGN_DET: {
+            const int det = op == 12 || op == ED_OP_SIGN_DET;
+            ok = hl > 0 && j->in[0] && j->in[1] && (det || j->in[2]) && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * NB && (op == 12 || len[2] == j->n * NB); break;
+            ok = ok && len[1] == j->n * NB && (det || len[2] == j->n * NB); break;
+    }
     case 6: case 10:
             ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
@@ -1248,7 +1287,8 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   j->out1_len = op == 5 || op >= 11 ? j->n * NB : j->n;
   j->out2_len = op == 5 || op >= 11 ? j->n : 0;
   j->out3_len = op == 5 || op >= 11 ? j->n : 0;
-  if (op >= 13) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
+  if (op == ED_OP_VERIFY) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
+  if (op >= 13 && op <= ECDH_OP_LAST) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
   /* (ops 16, 25: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
   j->out0 = (uint8_t*)malloc(ECDH_ENC_OP(op) ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
   j->out1 = (uint8_t*)malloc(j->out1_len ? j->out1_len : 1);
@@ -1273,7 +1313,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"open", fn_open}, {"createContext", fn_create}, {"destroyContext", fn_destroy},
     {"defer", fn_defer}, {"collect", fn_collect}, {"combBits", fn_comb_bits},
     {"curveId", fn_curve_id}, {"fieldBytes", fn_field_bytes}, {"orderBytes", fn_order_bytes},
-    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"defineMont", fn_define_mont}, {"defineShortDomain", fn_define_short_domain}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
+    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"defineMont", fn_define_mont}, {"defineShortDomain", fn_define_short_domain}, {"defineEdwardsDomain", fn_define_edwards_domain}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
     {"mulAdd2", fn_mul_add2}, {"ecdsaVerify", fn_verify}, {"x25519", fn_x25519}, {"x25519Derive", fn_x25519_derive},
     {"callAsync", fn_call_async}, {"decompress", fn_decompress},
     {"eddsaVerify", fn_eddsa_verify}, {"eddsaSign", fn_eddsa_sign}, {"ecdsaSign", fn_sign}, {"ecdsaRecover", fn_recover}, {"ecdsaSignDet", fn_sign_det},
@@ -1281,7 +1321,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"pointAdd", fn_point_add}, {"sigFromDer", fn_sig_from_der}, {"sigToDer", fn_sig_to_der}, {"ecdsaVerifyWire", fn_verify_wire},
     {"customDecompress", fn_custom_decompress}, {"customDecodePoints", fn_custom_decode_points},
     {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
-    {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det}, {"customEcdh", fn_custom_ecdh},
+    {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
+    {"customEdVerify", fn_custom_ed_verify}, {"customEdSign", fn_custom_ed_sign}, {"customEdSignDet", fn_custom_ed_sign_det}, {"customEcdh", fn_custom_ecdh},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

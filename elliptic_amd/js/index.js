@@ -112,6 +112,19 @@ Engine.prototype.defineEdwards = function defineEdwards(p, a, d) {
   this._edCoordBytes[id] = byteLength(buf(p));
   return id;
 };
+// An ECDSA domain on such an Edwards curve: the curve plus its order n and generator G = (gx, gy)
+// (ellgpu_curve_define_edwards_domain; `new elliptic.ec(new elliptic.curves.PresetCurve({type:
+// 'edwards', prime: null, p, a, c: '1', d, n, hash, gRed: false, g}))`).  Its id takes what a
+// defineEdwards id takes, and also customEdVerifyBatch / customEdSignBatch / customEdSignDetBatch.
+// All six arguments: BN-like (toArray) or 32-byte Buffers; p and n pass through as given.
+Engine.prototype.defineEdwardsDomain = function defineEdwardsDomain(p, a, d, n, gx, gy) {
+  function buf(v) {
+    return Buffer.isBuffer(v) ? v : Buffer.from(v.toArray('be', 32));
+  }
+  var id = this.addon.defineEdwardsDomain(this.ctx, buf(p), buf(a), buf(d), buf(n), buf(gx), buf(gy));
+  this._edCoordBytes[id] = byteLength(buf(p));
+  return id;
+};
 // The same for a Montgomery curve b y^2 = x^3 + a x^2 + x that is not curve25519 (`new
 // elliptic.curve.mont({p, a, b})`, lib/elliptic/curve/mont.js:11-21).  No b: no formula of the
 // reference's x-only model reads it.  Such an id takes customMontLadderBatch / customMontValidateBatch
@@ -343,6 +356,27 @@ Engine.prototype.customSignDetBatch = function customSignDetBatch(curve, hashes,
   return this.addon.customSignDet(this.ctx, this._id(curve), hashes, hashLen, msgBits | 0, priv, drbgHashId(drbgHash), !!canonical);
 };
 
+// ECDSA on a user-defined Edwards domain (an id from defineEdwardsDomain; ellgpu_custom_ed_verify /
+// _sign / _sign_det).  install() does not route to these.
+// customEdVerifyBatch: EC#verify per item; hashes Buffer(n x hashLen), hashLen 1..64, msgBits =
+// options.msgBitLength or 0; r, s Buffer(n x 32), pub Buffer(n x 64) affine x || y ->
+// { ok: Buffer(n) strictly 0 / 1, status: Buffer(n) }; status 2 where r and s are in range but the
+// key is off the curve (ok 0 there), else 0
+Engine.prototype.customEdVerifyBatch = function customEdVerifyBatch(curve, hashes, hashLen, msgBits, r, s, pub) {
+  this.stats.gpuCalls++; this.stats.gpuItems += r.length / 32;
+  return this.addon.customEdVerify(this.ctx, this._id(curve), hashes, hashLen, msgBits | 0, r, s, pub);
+};
+// customEdSignBatch / customEdSignDetBatch: the argument lists and results of customSignBatch /
+// customSignDetBatch.  A signature made with `canonical` generally does not verify on an Edwards
+// curve, in the reference either: -(x, y) = (-x, y)
+Engine.prototype.customEdSignBatch = function customEdSignBatch(curve, hashes, hashLen, msgBits, priv, nonces, canonical) {
+  this.stats.gpuCalls++; this.stats.gpuItems += priv.length / 32;
+  return this.addon.customEdSign(this.ctx, this._id(curve), hashes, hashLen, msgBits | 0, priv, nonces, !!canonical);
+};
+Engine.prototype.customEdSignDetBatch = function customEdSignDetBatch(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
+  this.stats.gpuCalls++; this.stats.gpuItems += priv.length / 32;
+  return this.addon.customEdSignDet(this.ctx, this._id(curve), hashes, hashLen, msgBits | 0, priv, drbgHashId(drbgHash), !!canonical);
+};
 // KeyPair#derive per item (ec/key.js:102-107): priv Buffer(n x B), pub Buffer(n x 2B) ->
 // { x: Buffer(n x B), status: Buffer(n) }; status 0 shared secret, 1 'public point not validated',
 // 2 the product is the point at infinity (the reference's getX throws)
@@ -560,6 +594,15 @@ Engine.prototype.customSignBatchAsync = function(curve, hashes, hashLen, msgBits
 };
 Engine.prototype.customSignDetBatchAsync = function(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
   return this._async(12, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
+};
+Engine.prototype.customEdVerifyBatchAsync = function(curve, hashes, hashLen, msgBits, r, s, pub) {
+  return this._async(26, curve, hashLen, msgBits | 0, hashes, r, s, pub);
+};
+Engine.prototype.customEdSignBatchAsync = function(curve, hashes, hashLen, msgBits, priv, nonces, canonical) {
+  return this._async(27, curve, hashLen, msgBits | 0, hashes, priv, nonces, null, canonical ? 1 : 0, 0);
+};
+Engine.prototype.customEdSignDetBatchAsync = function(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
+  return this._async(28, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
 };
 Engine.prototype.customDeriveBatchAsync = function(curve, privs, pubs) {
   return this._async(13, curve, 0, 0, privs, pubs, null, null, 0, 0);

@@ -542,6 +542,62 @@ int ellgpu_custom_ed_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const u
 int ellgpu_custom_ed_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                                        uint8_t* out_enc, void* stream);
 
+/* ECDSA on a user-defined Edwards domain: the `EC` class over
+ * `new elliptic.curves.PresetCurve({type: 'edwards', prime: null, p, a, c: '1', d, n, hash, g})` with
+ * parameters that are not ed25519's (the reference's own suite runs EC over its Edwards preset,
+ * test/ecdsa-test.js:130; nothing restricts that to the preset).
+ * ellgpu_curve_define_edwards_domain mirrors ellgpu_curve_define_short_domain: all arguments 32
+ *   bytes big-endian, the same id space (at most 16 ids per context), the same seven values twice
+ *   give the same id, and a domain id is never the id of the plain Edwards curve over the same
+ *   (p, a, d).  In a group: all members or none.  ELLGPU_E_ARG for n even or < 3, for G with a
+ *   coordinate >= p, for G off the curve a x^2 + y^2 = 1 + d x^2 y^2, and for G = (0, 1).  Neither
+ *   p nor n is tested for primality and n * G = O is not tested, as on a short domain.
+ *   A domain id is accepted by every call that accepts a plain Edwards id (ellgpu_mul_var,
+ *   ellgpu_mul_add2 with both points, ellgpu_point_add, every ellgpu_custom_ed_*) with identical
+ *   results; every other older entry point refuses it with the code it gives a plain Edwards id.
+ * The calls below answer ELLGPU_E_ARG on a preset or unknown id and ELLGPU_E_UNSUPPORTED on a short
+ * id, a Montgomery id and an Edwards id without a domain.  They are synchronous; a group runs them
+ * on its first member.  Exact where the addition law is complete (a a square, d not).
+ * ellgpu_custom_ed_verify: EC#verify (ec/index.js:188-229) per item, widths and truncation those of
+ *   ellgpu_ecdsa_verify on a short domain: r, s n x 32 bytes, pub_xy n x 64 bytes affine (reduced
+ *   mod p first, as toRed does), hash_len 1 .. 64, msg_bits = options.msgBitLength (0: 8 hash_len).
+ *   1 <= r, s < n, else 0; u1 = msg / s, u2 = r / s; P = u1 G + u2 Q in projective coordinates
+ *   (edwards.js:373-375); Point#isInfinity (:167-172: X = 0 and Y = Z) gives 0; then with
+ *   _maxwellTrick (floor(p / n) <= 100) Point#eqXToP (:415-431): X == (r + j n) Z for j = 0, 1, ...
+ *   while r + j n < p, r reduced mod p first -- else getX().umod(n) == r.
+ *   out_ok     a strict 0 / 1 mask
+ *   out_status (may be NULL) 2 for a key that fails the curve equation while r and s are in range
+ *              (verdict 0; the reference computes with such a key), else 0 -- the presets' convention
+ * ellgpu_custom_ed_sign / _sign_det: EC#sign (ec/index.js:110-186) with the argument lists and
+ *   semantics of ellgpu_custom_sign / ellgpu_custom_sign_det: one pass of the loop for supplied
+ *   nonces with _truncateToN(k, true) by the value's own byte length; ELLGPU_CUSTOM_SIGN_MAX_DRAWS
+ *   candidates of the HmacDRBG over drbg_hash; out_ok = 0 (r, s, recid zeroed) where the reference
+ *   goes on to its next nonce; _sign_det is ELLGPU_E_UNSUPPORTED where n.byteLength() < 24.  What
+ *   the curve adds: k * G on the Edwards law, kp.isInfinity() as above, r = getX() mod n as a
+ *   general reduction (x >= n is the common case where the cofactor is 4 or 8), recid = (getY() odd)
+ *   | (x != r ? 2 : 0).  There is no recovery on these domains: with a cofactor above 1 the bit
+ *   x != r cannot name the candidate (the reference throws). */
+int ellgpu_curve_define_edwards_domain(ellgpu_ctx* ctx, const uint8_t* p, const uint8_t* a, const uint8_t* d,
+                                       const uint8_t* n, const uint8_t* gx, const uint8_t* gy, int* out_curve);
+int ellgpu_custom_ed_verify(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                            const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_ok,
+                            uint8_t* out_status);
+int ellgpu_custom_ed_verify_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                                const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_ok,
+                                uint8_t* out_status, void* stream);
+int ellgpu_custom_ed_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                          const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                          uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok);
+int ellgpu_custom_ed_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                              const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
+                              uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream);
+int ellgpu_custom_ed_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                              const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r, uint8_t* out_s,
+                              uint8_t* out_recid, uint8_t* out_ok);
+int ellgpu_custom_ed_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
+                                  int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
+                                  uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream);
+
 /* ---- host-buffer entry points (what the N-API addon binds) -------------- */
 
 /* out[i] = k[i] * G */

@@ -62,7 +62,15 @@ keys) beside mul_var_dev on the same id and rows.  Device-resident buffers, HIP-
 alternate over three rounds and each figure is the median round.  Every status is asserted 0 and
 the two derives equal to mul_var's x; "kernels_ms" are the launches of one custom_ed_derive_wire call.
 
-    python tools/bench_custom_ecdsa.py --edwards [log2 n ...]                  (default: 18 20)"""
+    python tools/bench_custom_ecdsa.py --edwards [log2 n ...]                  (default: 18 20)
+
+--ed-ecdsa: ECDSA on the Edwards domain over Curve1174 (ellgpu_custom_ed_verify, _sign, _sign_det)
+beside mul_add2 (both points given) and mul_var on the plain curve over the same (p, a, d):
+verifies/s and signatures/s, and the kernel comparison the shared-table ladder answers to -- the
+median of five timed calls (Context.set_timing / get_timing, after two warm-up calls) of edc_ecdsa_ladder against
+edc_mul_add2, with the five values of each.
+
+    python tools/bench_custom_ecdsa.py --ed-ecdsa [log2 n ...]                 (default: 16)"""
 import json
 import os
 import sys
@@ -422,10 +430,77 @@ def run_edwards(ctx, name, n):
     return out
 
 
+def run_ed_ecdsa(ctx, n):
+    import numpy as np
+    import torch
+    import bench
+    import custom_ed_checks as CK
+    import custom_ed_ecdsa_checks as EC
+    spec = EC.spec_of("curve1174")
+    p, a, d, order, gx, gy = EC.params(spec)
+    dom = EC.define(ctx, spec)
+    plain = ctx.define_edwards(p, a, d)
+    rnd = lambda tag: bench.xof("custom-ed-ecdsa:%s" % tag, n * 32).reshape(n, 32).copy()
+    h, priv, k2 = rnd("h"), rnd("d"), rnd("k2")
+    priv[:, 0] &= 0x00                                   # below n: the key is the scalar mul_var takes
+    g = np.tile(CK.xy_rows([(gx, gy)]), (n, 1))
+    pub, inf = ctx.mul_var(plain, priv, g)
+    assert not inf.any()
+    r, s, rec, ok = ctx.custom_ed_sign_det(dom, h, priv)
+    assert ok.all()
+    dev = torch.device("cuda", 0)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    z = lambda *sh: torch.full(sh, 9, dtype=torch.uint8, device=dev)
+    dh, dd, dr, ds, dpub, dg, dk2 = t(h), t(priv), t(r), t(s), t(pub), t(g), t(k2)
+    vok, vst, sr, ss, sj, sok, mxy, minf = z(n), z(n), z(n, 32), z(n, 32), z(n), z(n), z(n, 64), z(n)
+    calls = (("custom_ed_verify", lambda: ctx.custom_ed_verify_dev(dom, dh, dr, ds, dpub, vok, vst)),
+             ("custom_ed_sign_det", lambda: ctx.custom_ed_sign_det_dev(dom, dh, dd, sr, ss, sj, sok)),
+             ("custom_ed_sign", lambda: ctx.custom_ed_sign_dev(dom, dh, dd, dk2, sr, ss, sj, sok)),
+             ("mul_add2", lambda: ctx.mul_add2_dev(plain, dd, dg, dk2, dpub, mxy, minf)),
+             ("mul_var", lambda: ctx.mul_var_dev(plain, dd, dpub, mxy, minf)))
+    out = {"lib": os.path.basename(os.environ.get("ELLGPU_LIB", "libellgpu.so")), "curve": "curve1174", "n": n}
+    for nm, fn in calls:
+        rounds = sorted(timed(fn) for _ in range(3))
+        out[nm + "_ms"] = round(rounds[1], 3)
+        out[nm + "_M_per_s"] = round(n / rounds[1] / 1e3, 3)
+    assert vok.all().item() and not vst.any().item()
+    # the kernels: five timed calls each
+    ker = {}
+    for nm, fn, kern in (("verify", calls[0][1], "edc_ecdsa_ladder"), ("mul_add2", calls[3][1], "edc_mul_add2")):
+        vals = []
+        for _ in range(2):                               # warm-up: the first calls of a kernel run long
+            fn()
+        torch.cuda.synchronize()
+        for _ in range(5):
+            ctx.set_timing(True)                         # (clears what the last call recorded)
+            fn()
+            torch.cuda.synchronize()
+            tm = ctx.get_timing()
+            vals.append(round(tm[kern][1] / max(1, tm[kern][0]), 4))
+            ker[nm + "_kernels_ms"] = {x: round(ms, 4) for x, (cnt, ms) in tm.items()}
+        out[kern + "_ms_five"] = vals
+        out[kern + "_ms_median"] = sorted(vals)[2]
+    ctx.set_timing(False)
+    out.update(ker)
+    spread = max(out["edc_mul_add2_ms_five"]) - min(out["edc_mul_add2_ms_five"])
+    out["ladder_minus_mul_add2_ms"] = round(out["edc_ecdsa_ladder_ms_median"] - out["edc_mul_add2_ms_median"], 4)
+    out["mul_add2_spread_ms"] = round(spread, 4)
+    return out
+
+
 def main():
     import torch
     import elliptic_amd
     import custom_domain_checks as CD
+    if sys.argv[1:2] == ["--ed-ecdsa"]:
+        torch.zeros(1, device="cuda:0")
+        ctx = elliptic_amd.Context(0)
+        try:
+            for lg in [int(a) for a in sys.argv[2:]] or [16]:
+                print(json.dumps(run_ed_ecdsa(ctx, 1 << lg)), flush=True)
+        finally:
+            ctx.close()
+        return
     if sys.argv[1:2] == ["--wire"]:
         torch.zeros(1, device="cuda:0")
         ctx = elliptic_amd.Context(0)
