@@ -398,7 +398,9 @@ static void ell_backend_destroy(ell::HipBackend* bk) {
 
 extern "C" int ellgpu_probe_valu(ellgpu_ctx* ctx, int kind, int blocks, int iters, double* ms_out,
                                  double* ops_out) {
-  ELL_ENTER(ctx, nullptr);
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  ELL_LOCK(ctx);
+  ell_enter(*ctx->eng, nullptr, Mem::host);
   if (blocks <= 0 || iters <= 0 || !ms_out || !ops_out) return set_err(ELLGPU_E_ARG, "bad probe arguments");
   ell::HipBackend& bk = ctx->eng->bk;
   ell::u32* out = (ell::u32*)bk.alloc((size_t)blocks * 256 * 4);
@@ -520,7 +522,9 @@ extern "C" int ellgpu_ctx_get_timing(ellgpu_ctx* ctx, char* buf, size_t cap) {
 extern "C" int ellgpu_debug_field_op(ellgpu_ctx* ctx, int field, int op, size_t n, const uint32_t* a,
                                      const uint32_t* b, uint32_t* r) {
   using namespace ell;
-  ELL_ENTER(ctx, nullptr);
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  ELL_LOCK(ctx);
+  ell_enter(*ctx->eng, nullptr, Mem::host);
   int L = 0;
   bool coop = false;
   const RtField* rt = nullptr;

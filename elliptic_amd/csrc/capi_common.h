@@ -274,18 +274,33 @@ int ellgpu_curve_define_edwards_domain(ellgpu_ctx* ctx, const uint8_t* p, const 
   return define_custom(ctx, 1, p, a, d, out_curve, dom);
 }
 
-#define ELL_ENTER(ctx, stream)                                      \
-  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");           \
-  ELL_LOCK(ctx);                                                    \
-  ctx->eng->err.clear();                                            \
-  ctx->eng->bk.use_stream(stream);                                  \
-  ctx->eng->set_lane(0);
-// *_dev entry points: the call works in the scratch arena of its stream (HipBackend::use_stream_dev)
-#define ELL_ENTER_DEV(ctx, stream)                                  \
-  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");           \
-  ELL_LOCK(ctx);                                                    \
-  ctx->eng->err.clear();                                            \
-  ctx->eng->set_lane(ctx->eng->bk.use_stream_dev(stream));
+}  // extern "C"
+
+// Every batch entry point is ell_call() around one Engine operation: ellgpu_X passes Mem::host (the
+// operands are host buffers; the call returns with its results back), ellgpu_X_dev Mem::device and
+// the caller's stream (device pointers; the call returns as soon as its work is enqueued, and works
+// in the scratch arena of its stream, HipBackend::use_stream_dev).  `op` gets the engine and `where`.
+typedef ell::Engine<ELL_BACKEND> Eng;
+using ell::Mem;
+// (the start of a call, under the context's lock: the white-box probes of capi.hip use it alone)
+static void ell_enter(Eng& e, void* stream, Mem where) {
+  e.err.clear();
+  if (where == Mem::host) {
+    e.bk.use_stream(stream);
+    e.set_lane(0);
+  } else {
+    e.set_lane(e.bk.use_stream_dev(stream));
+  }
+}
+template <class Op>
+static int ell_call(ellgpu_ctx* ctx, void* stream, Mem where, Op op) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  ELL_LOCK(ctx);
+  ell_enter(*ctx->eng, stream, where);
+  return finish(ctx, op(*ctx->eng, where), where == Mem::device);
+}
+
+extern "C" {
 
 // byte widths of a curve's field elements and scalars (for slicing the flat buffers of a group call)
 static int curve_widths(int curve, size_t& B, size_t& NB) {
@@ -307,8 +322,11 @@ int ellgpu_mul_fixed(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, uin
       return ellgpu_mul_fixed(m, curve, hi - lo, k + lo * B, out_xy + lo * 2 * B, out_inf ? out_inf + lo : nullptr);
     });
   }
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->mul_fixed_host(curve, n, k, out_xy, out_inf));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.mul_fixed(w, curve, n, k, out_xy, out_inf); });
+}
+int ellgpu_mul_fixed_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, uint8_t* out_xy,
+                         uint8_t* out_inf, void* stream) {
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.mul_fixed(w, curve, n, k, out_xy, out_inf); });
 }
 int ellgpu_mul_var(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_xy,
                    uint8_t* out_xy, uint8_t* out_inf) {
@@ -322,8 +340,11 @@ int ellgpu_mul_var(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const
                             out_inf ? out_inf + lo : nullptr);
     });
   }
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->mul_var_host(curve, n, k, in_xy, out_xy, out_inf));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.mul_var(w, curve, n, k, in_xy, out_xy, out_inf); });
+}
+int ellgpu_mul_var_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k,
+                       const uint8_t* in_xy, uint8_t* out_xy, uint8_t* out_inf, void* stream) {
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.mul_var(w, curve, n, k, in_xy, out_xy, out_inf); });
 }
 int ellgpu_mul_add2(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k1, const uint8_t* p1_xy,
                     const uint8_t* k2, const uint8_t* p2_xy, uint8_t* out_xy, uint8_t* out_inf) {
@@ -337,8 +358,12 @@ int ellgpu_mul_add2(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k1, con
                              p2_xy + lo * 2 * B, out_xy + lo * 2 * B, out_inf ? out_inf + lo : nullptr);
     });
   }
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->mul_add2_host(curve, n, k1, p1_xy, k2, p2_xy, out_xy, out_inf));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.mul_add2(w, curve, n, k1, p1_xy, k2, p2_xy, out_xy, out_inf); });
+}
+int ellgpu_mul_add2_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k1,
+                        const uint8_t* p1_xy, const uint8_t* k2, const uint8_t* p2_xy,
+                        uint8_t* out_xy, uint8_t* out_inf, void* stream) {
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.mul_add2(w, curve, n, k1, p1_xy, k2, p2_xy, out_xy, out_inf); });
 }
 int ellgpu_ecdsa_verify(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                         int msg_bits, const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy,
@@ -354,172 +379,160 @@ int ellgpu_ecdsa_verify(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* has
                                  out_status ? out_status + lo : nullptr);
     });
   }
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->ecdsa_verify_host(curve, n, hash, hash_len, msg_bits, r, s, pub_xy,
-                                                 out_ok, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.ecdsa_verify(w, curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status); });
+}
+int ellgpu_ecdsa_verify_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash,
+                            int hash_len, int msg_bits, const uint8_t* r, const uint8_t* s,
+                            const uint8_t* pub_xy, uint8_t* out_ok, uint8_t* out_status,
+                            void* stream) {
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.ecdsa_verify(w, curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status); });
 }
 int ellgpu_x25519_ladder(ellgpu_ctx* ctx, size_t n, const uint8_t* k, const uint8_t* in_x,
                          uint8_t* out_x, uint8_t* out_inf) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->x25519_host(n, k, in_x, out_x, out_inf));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.x25519(w, n, k, in_x, out_x, out_inf); });
+}
+int ellgpu_x25519_ladder_dev(ellgpu_ctx* ctx, size_t n, const uint8_t* k, const uint8_t* in_x,
+                             uint8_t* out_x, uint8_t* out_inf, void* stream) {
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.x25519(w, n, k, in_x, out_x, out_inf); });
 }
 
 int ellgpu_x25519_derive(ellgpu_ctx* ctx, size_t n, const uint8_t* k, const uint8_t* in_x,
                          uint8_t* out_x, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  if (n && !out_status) return set_err(ELLGPU_E_ARG, "null buffer");
-  // (never deferred: the status bytes are put together on the host)
-  ctx->eng->defer_collect();
-  std::vector<uint8_t> inf(n ? n : 1);
-  const int rc = ctx->eng->x25519_host(n, k, in_x, out_x, inf.data(), out_status);
-  if (!rc)
-    for (size_t i = 0; i < n; i++) out_status[i] = out_status[i] ? 1 : (inf[i] ? 2 : 0);
-  return finish(ctx, rc);
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    if (n && !out_status) return e.fail(ELLGPU_E_ARG, "null buffer");
+    // (never deferred: the status bytes are put together on the host)
+    e.defer_collect();
+    std::vector<uint8_t> inf(n ? n : 1);
+    const int rc = e.x25519(w, n, k, in_x, out_x, inf.data(), out_status);
+    if (!rc)
+      for (size_t i = 0; i < n; i++) out_status[i] = out_status[i] ? 1 : (inf[i] ? 2 : 0);
+    return rc;
+  });
 }
 
 int ellgpu_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
                       uint8_t* out_xy, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->decompress_host(curve, n, v, odd, out_xy, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.decompress(w, curve, n, v, odd, out_xy, out_ok); });
 }
 int ellgpu_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
                           uint8_t* out_xy, uint8_t* out_ok, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->decompress_dev(curve, n, v, odd, out_xy, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.decompress(w, curve, n, v, odd, out_xy, out_ok); });
 }
 
 // point codecs and key validation (decodePoint / encode / KeyPair#validate)
 int ellgpu_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
                          uint8_t* out_xy, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->decode_points_host(curve, n, enc, enc_len, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.decode_points(w, curve, n, enc, enc_len, out_xy, out_status); });
 }
 int ellgpu_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
                              uint8_t* out_xy, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->decode_points_dev(curve, n, enc, enc_len, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.decode_points(w, curve, n, enc, enc_len, out_xy, out_status); });
 }
 int ellgpu_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                          uint8_t* out_enc) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->encode_points_host(curve, n, xy, compact, out_enc));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.encode_points(w, curve, n, xy, compact, out_enc); });
 }
 int ellgpu_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                              uint8_t* out_enc, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->encode_points_dev(curve, n, xy, compact, out_enc), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.encode_points(w, curve, n, xy, compact, out_enc); });
 }
 int ellgpu_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
                     int check_order, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->validate_host(curve, n, xy, inf, check_order, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.validate(w, curve, n, xy, inf, check_order, out_status); });
 }
 int ellgpu_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
                         int check_order, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->validate_dev(curve, n, xy, inf, check_order, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.validate(w, curve, n, xy, inf, check_order, out_status); });
 }
 
 // Point#add on affine points
 int ellgpu_point_add(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy1, const uint8_t* inf1,
                      const uint8_t* xy2, const uint8_t* inf2, uint8_t* out_xy, uint8_t* out_inf) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->point_add_host(curve, n, xy1, inf1, xy2, inf2, out_xy, out_inf));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.point_add(w, curve, n, xy1, inf1, xy2, inf2, out_xy, out_inf); });
 }
 int ellgpu_point_add_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy1, const uint8_t* inf1,
                          const uint8_t* xy2, const uint8_t* inf2, uint8_t* out_xy, uint8_t* out_inf,
                          void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->point_add_dev(curve, n, xy1, inf1, xy2, inf2, out_xy, out_inf), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.point_add(w, curve, n, xy1, inf1, xy2, inf2, out_xy, out_inf); });
 }
 
 // signature DER codec and EC#verify on wire formats
 int ellgpu_sig_from_der(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* der, size_t stride,
                         const uint32_t* der_len, uint8_t* out_r, uint8_t* out_s, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->sig_from_der_host(curve, n, der, stride, der_len, out_r, out_s, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.sig_from_der(w, curve, n, der, stride, der_len, out_r, out_s, out_status); });
 }
 int ellgpu_sig_from_der_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* der, size_t stride,
                             const uint32_t* der_len, uint8_t* out_r, uint8_t* out_s, uint8_t* out_status,
                             void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->sig_from_der_dev(curve, n, der, stride, der_len, out_r, out_s, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.sig_from_der(w, curve, n, der, stride, der_len, out_r, out_s, out_status); });
 }
 int ellgpu_sig_to_der(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* r, const uint8_t* s,
                       uint8_t* out_der, size_t stride, uint32_t* out_len) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->sig_to_der_host(curve, n, r, s, out_der, stride, out_len));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.sig_to_der(w, curve, n, r, s, out_der, stride, out_len); });
 }
 int ellgpu_sig_to_der_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* r, const uint8_t* s,
                           uint8_t* out_der, size_t stride, uint32_t* out_len, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->sig_to_der_dev(curve, n, r, s, out_der, stride, out_len), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.sig_to_der(w, curve, n, r, s, out_der, stride, out_len); });
 }
 int ellgpu_ecdsa_verify_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                              int msg_bits, const uint8_t* der, size_t der_stride, const uint32_t* der_len,
                              const uint8_t* pub_enc, size_t pub_len, uint8_t* out_ok, uint8_t* out_err) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->ecdsa_verify_wire_host(curve, n, hash, hash_len, msg_bits, der, der_stride,
-                                                      der_len, pub_enc, pub_len, out_ok, out_err));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.ecdsa_verify_wire(w, curve, n, hash, hash_len, msg_bits, der, der_stride, der_len, pub_enc, pub_len, out_ok, out_err);
+  });
 }
 int ellgpu_ecdsa_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                                  int msg_bits, const uint8_t* der, size_t der_stride,
                                  const uint32_t* der_len, const uint8_t* pub_enc, size_t pub_len,
                                  uint8_t* out_ok, uint8_t* out_err, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->ecdsa_verify_wire_dev(curve, n, hash, hash_len, msg_bits, der, der_stride,
-                                                     der_len, pub_enc, pub_len, out_ok, out_err), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.ecdsa_verify_wire(w, curve, n, hash, hash_len, msg_bits, der, der_stride, der_len, pub_enc, pub_len, out_ok, out_err);
+  });
 }
 
 // wire formats on user-defined short curves (a group: member 0, like the presets' wire verify)
 int ellgpu_custom_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* x, const uint8_t* odd,
                              uint8_t* out_xy, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_decompress_host(curve, n, x, odd, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_decompress(w, curve, n, x, odd, out_xy, out_status); });
 }
 int ellgpu_custom_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* x, const uint8_t* odd,
                                  uint8_t* out_xy, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_decompress_dev(curve, n, x, odd, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_decompress(w, curve, n, x, odd, out_xy, out_status); });
 }
 int ellgpu_custom_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
                                 uint8_t* out_xy, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_decode_points_host(curve, n, enc, enc_len, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_decode_points(w, curve, n, enc, enc_len, out_xy, out_status); });
 }
 int ellgpu_custom_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
                                     uint8_t* out_xy, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_decode_points_dev(curve, n, enc, enc_len, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_decode_points(w, curve, n, enc, enc_len, out_xy, out_status); });
 }
 int ellgpu_custom_verify_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                               int msg_bits, const uint8_t* der, size_t der_stride, const uint32_t* der_len,
                               const uint8_t* pub_enc, size_t pub_len, uint8_t* out_ok, uint8_t* out_err) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_verify_wire_host(curve, n, hash, hash_len, msg_bits, der, der_stride,
-                                                       der_len, pub_enc, pub_len, out_ok, out_err));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.custom_verify_wire(w, curve, n, hash, hash_len, msg_bits, der, der_stride, der_len, pub_enc, pub_len, out_ok, out_err);
+  });
 }
 int ellgpu_custom_verify_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                                   int msg_bits, const uint8_t* der, size_t der_stride,
                                   const uint32_t* der_len, const uint8_t* pub_enc, size_t pub_len,
                                   uint8_t* out_ok, uint8_t* out_err, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_verify_wire_dev(curve, n, hash, hash_len, msg_bits, der, der_stride,
-                                                      der_len, pub_enc, pub_len, out_ok, out_err), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.custom_verify_wire(w, curve, n, hash, hash_len, msg_bits, der, der_stride, der_len, pub_enc, pub_len, out_ok, out_err);
+  });
 }
 
 // EC#recoverPubKey on a user-defined ECDSA domain (a group: member 0)
 int ellgpu_custom_recover(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                           const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
                           uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_recover_host(curve, n, hash, hash_len, r, s, recid, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_recover(w, curve, n, hash, hash_len, r, s, recid, out_xy, out_status); });
 }
 int ellgpu_custom_recover_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                               const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
                               uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_recover_dev(curve, n, hash, hash_len, r, s, recid, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_recover(w, curve, n, hash, hash_len, r, s, recid, out_xy, out_status); });
 }
 
 // EC#sign on a user-defined ECDSA domain (a group: member 0): supplied nonces, or HmacDRBG over drbg_hash
@@ -527,316 +540,242 @@ static_assert(ELLGPU_CUSTOM_SIGN_MAX_DRAWS == ell::CUSTOM_SIGN_MAX_DRAWS, "the h
 int ellgpu_custom_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                        const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                        uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_sign_host(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
-                                                out_r, out_s, out_recid, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.custom_sign(w, curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_custom_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                            const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                            uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
-                                               out_r, out_s, out_recid, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.custom_sign(w, curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_custom_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                            const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r, uint8_t* out_s,
                            uint8_t* out_recid, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_sign_host(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
-                                                canonical, out_r, out_s, out_recid, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.custom_sign(w, curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_custom_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                                int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
                                uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
-                                               canonical, out_r, out_s, out_recid, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.custom_sign(w, curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 
 // KeyPair#derive, KeyPair#validate and BasePoint#encode on a user-defined short curve (a group: member 0)
 int ellgpu_custom_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
                          uint8_t* out_x, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_derive_host(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_derive(w, curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr); });
 }
 int ellgpu_custom_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
                              uint8_t* out_x, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_derive_dev(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_derive(w, curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr); });
 }
 int ellgpu_custom_derive_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
                               size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_derive_host(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_derive(w, curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err); });
 }
 int ellgpu_custom_derive_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
                                   size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err,
                                   void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_derive_dev(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err),
-                true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_derive(w, curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err); });
 }
 int ellgpu_custom_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
                            int check_order, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_validate_host(curve, n, xy, inf, check_order, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_validate(w, curve, n, xy, inf, check_order, out_status); });
 }
 int ellgpu_custom_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* inf,
                                int check_order, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_validate_dev(curve, n, xy, inf, check_order, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_validate(w, curve, n, xy, inf, check_order, out_status); });
 }
 int ellgpu_custom_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                                 uint8_t* out_enc) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_encode_points_host(curve, n, xy, compact, out_enc));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_encode_points(w, curve, n, xy, compact, out_enc); });
 }
 int ellgpu_custom_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                                     uint8_t* out_enc, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_encode_points_dev(curve, n, xy, compact, out_enc), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_encode_points(w, curve, n, xy, compact, out_enc); });
 }
 
 // pointFromX / pointFromY, decodePoint, KeyPair#validate, KeyPair#derive and BasePoint#encode on a
 // user-defined Edwards curve (a group: member 0)
 int ellgpu_custom_ed_decompress(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
                                 int from_y, uint8_t* out_xy, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_decompress_host(curve, n, v, odd, from_y, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_decompress(w, curve, n, v, odd, from_y, out_xy, out_status); });
 }
 int ellgpu_custom_ed_decompress_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* v, const uint8_t* odd,
                                     int from_y, uint8_t* out_xy, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_decompress_dev(curve, n, v, odd, from_y, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_decompress(w, curve, n, v, odd, from_y, out_xy, out_status); });
 }
 int ellgpu_custom_ed_decode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
                                    uint8_t* out_xy, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_decode_points_host(curve, n, enc, enc_len, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_decode_points(w, curve, n, enc, enc_len, out_xy, out_status); });
 }
 int ellgpu_custom_ed_decode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* enc, size_t enc_len,
                                        uint8_t* out_xy, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_decode_points_dev(curve, n, enc, enc_len, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_decode_points(w, curve, n, enc, enc_len, out_xy, out_status); });
 }
 int ellgpu_custom_ed_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* order_host,
                               uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_validate_host(curve, n, xy, order_host, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_validate(w, curve, n, xy, order_host, out_status); });
 }
 int ellgpu_custom_ed_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, const uint8_t* order_host,
                                   uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_validate_dev(curve, n, xy, order_host, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_validate(w, curve, n, xy, order_host, out_status); });
 }
 int ellgpu_custom_ed_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
                             uint8_t* out_x, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_derive_host(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_derive(w, curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr); });
 }
 int ellgpu_custom_ed_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_xy,
                                 uint8_t* out_x, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_derive_dev(curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_derive(w, curve, n, priv, pub_xy, false, 0, out_x, out_status, nullptr); });
 }
 int ellgpu_custom_ed_derive_wire(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
                                  size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_derive_host(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_derive(w, curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err); });
 }
 int ellgpu_custom_ed_derive_wire_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_enc,
                                      size_t pub_len, uint8_t* out_x, uint8_t* out_status, uint8_t* out_err,
                                      void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_derive_dev(curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err),
-                true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_derive(w, curve, n, priv, pub_enc, true, pub_len, out_x, out_status, out_err); });
 }
 int ellgpu_custom_ed_encode_points(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                                    uint8_t* out_enc) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_encode_points_host(curve, n, xy, compact, out_enc));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_encode_points(w, curve, n, xy, compact, out_enc); });
 }
 int ellgpu_custom_ed_encode_points_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* xy, int compact,
                                        uint8_t* out_enc, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_encode_points_dev(curve, n, xy, compact, out_enc), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_encode_points(w, curve, n, xy, compact, out_enc); });
 }
 
 // EC#verify and EC#sign on a user-defined Edwards domain (a group: member 0)
 int ellgpu_custom_ed_verify(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                             const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_ok,
                             uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_verify_host(curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_ed_verify(w, curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status); });
 }
 int ellgpu_custom_ed_verify_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                                 const uint8_t* r, const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_ok,
                                 uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_verify_dev(curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status),
-                true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_ed_verify(w, curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status); });
 }
 int ellgpu_custom_ed_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                           const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                           uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_sign_host(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
-                                                   out_r, out_s, out_recid, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.custom_ed_sign(w, curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_custom_ed_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                               const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                               uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical,
-                                                  out_r, out_s, out_recid, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.custom_ed_sign(w, curve, n, hash, hash_len, msg_bits, priv, nonces, false, 0, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_custom_ed_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                               const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r, uint8_t* out_s,
                               uint8_t* out_recid, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_ed_sign_host(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
-                                                   canonical, out_r, out_s, out_recid, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.custom_ed_sign(w, curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_custom_ed_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                                   int msg_bits, const uint8_t* priv, int drbg_hash, int canonical, uint8_t* out_r,
                                   uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_ed_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash,
-                                                  canonical, out_r, out_s, out_recid, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.custom_ed_sign(w, curve, n, hash, hash_len, msg_bits, priv, nullptr, true, drbg_hash, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 
 // Point#mul + getX, MontCurve#validate and KeyPair#derive on a user-defined Montgomery curve (a group: member 0)
 int ellgpu_custom_mont_ladder(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
                               uint8_t* out_x, uint8_t* out_inf) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_mont_host(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_LADDER, n, k, in_x, out_x, out_inf));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_mont(w, curve, Eng::OP_MONTC_LADDER, n, k, in_x, out_x, out_inf); });
 }
 int ellgpu_custom_mont_ladder_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_x,
                                   uint8_t* out_x, uint8_t* out_inf, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_mont_dev(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_LADDER, n, k, in_x, out_x, out_inf), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_mont(w, curve, Eng::OP_MONTC_LADDER, n, k, in_x, out_x, out_inf); });
 }
 int ellgpu_custom_mont_validate(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* in_x, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_mont_host(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_VALIDATE, n, nullptr, in_x, nullptr, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_mont(w, curve, Eng::OP_MONTC_VALIDATE, n, nullptr, in_x, nullptr, out_status); });
 }
 int ellgpu_custom_mont_validate_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* in_x, uint8_t* out_status,
                                     void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_mont_dev(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_VALIDATE, n, nullptr, in_x, nullptr, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_mont(w, curve, Eng::OP_MONTC_VALIDATE, n, nullptr, in_x, nullptr, out_status); });
 }
 int ellgpu_custom_mont_derive(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
                               uint8_t* out_x, uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->custom_mont_host(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_DERIVE, n, priv, pub_x, out_x, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.custom_mont(w, curve, Eng::OP_MONTC_DERIVE, n, priv, pub_x, out_x, out_status); });
 }
 int ellgpu_custom_mont_derive_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* priv, const uint8_t* pub_x,
                                   uint8_t* out_x, uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->custom_mont_dev(curve, ell::Engine<ELL_BACKEND>::OP_MONTC_DERIVE, n, priv, pub_x, out_x, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.custom_mont(w, curve, Eng::OP_MONTC_DERIVE, n, priv, pub_x, out_x, out_status); });
 }
 
+// ECDSA sign and recover on the presets, EdDSA
 int ellgpu_ecdsa_sign(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
                       const uint8_t* priv, const uint8_t* nonces, int canonical, uint8_t* out_r,
                       uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->ecdsa_sign_host(curve, n, hash, hash_len, msg_bits, priv, nonces, canonical,
-                                               out_r, out_s, out_recid, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.ecdsa_sign(w, curve, n, hash, hash_len, msg_bits, priv, nonces, false, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_ecdsa_sign_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                           int msg_bits, const uint8_t* priv, const uint8_t* nonces, int canonical,
                           uint8_t* out_r, uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok,
                           void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->ecdsa_sign_dev(curve, n, hash, hash_len, msg_bits, priv, nonces, canonical,
-                                              out_r, out_s, out_recid, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.ecdsa_sign(w, curve, n, hash, hash_len, msg_bits, priv, nonces, false, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
-
-int ellgpu_eddsa_verify(ellgpu_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
-                        size_t msg_len, const uint8_t* sigs, const uint8_t* pubs, uint8_t* out_ok,
-                        uint8_t* out_err) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->eddsa_verify_host(n, msgs, (const ell::u64*)msg_off, msg_len, sigs, pubs,
-                                                 out_ok, out_err));
-}
-int ellgpu_eddsa_verify_dev(ellgpu_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
-                            size_t msg_len, const uint8_t* sigs, const uint8_t* pubs,
-                            uint8_t* out_ok, uint8_t* out_err, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->eddsa_verify_dev(n, msgs, (const ell::u64*)msg_off, msg_len, sigs, pubs,
-                                                out_ok, out_err), true);
-}
-
 int ellgpu_ecdsa_sign_det(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                           int msg_bits, const uint8_t* priv, int canonical, uint8_t* out_r, uint8_t* out_s,
                           uint8_t* out_recid, uint8_t* out_ok) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->ecdsa_sign_det_host(curve, n, hash, hash_len, msg_bits, priv, canonical, out_r,
-                                                   out_s, out_recid, out_ok));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) {
+    return e.ecdsa_sign(w, curve, n, hash, hash_len, msg_bits, priv, nullptr, true, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
 int ellgpu_ecdsa_sign_det_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                               int msg_bits, const uint8_t* priv, int canonical, uint8_t* out_r,
                               uint8_t* out_s, uint8_t* out_recid, uint8_t* out_ok, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->ecdsa_sign_det_dev(curve, n, hash, hash_len, msg_bits, priv, canonical, out_r,
-                                                  out_s, out_recid, out_ok), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) {
+    return e.ecdsa_sign(w, curve, n, hash, hash_len, msg_bits, priv, nullptr, true, canonical, out_r, out_s, out_recid, out_ok);
+  });
 }
-
 int ellgpu_ecdsa_recover(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                          const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
                          uint8_t* out_status) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->ecdsa_recover_host(curve, n, hash, hash_len, r, s, recid, out_xy, out_status));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.ecdsa_recover(w, curve, n, hash, hash_len, r, s, recid, out_xy, out_status); });
 }
 int ellgpu_ecdsa_recover_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len,
                              const uint8_t* r, const uint8_t* s, const uint8_t* recid, uint8_t* out_xy,
                              uint8_t* out_status, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->ecdsa_recover_dev(curve, n, hash, hash_len, r, s, recid, out_xy, out_status), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.ecdsa_recover(w, curve, n, hash, hash_len, r, s, recid, out_xy, out_status); });
 }
-
+int ellgpu_eddsa_verify(ellgpu_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
+                        size_t msg_len, const uint8_t* sigs, const uint8_t* pubs, uint8_t* out_ok,
+                        uint8_t* out_err) {
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.eddsa_verify(w, n, msgs, (const ell::u64*)msg_off, msg_len, sigs, pubs, out_ok, out_err); });
+}
+int ellgpu_eddsa_verify_dev(ellgpu_ctx* ctx, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
+                            size_t msg_len, const uint8_t* sigs, const uint8_t* pubs,
+                            uint8_t* out_ok, uint8_t* out_err, void* stream) {
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.eddsa_verify(w, n, msgs, (const ell::u64*)msg_off, msg_len, sigs, pubs, out_ok, out_err); });
+}
 int ellgpu_eddsa_sign(ellgpu_ctx* ctx, size_t n, const uint8_t* secrets, const uint8_t* msgs,
                       const uint64_t* msg_off, size_t msg_len, uint8_t* out_sig, uint8_t* out_pub) {
-  ELL_ENTER(ctx, nullptr);
-  return finish(ctx, ctx->eng->eddsa_sign_host(n, secrets, msgs, (const ell::u64*)msg_off, msg_len, out_sig,
-                                               out_pub));
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem w) { return e.eddsa_sign(w, n, secrets, msgs, (const ell::u64*)msg_off, msg_len, out_sig, out_pub); });
 }
 int ellgpu_eddsa_sign_dev(ellgpu_ctx* ctx, size_t n, const uint8_t* secrets, const uint8_t* msgs,
                           const uint64_t* msg_off, size_t msg_len, uint8_t* out_sig, uint8_t* out_pub,
                           void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->eddsa_sign_dev(n, secrets, msgs, (const ell::u64*)msg_off, msg_len, out_sig,
-                                              out_pub), true);
-}
-
-int ellgpu_mul_fixed_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, uint8_t* out_xy,
-                         uint8_t* out_inf, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->mul_fixed_dev(curve, n, k, out_xy, out_inf), true);
-}
-int ellgpu_mul_var_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k,
-                       const uint8_t* in_xy, uint8_t* out_xy, uint8_t* out_inf, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->mul_var_dev(curve, n, k, in_xy, out_xy, out_inf), true);
-}
-int ellgpu_mul_add2_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k1,
-                        const uint8_t* p1_xy, const uint8_t* k2, const uint8_t* p2_xy,
-                        uint8_t* out_xy, uint8_t* out_inf, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->mul_add2_dev(curve, n, k1, p1_xy, k2, p2_xy, out_xy, out_inf), true);
-}
-int ellgpu_ecdsa_verify_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash,
-                            int hash_len, int msg_bits, const uint8_t* r, const uint8_t* s,
-                            const uint8_t* pub_xy, uint8_t* out_ok, uint8_t* out_status,
-                            void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->ecdsa_verify_dev(curve, n, hash, hash_len, msg_bits, r, s, pub_xy,
-                                                out_ok, out_status), true);
-}
-int ellgpu_x25519_ladder_dev(ellgpu_ctx* ctx, size_t n, const uint8_t* k, const uint8_t* in_x,
-                             uint8_t* out_x, uint8_t* out_inf, void* stream) {
-  ELL_ENTER_DEV(ctx, stream);
-  return finish(ctx, ctx->eng->x25519_dev(n, k, in_x, out_x, out_inf), true);
+  return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.eddsa_sign(w, n, secrets, msgs, (const ell::u64*)msg_off, msg_len, out_sig, out_pub); });
 }
 
 }  // extern "C"

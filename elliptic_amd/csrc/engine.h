@@ -1274,6 +1274,9 @@ inline const CurveInfo* curve_info(int id) {
   return &tab[id];
 }
 
+// where the operands of a batch call live: device pointers, or host buffers that the engine stages
+enum class Mem { device, host };
+
 inline bool is_custom(int curve) { return curve >= CURVE_CUSTOM0 && curve < CURVE_CUSTOM0 + CURVE_CUSTOM_MAX; }
 // The custom-curve kernels read their modulus from ONE parameter block per device (fp_rt.h):
 // calls on user-defined curves are serialised per device, from the upload of the block to the
@@ -1762,7 +1765,8 @@ class Engine {
   // Brackets one call on a user-defined curve: takes the device's custom-curve lock, uploads the
   // curve's parameter block (synchronously: every earlier user of the block has finished, see the
   // destructor) and, at the end, waits for the call's device work before the lock is released.
-  // Nested uses (the host-buffer wrappers call the *_dev forms chunk by chunk) are no-ops.
+  // Nested uses (a composed operation -- ecdsa_verify_wire, custom_verify_wire -- calls the
+  // operations it is made of on scratch, with Mem::device, from inside its own scope) are no-ops.
   struct CustomScope {
     Engine* e;
     bool owner = false;
@@ -1822,852 +1826,12 @@ class Engine {
     return E_OK;
   }
 
-  int mul_fixed_dev(int curve, size_t n, const u8* k, u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519)
-      return fail(E_UNSUPPORTED, "curve25519 has no affine fixed-base form; use x25519_ladder");
-    if (n && (!k || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const bool dom = custom_is_domain(curve);
-    CustomScope sc(this, dom ? curve : -1);
-    if (sc.rc) return sc.rc;
-    int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
-    if (rc) return rc;
-    const size_t B = ci->field_bytes;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
-      else if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, k + o * B, out_xy + o * 2 * B, out_inf + o);
-      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, k + o * B, out_xy + o * 2 * B, out_inf + o));
-      return rc;
-    });
-  }
-
-  static bool overlap(const u8* a, const u8* b, size_t bytes) {
-    return a && b && bytes && (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
-  }
-  int mul_var_dev(int curve, size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519)
-      return fail(E_UNSUPPORTED, "curve25519 is x-only; use x25519_ladder");
-    if (n && (!k || !xy || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    // the operands are read again AFTER the results are written (the curve test of
-    // Work::domain_mark / mul_join): a result written over its own operand would be tested in its place
-    if (overlap(xy, out_xy, n * 2 * B)) return fail(E_ARG, "in_xy and out_xy must not overlap");
-    int rc = E_OK;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      if (custom_is_edwards(curve))
-        rc = edc_chunk(0, m, k + o * B, xy + o * 2 * B, nullptr, nullptr, nullptr, nullptr, out_xy + o * 2 * B, out_inf + o);
-      else if (is_custom(curve))
-        rc = mul_var_chunk<CvCustom>(m, k + o * B, xy + o * 2 * B, out_xy + o * 2 * B, out_inf + o, nullptr);
-      else if (curve == CURVE_ED25519)
-        rc = ed_mul_var_chunk(m, k + o * B, xy + o * 2 * B, out_xy + o * 2 * B, out_inf + o, nullptr);
-      else
-        ELL_SHORT_DISPATCH(curve, rc = mul_var_chunk<CV>(m, k + o * B, xy + o * 2 * B,
-                                                         out_xy + o * 2 * B, out_inf + o, nullptr));
-      return rc;
-    });
-  }
-
-  int mul_add2_dev(int curve, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
-                   u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519)
-      return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");     // mont.js:155-157
-    if (n && (!k1 || !k2 || !xy2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    int rc = E_OK;
-    const bool dom = custom_is_domain(curve);
-    if (is_custom(curve) && !xy1 && !dom)
-      return fail(E_UNSUPPORTED, "user-defined curves without a generator have no fixed-base table: pass the generator as p1");
-    if (!xy1 && !dom) { rc = prepare_curve(curve); if (rc) return rc; }
-    const size_t B = ci->field_bytes;
-    if (overlap(xy2, out_xy, n * 2 * B) || (xy1 && overlap(xy1, out_xy, n * 2 * B)))   // see mul_var_dev
-      return fail(E_ARG, "p1_xy / p2_xy and out_xy must not overlap");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    if (!xy1 && dom) { rc = ensure_comb<CvCustomDomain>(); if (rc) return rc; }
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      const u8* p1 = xy1 ? xy1 + o * 2 * B : nullptr;
-      if (custom_is_edwards(curve))
-        rc = edc_chunk(1, m, k1 + o * B, p1, k2 + o * B, xy2 + o * 2 * B, nullptr, nullptr, out_xy + o * 2 * B,
-                       out_inf + o);
-      else if (is_custom(curve) && !p1)
-        rc = mul_add_g_chunk<CvCustomDomain>(m, k1 + o * B, k2 + o * B, xy2 + o * 2 * B, out_xy + o * 2 * B,
-                                             out_inf + o);
-      else if (is_custom(curve))
-        rc = mul_add2_chunk<CvCustom>(m, k1 + o * B, p1, k2 + o * B, xy2 + o * 2 * B, out_xy + o * 2 * B,
-                                      out_inf + o);
-      else if (curve == CURVE_ED25519)
-        rc = ed_mul_add2_chunk(m, k1 + o * B, p1, k2 + o * B, xy2 + o * 2 * B, out_xy + o * 2 * B,
-                               out_inf + o);
-      else
-        ELL_SHORT_DISPATCH(curve, rc = p1 ? mul_add2_chunk<CV>(m, k1 + o * B, p1, k2 + o * B,
-                                                               xy2 + o * 2 * B, out_xy + o * 2 * B,
-                                                               out_inf + o)
-                                              : mul_add_g_chunk<CV>(m, k1 + o * B, k2 + o * B,
-                                                                    xy2 + o * 2 * B,
-                                                                    out_xy + o * 2 * B, out_inf + o));
-      return rc;
-    });
-  }
-
-  // ok: the verdicts, strictly 0 / 1.  st (may be null): the domain status per item -- 2 where the
-  // key is not on the curve (verdict 0 there), else 0 (Work::store_verdict)
-  int ecdsa_verify_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
-                       const u8* r, const u8* s, const u8* pub, u8* ok, u8* st) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    const bool dom = custom_is_domain(curve);
-    if (curve >= CURVE_ED25519 && !dom)
-      return fail(E_UNSUPPORTED, is_custom(curve) ? "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"
-                                                  : "ECDSA verify is implemented for the short Weierstrass presets");
-    if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
-    int shift;                     // a domain's own n, in 8 words
-    int rc = dom ? truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift)
-                 : truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
-    if (rc) return rc;
-    CustomScope sc(this, dom ? curve : -1);
-    if (sc.rc) return sc.rc;
-    rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
-    if (rc) return rc;
-    const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      if (dom)
-        rc = ecdsa_chunk<CvCustomDomain>(m, hash + o * hash_len, hash_len, shift, r + o * NB, s + o * NB,
-                                         pub + o * 2 * B, ok + o, st ? st + o : nullptr);
-      else
-      ELL_SHORT_DISPATCH(curve, rc = ecdsa_chunk<CV>(m, hash + o * hash_len, hash_len, shift,
-                                                     r + o * NB, s + o * NB, pub + o * 2 * B,
-                                                     ok + o, st ? st + o : nullptr));
-      return rc;
-    });
-  }
-
-  // out_bad (may be null): out_bad[i] = 1 where x[i] is no abscissa of the curve (KeyPair#derive's validate)
-  int x25519_dev(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
-    if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return x25519_chunk(m, k + o * 32, x + o * 32, out_x + o * 32, out_inf + o, out_bad ? out_bad + o : nullptr);
-    });
-  }
-
-  // ECDSA sign with caller-supplied nonces (one pass of EC#sign's loop per item)
-  int ecdsa_sign_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                     const u8* nonces, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve >= CURVE_ED25519)
-      return fail(E_UNSUPPORTED, "ECDSA sign is implemented for the short Weierstrass presets");
-    if (n && (!hash || !priv || !nonces || !out_r || !out_s || !out_recid || !out_ok))
-      return fail(E_ARG, "null pointer");
-    int shift;
-    int rc = truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
-    if (rc) return rc;
-    rc = prepare_curve(curve);
-    if (rc) return rc;
-    const size_t NB = ci->order_bytes;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      ELL_SHORT_DISPATCH(curve, rc = sign_chunk<CV>(m, hash + o * hash_len, hash_len, shift, priv + o * NB,
-                                                    nonces + o * NB, canonical, out_r + o * NB,
-                                                    out_s + o * NB, out_recid + o, out_ok + o));
-      return rc;
-    });
-  }
-  int ecdsa_sign_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                      const u8* nonces, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!hash || !priv || !nonces || !out_r || !out_s || !out_recid || !out_ok))
-      return fail(E_ARG, "null pointer");
-    if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    const size_t NB = ci->order_bytes;
-    return staged(n, {In{hash, (size_t)hash_len}, In{priv, NB}, In{nonces, NB}},
-                  {Out{out_r, NB}, Out{out_s, NB}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
-      return ecdsa_sign_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], canonical, r[0], r[1], r[2], r[3]);
-    });
-  }
-
-  // EC#sign with the reference's own nonce source (HmacDRBG, deterministic): nonces == nullptr
-  // in the calls below means "derive them"
-  int ecdsa_sign_det_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                         int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve >= CURVE_ED25519)
-      return fail(E_UNSUPPORTED, "ECDSA sign is implemented for the short Weierstrass presets");
-    if (n && (!hash || !priv || !out_r || !out_s || !out_recid || !out_ok)) return fail(E_ARG, "null pointer");
-    int shift;
-    int rc = truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
-    if (rc) return rc;
-    rc = prepare_curve(curve);
-    if (rc) return rc;
-    const size_t NB = ci->order_bytes;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      ELL_SHORT_DISPATCH(curve, rc = sign_det_chunk<CV>(m, hash + o * hash_len, hash_len, shift, priv + o * NB,
-                                                        canonical, out_r + o * NB, out_s + o * NB,
-                                                        out_recid + o, out_ok + o));
-      return rc;
-    });
-  }
-  int ecdsa_sign_det_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                          int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!hash || !priv || !out_r || !out_s || !out_recid || !out_ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    const size_t NB = ci->order_bytes;
-    return staged(n, {In{hash, (size_t)hash_len}, In{priv, NB}},
-                  {Out{out_r, NB}, Out{out_s, NB}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
-      return ecdsa_sign_det_dev(curve, m, d[0], hash_len, msg_bits, d[1], canonical, r[0], r[1], r[2], r[3]);
-    });
-  }
-
-  // EC#recoverPubKey (ec/index.js:231-259) over a batch: status 0 point / 1 infinity /
-  // 2 the reference throws / 3 outside the engine's domain (r = 0 or r >= n)
-  int ecdsa_recover_dev(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
-                        const u8* recid, u8* out_xy, u8* out_status) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve >= CURVE_ED25519)
-      return fail(E_UNSUPPORTED, "public-key recovery is an ECDSA (short Weierstrass) operation");
-    if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    int ln = (ci->order_bits + 31) / 32;
-    if (hash_len <= 0 || hash_len > 8 * ln) return fail(E_ARG, "hash_len must be 1 .. twice the order width");
-    int rc = prepare_curve(curve);
-    if (rc) return rc;
-    const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      ELL_SHORT_DISPATCH(curve, rc = recover_chunk<CV>(m, hash + o * hash_len, hash_len, r + o * NB, s + o * NB,
-                                                       recid + o, out_xy + o * 2 * B, out_status + o));
-      return rc;
-    });
-  }
-  int ecdsa_recover_host(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
-                         const u8* recid, u8* out_xy, u8* out_status) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    return staged(n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{recid, 1}},
-                  {Out{out_xy, 2 * B}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
-      return ecdsa_recover_dev(curve, m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]);
-    });
-  }
-
-  // EdDSA (ed25519) verify.  msgs: concatenated message bytes; off (n+1 offsets, device
-  // memory for the _dev form) or, if null, a uniform stride msg_len.
-  int eddsa_verify_dev(size_t n, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
-                       const u8* pubs, u8* ok, u8* err) {
-    if (n && (!sigs || !pubs || !ok || (!msgs && (off || msg_len)))) return fail(E_ARG, "null pointer");
-    int rc = prepare_curve(CURVE_ED25519);
-    if (rc) return rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      rc = eddsa_chunk(m, o, msgs, off, msg_len, sigs, pubs, ok, err);
-      return rc;
-    });
-  }
-  int eddsa_verify_host(size_t n, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
-                        const u8* pubs, u8* ok, u8* err) {
-    if (n && (!sigs || !pubs || !ok)) return fail(E_ARG, "null pointer");
-    if (off)                       // len = off[i+1] - off[i] per item: offsets must not decrease
-      for (size_t i = 0; i < n; i++)
-        if (off[i] > off[i + 1]) return fail(E_ARG, "message offsets must be non-decreasing");
-    size_t total = off ? (size_t)off[n] : n * msg_len;
-    if (total && !msgs) return fail(E_ARG, "null message pointer");
-    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
-                            In{sigs, n * 64}, In{pubs, n * 32}},
-                        {Out{ok, n}, Out{err, n}}, [&](auto d, auto r) {
-      return eddsa_verify_dev(n, d[0], (const u64*)d[1], msg_len, d[2], d[3], r[0], r[1]);
-    });
-  }
-
-  // EdDSA (ed25519) sign from 32-byte secrets: EDDSA#sign with KeyPair.fromSecret.  Messages as
-  // for eddsa_verify_dev; pub (n x 32, the encoded public keys) may be null.
-  int eddsa_sign_dev(size_t n, const u8* secrets, const u8* msgs, const u64* off, size_t msg_len,
-                     u8* sig, u8* pub) {
-    if (n && (!secrets || !sig || (!msgs && (off || msg_len)))) return fail(E_ARG, "null pointer");
-    int rc = prepare_curve(CURVE_ED25519);
-    if (rc) return rc;
-    return for_chunks(n, CHUNK / 2, [&](size_t o, size_t m) {     // two fixed-base multiplications per item
-      return eddsa_sign_chunk(m, o, secrets, msgs, off, msg_len, sig, pub);
-    });
-  }
-  int eddsa_sign_host(size_t n, const u8* secrets, const u8* msgs, const u64* off, size_t msg_len,
-                      u8* sig, u8* pub) {
-    if (n && (!secrets || !sig)) return fail(E_ARG, "null pointer");
-    if (off)                       // len = off[i+1] - off[i] per item: offsets must not decrease
-      for (size_t i = 0; i < n; i++)
-        if (off[i] > off[i + 1]) return fail(E_ARG, "message offsets must be non-decreasing");
-    size_t total = off ? (size_t)off[n] : n * msg_len;
-    if (total && !msgs) return fail(E_ARG, "null message pointer");
-    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
-                            In{secrets, n * 32}},
-                        {Out{sig, n * 64}, Out{pub, n * 32}}, [&](auto d, auto r) {
-      return eddsa_sign_dev(n, d[2], d[0], (const u64*)d[1], msg_len, r[0], r[1]);
-    });
-  }
-
-  // point decompression: short curves from x (pointFromX), ed25519 from y (pointFromY)
-  int decompress_dev(int curve, size_t n, const u8* v, const u8* odd, u8* out_xy, u8* out_ok) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
-    if (n && (!v || !odd || !out_xy || !out_ok)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    int rc = E_OK;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      if (curve == CURVE_ED25519) rc = ed_decompress_chunk(m, v + o * B, odd + o, out_xy + o * 2 * B, out_ok + o);
-      else ELL_SHORT_DISPATCH(curve, rc = decompress_chunk<CV>(m, v + o * B, odd + o, out_xy + o * 2 * B, out_ok + o));
-      return rc;
-    });
-  }
-  int decompress_host(int curve, size_t n, const u8* v, const u8* odd, u8* out_xy, u8* out_ok) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!v || !odd || !out_xy || !out_ok)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    return staged(n, {In{v, B}, In{odd, 1}}, {Out{out_xy, 2 * B}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
-      return decompress_dev(curve, m, d[0], d[1], r[0], r[1]);
-    });
-  }
-
-  // ---- SEC1 / EdDSA point codecs and key validation --------------------------------
-  enum { OP_DECODE = 0, OP_ENCODE = 1, OP_VALIDATE = 2 };
-  // decodePoint (base.js:270-293; eddsa/index.js:99-109): n encodings of enc_len bytes each
-  int decode_points_dev(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
-    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    if (curve == CURVE_ED25519 && enc_len != 32) return fail(E_ARG, "ed25519 encodings are 32 bytes");
-    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
-    int rc = E_OK;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      if (curve == CURVE_ED25519)
-        rc = ed_codec_chunk(OP_DECODE, m, enc + o * enc_len, 0, nullptr, out_xy + o * 2 * B, out_status + o);
-      else
-        ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_DECODE, m, enc + o * enc_len, enc_len, 0, nullptr,
-                                                       out_xy + o * 2 * B, out_status + o));
-      return rc;
-    });
-  }
-  static size_t encoded_len(int curve, size_t B, int compact) {
-    return curve == CURVE_ED25519 ? 32 : (compact ? 1 + B : 1 + 2 * B);
-  }
-  // BasePoint#encode (base.js:295-311) / EDDSA#encodePoint (eddsa/index.js:94-98)
-  int encode_points_dev(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
-    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes, EL = encoded_len(curve, B, compact);
-    int rc = E_OK;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      if (curve == CURVE_ED25519)
-        rc = ed_codec_chunk(OP_ENCODE, m, xy + o * 2 * B, 0, nullptr, out_enc + o * EL, nullptr);
-      else
-        ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_ENCODE, m, xy + o * 2 * B, 0, compact, nullptr,
-                                                       out_enc + o * EL, nullptr));
-      return rc;
-    });
-  }
-  // KeyPair#validate (ec/key.js:41-52): 0 ok, 1 'Invalid public key' (inf[i] set), 2 'Public key
-  // is not a point', 3 'Public key * N != O' (only tested when check_order)
-  int validate_dev(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
-    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    int rc = E_OK;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      const u8* fi = inf ? inf + o : nullptr;
-      if (curve == CURVE_ED25519)
-        rc = ed_codec_chunk(OP_VALIDATE, m, xy + o * 2 * B, check_order, fi, nullptr, out_status + o);
-      else
-        ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_VALIDATE, m, xy + o * 2 * B, 0, check_order, fi,
-                                                       nullptr, out_status + o));
-      return rc;
-    });
-  }
-  int decode_points_host(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    return staged(n, {In{enc, enc_len}}, {Out{out_xy, 2 * B}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return decode_points_dev(curve, m, d[0], enc_len, r[0], r[1]);
-    });
-  }
-  int encode_points_host(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    return staged(n, {In{xy, 2 * B}}, {Out{out_enc, encoded_len(curve, B, compact)}}, [&](size_t m, auto d, auto r) {
-      return encode_points_dev(curve, m, d[0], compact, r[0]);
-    });
-  }
-  int validate_host(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    return staged(n, {In{xy, 2 * B}, In{inf, 1}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return validate_dev(curve, m, d[0], d[1], check_order, r[0]);
-    });
-  }
-
-  // ---- Point#add on affine points (short.js:365-412, edwards.js:350-360) ----------------
-  int point_add_dev(int curve, size_t n, const u8* xy1, const u8* inf1, const u8* xy2, const u8* inf2,
-                    u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");   // mont.js:103-105
-    if (n && (!xy1 || !xy2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    int rc = E_OK;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      const u8* i1 = inf1 ? inf1 + o : nullptr;
-      const u8* i2 = inf2 ? inf2 + o : nullptr;
-      if (custom_is_edwards(curve))
-        rc = edc_chunk(2, m, nullptr, xy1 + o * 2 * B, nullptr, xy2 + o * 2 * B, i1, i2, out_xy + o * 2 * B, out_inf + o);
-      else if (is_custom(curve))
-        rc = point_add_chunk<CvCustom>(m, xy1 + o * 2 * B, i1, xy2 + o * 2 * B, i2, out_xy + o * 2 * B, out_inf + o);
-      else if (curve == CURVE_ED25519)
-        rc = ed_point_add_chunk(m, xy1 + o * 2 * B, i1, xy2 + o * 2 * B, i2, out_xy + o * 2 * B, out_inf + o);
-      else
-        ELL_SHORT_DISPATCH(curve, rc = point_add_chunk<CV>(m, xy1 + o * 2 * B, i1, xy2 + o * 2 * B, i2,
-                                                           out_xy + o * 2 * B, out_inf + o));
-      return rc;
-    });
-  }
-  int point_add_host(int curve, size_t n, const u8* xy1, const u8* inf1, const u8* xy2, const u8* inf2,
-                     u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!xy1 || !xy2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{xy1, 2 * B}, In{inf1, 1}, In{xy2, 2 * B}, In{inf2, 1}},
-                  {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
-      return point_add_dev(curve, m, d[0], d[1], d[2], d[3], r[0], r[1]);
-    });
-  }
-
-  // ---- signature DER codec and EC#verify on wire formats ------------------------------
-  enum { OP_FROM_DER = 0, OP_TO_DER = 1, OP_WIRE_STATUS = 2 };
-  int check_short(int curve, const CurveInfo*& ci) {
-    ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (curve >= CURVE_ED25519) return fail(E_UNSUPPORTED, "ECDSA signatures belong to the short Weierstrass presets");
-    return E_OK;
-  }
-  // Signature#_importDER (ec/signature.js:83-147): der = n records of `stride` bytes, der_len[i] used
-  int sig_from_der_dev(int curve, size_t n, const u8* der, size_t stride, const u32* der_len,
-                       u8* out_r, u8* out_s, u8* out_status) {
-    const CurveInfo* ci;
-    int rc = check_short(curve, ci);
-    if (rc) return rc;
-    if (n && (!der || !der_len || !out_r || !out_s || !out_status)) return fail(E_ARG, "null pointer");
-    if (stride == 0) return fail(E_ARG, "stride must be positive");
-    const size_t NB = ci->order_bytes;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_FROM_DER, m, der + o * stride, nullptr, stride,
-                                                   (u32*)der_len + o, out_r + o * NB, out_s + o * NB,
-                                                   out_status + o));
-      return rc;
-    });
-  }
-  // Signature#toDER (ec/signature.js:149-176): out = n records of `stride` >= 2 NB + 9 bytes
-  int sig_to_der_dev(int curve, size_t n, const u8* r, const u8* s, u8* out_der, size_t stride, u32* out_len) {
-    const CurveInfo* ci;
-    int rc = check_short(curve, ci);
-    if (rc) return rc;
-    if (n && (!r || !s || !out_der || !out_len)) return fail(E_ARG, "null pointer");
-    const size_t NB = ci->order_bytes;
-    if (stride < 2 * NB + 9) return fail(E_ARG, "stride must be at least 2 * order_bytes + 9");
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_TO_DER, m, r + o * NB, s + o * NB, stride, out_len + o,
-                                                   out_der + o * stride, nullptr, nullptr));
-      return rc;
-    });
-  }
-  // EC#verify(msg, derSignature, encodedKey) (ec/index.js:188-229 with keyFromPublic ->
-  // decodePoint and new Signature(der)): decode, parse and verify on the device
-  int ecdsa_verify_wire_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
-                            const u8* der, size_t der_stride, const u32* der_len, const u8* pub_enc,
-                            size_t pub_len, u8* ok, u8* err) {
-    const CurveInfo* ci;
-    int rc = check_short(curve, ci);
-    if (rc) return rc;
-    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
-    const size_t B = ci->field_bytes, NB = ci->order_bytes, HL = (size_t)hash_len;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      u8* tmp = (u8*)scratch(S_WIRE, m * (2 * NB + 2 * B + 3));
-      if (!tmp) return fail(E_NOMEM, "scratch allocation failed");
-      u8* r = tmp;
-      u8* s = r + m * NB;
-      u8* xy = s + m * NB;
-      u8* kst = xy + m * 2 * B;
-      u8* sst = kst + m;
-      u8* vst = sst + m;
-      rc = decode_points_dev(curve, m, pub_enc + o * pub_len, pub_len, xy, kst);
-      if (rc) return rc;
-      rc = sig_from_der_dev(curve, m, der + o * der_stride, der_stride, der_len + o, r, s, sst);
-      if (rc) return rc;
-      rc = ecdsa_verify_dev(curve, m, hash + o * HL, hash_len, msg_bits, r, s, xy, ok + o, vst);
-      if (rc) return rc;
-      ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_WIRE_STATUS, m, kst, sst, 0, nullptr, ok + o,
-                                                   err ? err + o : nullptr, vst));
-      return rc;
-    });
-  }
-  int sig_from_der_host(int curve, size_t n, const u8* der, size_t stride, const u32* der_len,
-                        u8* out_r, u8* out_s, u8* out_status) {
-    const CurveInfo* ci;
-    int rc = check_short(curve, ci);
-    if (rc) return rc;
-    if (n && (!der || !der_len || !out_r || !out_s || !out_status)) return fail(E_ARG, "null pointer");
-    const size_t NB = ci->order_bytes;
-    return staged(n, {In{der, stride}, In{der_len, 4}}, {Out{out_r, NB}, Out{out_s, NB}, Out{out_status, 1}},
-                  [&](size_t m, auto d, auto r) {
-      return sig_from_der_dev(curve, m, d[0], stride, (const u32*)d[1], r[0], r[1], r[2]);
-    });
-  }
-  int sig_to_der_host(int curve, size_t n, const u8* r, const u8* s, u8* out_der, size_t stride, u32* out_len) {
-    const CurveInfo* ci;
-    int rc = check_short(curve, ci);
-    if (rc) return rc;
-    if (n && (!r || !s || !out_der || !out_len)) return fail(E_ARG, "null pointer");
-    const size_t NB = ci->order_bytes;
-    return staged(n, {In{r, NB}, In{s, NB}}, {Out{out_der, stride}, Out{out_len, 4}}, [&](size_t m, auto d, auto o) {
-      return sig_to_der_dev(curve, m, d[0], d[1], o[0], stride, (u32*)o[1]);
-    });
-  }
-  int ecdsa_verify_wire_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
-                             const u8* der, size_t der_stride, const u32* der_len, const u8* pub_enc,
-                             size_t pub_len, u8* ok, u8* err) {
-    const CurveInfo* ci;
-    int rc = check_short(curve, ci);
-    if (rc) return rc;
-    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    return staged(n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
-                  {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto r) {
-      return ecdsa_verify_wire_dev(curve, m, d[0], hash_len, msg_bits, d[1], der_stride, (const u32*)d[2], d[3],
-                                   pub_len, r[0], r[1]);
-    });
-  }
-
-  // ---- wire formats on user-defined short curves -------------------------------------------
-  // ShortCurve#pointFromX, BaseCurve#decodePoint and EC#verify(msg, der, key) where the curve
-  // is the caller's own (ellgpu_custom_*).  Entry points of their own: the preset-named ones
-  // refuse user-defined ids before a kernel is chosen, and keep doing so.  Coordinates in and
-  // out are 32 bytes; a SEC1 coordinate is p.byteLength() bytes, the block's pbytes.
-  enum { OP_RT_DECOMPRESS = 0, OP_RT_DECODE = 1, OP_RT_FROM_DER = 2, OP_RT_WIRE_STATUS = 3 };
-  int check_custom_short(int curve, bool need_domain) {
-    if (!is_custom(curve))
-      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (the presets have ellgpu_decompress, ellgpu_decode_points and ellgpu_ecdsa_verify_wire)")
-                               : fail(E_ARG, "unknown curve id");
-    const RtField* f = custom_block(curve);
-    if (!f) return fail(E_ARG, "unknown curve id");
-    if (f->kind == 2) return fail(E_UNSUPPORTED, "not available on user-defined Montgomery curves (x-only: ellgpu_custom_mont_ladder, _validate, _derive)");
-    if (f->kind != 0) return fail(E_UNSUPPORTED, "not available on user-defined Edwards curves");
-    if (need_domain && !f->domain)
-      return fail(E_UNSUPPORTED, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
-    return E_OK;
-  }
-  int custom_decompress_dev(int curve, size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!x || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_wire_chunk(OP_RT_DECOMPRESS, m, x + o * 32, odd + o, 0, nullptr, out_xy + o * 64, out_status + o, nullptr);
-    });
-  }
-  int custom_decompress_host(int curve, size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!x || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{x, 32}, In{odd, 1}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_decompress_dev(curve, m, d[0], d[1], r[0], r[1]);
-    });
-  }
-  // enc_len other than 1 + pbytes and 1 + 2 pbytes is no error of the call: every item is then
-  // 'Unknown point format', as in the reference
-  int custom_decode_points_dev(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_wire_chunk(OP_RT_DECODE, m, enc + o * enc_len, nullptr, enc_len, nullptr, out_xy + o * 64, out_status + o,
-                           nullptr);
-    });
-  }
-  int custom_decode_points_host(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{enc, enc_len}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_decode_points_dev(curve, m, d[0], enc_len, r[0], r[1]);
-    });
-  }
-  // EC#verify(msg, derSignature, encodedKey) on a domain: decode, parse and verify on the device,
-  // composed like ecdsa_verify_wire_dev
-  int custom_verify_wire_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* der,
-                             size_t der_stride, const u32* der_len, const u8* pub_enc, size_t pub_len, u8* ok,
-                             u8* err) {
-    int rc = check_custom_short(curve, true);
-    if (rc) return rc;
-    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    const size_t HL = (size_t)hash_len;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      u8* tmp = (u8*)scratch(S_WIRE, m * (2 * 32 + 64 + 3));
-      if (!tmp) return fail(E_NOMEM, "scratch allocation failed");
-      u8* r = tmp;
-      u8* s = r + m * 32;
-      u8* xy = s + m * 32;
-      u8* kst = xy + m * 64;
-      u8* sst = kst + m;
-      u8* vst = sst + m;
-      rc = rt_wire_chunk(OP_RT_DECODE, m, pub_enc + o * pub_len, nullptr, pub_len, nullptr, xy, kst, nullptr);
-      if (rc) return rc;
-      rc = rt_wire_chunk(OP_RT_FROM_DER, m, der + o * der_stride, nullptr, der_stride, der_len + o, r, s, sst);
-      if (rc) return rc;
-      rc = ecdsa_verify_dev(curve, m, hash + o * HL, hash_len, msg_bits, r, s, xy, ok + o, vst);
-      if (rc) return rc;
-      return rt_wire_chunk(OP_RT_WIRE_STATUS, m, kst, sst, 0, nullptr, ok + o, err ? err + o : nullptr, vst);
-    });
-  }
-  int custom_verify_wire_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* der,
-                              size_t der_stride, const u32* der_len, const u8* pub_enc, size_t pub_len, u8* ok,
-                              u8* err) {
-    int rc = check_custom_short(curve, true);
-    if (rc) return rc;
-    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
-    if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
-                  {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_verify_wire_dev(curve, m, d[0], hash_len, msg_bits, d[1], der_stride, (const u32*)d[2], d[3],
-                                    pub_len, r[0], r[1]);
-    });
-  }
-
-  // EC#recoverPubKey (ec/index.js:231-259) on a domain: status 0 point / 1 infinity / 2 the
-  // reference throws / 3 r = 0 or r >= n, as ecdsa_recover_dev.  e = new BN(hash) is not
-  // truncated, only reduced mod n; s is not range-checked (the reference reduces it).
-  int check_custom_recover(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
-                           const u8* recid, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (!custom_is_domain(curve))
-      return fail(E_UNSUPPORTED, "public-key recovery on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
-    if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
-    return E_OK;
-  }
-  int custom_recover_dev(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
-                         const u8* recid, u8* out_xy, u8* out_status) {
-    int rc = check_custom_recover(curve, n, hash, hash_len, r, s, recid, out_xy, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    rc = ensure_comb<CvCustomDomain>();
-    if (rc) return rc;
-    const size_t HL = (size_t)hash_len;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_recover_chunk(m, hash + o * HL, hash_len, r + o * 32, s + o * 32, recid + o, out_xy + o * 64,
-                              out_status + o);
-    });
-  }
-  int custom_recover_host(int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
-                          const u8* recid, u8* out_xy, u8* out_status) {
-    int rc = check_custom_recover(curve, n, hash, hash_len, r, s, recid, out_xy, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{hash, (size_t)hash_len}, In{r, 32}, In{s, 32}, In{recid, 1}},
-                  {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
-      return custom_recover_dev(curve, m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]);
-    });
-  }
-
-  // EC#sign (ec/index.js:110-186) on a domain: one pass of its loop for supplied nonces
-  // (nonces != null), or with the reference's own HmacDRBG over drbg_hash (nonces == null)
-  int check_custom_sign(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                        const u8* nonces, bool det, int drbg_hash, u8* out_r, u8* out_s, u8* out_recid,
-                        u8* out_ok, int& shift) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (!custom_is_domain(curve))
-      return fail(E_UNSUPPORTED, "ECDSA sign on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
-    if (n && (!hash || !priv || (!det && !nonces) || !out_r || !out_s || !out_recid || !out_ok))
-      return fail(E_ARG, "null pointer");
-    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
-    if (det && (drbg_hash < 0 || drbg_hash > 2)) return fail(E_ARG, "drbg_hash must be ELLGPU_HASH_SHA256, _SHA384 or _SHA512");
-    const int nbits = (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits;
-    rc = truncate_shift(hash_len, msg_bits, nbits, 8, shift);
-    if (rc) return rc;
-    // hmac-drbg's constructor: entropy of n.byteLength() bytes against hmacStrength = 192 bits
-    if (det && (nbits + 7) / 8 < 24)
-      return fail(E_UNSUPPORTED, "EC#sign throws on this domain: 'Not enough entropy. Minimum is: 192 bits' (n.byteLength() < 24)");
-    return E_OK;
-  }
-  int custom_sign_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                      const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
-                      u8* out_recid, u8* out_ok) {
-    int shift;
-    int rc = check_custom_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
-                               out_recid, out_ok, shift);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    rc = ensure_comb<CvCustomDomain>();
-    if (rc) return rc;
-    const size_t HL = (size_t)hash_len;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_sign_chunk(m, hash + o * HL, hash_len, shift, priv + o * 32, det ? nullptr : nonces + o * 32,
-                           drbg_hash, canonical, out_r + o * 32, out_s + o * 32, out_recid + o, out_ok + o);
-    });
-  }
-  int custom_sign_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                       const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
-                       u8* out_recid, u8* out_ok) {
-    int shift;
-    int rc = check_custom_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
-                               out_recid, out_ok, shift);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{hash, (size_t)hash_len}, In{priv, 32}, In{det ? nullptr : nonces, 32}},
-                  {Out{out_r, 32}, Out{out_s, 32}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto o) {
-      return custom_sign_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], det, drbg_hash, canonical, o[0], o[1],
-                             o[2], o[3]);
-    });
-  }
-
-  // ---- the key side on user-defined short curves: ECDH, validation, SEC1 encoding ---------------
-  // KeyPair#derive (ec/key.js:101-107), KeyPair#validate (key.js:40-51) and BasePoint#encode
-  // (base.js:295-311).  derive and encode need neither n nor G: a plain define_short id will do;
-  // validate's order test needs the domain's n.
-  int custom_pbytes() const { return (int)custom_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].pbytes; }
-  // pub_len == 0: pub is n x 64 raw coordinates (ellgpu_custom_derive); else n SEC1 encodings of
-  // pub_len bytes (ellgpu_custom_derive_wire) -- a length that is neither 1 + pbytes nor
-  // 1 + 2 pbytes is no error of the call: every item is then 'Unknown point format'
-  int check_custom_derive(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len,
-                          u8* out_x, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!priv || !pub || !out_x || !out_status)) return fail(E_ARG, "null pointer");
-    if (wire && pub_len == 0) return fail(E_ARG, "pub_len must be positive");
-    return E_OK;
-  }
-  int custom_derive_dev(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
-                        u8* out_status, u8* out_err) {
-    int rc = check_custom_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    const size_t PS = wire ? pub_len : 64;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_derive_chunk(m, priv + o * 32, pub + o * PS, wire ? pub_len : 0, out_x + o * 32, out_status + o,
-                             out_err ? out_err + o : nullptr);
-    });
-  }
-  int custom_derive_host(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
-                         u8* out_status, u8* out_err) {
-    int rc = check_custom_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{priv, 32}, In{pub, wire ? pub_len : 64}}, {Out{out_x, 32}, Out{out_status, 1}, Out{out_err, 1}},
-                  [&](size_t m, auto d, auto o) {
-      return custom_derive_dev(curve, m, d[0], d[1], wire, pub_len, o[0], o[1], o[2]);
-    });
-  }
-  // statuses as validate_dev's; check_order on a plain id: it has no n
-  int check_custom_validate(int curve, size_t n, const u8* xy, int check_order, u8* out_status) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (check_order && !custom_is_domain(curve))
-      return fail(E_UNSUPPORTED, "the order test on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
-    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
-    return E_OK;
-  }
-  int custom_validate_dev(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
-    int rc = check_custom_validate(curve, n, xy, check_order, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_validate_chunk(m, xy + o * 64, inf ? inf + o : nullptr, check_order != 0, out_status + o);
-    });
-  }
-  int custom_validate_host(int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
-    int rc = check_custom_validate(curve, n, xy, check_order, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{xy, 64}, In{inf, 1}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
-      return custom_validate_dev(curve, m, d[0], d[1], check_order, o[0]);
-    });
-  }
-  // rows of 1 + pbytes (compact) or 1 + 2 pbytes bytes
-  int custom_encode_points_dev(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_pbytes();
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return rt_encode_chunk(m, xy + o * 64, compact, out_enc + o * EL);
-    });
-  }
-  int custom_encode_points_host(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
-    int rc = check_custom_short(curve, false);
-    if (rc) return rc;
-    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_pbytes();
-    return staged(n, {In{xy, 64}}, {Out{out_enc, EL}}, [&](size_t m, auto d, auto o) {
-      return custom_encode_points_dev(curve, m, d[0], compact, o[0]);
-    });
-  }
-
-  // ---- host-buffer wrappers: stage through device buffers --------------------
-  // An operand of a host-buffer call: n items of `stride` bytes.  A null host pointer is an absent
-  // optional operand (the wrappers have refused the required ones): it gets no device copy, and
-  // the body sees nullptr in its place.
-  struct In { const void* host; size_t stride; bool opt = false; };   // opt: see staged_whole()
-  struct Out { void* host; size_t stride; };
+  // ---- the operands of a batch call, wherever they live -----------------------
+  // An operand: n items of `stride` bytes.  A null pointer is an absent optional operand (the
+  // operations have refused the required ones): the body sees nullptr in its place, and a host
+  // call gives it no device copy.
+  struct In { const void* ptr; size_t stride; bool opt = false; };   // opt: see staged_whole()
+  struct Out { void* ptr; size_t stride; };
   static constexpr int STAGED_MAX = 4;        // operands each way (pipelined(), small_call())
   // gives every present operand a staging buffer of its own, inputs and outputs in order
   template <int NI, int NO>
@@ -2677,36 +1841,47 @@ class Engine {
       return host ? (u8*)grow(staging_[i], bytes ? bytes : 1) : nullptr;
     };
     bool ok = true;
-    for (int i = 0; i < NI; i++) ok &= (d[i] = slot(i, in[i].host, n * in[i].stride)) || !in[i].host;
-    for (int i = 0; i < NO; i++) ok &= (r[i] = slot(STAGED_MAX + i, out[i].host, n * out[i].stride)) || !out[i].host;
+    for (int i = 0; i < NI; i++) ok &= (d[i] = slot(i, in[i].ptr, n * in[i].stride)) || !in[i].ptr;
+    for (int i = 0; i < NO; i++) ok &= (r[i] = slot(STAGED_MAX + i, out[i].ptr, n * out[i].stride)) || !out[i].ptr;
     return ok ? E_OK : nomem();
   }
   int nomem() { return fail(E_NOMEM, "staging allocation failed"); }
-  // One host-buffer call: stages its operands and runs body(m, d, r) through pipelined(), where
-  // d / r are the device copies of the inputs / outputs, already offset to the chunk's first item.
+  // One batch call: body(m, d, r) on at most CHUNK items at a time, where d / r are DEVICE pointers
+  // to the inputs / outputs, already offset to the first of the m items -- the only place that
+  // does operand pointer arithmetic.  Mem::device: the caller's pointers, chunk by chunk.
+  // Mem::host: the operands are staged and the body runs inside each step of pipelined(), on that
+  // step's lane, over the device copies.
   template <int NI, int NO, class Body>
-  int staged(size_t n, const In (&in)[NI], const Out (&out)[NO], Body body) {
+  int batch(Mem where, size_t n, const In (&in)[NI], const Out (&out)[NO], Body body) {
     u8* d[NI];
     u8* r[NO];
+    auto chunks = [&](size_t first, size_t count) {
+      return for_chunks(count, CHUNK, [&](size_t o, size_t m) {
+        const u8* di[NI];
+        u8* ro[NO];
+        for (int i = 0; i < NI; i++) di[i] = d[i] ? d[i] + (first + o) * in[i].stride : nullptr;
+        for (int i = 0; i < NO; i++) ro[i] = r[i] ? r[i] + (first + o) * out[i].stride : nullptr;
+        return body(m, di, ro);
+      });
+    };
+    if (where == Mem::device) {
+      for (int i = 0; i < NI; i++) d[i] = (u8*)in[i].ptr;
+      for (int i = 0; i < NO; i++) r[i] = (u8*)out[i].ptr;
+      return chunks(0, n);
+    }
     if (int rc = stage(n, in, out, d, r)) return rc;
     HostIn hi[NI];
     HostOut ho[NO];
     int ni = 0, no = 0;
-    for (int i = 0; i < NI; i++) if (d[i]) hi[ni++] = {d[i], (const u8*)in[i].host, in[i].stride};
-    for (int i = 0; i < NO; i++) if (r[i]) ho[no++] = {(u8*)out[i].host, r[i], out[i].stride};
-    return pipelined(n, hi, ni, ho, no, [&](size_t o, size_t m) {
-      const u8* di[NI];
-      u8* ro[NO];
-      for (int i = 0; i < NI; i++) di[i] = d[i] ? d[i] + o * in[i].stride : nullptr;
-      for (int i = 0; i < NO; i++) ro[i] = r[i] ? r[i] + o * out[i].stride : nullptr;
-      return body(m, di, ro);
-    });
+    for (int i = 0; i < NI; i++) if (d[i]) hi[ni++] = {d[i], (const u8*)in[i].ptr, in[i].stride};
+    for (int i = 0; i < NO; i++) if (r[i]) ho[no++] = {(u8*)out[i].ptr, r[i], out[i].stride};
+    return pipelined(n, hi, ni, ho, no, chunks);
   }
   // The EdDSA calls: their operands are whole buffers (`stride` = all their bytes), since the
   // message offsets index the whole message buffer.  So no pipelining: a few items go through
   // small_call(), more are copied in, run as one batch and copied out.  On that path only an
   // optional input may be absent: a null one that is required (possible at n = 0 only, the
-  // wrappers refuse it sooner) fails as an allocation.
+  // operations refuse it sooner) fails as an allocation.
   template <int NI, int NO, class Body>
   int staged_whole(size_t n, const In (&in)[NI], const Out (&out)[NO], Body body) {
     u8* d[NI];
@@ -2715,20 +1890,20 @@ class Engine {
     if (n && n <= bk.pipeline_quantum()) {
       SpanIn si[NI];
       SpanOut so[NO];
-      for (int i = 0; i < NI; i++) si[i] = {d[i], (const u8*)in[i].host, in[i].stride};
-      for (int i = 0; i < NO; i++) so[i] = {(u8*)out[i].host, r[i], out[i].stride};
+      for (int i = 0; i < NI; i++) si[i] = {d[i], (const u8*)in[i].ptr, in[i].stride};
+      for (int i = 0; i < NO; i++) so[i] = {(u8*)out[i].ptr, r[i], out[i].stride};
       int rc = E_OK;
       if (small_call(si, NI, so, NO, [&]() { return body(d, r); }, &rc)) return rc;
     }
     defer_skip();
     for (int i = 0; i < NI; i++) {
-      if (!in[i].host && !in[i].opt) return nomem();
-      if (in[i].host && in[i].stride) bk.h2d(d[i], in[i].host, in[i].stride);
+      if (!in[i].ptr && !in[i].opt) return nomem();
+      if (in[i].ptr && in[i].stride) bk.h2d(d[i], in[i].ptr, in[i].stride);
     }
     const int rc = body(d, r);
     if (rc) return rc;
     for (int i = 0; i < NO; i++)
-      if (r[i]) bk.d2h(out[i].host, r[i], out[i].stride);
+      if (r[i]) bk.d2h(out[i].ptr, r[i], out[i].stride);
     return bk.sync();
   }
 
@@ -2879,91 +2054,642 @@ class Engine {
     return rc ? rc : rs;
   }
 
-  int mul_fixed_host(int curve, size_t n, const u8* k, u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!k || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
-      return mul_fixed_dev(curve, m, d[0], r[0], r[1]);
-    });
-  }
-  int mul_var_host(int curve, size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!k || !xy || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{k, B}, In{xy, 2 * B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
-      return mul_var_dev(curve, m, d[0], d[1], r[0], r[1]);
-    });
-  }
-  int mul_add2_host(int curve, size_t n, const u8* k1, const u8* xy1, const u8* k2,
-                    const u8* xy2, u8* out_xy, u8* out_inf) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!k1 || !k2 || !xy2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
-    const size_t B = ci->field_bytes;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{k1, B}, In{xy1, 2 * B}, In{k2, B}, In{xy2, 2 * B}},
-                  {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
-      return mul_add2_dev(curve, m, d[0], d[1], d[2], d[3], r[0], r[1]);
-    });
-  }
-  int ecdsa_verify_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
-                        const u8* r, const u8* s, const u8* pub, u8* ok, u8* st) {
-    const CurveInfo* ci = curve_info(curve);
-    if (!ci) return fail(E_ARG, "unknown curve id");
-    if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
+  // ---- the operations: one function each, `where` says where the operands live ------------------
+  // Every operation is: its checks, its CustomScope, batch().  What the two forms refuse is the
+  // same; the ORDER in which the preset operations refuse is each form's own, and both are pinned
+  // (tests/test_hostsim_forms.py, tests/test_entry_forms_hostsim.py).  A host call answers first
+  // for what staging reads -- a null buffer, a hash_len that is no stride (host_first) -- and
+  // only a batch with items asks what its curve and its lengths allow; a device call asks the
+  // curve first, whatever n is (asks_curve).
+  int host_first(Mem where, bool nul, int hash_len = 1) {
+    if (where != Mem::host) return E_OK;
+    if (nul) return fail(E_ARG, "null pointer");
     if (hash_len <= 0) return fail(E_ARG, "bad hash_len");
-    const size_t B = ci->field_bytes, NB = ci->order_bytes;
-    CustomScope sc(this, curve);
+    return E_OK;
+  }
+  static bool asks_curve(Mem where, size_t n) { return where == Mem::device || n; }
+
+  int mul_fixed(Mem where, int curve, size_t n, const u8* k, u8* out_xy, u8* out_inf) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!k || !out_xy || !out_inf);
+    if (int rc = host_first(where, nul)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519)
+        return fail(E_UNSUPPORTED, "curve25519 has no affine fixed-base form; use x25519_ladder");
+      if (nul) return fail(E_ARG, "null pointer");
+    }
+    // (a host call opens the scope of any user-defined id, and so names an unknown or a Montgomery
+    // one as such before its first step finds no table; a device call opens a domain's only and
+    // refuses every other one here, empty batch or not)
+    const bool dom = custom_is_domain(curve);
+    if (where == Mem::device && is_custom(curve) && !dom) return prepare_curve(curve);
+    CustomScope sc(this, dom || where == Mem::host ? curve : -1);
     if (sc.rc) return sc.rc;
-    return staged(n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{pub, 2 * B}},
-                  {Out{ok, 1}, Out{st, 1}}, [&](size_t m, auto d, auto o) {
-      return ecdsa_verify_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], d[3], o[0], o[1]);
+    const size_t B = ci->field_bytes;
+    return batch(where, n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
+      int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
+      if (rc) return rc;
+      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], r[0], r[1]);
+      else if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, d[0], r[0], r[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], r[0], r[1]));
+      return rc;
     });
   }
+
+  static bool overlap(const u8* a, const u8* b, size_t bytes) {
+    return a && b && bytes && (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
+  }
+  int mul_var(Mem where, int curve, size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!k || !xy || !out_xy || !out_inf);
+    if (int rc = host_first(where, nul)) return rc;
+    const size_t B = ci->field_bytes;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519)
+        return fail(E_UNSUPPORTED, "curve25519 is x-only; use x25519_ladder");
+      if (nul) return fail(E_ARG, "null pointer");
+      // the operands are read again AFTER the results are written (the curve test of
+      // Work::domain_mark / mul_join): a result written over its own operand would be tested in its
+      // place.  Device pointers only: a host caller's operand and result never share a staging buffer.
+      if (where == Mem::device && overlap(xy, out_xy, n * 2 * B)) return fail(E_ARG, "in_xy and out_xy must not overlap");
+    }
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{k, B}, In{xy, 2 * B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (custom_is_edwards(curve)) rc = edc_chunk(0, m, d[0], d[1], nullptr, nullptr, nullptr, nullptr, r[0], r[1]);
+      else if (is_custom(curve)) rc = mul_var_chunk<CvCustom>(m, d[0], d[1], r[0], r[1], nullptr);
+      else if (curve == CURVE_ED25519) rc = ed_mul_var_chunk(m, d[0], d[1], r[0], r[1], nullptr);
+      else ELL_SHORT_DISPATCH(curve, rc = mul_var_chunk<CV>(m, d[0], d[1], r[0], r[1], nullptr));
+      return rc;
+    });
+  }
+
+  // xy1 == null: k1 * G + k2 * P2 over the curve's fixed-base table
+  int mul_add2(Mem where, int curve, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
+               u8* out_xy, u8* out_inf) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!k1 || !k2 || !xy2 || !out_xy || !out_inf);
+    if (int rc = host_first(where, nul)) return rc;
+    const size_t B = ci->field_bytes;
+    const bool dom = custom_is_domain(curve);
+    // (a device call says so before it opens the curve's scope, a host call with items after)
+    const bool no_table = is_custom(curve) && !xy1 && !dom;
+    const char* const no_table_msg = "user-defined curves without a generator have no fixed-base table: pass the generator as p1";
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519)
+        return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");     // mont.js:155-157
+      if (nul) return fail(E_ARG, "null pointer");
+      if (where == Mem::device) {
+        if (no_table) return fail(E_UNSUPPORTED, no_table_msg);
+        if (overlap(xy2, out_xy, n * 2 * B) || overlap(xy1, out_xy, n * 2 * B))   // see mul_var
+          return fail(E_ARG, "p1_xy / p2_xy and out_xy must not overlap");
+      }
+    }
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    if (no_table && n) return fail(E_UNSUPPORTED, no_table_msg);
+    return batch(where, n, {In{k1, B}, In{xy1, 2 * B}, In{k2, B}, In{xy2, 2 * B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}},
+                 [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (!d[1]) {
+        rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
+        if (rc) return rc;
+      }
+      if (custom_is_edwards(curve)) rc = edc_chunk(1, m, d[0], d[1], d[2], d[3], nullptr, nullptr, r[0], r[1]);
+      else if (is_custom(curve) && !d[1]) rc = mul_add_g_chunk<CvCustomDomain>(m, d[0], d[2], d[3], r[0], r[1]);
+      else if (is_custom(curve)) rc = mul_add2_chunk<CvCustom>(m, d[0], d[1], d[2], d[3], r[0], r[1]);
+      else if (curve == CURVE_ED25519) rc = ed_mul_add2_chunk(m, d[0], d[1], d[2], d[3], r[0], r[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = d[1] ? mul_add2_chunk<CV>(m, d[0], d[1], d[2], d[3], r[0], r[1])
+                                               : mul_add_g_chunk<CV>(m, d[0], d[2], d[3], r[0], r[1]));
+      return rc;
+    });
+  }
+
+  // ok: the verdicts, strictly 0 / 1.  st (may be null): the domain status per item -- 2 where the
+  // key is not on the curve (verdict 0 there), else 0 (Work::store_verdict)
+  int ecdsa_verify(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
+                   const u8* r, const u8* s, const u8* pub, u8* ok, u8* st) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!hash || !r || !s || !pub || !ok);
+    if (int rc = host_first(where, nul, hash_len)) return rc;
+    const bool dom = custom_is_domain(curve);
+    CustomScope sc(this, dom || where == Mem::host ? curve : -1);      // as mul_fixed
+    if (sc.rc) return sc.rc;
+    int shift = 0;                 // a domain's own n, in 8 words
+    if (asks_curve(where, n)) {
+      if (curve >= CURVE_ED25519 && !dom)
+        return fail(E_UNSUPPORTED, is_custom(curve) ? "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"
+                                                    : "ECDSA verify is implemented for the short Weierstrass presets");
+      if (nul) return fail(E_ARG, "null pointer");
+      int rc = dom ? truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift)
+                   : truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift);
+      if (rc) return rc;
+    }
+    const size_t B = ci->field_bytes, NB = ci->order_bytes;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{pub, 2 * B}}, {Out{ok, 1}, Out{st, 1}},
+                 [&](size_t m, auto d, auto o) {
+      int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
+      if (rc) return rc;
+      if (dom) rc = ecdsa_chunk<CvCustomDomain>(m, d[0], hash_len, shift, d[1], d[2], d[3], o[0], o[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = ecdsa_chunk<CV>(m, d[0], hash_len, shift, d[1], d[2], d[3], o[0], o[1]));
+      return rc;
+    });
+  }
+
+  // out_bad (may be null): out_bad[i] = 1 where x[i] is no abscissa of the curve (KeyPair#derive's validate)
+  int x25519(Mem where, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
+    if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
+    return batch(where, n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_inf, 1}, Out{out_bad, 1}},
+                 [&](size_t m, auto d, auto r) { return x25519_chunk(m, d[0], d[1], r[0], r[1], r[2]); });
+  }
+
+  // ECDSA sign on the presets.  nonces != null: caller-supplied nonces, one pass of EC#sign's loop
+  // per item; nonces == null (det): the reference's own nonce source (HmacDRBG, deterministic)
+  int ecdsa_sign(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                 const u8* nonces, bool det, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!hash || !priv || (!det && !nonces) || !out_r || !out_s || !out_recid || !out_ok);
+    if (int rc = host_first(where, nul, hash_len)) return rc;
+    int shift = 0;
+    if (asks_curve(where, n)) {
+      if (curve >= CURVE_ED25519)
+        return fail(E_UNSUPPORTED, "ECDSA sign is implemented for the short Weierstrass presets");
+      if (nul) return fail(E_ARG, "null pointer");
+      if (int rc = truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift)) return rc;
+    }
+    const size_t NB = ci->order_bytes;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{priv, NB}, In{det ? nullptr : nonces, NB}},
+                 {Out{out_r, NB}, Out{out_s, NB}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
+      int rc = prepare_curve(curve);
+      if (rc) return rc;
+      if (det) ELL_SHORT_DISPATCH(curve, rc = sign_det_chunk<CV>(m, d[0], hash_len, shift, d[1], canonical, r[0], r[1], r[2], r[3]))
+      else ELL_SHORT_DISPATCH(curve, rc = sign_chunk<CV>(m, d[0], hash_len, shift, d[1], d[2], canonical, r[0], r[1], r[2], r[3]));
+      return rc;
+    });
+  }
+
+  // EC#recoverPubKey (ec/index.js:231-259) over a batch: status 0 point / 1 infinity /
+  // 2 the reference throws / 3 outside the engine's domain (r = 0 or r >= n)
+  int ecdsa_recover(Mem where, int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                    const u8* recid, u8* out_xy, u8* out_status) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!hash || !r || !s || !recid || !out_xy || !out_status);
+    if (int rc = host_first(where, nul, hash_len)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve >= CURVE_ED25519)
+        return fail(E_UNSUPPORTED, "public-key recovery is an ECDSA (short Weierstrass) operation");
+      if (nul) return fail(E_ARG, "null pointer");
+      if (hash_len <= 0 || hash_len > 8 * ((ci->order_bits + 31) / 32))
+        return fail(E_ARG, "hash_len must be 1 .. twice the order width");
+    }
+    const size_t B = ci->field_bytes, NB = ci->order_bytes;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{recid, 1}},
+                 {Out{out_xy, 2 * B}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      int rc = prepare_curve(curve);
+      if (rc) return rc;
+      ELL_SHORT_DISPATCH(curve, rc = recover_chunk<CV>(m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]));
+      return rc;
+    });
+  }
+
+  // EdDSA (ed25519).  msgs: concatenated message bytes; off (n + 1 offsets, in the memory the
+  // other operands are in) or, if null, a uniform stride msg_len.  Whole-buffer operands: a host
+  // call goes through staged_whole(), and tests the offsets it can read.
+  int check_eddsa_messages(size_t n, const u8* msgs, const u64* off, size_t msg_len, size_t& total) {
+    if (off)                       // len = off[i+1] - off[i] per item: offsets must not decrease
+      for (size_t i = 0; i < n; i++)
+        if (off[i] > off[i + 1]) return fail(E_ARG, "message offsets must be non-decreasing");
+    total = off ? (size_t)off[n] : n * msg_len;
+    if (total && !msgs) return fail(E_ARG, "null message pointer");
+    return E_OK;
+  }
+  int eddsa_verify(Mem where, size_t n, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
+                   const u8* pubs, u8* ok, u8* err) {
+    auto run = [&](const u8* dm, const u64* doff, const u8* ds, const u8* dp, u8* dok, u8* derr) {
+      if (n && (!ds || !dp || !dok || (!dm && (doff || msg_len)))) return fail(E_ARG, "null pointer");
+      return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+        if (int rc = prepare_curve(CURVE_ED25519)) return rc;
+        return eddsa_chunk(m, o, dm, doff, msg_len, ds, dp, dok, derr);
+      });
+    };
+    if (where == Mem::device) return run(msgs, off, sigs, pubs, ok, err);
+    if (n && (!sigs || !pubs || !ok)) return fail(E_ARG, "null pointer");
+    size_t total;
+    if (int rc = check_eddsa_messages(n, msgs, off, msg_len, total)) return rc;
+    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
+                            In{sigs, n * 64}, In{pubs, n * 32}},
+                        {Out{ok, n}, Out{err, n}}, [&](auto d, auto r) {
+      return run(d[0], (const u64*)d[1], d[2], d[3], r[0], r[1]);
+    });
+  }
+  // EDDSA#sign with KeyPair.fromSecret, from 32-byte secrets; pub (n x 32, the encoded public
+  // keys) may be null
+  int eddsa_sign(Mem where, size_t n, const u8* secrets, const u8* msgs, const u64* off, size_t msg_len,
+                 u8* sig, u8* pub) {
+    auto run = [&](const u8* dsec, const u8* dm, const u64* doff, u8* dsig, u8* dpub) {
+      if (n && (!dsec || !dsig || (!dm && (doff || msg_len)))) return fail(E_ARG, "null pointer");
+      return for_chunks(n, CHUNK / 2, [&](size_t o, size_t m) {     // two fixed-base multiplications per item
+        if (int rc = prepare_curve(CURVE_ED25519)) return rc;
+        return eddsa_sign_chunk(m, o, dsec, dm, doff, msg_len, dsig, dpub);
+      });
+    };
+    if (where == Mem::device) return run(secrets, msgs, off, sig, pub);
+    if (n && (!secrets || !sig)) return fail(E_ARG, "null pointer");
+    size_t total;
+    if (int rc = check_eddsa_messages(n, msgs, off, msg_len, total)) return rc;
+    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
+                            In{secrets, n * 32}},
+                        {Out{sig, n * 64}, Out{pub, n * 32}}, [&](auto d, auto r) {
+      return run(d[2], d[0], (const u64*)d[1], r[0], r[1]);
+    });
+  }
+
+  // point decompression: short curves from x (pointFromX), ed25519 from y (pointFromY)
+  int decompress(Mem where, int curve, size_t n, const u8* v, const u8* odd, u8* out_xy, u8* out_ok) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!v || !odd || !out_xy || !out_ok);
+    if (int rc = host_first(where, nul)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
+      if (nul) return fail(E_ARG, "null pointer");
+    }
+    const size_t B = ci->field_bytes;
+    return batch(where, n, {In{v, B}, In{odd, 1}}, {Out{out_xy, 2 * B}, Out{out_ok, 1}}, [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (curve == CURVE_ED25519) rc = ed_decompress_chunk(m, d[0], d[1], r[0], r[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = decompress_chunk<CV>(m, d[0], d[1], r[0], r[1]));
+      return rc;
+    });
+  }
+
+  // ---- SEC1 / EdDSA point codecs and key validation --------------------------------
+  enum { OP_DECODE = 0, OP_ENCODE = 1, OP_VALIDATE = 2 };
+  // decodePoint (base.js:270-293; eddsa/index.js:99-109): n encodings of enc_len bytes each
+  int decode_points(Mem where, int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!enc || !out_xy || !out_status);
+    if (int rc = host_first(where, nul)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
+      if (nul) return fail(E_ARG, "null pointer");
+      if (curve == CURVE_ED25519 && enc_len != 32) return fail(E_ARG, "ed25519 encodings are 32 bytes");
+      if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
+    }
+    const size_t B = ci->field_bytes;
+    return batch(where, n, {In{enc, enc_len}}, {Out{out_xy, 2 * B}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (curve == CURVE_ED25519) rc = ed_codec_chunk(OP_DECODE, m, d[0], 0, nullptr, r[0], r[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_DECODE, m, d[0], enc_len, 0, nullptr, r[0], r[1]));
+      return rc;
+    });
+  }
+  static size_t encoded_len(int curve, size_t B, int compact) {
+    return curve == CURVE_ED25519 ? 32 : (compact ? 1 + B : 1 + 2 * B);
+  }
+  // BasePoint#encode (base.js:295-311) / EDDSA#encodePoint (eddsa/index.js:94-98)
+  int encode_points(Mem where, int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!xy || !out_enc);
+    if (int rc = host_first(where, nul)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
+      if (nul) return fail(E_ARG, "null pointer");
+    }
+    const size_t B = ci->field_bytes;
+    return batch(where, n, {In{xy, 2 * B}}, {Out{out_enc, encoded_len(curve, B, compact)}}, [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (curve == CURVE_ED25519) rc = ed_codec_chunk(OP_ENCODE, m, d[0], 0, nullptr, r[0], nullptr);
+      else ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_ENCODE, m, d[0], 0, compact, nullptr, r[0], nullptr));
+      return rc;
+    });
+  }
+  // KeyPair#validate (ec/key.js:41-52): 0 ok, 1 'Invalid public key' (inf[i] set), 2 'Public key
+  // is not a point', 3 'Public key * N != O' (only tested when check_order)
+  int validate(Mem where, int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!xy || !out_status);
+    if (int rc = host_first(where, nul)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 points are x-only");
+      if (nul) return fail(E_ARG, "null pointer");
+    }
+    const size_t B = ci->field_bytes;
+    return batch(where, n, {In{xy, 2 * B}, In{inf, 1}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (curve == CURVE_ED25519) rc = ed_codec_chunk(OP_VALIDATE, m, d[0], check_order, d[1], nullptr, r[0]);
+      else ELL_SHORT_DISPATCH(curve, rc = codec_chunk<CV>(OP_VALIDATE, m, d[0], 0, check_order, d[1], nullptr, r[0]));
+      return rc;
+    });
+  }
+
+  // ---- Point#add on affine points (short.js:365-412, edwards.js:350-360) ----------------
+  int point_add(Mem where, int curve, size_t n, const u8* xy1, const u8* inf1, const u8* xy2, const u8* inf2,
+                u8* out_xy, u8* out_inf) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    const bool nul = n && (!xy1 || !xy2 || !out_xy || !out_inf);
+    if (int rc = host_first(where, nul)) return rc;
+    if (asks_curve(where, n)) {
+      if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");   // mont.js:103-105
+      if (nul) return fail(E_ARG, "null pointer");
+    }
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t B = ci->field_bytes;
+    return batch(where, n, {In{xy1, 2 * B}, In{inf1, 1}, In{xy2, 2 * B}, In{inf2, 1}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}},
+                 [&](size_t m, auto d, auto r) {
+      int rc = E_OK;
+      if (custom_is_edwards(curve)) rc = edc_chunk(2, m, nullptr, d[0], nullptr, d[2], d[1], d[3], r[0], r[1]);
+      else if (is_custom(curve)) rc = point_add_chunk<CvCustom>(m, d[0], d[1], d[2], d[3], r[0], r[1]);
+      else if (curve == CURVE_ED25519) rc = ed_point_add_chunk(m, d[0], d[1], d[2], d[3], r[0], r[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = point_add_chunk<CV>(m, d[0], d[1], d[2], d[3], r[0], r[1]));
+      return rc;
+    });
+  }
+
+  // ---- signature DER codec and EC#verify on wire formats ------------------------------
+  enum { OP_FROM_DER = 0, OP_TO_DER = 1, OP_WIRE_STATUS = 2 };
+  int check_short(int curve, const CurveInfo*& ci) {
+    ci = curve_info(curve);
+    if (!ci) return fail(E_ARG, "unknown curve id");
+    if (curve >= CURVE_ED25519) return fail(E_UNSUPPORTED, "ECDSA signatures belong to the short Weierstrass presets");
+    return E_OK;
+  }
+  // Signature#_importDER (ec/signature.js:83-147): der = n records of `stride` bytes, der_len[i] used
+  int sig_from_der(Mem where, int curve, size_t n, const u8* der, size_t stride, const u32* der_len,
+                   u8* out_r, u8* out_s, u8* out_status) {
+    const CurveInfo* ci;
+    int rc = check_short(curve, ci);
+    if (rc) return rc;
+    if (n && (!der || !der_len || !out_r || !out_s || !out_status)) return fail(E_ARG, "null pointer");
+    if (asks_curve(where, n) && stride == 0) return fail(E_ARG, "stride must be positive");
+    const size_t NB = ci->order_bytes;
+    return batch(where, n, {In{der, stride}, In{der_len, 4}}, {Out{out_r, NB}, Out{out_s, NB}, Out{out_status, 1}},
+                 [&](size_t m, auto d, auto r) {
+      ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_FROM_DER, m, d[0], nullptr, stride, (u32*)d[1], r[0], r[1], r[2]));
+      return rc;
+    });
+  }
+  // Signature#toDER (ec/signature.js:149-176): out = n records of `stride` >= 2 NB + 9 bytes
+  int sig_to_der(Mem where, int curve, size_t n, const u8* r, const u8* s, u8* out_der, size_t stride, u32* out_len) {
+    const CurveInfo* ci;
+    int rc = check_short(curve, ci);
+    if (rc) return rc;
+    if (n && (!r || !s || !out_der || !out_len)) return fail(E_ARG, "null pointer");
+    const size_t NB = ci->order_bytes;
+    if (asks_curve(where, n) && stride < 2 * NB + 9) return fail(E_ARG, "stride must be at least 2 * order_bytes + 9");
+    return batch(where, n, {In{r, NB}, In{s, NB}}, {Out{out_der, stride}, Out{out_len, 4}}, [&](size_t m, auto d, auto o) {
+      ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_TO_DER, m, d[0], d[1], stride, (u32*)o[1], o[0], nullptr, nullptr));
+      return rc;
+    });
+  }
+  // the scratch of a wire verify of m items: r, s (NB bytes each), the decoded key (2 B), and the
+  // statuses of the key, the signature and the verify
+  struct WireTmp { u8 *r, *s, *xy, *kst, *sst, *vst; };
+  bool wire_tmp(size_t m, size_t B, size_t NB, WireTmp& t) {
+    t.r = (u8*)scratch(S_WIRE, m * (2 * NB + 2 * B + 3));
+    if (!t.r) return false;
+    t.s = t.r + m * NB;
+    t.xy = t.s + m * NB;
+    t.kst = t.xy + m * 2 * B;
+    t.sst = t.kst + m;
+    t.vst = t.sst + m;
+    return true;
+  }
+  // EC#verify(msg, derSignature, encodedKey) (ec/index.js:188-229 with keyFromPublic ->
+  // decodePoint and new Signature(der)): decode, parse and verify on the device -- the three
+  // operations above, on scratch
+  int ecdsa_verify_wire(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits,
+                        const u8* der, size_t der_stride, const u32* der_len, const u8* pub_enc,
+                        size_t pub_len, u8* ok, u8* err) {
+    const CurveInfo* ci;
+    int rc = check_short(curve, ci);
+    if (rc) return rc;
+    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
+    if ((rc = host_first(where, false, hash_len))) return rc;
+    if (asks_curve(where, n) && (hash_len <= 0 || der_stride == 0 || pub_len == 0))
+      return fail(E_ARG, "bad hash_len / stride / pub_len");
+    const size_t B = ci->field_bytes, NB = ci->order_bytes;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
+                 {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto o) {
+      WireTmp t;
+      if (!wire_tmp(m, B, NB, t)) return fail(E_NOMEM, "scratch allocation failed");
+      rc = decode_points(Mem::device, curve, m, d[3], pub_len, t.xy, t.kst);
+      if (rc) return rc;
+      rc = sig_from_der(Mem::device, curve, m, d[1], der_stride, (const u32*)d[2], t.r, t.s, t.sst);
+      if (rc) return rc;
+      rc = ecdsa_verify(Mem::device, curve, m, d[0], hash_len, msg_bits, t.r, t.s, t.xy, o[0], t.vst);
+      if (rc) return rc;
+      ELL_SHORT_DISPATCH(curve, rc = der_chunk<CV>(OP_WIRE_STATUS, m, t.kst, t.sst, 0, nullptr, o[0], o[1], t.vst));
+      return rc;
+    });
+  }
+
+  // ---- wire formats on user-defined short curves -------------------------------------------
+  // ShortCurve#pointFromX, BaseCurve#decodePoint and EC#verify(msg, der, key) where the curve
+  // is the caller's own (ellgpu_custom_*).  Entry points of their own: the preset-named ones
+  // refuse user-defined ids before a kernel is chosen, and keep doing so.  Coordinates in and
+  // out are 32 bytes; a SEC1 coordinate is p.byteLength() bytes, the block's pbytes.
+  // The checks of the custom_* operations are the same in both forms, in the same order.
+  enum { OP_RT_DECOMPRESS = 0, OP_RT_DECODE = 1, OP_RT_FROM_DER = 2, OP_RT_WIRE_STATUS = 3 };
+  int check_custom_short(int curve, bool need_domain) {
+    if (!is_custom(curve))
+      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (the presets have ellgpu_decompress, ellgpu_decode_points and ellgpu_ecdsa_verify_wire)")
+                               : fail(E_ARG, "unknown curve id");
+    const RtField* f = custom_block(curve);
+    if (!f) return fail(E_ARG, "unknown curve id");
+    if (f->kind == 2) return fail(E_UNSUPPORTED, "not available on user-defined Montgomery curves (x-only: ellgpu_custom_mont_ladder, _validate, _derive)");
+    if (f->kind != 0) return fail(E_UNSUPPORTED, "not available on user-defined Edwards curves");
+    if (need_domain && !f->domain)
+      return fail(E_UNSUPPORTED, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    return E_OK;
+  }
+  // ... and a domain on it, for the operations that need n and G (msg: what to say to a plain id)
+  int check_custom_short_domain(int curve, const char* msg) {
+    const int rc = check_custom_short(curve, false);
+    return rc || custom_is_domain(curve) ? rc : fail(E_UNSUPPORTED, msg);
+  }
+  int custom_decompress(Mem where, int curve, size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!x || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{x, 32}, In{odd, 1}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return rt_wire_chunk(OP_RT_DECOMPRESS, m, d[0], d[1], 0, nullptr, r[0], r[1], nullptr);
+    });
+  }
+  // enc_len other than 1 + pbytes and 1 + 2 pbytes is no error of the call: every item is then
+  // 'Unknown point format', as in the reference
+  int custom_decode_points(Mem where, int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{enc, enc_len}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return rt_wire_chunk(OP_RT_DECODE, m, d[0], nullptr, enc_len, nullptr, r[0], r[1], nullptr);
+    });
+  }
+  // EC#verify(msg, derSignature, encodedKey) on a domain: decode, parse and verify on the device,
+  // composed like ecdsa_verify_wire
+  int custom_verify_wire(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* der,
+                         size_t der_stride, const u32* der_len, const u8* pub_enc, size_t pub_len, u8* ok, u8* err) {
+    int rc = check_custom_short(curve, true);
+    if (rc) return rc;
+    if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
+    if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
+                 {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto o) {
+      WireTmp t;
+      if (!wire_tmp(m, 32, 32, t)) return fail(E_NOMEM, "scratch allocation failed");
+      rc = rt_wire_chunk(OP_RT_DECODE, m, d[3], nullptr, pub_len, nullptr, t.xy, t.kst, nullptr);
+      if (rc) return rc;
+      rc = rt_wire_chunk(OP_RT_FROM_DER, m, d[1], nullptr, der_stride, (const u32*)d[2], t.r, t.s, t.sst);
+      if (rc) return rc;
+      rc = ecdsa_verify(Mem::device, curve, m, d[0], hash_len, msg_bits, t.r, t.s, t.xy, o[0], t.vst);
+      if (rc) return rc;
+      return rt_wire_chunk(OP_RT_WIRE_STATUS, m, t.kst, t.sst, 0, nullptr, o[0], o[1], t.vst);
+    });
+  }
+
+  // EC#recoverPubKey (ec/index.js:231-259) on a domain: status 0 point / 1 infinity / 2 the
+  // reference throws / 3 r = 0 or r >= n, as ecdsa_recover.  e = new BN(hash) is not
+  // truncated, only reduced mod n; s is not range-checked (the reference reduces it).
+  int custom_recover(Mem where, int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                     const u8* recid, u8* out_xy, u8* out_status) {
+    int rc = check_custom_short_domain(curve, "public-key recovery on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (rc) return rc;
+    if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
+    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{r, 32}, In{s, 32}, In{recid, 1}},
+                 {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      if ((rc = ensure_comb<CvCustomDomain>())) return rc;
+      return rt_recover_chunk(m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]);
+    });
+  }
+
+  // EC#sign (ec/index.js:110-186) on a domain: one pass of its loop for supplied nonces
+  // (nonces != null), or with the reference's own HmacDRBG over drbg_hash (nonces == null).
+  // The checks behind the domain check (rc: its result) are those of a short and of an Edwards domain.
+  int check_custom_sign(int rc, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                        const u8* nonces, bool det, int drbg_hash, u8* out_r, u8* out_s, u8* out_recid,
+                        u8* out_ok, int& shift) {
+    if (rc) return rc;
+    if (n && (!hash || !priv || (!det && !nonces) || !out_r || !out_s || !out_recid || !out_ok))
+      return fail(E_ARG, "null pointer");
+    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
+    if (det && (drbg_hash < 0 || drbg_hash > 2)) return fail(E_ARG, "drbg_hash must be ELLGPU_HASH_SHA256, _SHA384 or _SHA512");
+    const int nbits = (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits;
+    rc = truncate_shift(hash_len, msg_bits, nbits, 8, shift);
+    if (rc) return rc;
+    // hmac-drbg's constructor: entropy of n.byteLength() bytes against hmacStrength = 192 bits
+    if (det && (nbits + 7) / 8 < 24)
+      return fail(E_UNSUPPORTED, "EC#sign throws on this domain: 'Not enough entropy. Minimum is: 192 bits' (n.byteLength() < 24)");
+    return E_OK;
+  }
+  int custom_sign(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                  const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                  u8* out_recid, u8* out_ok) {
+    int shift;
+    int rc = check_custom_sign(check_custom_short_domain(curve, "ECDSA sign on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"),
+                               curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s, out_recid, out_ok, shift);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{priv, 32}, In{det ? nullptr : nonces, 32}},
+                 {Out{out_r, 32}, Out{out_s, 32}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto o) {
+      if ((rc = ensure_comb<CvCustomDomain>())) return rc;
+      return rt_sign_chunk(m, d[0], hash_len, shift, d[1], d[2], drbg_hash, canonical, o[0], o[1], o[2], o[3]);
+    });
+  }
+
+  // ---- the key side on user-defined short curves: ECDH, validation, SEC1 encoding ---------------
+  // KeyPair#derive (ec/key.js:101-107), KeyPair#validate (key.js:40-51) and BasePoint#encode
+  // (base.js:295-311).  derive and encode need neither n nor G: a plain define_short id will do;
+  // validate's order test needs the domain's n.
+  int custom_pbytes() const { return (int)custom_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].pbytes; }
+  // wire: pub is n SEC1 encodings of pub_len bytes (ellgpu_custom_derive_wire) -- a length that is
+  // neither 1 + pbytes nor 1 + 2 pbytes is no error of the call: every item is then 'Unknown point
+  // format' -- else n x 64 raw coordinates (ellgpu_custom_derive).  rc: the curve check's result;
+  // the rest is the same on a short and on an Edwards curve.
+  int check_custom_derive(int rc, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                          u8* out_status) {
+    if (rc) return rc;
+    if (n && (!priv || !pub || !out_x || !out_status)) return fail(E_ARG, "null pointer");
+    if (wire && pub_len == 0) return fail(E_ARG, "pub_len must be positive");
+    return E_OK;
+  }
+  int custom_derive(Mem where, int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                    u8* out_status, u8* out_err) {
+    int rc = check_custom_derive(check_custom_short(curve, false), n, priv, pub, wire, pub_len, out_x, out_status);
+    if (rc) return rc;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{priv, 32}, In{pub, wire ? pub_len : 64}}, {Out{out_x, 32}, Out{out_status, 1}, Out{out_err, 1}},
+                 [&](size_t m, auto d, auto o) {
+      return rt_derive_chunk(m, d[0], d[1], wire ? pub_len : 0, o[0], o[1], o[2]);
+    });
+  }
+  // statuses as validate's; check_order on a plain id: it has no n
+  int custom_validate(Mem where, int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (check_order && !custom_is_domain(curve))
+      return fail(E_UNSUPPORTED, "the order test on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    return batch(where, n, {In{xy, 64}, In{inf, 1}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      return rt_validate_chunk(m, d[0], d[1], check_order != 0, o[0]);
+    });
+  }
+  // rows of 1 + pbytes (compact) or 1 + 2 pbytes bytes
+  int custom_encode_points(Mem where, int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+    int rc = check_custom_short(curve, false);
+    if (rc) return rc;
+    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_pbytes();
+    return batch(where, n, {In{xy, 64}}, {Out{out_enc, EL}}, [&](size_t m, auto d, auto o) {
+      return rt_encode_chunk(m, d[0], compact, o[0]);
+    });
+  }
+
   // ---- user-defined Montgomery curves (ellgpu_custom_mont_*) --------------------------------
   // op as montc_chunk's.  A preset or unknown id is an argument error, a short or Edwards
   // user-defined id is unsupported.
   enum { OP_MONTC_LADDER = 0, OP_MONTC_VALIDATE = 1, OP_MONTC_DERIVE = 2 };
-  int check_custom_mont(int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
+  int custom_mont(Mem where, int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
     if (!is_custom(curve))
       return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (curve25519 has ellgpu_x25519_ladder and ellgpu_x25519_derive)")
                                : fail(E_ARG, "unknown curve id");
     const RtField* f = custom_block(curve);
     if (!f) return fail(E_ARG, "unknown curve id");
     if (f->kind != 2) return fail(E_UNSUPPORTED, "not a user-defined Montgomery curve (ellgpu_curve_define_mont)");
-    if (n && (!x || !out_flag || (op != OP_MONTC_VALIDATE && (!k || !out_x)))) return fail(E_ARG, "null pointer");
-    return E_OK;
-  }
-  int custom_mont_dev(int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
-    int rc = check_custom_mont(curve, op, n, k, x, out_x, out_flag);
-    if (rc) return rc;
+    const bool v = op == OP_MONTC_VALIDATE;        // (k and out_x unused: absent operands)
+    if (n && (!x || !out_flag || (!v && (!k || !out_x)))) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve, true);
     if (sc.rc) return sc.rc;
-    const bool v = op == OP_MONTC_VALIDATE;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return montc_chunk(op, m, v ? nullptr : k + o * 32, x + o * 32, v ? nullptr : out_x + o * 32, out_flag + o);
-    });
-  }
-  int custom_mont_host(int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
-    int rc = check_custom_mont(curve, op, n, k, x, out_x, out_flag);
-    if (rc) return rc;
-    CustomScope sc(this, curve, true);
-    if (sc.rc) return sc.rc;
-    if (op == OP_MONTC_VALIDATE)
-      return staged(n, {In{x, 32}}, {Out{out_flag, 1}}, [&](size_t m, auto d, auto r) {
-        return custom_mont_dev(curve, op, m, nullptr, d[0], nullptr, r[0]);
-      });
-    return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_flag, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_mont_dev(curve, op, m, d[0], d[1], r[0], r[1]);
-    });
+    return batch(where, n, {In{v ? nullptr : k, 32}, In{x, 32}}, {Out{v ? nullptr : out_x, 32}, Out{out_flag, 1}},
+                 [&](size_t m, auto d, auto r) { return montc_chunk(op, m, d[0], d[1], r[0], r[1]); });
   }
 
   // ---- the key side of user-defined Edwards curves (ellgpu_custom_ed_*) --------------------------
@@ -2982,123 +2708,61 @@ class Engine {
     if (f->kind != 1) return fail(E_UNSUPPORTED, "not a user-defined Edwards curve (ellgpu_curve_define_edwards)");
     return E_OK;
   }
-  int custom_ed_decompress_dev(int curve, size_t n, const u8* v, const u8* odd, int from_y, u8* out_xy, u8* out_status) {
+  int custom_ed_decompress(Mem where, int curve, size_t n, const u8* v, const u8* odd, int from_y, u8* out_xy, u8* out_status) {
     int rc = check_custom_ed(curve);
     if (rc) return rc;
     if (n && (!v || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve, false, true);
     if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edk_point_chunk(m, v + o * 32, odd + o, from_y ? 1 : 0, 0, out_xy + o * 64, out_status + o, nullptr);
-    });
-  }
-  int custom_ed_decompress_host(int curve, size_t n, const u8* v, const u8* odd, int from_y, u8* out_xy, u8* out_status) {
-    int rc = check_custom_ed(curve);
-    if (rc) return rc;
-    if (n && (!v || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve, false, true);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{v, 32}, In{odd, 1}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_ed_decompress_dev(curve, m, d[0], d[1], from_y, r[0], r[1]);
+    return batch(where, n, {In{v, 32}, In{odd, 1}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return edk_point_chunk(m, d[0], d[1], from_y ? 1 : 0, 0, r[0], r[1], nullptr);
     });
   }
   // enc_len other than 1 + PL and 1 + 2 PL is no error of the call: every item is then 'Unknown point format'
-  int custom_ed_decode_points_dev(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
+  int custom_ed_decode_points(Mem where, int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
     int rc = check_custom_ed(curve);
     if (rc) return rc;
     if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
     CustomScope sc(this, curve, false, true);
     if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edk_point_chunk(m, enc + o * enc_len, nullptr, 0, enc_len, out_xy + o * 64, out_status + o, nullptr);
+    return batch(where, n, {In{enc, enc_len}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return edk_point_chunk(m, d[0], nullptr, 0, enc_len, r[0], r[1], nullptr);
     });
   }
-  int custom_ed_decode_points_host(int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
-    int rc = check_custom_ed(curve);
-    if (rc) return rc;
-    if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
-    if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
-    CustomScope sc(this, curve, false, true);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{enc, enc_len}}, {Out{out_xy, 64}, Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_ed_decode_points_dev(curve, m, d[0], enc_len, r[0], r[1]);
-    });
-  }
-  // order: 32 bytes in HOST memory in both forms (a parameter of the call, not a batch operand), or null
-  int custom_ed_validate_dev(int curve, size_t n, const u8* xy, const u8* order_host, u8* out_status) {
+  // order_host: 32 bytes in HOST memory wherever the operands are (a parameter of the call, not a batch operand), or null
+  int custom_ed_validate(Mem where, int curve, size_t n, const u8* xy, const u8* order_host, u8* out_status) {
     int rc = check_custom_ed(curve);
     if (rc) return rc;
     if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve, false, true);
     if (sc.rc) return sc.rc;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edk_validate_chunk(m, xy + o * 64, order_host, out_status + o);
-    });
-  }
-  int custom_ed_validate_host(int curve, size_t n, const u8* xy, const u8* order, u8* out_status) {
-    int rc = check_custom_ed(curve);
-    if (rc) return rc;
-    if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve, false, true);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{xy, 64}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
-      return custom_ed_validate_dev(curve, m, d[0], order, r[0]);
+    return batch(where, n, {In{xy, 64}}, {Out{out_status, 1}}, [&](size_t m, auto d, auto r) {
+      return edk_validate_chunk(m, d[0], order_host, r[0]);
     });
   }
   // wire: pub is n SEC1 encodings of pub_len bytes (ellgpu_custom_ed_derive_wire), else n x 64 raw coordinates
-  int check_custom_ed_derive(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
-                             u8* out_status) {
-    int rc = check_custom_ed(curve);
-    if (rc) return rc;
-    if (n && (!priv || !pub || !out_x || !out_status)) return fail(E_ARG, "null pointer");
-    if (wire && pub_len == 0) return fail(E_ARG, "pub_len must be positive");
-    return E_OK;
-  }
-  int custom_ed_derive_dev(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
-                           u8* out_status, u8* out_err) {
-    int rc = check_custom_ed_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
+  int custom_ed_derive(Mem where, int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
+                       u8* out_status, u8* out_err) {
+    int rc = check_custom_derive(check_custom_ed(curve), n, priv, pub, wire, pub_len, out_x, out_status);
     if (rc) return rc;
     CustomScope sc(this, curve, false, true);
     if (sc.rc) return sc.rc;
-    const size_t PS = wire ? pub_len : 64;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edk_derive_chunk(m, priv + o * 32, pub + o * PS, wire ? pub_len : 0, out_x + o * 32, out_status + o,
-                              out_err ? out_err + o : nullptr);
-    });
-  }
-  int custom_ed_derive_host(int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
-                            u8* out_status, u8* out_err) {
-    int rc = check_custom_ed_derive(curve, n, priv, pub, wire, pub_len, out_x, out_status);
-    if (rc) return rc;
-    CustomScope sc(this, curve, false, true);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{priv, 32}, In{pub, wire ? pub_len : 64}}, {Out{out_x, 32}, Out{out_status, 1}, Out{out_err, 1}},
-                  [&](size_t m, auto d, auto o) {
-      return custom_ed_derive_dev(curve, m, d[0], d[1], wire, pub_len, o[0], o[1], o[2]);
+    return batch(where, n, {In{priv, 32}, In{pub, wire ? pub_len : 64}}, {Out{out_x, 32}, Out{out_status, 1}, Out{out_err, 1}},
+                 [&](size_t m, auto d, auto o) {
+      return edk_derive_chunk(m, d[0], d[1], wire ? pub_len : 0, o[0], o[1], o[2]);
     });
   }
   // rows of 1 + PL (compact) or 1 + 2 PL bytes: the short curve's row writer (Work::rt_encode_point)
-  int custom_ed_encode_points_dev(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
+  int custom_ed_encode_points(Mem where, int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
     int rc = check_custom_ed(curve);
     if (rc) return rc;
     if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve, false, true);
     if (sc.rc) return sc.rc;
     const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_ed_pbytes();
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edk_encode_chunk(m, xy + o * 64, compact, out_enc + o * EL);
-    });
-  }
-  int custom_ed_encode_points_host(int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
-    int rc = check_custom_ed(curve);
-    if (rc) return rc;
-    if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
-    CustomScope sc(this, curve, false, true);
-    if (sc.rc) return sc.rc;
-    const size_t EL = 1 + (compact ? 1 : 2) * (size_t)custom_ed_pbytes();
-    return staged(n, {In{xy, 64}}, {Out{out_enc, EL}}, [&](size_t m, auto d, auto o) {
-      return custom_ed_encode_points_dev(curve, m, d[0], compact, o[0]);
+    return batch(where, n, {In{xy, 64}}, {Out{out_enc, EL}}, [&](size_t m, auto d, auto o) {
+      return edk_encode_chunk(m, d[0], compact, o[0]);
     });
   }
 
@@ -3115,98 +2779,42 @@ class Engine {
       return fail(E_UNSUPPORTED, "ECDSA on a user-defined Edwards curve needs its domain (ellgpu_curve_define_edwards_domain)");
     return E_OK;
   }
-  int check_custom_ed_verify(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
-                             const u8* s, const u8* pub, u8* ok, int& shift) {
+  int custom_ed_verify(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
+                       const u8* s, const u8* pub, u8* ok, u8* st) {
+    int shift;
     int rc = check_custom_ed_domain(curve);
     if (rc) return rc;
     if (n && (!hash || !r || !s || !pub || !ok)) return fail(E_ARG, "null pointer");
     if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
-    return truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift);
-  }
-  int custom_ed_verify_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
-                           const u8* s, const u8* pub, u8* ok, u8* st) {
-    int shift;
-    int rc = check_custom_ed_verify(curve, n, hash, hash_len, msg_bits, r, s, pub, ok, shift);
+    rc = truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift);
     if (rc) return rc;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    rc = ensure_ed_gtable();
-    if (rc) return rc;
-    const size_t HL = (size_t)hash_len;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edc_verify_chunk(m, hash + o * HL, hash_len, shift, r + o * 32, s + o * 32, pub + o * 64, ok + o,
-                              st ? st + o : nullptr);
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{r, 32}, In{s, 32}, In{pub, 64}}, {Out{ok, 1}, Out{st, 1}},
+                 [&](size_t m, auto d, auto o) {
+      if ((rc = ensure_ed_gtable())) return rc;
+      return edc_verify_chunk(m, d[0], hash_len, shift, d[1], d[2], d[3], o[0], o[1]);
     });
   }
-  int custom_ed_verify_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
-                            const u8* s, const u8* pub, u8* ok, u8* st) {
+  // the argument list and semantics of custom_sign on a short domain
+  int custom_ed_sign(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
+                     const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
+                     u8* out_recid, u8* out_ok) {
     int shift;
-    int rc = check_custom_ed_verify(curve, n, hash, hash_len, msg_bits, r, s, pub, ok, shift);
+    int rc = check_custom_sign(check_custom_ed_domain(curve), curve, n, hash, hash_len, msg_bits, priv, nonces, det,
+                               drbg_hash, out_r, out_s, out_recid, out_ok, shift);
     if (rc) return rc;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    return staged(n, {In{hash, (size_t)hash_len}, In{r, 32}, In{s, 32}, In{pub, 64}}, {Out{ok, 1}, Out{st, 1}},
-                  [&](size_t m, auto d, auto o) {
-      return custom_ed_verify_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], d[3], o[0], o[1]);
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{priv, 32}, In{det ? nullptr : nonces, 32}},
+                 {Out{out_r, 32}, Out{out_s, 32}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto o) {
+      if ((rc = ensure_ed_gtable())) return rc;
+      return edc_sign_chunk(m, d[0], hash_len, shift, d[1], d[2], drbg_hash, canonical, o[0], o[1], o[2], o[3]);
     });
-  }
-  // the argument lists and semantics of check_custom_sign / custom_sign_* on a short domain
-  int check_custom_ed_sign(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                           const u8* nonces, bool det, int drbg_hash, u8* out_r, u8* out_s, u8* out_recid,
-                           u8* out_ok, int& shift) {
-    int rc = check_custom_ed_domain(curve);
-    if (rc) return rc;
-    if (n && (!hash || !priv || (!det && !nonces) || !out_r || !out_s || !out_recid || !out_ok))
-      return fail(E_ARG, "null pointer");
-    if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
-    if (det && (drbg_hash < 0 || drbg_hash > 2)) return fail(E_ARG, "drbg_hash must be ELLGPU_HASH_SHA256, _SHA384 or _SHA512");
-    const int nbits = (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits;
-    rc = truncate_shift(hash_len, msg_bits, nbits, 8, shift);
-    if (rc) return rc;
-    if (det && (nbits + 7) / 8 < 24)
-      return fail(E_UNSUPPORTED, "EC#sign throws on this domain: 'Not enough entropy. Minimum is: 192 bits' (n.byteLength() < 24)");
-    return E_OK;
-  }
-  int custom_ed_sign_dev(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                         const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
-                         u8* out_recid, u8* out_ok) {
-    int shift;
-    int rc = check_custom_ed_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
-                                  out_recid, out_ok, shift);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    rc = ensure_ed_gtable();
-    if (rc) return rc;
-    const size_t HL = (size_t)hash_len;
-    return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
-      return edc_sign_chunk(m, hash + o * HL, hash_len, shift, priv + o * 32, det ? nullptr : nonces + o * 32,
-                            drbg_hash, canonical, out_r + o * 32, out_s + o * 32, out_recid + o, out_ok + o);
-    });
-  }
-  int custom_ed_sign_host(int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* priv,
-                          const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
-                          u8* out_recid, u8* out_ok) {
-    int shift;
-    int rc = check_custom_ed_sign(curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s,
-                                  out_recid, out_ok, shift);
-    if (rc) return rc;
-    CustomScope sc(this, curve);
-    if (sc.rc) return sc.rc;
-    return staged(n, {In{hash, (size_t)hash_len}, In{priv, 32}, In{det ? nullptr : nonces, 32}},
-                  {Out{out_r, 32}, Out{out_s, 32}, Out{out_recid, 1}, Out{out_ok, 1}}, [&](size_t m, auto d, auto o) {
-      return custom_ed_sign_dev(curve, m, d[0], hash_len, msg_bits, d[1], d[2], det, drbg_hash, canonical, o[0], o[1],
-                                o[2], o[3]);
-    });
-  }
-  int x25519_host(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad = nullptr) {
-    if (n && (!k || !x || !out_x || !out_inf)) return fail(E_ARG, "null pointer");
-    return staged(n, {In{k, 32}, In{x, 32}}, {Out{out_x, 32}, Out{out_inf, 1}, Out{out_bad, 1}},
-                  [&](size_t m, auto d, auto r) { return x25519_dev(m, d[0], d[1], r[0], r[1], r[2]); });
   }
 
-  // scratch arena of the current call (0 / 1: the compute lanes of pipelined(); a *_dev call takes
-  // the lane of its stream, HipBackend::use_stream_dev)
+  // scratch arena of the current call (0 / 1: the compute lanes of pipelined(); a device-pointer
+  // call takes the lane of its stream, HipBackend::use_stream_dev)
   void set_lane(int l) { lane_ = l & 1; }
   int reserve(int curve, size_t n) {
     // run a dummy-sized allocation pass by touching the arena the way a verify /
