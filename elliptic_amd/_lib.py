@@ -38,6 +38,11 @@ _SIGS = {
     "ellgpu_ctx_synchronize": (ctypes.c_int, [ctypes.c_void_p]),
     "ellgpu_ctx_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]),
     "ellgpu_ctx_comb_bits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "ellgpu_base_define": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_u8p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "ellgpu_base_release": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "ellgpu_base_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
+    "ellgpu_mul_base": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, c_u8p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_void_p]),
+    "ellgpu_mul_base2": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_void_p]),
     "ellgpu_mul_fixed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, c_u8p, c_u8p, c_u8p]),
     "ellgpu_mul_var": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, c_u8p, c_u8p, c_u8p, c_u8p]),
     "ellgpu_mul_add2": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),

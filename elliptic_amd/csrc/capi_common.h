@@ -328,6 +328,113 @@ int ellgpu_mul_fixed_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k,
                          uint8_t* out_inf, void* stream) {
   return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.mul_fixed(w, curve, n, k, out_xy, out_inf); });
 }
+
+// ---- fixed-base tables of caller-chosen points (Engine::define_base) ----
+int ellgpu_base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window_bits, int* out_base) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  ELL_LOCK(ctx);
+  if (!ctx->members.empty()) {
+    // all or nothing, with one handle: what the members built before one of them refused is
+    // released again (never a base that existed before this call)
+    if (!out_base) return set_err(ELLGPU_E_ARG, "null pointer");
+    std::vector<int> made(ctx->members.size(), -1);
+    int id = -1, rc = ELLGPU_OK;
+    std::string msg;
+    for (size_t i = 0; i < ctx->members.size() && rc == ELLGPU_OK; i++) {
+      ellgpu_ctx* m = ctx->members[i];
+      std::lock_guard<std::recursive_mutex> g(m->mu);
+      ell_enter(*m->eng, nullptr, Mem::host);
+      int h = -1;
+      bool created = false;
+      rc = finish(m, m->eng->define_base(curve, xy, window_bits, &h, &created));
+      if (rc) { msg = g_last_error; break; }
+      if (created) made[i] = h;
+      if (i && h != id) { rc = ELLGPU_E_ARG; msg = "group members disagree on the base handle (bases were defined on a member directly)"; }
+      id = h;
+    }
+    if (rc) {
+      for (size_t i = 0; i < ctx->members.size(); i++)
+        if (made[i] >= 0) {
+          ellgpu_ctx* m = ctx->members[i];
+          std::lock_guard<std::recursive_mutex> g(m->mu);
+          ell_enter(*m->eng, nullptr, Mem::host);
+          finish(m, m->eng->release_base(made[i], true));     // never issued: the member's counter goes back
+        }
+      return set_err(rc, msg);
+    }
+    *out_base = id;
+    return ELLGPU_OK;
+  }
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem) { return e.define_base(curve, xy, window_bits, out_base); });
+}
+int ellgpu_base_release(ellgpu_ctx* ctx, int base) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  if (!ctx->members.empty()) {
+    ELL_LOCK(ctx);
+    int rc = ELLGPU_OK;
+    for (ellgpu_ctx* m : ctx->members) {
+      const int r = ellgpu_base_release(m, base);
+      if (r && !rc) rc = r;
+    }
+    return rc;
+  }
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem) { return e.release_base(base); });
+}
+int ellgpu_base_info(ellgpu_ctx* ctx, int base, int* out_curve, int* out_window_bits, uint64_t* out_table_bytes) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem) {
+    ell::u64 bytes = 0;
+    const int rc = e.base_info(base, out_curve, out_window_bits, &bytes);
+    if (rc == ELLGPU_OK && out_table_bytes) *out_table_bytes = (uint64_t)bytes;
+    return rc;
+  });
+}
+// `mem` / `stream` of the calls that have one form: -> where the operands live, or a refusal
+static int mem_of(int mem, void* stream, Mem& where) {
+  if (mem != ELLGPU_MEM_HOST && mem != ELLGPU_MEM_DEVICE) return set_err(ELLGPU_E_ARG, "mem: ELLGPU_MEM_HOST or ELLGPU_MEM_DEVICE");
+  if (mem == ELLGPU_MEM_HOST && stream) return set_err(ELLGPU_E_ARG, "a stream goes with ELLGPU_MEM_DEVICE: host memory takes NULL");
+  where = mem == ELLGPU_MEM_HOST ? Mem::host : Mem::device;
+  return ELLGPU_OK;
+}
+int ellgpu_mul_base(ellgpu_ctx* ctx, int base, size_t n, const uint8_t* k, uint8_t* out_xy, uint8_t* out_inf,
+                    int mem, void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (!ctx->members.empty() && where == Mem::host) {
+    ELL_LOCK(ctx);
+    int curve = -1;
+    if (int rc = ellgpu_base_info(ctx, base, &curve, nullptr, nullptr)) return rc;
+    size_t B, NB;
+    if (curve_widths(curve, B, NB)) return ELLGPU_E_ARG;
+    if (n && (!k || !out_xy || !out_inf)) return set_err(ELLGPU_E_ARG, "null pointer");
+    return group_shard(ctx, n, [=](ellgpu_ctx* m, size_t lo, size_t hi) {
+      return ellgpu_mul_base(m, base, hi - lo, k + lo * B, out_xy + lo * 2 * B, out_inf + lo, mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) { return e.mul_base(w, base, n, k, out_xy, out_inf); });
+}
+int ellgpu_mul_base2(ellgpu_ctx* ctx, int base1, int base2, size_t n, const uint8_t* k1, const uint8_t* k2,
+                     uint8_t* out_xy, uint8_t* out_inf, int mem, void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (!ctx->members.empty() && where == Mem::host) {
+    ELL_LOCK(ctx);
+    int c1 = -1, c2 = -1;
+    if (int rc = ellgpu_base_info(ctx, base1, &c1, nullptr, nullptr)) return rc;
+    if (int rc = ellgpu_base_info(ctx, base2, &c2, nullptr, nullptr)) return rc;
+    if (c1 != c2) return set_err(ELLGPU_E_ARG, "the two bases are on different curves");
+    size_t B, NB;
+    if (curve_widths(c1, B, NB)) return ELLGPU_E_ARG;
+    if (n && (!k1 || !k2 || !out_xy || !out_inf)) return set_err(ELLGPU_E_ARG, "null pointer");
+    return group_shard(ctx, n, [=](ellgpu_ctx* m, size_t lo, size_t hi) {
+      return ellgpu_mul_base2(m, base1, base2, hi - lo, k1 + lo * B, k2 + lo * B, out_xy + lo * 2 * B, out_inf + lo,
+                              mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) { return e.mul_base2(w, base1, base2, n, k1, k2, out_xy, out_inf); });
+}
 int ellgpu_mul_var(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k, const uint8_t* in_xy,
                    uint8_t* out_xy, uint8_t* out_inf) {
   if (ctx && !ctx->members.empty()) {

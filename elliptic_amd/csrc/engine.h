@@ -186,6 +186,76 @@ struct FnCombGen {
     store_be<W::L>(xy + i * 2 * W::BYTES + W::BYTES, gy, W::BYTES);
   }
 };
+// ... of a caller-chosen base (Engine::define_base): FnCombGen with the point read from a device
+// buffer, x || y big-endian.  The scalar is reduced mod n on the presets -- every point of a preset
+// has the prime order n, so ((d << sh) mod n) * P is exact and never O -- and left as it stands on
+// a user-defined curve, whose bases have no known order (an entry that comes out O refuses the base)
+template <class CV>
+struct FnBaseCombGen {
+  static constexpr const char* NAME = "base_comb_gen";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; size_t first; const u8* pt; u8* k; u8* xy; int cb;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i >= n) return;
+    const size_t idx = first + i;
+    const size_t per = W::COMB_SIGNED ? ((size_t)1 << (cb - 1)) : (size_t)W::COMB_DIG;
+    const int w = (int)(idx / per);
+    const u32 d = (u32)(idx % per) + 1u;
+    const int sh = w * (W::COMB_SIGNED ? cb : W::COMB_BITS);
+    constexpr int LN = W::LN;
+    u32 v[2 * LN];
+    ELL_UNROLL
+    for (int l = 0; l < 2 * LN; l++) v[l] = 0;
+    const int li = sh >> 5, bs = sh & 31;
+    ELL_UNROLL
+    for (int l = 0; l < 2 * LN; l++) {
+      if (l == li) v[l] = d << bs;
+      if (l == li + 1 && bs) v[l] = d >> (32 - bs);
+    }
+    u32 kk[W::L];
+    if constexpr (CV::RT_ORDER) {
+      ELL_UNROLL
+      for (int l = 0; l < W::L; l++) kk[l] = v[l];
+    } else {
+      u8 vb[8 * LN];
+      store_be<2 * LN>(vb, v, 8 * LN);
+      typename W::Nl km = W::bytes_mod_n(vb, 8 * LN);
+      u32 kn[LN];
+      W::Fn::to_plain(kn, km);
+      ELL_UNROLL
+      for (int l = 0; l < W::L; l++) kk[l] = l < LN ? kn[l] : 0u;
+    }
+    store_be<W::L>(k + i * W::BYTES, kk, W::BYTES);
+    ELL_NOUNROLL
+    for (int b = 0; b < 2 * W::BYTES; b++) xy[i * 2 * W::BYTES + b] = pt[b];
+  }
+};
+// the test of a base before its table is built: flag[0] = 1 where a coordinate is >= p or the
+// point is not on the curve
+template <class CV>
+struct FnBaseCheck {
+  static constexpr const char* NAME = "base_check";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  const u8* pt; u8* flag;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i) return;
+    flag[0] = W::base_ok(pt) ? 0 : 1;
+  }
+};
+// k1 * B1 + k2 * B2 over two fixed-base tables, one item per lane (Work::mul_base2)
+template <class CV, int MW = 0>
+struct FnMulBase2 {
+  static constexpr const char* NAME = "mul_base2";
+  typedef Work<CV> W;
+  static constexpr int MIN_WAVES = MW ? MW : (W::L <= 8 ? ELL_FIXED_MIN_WAVES : 1);
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* k1; const typename W::A* t1; const u8* k2; const typename W::A* t2; u32* jac;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::mul_base2(i, n, k1, t1, k2, t2, jac);
+  }
+};
 template <class CV>
 struct FnNormalize {
   static constexpr const char* NAME = "normalize";
@@ -1437,6 +1507,8 @@ class Engine {
   ~Engine() {
     for (int i = 0; i < COMB_SLOTS; i++)
       if (comb_[i]) bk.free_(comb_base_[i] ? comb_base_[i] : comb_[i]);
+    for (auto& r : bases_)
+      if (!r.alias) bk.free_(r.t.base);
     for (auto& a : scratch_)
       for (auto& s : a)
         if (s.p) bk.free_(s.p);
@@ -1463,6 +1535,8 @@ class Engine {
   int fail(int code, const char* msg) { err = msg; return code; }
 
   // ---- fixed-base comb tables, built on the device with our own kernels ----
+  // a built table: entry 0, what was allocated, the window width in use, the allocation's bytes
+  struct CombTable { void* comb = nullptr; void* base = nullptr; int bits = 0; size_t bytes = 0; };
   template <class CV>
   int ensure_comb();
   template <class CV>
@@ -1470,8 +1544,21 @@ class Engine {
   template <class CV>
   int mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf,
                     typename Work<CV>::A* raw);
+  // (comb: the curve's own table for mul_fixed, a caller-chosen base's for mul_base)
   template <class CV>
-  int mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_inf);
+  int mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, u8* out_xy, u8* out_inf);
+  // the loop that builds a comb: gen(m, first, dk, dp, cb) writes the scalars and points of the
+  // entries [first, first + m), the variable-base kernel turns them into the entries.  cb: the
+  // window width to start from; narrow: go on to narrower signed combs on E_NOMEM; check_inf
+  // (user-defined ids): fetch the entries' infinity flags and refuse a table that holds O
+  template <class CV, class Gen>
+  int build_comb(int cb, bool narrow, bool check_inf, Gen gen, CombTable& out);
+  // tests a caller-chosen base on the device and builds its table (define_base)
+  template <class CV>
+  int base_table(const u8* xy, int window_bits, CombTable& out);
+  template <class CV>
+  int mul_base2_chunk(size_t n, const u8* k1, const typename Work<CV>::A* t1, const u8* k2,
+                      const typename Work<CV>::A* t2, u8* out_xy, u8* out_inf);
   template <class CV>
   int mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                      u8* out_xy, u8* out_inf);
@@ -2090,15 +2177,19 @@ class Engine {
     return batch(where, n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
       int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
       if (rc) return rc;
-      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], r[0], r[1]);
+      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], comb_of<CvCustomDomain>(), r[0], r[1]);
       else if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, d[0], r[0], r[1]);
-      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], r[0], r[1]));
+      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], comb_of<CV>(), r[0], r[1]));
       return rc;
     });
   }
 
   static bool overlap(const u8* a, const u8* b, size_t bytes) {
     return a && b && bytes && (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
+  }
+  // ... of two ranges with sizes of their own
+  static bool overlap2(const u8* a, size_t na, const u8* b, size_t nb) {
+    return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
   }
   int mul_var(Mem where, int curve, size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
     const CurveInfo* ci = curve_info(curve);
@@ -2165,6 +2256,216 @@ class Engine {
       else if (curve == CURVE_ED25519) rc = ed_mul_add2_chunk(m, d[0], d[1], d[2], d[3], r[0], r[1]);
       else ELL_SHORT_DISPATCH(curve, rc = d[1] ? mul_add2_chunk<CV>(m, d[0], d[1], d[2], d[3], r[0], r[1])
                                                : mul_add_g_chunk<CV>(m, d[0], d[2], d[3], r[0], r[1]));
+      return rc;
+    });
+  }
+
+  // ---- fixed-base tables of caller-chosen points: BasePoint#precompute on the device ----------
+  // define_base builds the comb of a point the caller uses repeatedly (a Pedersen H, a recipient's
+  // or a verifier's key, a static ECDH key); mul_base is then mul_fixed over that table and
+  // mul_base2 walks two tables into one accumulator.  Short curves only: the six presets and
+  // user-defined short ids, plain and domain.
+  //   xy == null      the curve's own generator: the handle ALIASES the curve's table (built at
+  //                   first use by ensure_comb; release does not free it)
+  //   window_bits     signed combs (Work::COMB_SIGNED): 0, 4, 8, 12, 16 or 22, 0 = 16 (or G's own
+  //                   width where that is narrower: the CPU unit-test build), narrowed on E_NOMEM
+  //                   as ensure_comb narrows; an explicit width that does not fit is E_NOMEM.
+  //                   Unsigned combs: 0 or 8.
+  // Order of the base.  On a preset every curve point has the prime order n, so the entries
+  // ((d << sh) mod n) * P are exact and never O.  On a user-defined id nothing is reduced and the
+  // base may have a small order: an entry that is O (stored as (0, 0), which the walks would add
+  // as a point) refuses the base.
+  // The same (curve, point, width in use) gives the same handle; handles are never reused.
+  static constexpr int BASE_MAX = 16;
+  struct BaseRec {
+    int handle, curve, asked;
+    bool alias;
+    CombTable t;
+    u8 xy[2 * 66];
+  };
+  BaseRec* base_rec(int handle) {
+    for (auto& r : bases_)
+      if (r.handle == handle) return &r;
+    fail(E_ARG, "unknown base handle");
+    return nullptr;
+  }
+  // is the curve's comb a signed one (E_OK), with the refusals of define_base for the others
+  int base_curve_kind(int curve, bool& sgn) {
+    if (!curve_info(curve)) return fail(E_ARG, "unknown curve id");
+    if (curve == CURVE_ED25519 || curve == CURVE_CURVE25519)
+      return fail(E_UNSUPPORTED, "fixed-base tables of caller-chosen points are implemented for short Weierstrass curves");
+    sgn = false;
+    if (is_custom(curve)) {
+      size_t slot = (size_t)(curve - CURVE_CUSTOM0);
+      if (slot >= custom_.size()) return fail(E_ARG, "unknown curve id");
+      if (custom_[slot].kind != 0)
+        return fail(E_UNSUPPORTED, "fixed-base tables of caller-chosen points are implemented for short Weierstrass curves");
+      return E_OK;
+    }
+    ELL_SHORT_DISPATCH(curve, sgn = Work<CV>::COMB_SIGNED);
+    return E_OK;
+  }
+  // The kernels of a base on a user-defined id are the domain's (CvCustomDomain: the comb walks
+  // read the field alone), so a PLAIN id's block goes to their code object as well: the backend
+  // uploads it there for a block marked as a domain, and no kernel reads that mark.
+  void base_upload(int curve) {
+    if (!is_custom(curve) || custom_is_domain(curve)) return;
+    RtField f = custom_[(size_t)(curve - CURVE_CUSTOM0)];
+    f.domain = 1;
+    bk.rt_upload(f);
+  }
+  int define_base(int curve, const u8* xy, int window_bits, int* out_base, bool* created = nullptr) {
+    if (created) *created = false;
+    if (!out_base) return fail(E_ARG, "null pointer");
+    bool sgn = false;
+    if (int rc = base_curve_kind(curve, sgn)) return rc;
+    const bool dom = custom_is_domain(curve);
+    const size_t B = (size_t)curve_info(curve)->field_bytes;
+    if (!xy) {
+      if (is_custom(curve) && !dom) return fail(E_ARG, "a user-defined curve without a domain has no generator: pass the base's coordinates");
+      if (window_bits) return fail(E_ARG, "the curve's own generator comes with its own table: window_bits must be 0");
+    } else if (sgn ? !(window_bits == 0 || window_bits == 4 || window_bits == 8 || window_bits == 12 ||
+                       window_bits == 16 || window_bits == 22)
+                   : !(window_bits == 0 || window_bits == 8)) {
+      return fail(E_ARG, sgn ? "window_bits of a signed comb: 0, 4, 8, 12, 16 or 22" : "window_bits of an unsigned comb: 0 or 8");
+    }
+    auto same = [&](const BaseRec& r, int bits) {
+      if (r.curve != curve || r.alias != !xy) return false;
+      return r.alias || (memcmp(r.xy, xy, 2 * B) == 0 && (bits ? r.t.bits == bits : r.asked == 0));
+    };
+    for (auto& r : bases_)
+      if (same(r, window_bits)) { *out_base = r.handle; return E_OK; }
+    if ((int)bases_.size() >= BASE_MAX) return fail(E_UNSUPPORTED, "at most 16 live bases per context");
+    BaseRec rec;
+    rec.curve = curve;
+    rec.asked = window_bits;
+    rec.alias = !xy;
+    memset(rec.xy, 0, sizeof rec.xy);
+    if (xy) {
+      memcpy(rec.xy, xy, 2 * B);
+      CustomScope sc(this, curve);
+      if (sc.rc) return sc.rc;
+      base_upload(curve);
+      int rc = E_OK;
+      if (is_custom(curve)) rc = base_table<CvCustomDomain>(xy, window_bits, rec.t);
+      else ELL_SHORT_DISPATCH(curve, rc = base_table<CV>(xy, window_bits, rec.t));
+      if (rc) return rc;
+      // (a default width that narrowed may have arrived at a table that exists)
+      for (auto& r : bases_)
+        if (same(r, rec.t.bits)) {
+          bk.free_(rec.t.base);
+          *out_base = r.handle;
+          return E_OK;
+        }
+    }
+    rec.handle = next_base_++;
+    bases_.push_back(rec);
+    *out_base = rec.handle;
+    if (created) *created = true;
+    return E_OK;
+  }
+  // unissued: the handle never reached the caller (a group's define that another member refused
+  // takes it back, capi_common.h) -- the newest handle is then free again, so that the members'
+  // counters stay in step
+  int release_base(int handle, bool unissued = false) {
+    for (size_t i = 0; i < bases_.size(); i++)
+      if (bases_[i].handle == handle) {
+        if (unissued && handle == next_base_ - 1) next_base_--;
+        if (!bases_[i].alias) {
+          bk.sync_all();                          // a call on a caller's stream may still be walking the table
+          bk.free_(bases_[i].t.base);
+        }
+        bases_.erase(bases_.begin() + (long)i);
+        return E_OK;
+      }
+    return fail(E_ARG, "unknown base handle");
+  }
+  // an alias whose curve has not built its table yet reports 0 bits and 0 bytes
+  int base_info(int handle, int* out_curve, int* out_bits, u64* out_bytes) {
+    BaseRec* r = base_rec(handle);
+    if (!r) return E_ARG;
+    int bits = r->t.bits;
+    size_t bytes = r->t.bytes;
+    if (r->alias) {
+      bits = comb_[r->curve] ? (comb_bits_[r->curve] ? comb_bits_[r->curve] : 8) : 0;
+      bytes = 0;
+      if (bits) {
+        if (is_custom(r->curve)) bytes = comb_bytes<CvCustomDomain>(bits);
+        else ELL_SHORT_DISPATCH(r->curve, bytes = comb_bytes<CV>(bits));
+      }
+    }
+    if (out_curve) *out_curve = r->curve;
+    if (out_bits) *out_bits = bits;
+    if (out_bytes) *out_bytes = (u64)bytes;
+    return E_OK;
+  }
+  // entries (and bytes, with the header slot) of curve type CV's comb at window width cb
+  template <class CV>
+  static size_t comb_entries(int cb) {
+    typedef Work<CV> W;
+    return W::COMB_SIGNED ? (size_t)comb_windows(8 * W::BYTES, cb) << (cb - 1) : W::COMB_ENTRIES;
+  }
+  template <class CV>
+  static size_t comb_bytes(int cb) { return (comb_entries<CV>(cb) + 1) * sizeof(typename Work<CV>::A); }
+  // the table a base stands for, for the call in progress (an alias: the curve's own, built here
+  // on first use)
+  int base_table_ptr(const BaseRec& r, const void*& comb) {
+    if (!r.alias) { comb = r.t.comb; return E_OK; }
+    const int rc = custom_is_domain(r.curve) ? ensure_comb<CvCustomDomain>() : prepare_curve(r.curve);
+    comb = comb_[r.curve];
+    return rc;
+  }
+  // P.precompute(); P.mul(k): k as it stands (field_bytes bytes, neither reduced nor truncated, as
+  // in mul_fixed), out_inf = 1 and a zeroed result at O.  No status 2: the base was tested when defined.
+  int mul_base(Mem where, int base, size_t n, const u8* k, u8* out_xy, u8* out_inf) {
+    const BaseRec* r = base_rec(base);
+    if (!r) return E_ARG;
+    if (n && (!k || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
+    const int curve = r->curve;
+    const size_t B = (size_t)curve_info(curve)->field_bytes;
+    if (where == Mem::device && (overlap2(k, n * B, out_xy, n * 2 * B) || overlap2(k, n * B, out_inf, n)))
+      return fail(E_ARG, "k and the results must not overlap");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    base_upload(curve);
+    return batch(where, n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto o) {
+      const void* t = nullptr;
+      int rc = base_table_ptr(*r, t);
+      if (rc) return rc;
+      if (is_custom(curve)) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], (const Work<CvCustomDomain>::A*)t, o[0], o[1]);
+      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], (const typename Work<CV>::A*)t, o[0], o[1]));
+      return rc;
+    });
+  }
+  // k1 * B1 + k2 * B2 (_wnafMulAdd on two precomputed operands); base1 == base2 is allowed
+  int mul_base2(Mem where, int base1, int base2, size_t n, const u8* k1, const u8* k2, u8* out_xy, u8* out_inf) {
+    const BaseRec* r1 = base_rec(base1);
+    const BaseRec* r2 = r1 ? base_rec(base2) : nullptr;
+    if (!r1 || !r2) return E_ARG;
+    if (r1->curve != r2->curve) return fail(E_ARG, "the two bases are on different curves");
+    if (n && (!k1 || !k2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
+    const int curve = r1->curve;
+    const size_t B = (size_t)curve_info(curve)->field_bytes;
+    if (where == Mem::device)
+      for (const u8* k : {k1, k2})
+        if (overlap2(k, n * B, out_xy, n * 2 * B) || overlap2(k, n * B, out_inf, n))
+          return fail(E_ARG, "k1 / k2 and the results must not overlap");
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    base_upload(curve);
+    return batch(where, n, {In{k1, B}, In{k2, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto o) {
+      const void* t1 = nullptr;
+      const void* t2 = nullptr;
+      int rc = base_table_ptr(*r1, t1);
+      if (rc == E_OK) rc = base_table_ptr(*r2, t2);
+      if (rc) return rc;
+      if (is_custom(curve)) {
+        typedef const Work<CvCustomDomain>::A* T;
+        rc = mul_base2_chunk<CvCustomDomain>(m, d[0], (T)t1, d[1], (T)t2, o[0], o[1]);
+      } else {
+        ELL_SHORT_DISPATCH(curve, rc = mul_base2_chunk<CV>(m, d[0], (const typename Work<CV>::A*)t1, d[1],
+                                                            (const typename Work<CV>::A*)t2, o[0], o[1]));
+      }
       return rc;
     });
   }
@@ -2845,6 +3146,8 @@ class Engine {
   void* comb_[COMB_SLOTS];                   // entry 0 of the fixed-base table (the slot in front of it: its geometry)
   void* comb_base_[COMB_SLOTS];              // what was allocated
   int comb_bits_[COMB_SLOTS];                // window width in use (signed combs may be narrower than the default)
+  std::vector<BaseRec> bases_;               // the live caller-chosen bases (define_base), at most BASE_MAX
+  int next_base_ = 0;                        // handles are never reused
   Buf scratch_[2][S_COUNT];   // one scratch arena per compute lane (see pipelined())
   int lane_ = 0;
   Buf staging_[2 * STAGED_MAX];   // the host-buffer calls' device copies: inputs, then outputs (stage())
@@ -2863,8 +3166,24 @@ template <class CV>
 int Engine<BK>::ensure_comb() {
   typedef Work<CV> W;
   if (comb_[comb_idx<CV>()]) return E_OK;
+  CombTable t;
+  const int rc = build_comb<CV>(W::COMB_BITS, true, false, [&](size_t m, size_t first, u8* dk, u8* dp, int cb) {
+    FnCombGen<CV> g{m, first, dk, dp, cb};
+    bk.launch(g, m);
+  }, t);
+  if (rc) return rc;
+  comb_[comb_idx<CV>()] = t.comb;
+  comb_base_[comb_idx<CV>()] = t.base;
+  comb_bits_[comb_idx<CV>()] = t.bits;
+  return E_OK;
+}
+
+template <class BK>
+template <class CV, class Gen>
+int Engine<BK>::build_comb(int cb, bool narrow, bool check_inf, Gen gen, CombTable& out) {
+  typedef Work<CV> W;
   // Built by the engine itself: the variable-base kernel on the scalars d << (COMB_BITS w) and
-  // the generator, in slices of at most 2^20 entries (the 22-bit signed comb of the 256-bit
+  // the base, in slices of at most 2^20 entries (the 22-bit signed comb of the 256-bit
   // curves has 25 M entries = 1.6 GB; a slice needs 1 GB of window-table scratch).
   // A SIGNED comb (the 256-bit curves) carries its window width in the slot in front of entry 0
   // (ladder.h comb_bits_of): when the device cannot hold the default table -- 12 windows x 2^21
@@ -2872,48 +3191,87 @@ int Engine<BK>::ensure_comb() {
   // 36 MB), 12, 8, 4.  ELLGPU_COMB_MAX_BYTES (developer / test override, read when the context is
   // created) refuses larger tables as if the allocation had failed.
   const int B = W::BYTES;
-  int cb = W::COMB_BITS;
   for (;;) {
-    const size_t n = W::COMB_SIGNED ? (size_t)comb_windows(8 * B, cb) << (cb - 1) : W::COMB_ENTRIES;
+    const size_t n = comb_entries<CV>(cb);
     const size_t bytes = (n + 1) * sizeof(typename W::A);
     const size_t slice = n < (size_t)ELL_COMB_SLICE ? n : (size_t)ELL_COMB_SLICE;
     typename W::A* base = (tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) ? nullptr : (typename W::A*)bk.alloc(bytes);
     u8* dk = base ? (u8*)bk.alloc(slice * B) : nullptr;
     u8* dp = dk ? (u8*)bk.alloc(slice * 2 * B) : nullptr;
-    int rc = (base && dk && dp) ? E_OK : E_NOMEM;
+    // (check_inf: the entries as bytes, which nobody reads, and their infinity flags behind them)
+    u8* dchk = dp && check_inf ? (u8*)bk.alloc(slice * (2 * B + 1)) : nullptr;
+    int rc = (base && dk && dp && (dchk || !check_inf)) ? E_OK : E_NOMEM;
     if (rc == E_OK) {
       typename W::A* comb = base + 1;
       u32 hdr[sizeof(typename W::A) / 4] = {0};
       hdr[0] = (u32)cb;
       bk.h2d(base, hdr, sizeof hdr);
+      std::vector<u8> flags(check_inf ? slice : 0);
+      bool holds_inf = false;
       for (size_t first = 0; first < n && rc == E_OK; first += slice) {
         const size_t m = n - first < slice ? n - first : slice;
-        FnCombGen<CV> g{m, first, dk, dp, cb};
-        bk.launch(g, m);
+        gen(m, first, dk, dp, cb);
         // (a domain's entries come from the user-defined curves' own ladder: the same field and
         // points, no second instantiation of it)
         typedef typename std::conditional<CV::RT_ORDER, CvCustom, CV>::type CVL;
-        rc = mul_var_chunk<CVL>(m, dk, dp, nullptr, nullptr, comb + first);
+        rc = mul_var_chunk<CVL>(m, dk, dp, dchk, dchk ? dchk + slice * 2 * B : nullptr, comb + first);
+        if (rc == E_OK && check_inf) {
+          bk.d2h(flags.data(), dchk + slice * 2 * B, m);
+          if (bk.sync() == E_OK)
+            for (size_t i = 0; i < m; i++) holds_inf |= flags[i] != 0;
+        }
       }
       const int src = bk.sync();                   // a failed launch (comb_gen included) surfaces here
       if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
+      if (rc == E_OK && holds_inf) rc = fail(E_ARG, "a multiple of the base inside the table is the point at infinity");
       if (rc == E_OK) {
         bk.free_(dk);
         bk.free_(dp);
-        comb_[comb_idx<CV>()] = comb;
-        comb_base_[comb_idx<CV>()] = base;
-        comb_bits_[comb_idx<CV>()] = cb;
+        if (dchk) bk.free_(dchk);
+        out.comb = comb;
+        out.base = base;
+        out.bits = cb;
+        out.bytes = bytes;
         return E_OK;
       }
     }
+    if (dchk) bk.free_(dchk);
     if (dp) bk.free_(dp);
     if (dk) bk.free_(dk);
     if (base) bk.free_(base);
     // out of memory (the table, or the window-table scratch of its build): a narrower comb
-    if (rc != E_NOMEM || !W::COMB_SIGNED || cb <= 4) return rc == E_NOMEM ? fail(E_NOMEM, "comb table allocation failed") : rc;
+    if (rc != E_NOMEM || !narrow || !W::COMB_SIGNED || cb <= 4) return rc == E_NOMEM ? fail(E_NOMEM, "comb table allocation failed") : rc;
     err.clear();
     cb = cb > 16 ? 16 : (cb > 12 ? 12 : (cb > 8 ? 8 : 4));
   }
+}
+
+template <class BK>
+template <class CV>
+int Engine<BK>::base_table(const u8* xy, int window_bits, CombTable& out) {
+  typedef Work<CV> W;
+  const size_t B = W::BYTES;
+  u8* dpt = (u8*)bk.alloc(2 * B + 1);            // the point and, behind it, the test's flag
+  if (!dpt) return fail(E_NOMEM, "scratch allocation failed");
+  u8 flag = 1;
+  bk.h2d(dpt, xy, 2 * B);
+  FnBaseCheck<CV> chk{dpt, dpt + 2 * B};
+  bk.launch(chk, 1);
+  bk.d2h(&flag, dpt + 2 * B, 1);
+  int rc = bk.sync();
+  if (rc) rc = fail(rc, "testing the base failed on the device");
+  else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
+  if (rc == E_OK) {
+    // 0: 16 bits (36 MB, 17 additions per item) -- not G's 22 (1.6 GB): a caller may hold 16 bases
+    const int dflt = W::COMB_SIGNED ? (W::COMB_BITS < 16 ? W::COMB_BITS : 16) : W::COMB_BITS;
+    rc = build_comb<CV>(window_bits ? window_bits : dflt, window_bits == 0, CV::RT_ORDER,
+                        [&](size_t m, size_t first, u8* dk, u8* dp, int cb) {
+      FnBaseCombGen<CV> g{m, first, dpt, dk, dp, cb};
+      bk.launch(g, m);
+    }, out);
+  }
+  bk.free_(dpt);
+  return rc;
 }
 
 
@@ -2978,7 +3336,7 @@ int Engine<BK>::mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u
 
 template <class BK>
 template <class CV>
-int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_inf) {
+int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, u8* out_xy, u8* out_inf) {
   typedef Work<CV> W;
   // a handful of items: the comb and the item's own inversion on a wave, one launch (the scalar is
   // Point#mul's: BYTES bytes as they stand -- coop_sign_point<CW, false>, no _truncateToN)
@@ -2987,14 +3345,27 @@ int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_inf) 
   if constexpr ((row_k256 || row_nist) && W::NBYTES == W::BYTES) {
     if (n <= coop_grid_of<CV>() && out_inf) {
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
-      FnMulFixedC<CV, CW> fc{n, k, comb_of<CV>(), out_xy, out_inf};
+      FnMulFixedC<CV, CW> fc{n, k, comb, out_xy, out_inf};
       bk.launch_coop(fc, n);
       return E_OK;
     }
   }
   u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
   if (!jac) return fail(E_NOMEM, "scratch allocation failed");
-  launch_paired<FnMulFixed, CV>(n, k, comb_of<CV>(), jac);
+  launch_paired<FnMulFixed, CV>(n, k, comb, jac);
+  return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
+}
+
+
+template <class BK>
+template <class CV>
+int Engine<BK>::mul_base2_chunk(size_t n, const u8* k1, const typename Work<CV>::A* t1, const u8* k2,
+                                const typename Work<CV>::A* t2, u8* out_xy, u8* out_inf) {
+  typedef Work<CV> W;
+  // one item per lane at every n, and one normalisation for the sum
+  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
+  if (!jac) return fail(E_NOMEM, "scratch allocation failed");
+  launch_paired<FnMulBase2, CV>(n, k1, t1, k2, t2, jac);
   return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
 }
 

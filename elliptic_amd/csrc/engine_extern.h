@@ -16,7 +16,10 @@ namespace ell {
                                                           Work<CV>::A*);                           \
   KW template int Engine<HipBackend>::ensure_comb<CV>();
 #define ELL_DECL_G1(KW, CV) \
-  KW template int Engine<HipBackend>::mul_fixed_chunk<CV>(size_t, const u8*, u8*, u8*);
+  KW template int Engine<HipBackend>::mul_fixed_chunk<CV>(size_t, const u8*, const Work<CV>::A*, u8*, u8*); \
+  KW template int Engine<HipBackend>::base_table<CV>(const u8*, int, Engine<HipBackend>::CombTable&);      \
+  KW template int Engine<HipBackend>::mul_base2_chunk<CV>(size_t, const u8*, const Work<CV>::A*,           \
+                                                          const u8*, const Work<CV>::A*, u8*, u8*);
 #define ELL_DECL_G2(KW, CV)                                                                  \
   KW template int Engine<HipBackend>::mul_add2_chunk<CV>(size_t, const u8*, const u8*,       \
                                                          const u8*, const u8*, u8*, u8*);
@@ -96,13 +99,19 @@ namespace ell {
                                                          u8*, u8*);                                  \
   KW template int Engine<HipBackend>::rt_validate_chunk<0>(size_t, const u8*, const u8*, bool, u8*); \
   KW template int Engine<HipBackend>::rt_encode_chunk<0>(size_t, const u8*, int, u8*);
-// user-defined ECDSA domains (CvCustomDomain): verify, recovery, sign, k*G and k1*G + k2*Q -- their own translation
+// user-defined ECDSA domains (CvCustomDomain): verify, recovery, sign, k*G, k1*G + k2*Q and the tables of
+// caller-chosen bases (on plain ids too: Engine::base_upload) -- their own translation
 // unit (group 17, with its own parameter block); the window ladder of the comb build is CvCustom's
 #define ELL_DECL_DOMAIN(KW)                                                                          \
   KW template int Engine<HipBackend>::ensure_comb<CvCustomDomain>();                                 \
   KW template int Engine<HipBackend>::normalize_chunk<CvCustomDomain>(size_t, const u32*, u8*, u8*,  \
                                                                       Work<CvCustomDomain>::A*);     \
-  KW template int Engine<HipBackend>::mul_fixed_chunk<CvCustomDomain>(size_t, const u8*, u8*, u8*);  \
+  KW template int Engine<HipBackend>::mul_fixed_chunk<CvCustomDomain>(size_t, const u8*,             \
+                                                                      const Work<CvCustomDomain>::A*, u8*, u8*); \
+  KW template int Engine<HipBackend>::base_table<CvCustomDomain>(const u8*, int,                     \
+                                                                 Engine<HipBackend>::CombTable&);    \
+  KW template int Engine<HipBackend>::mul_base2_chunk<CvCustomDomain>(                               \
+      size_t, const u8*, const Work<CvCustomDomain>::A*, const u8*, const Work<CvCustomDomain>::A*, u8*, u8*); \
   KW template int Engine<HipBackend>::mul_add_g_chunk<CvCustomDomain>(size_t, const u8*, const u8*,  \
                                                                       const u8*, u8*, u8*);          \
   KW template int Engine<HipBackend>::ecdsa_chunk<CvCustomDomain>(size_t, const u8*, int, int,       \

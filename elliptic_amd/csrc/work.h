@@ -353,6 +353,36 @@ struct Work {
     store_jac(jac, n, i, r);
   }
 
+  // k1*B1 + k2*B2 over the tables of two caller-chosen bases (_wnafMulAdd on two precomputed
+  // operands, base.js:190-298) -> Jacobian.  One accumulator: the comb of k1 over t1, then the
+  // comb of k2 over t2 added onto it.  The tables may have different widths (each walk reads its
+  // own table's header), B2 may be +-B1: the accumulator meeting +- an entry and leaving O in the
+  // middle of the second walk are ordinary paths here (add_mixed_lean's rare branch).
+  ELL_HD static void mul_base2(size_t i, size_t n, const u8* k1s, const A* t1, const u8* k2s, const A* t2,
+                               u32* jac) {
+    u32 k[L];
+    load_be<L>(k, k1s + i * BYTES, BYTES);
+    bool inf = true;
+    J r = LD::template comb_add<L, COMB_W, COMB_BITS, false, COMB_SIGNED>(G::infinity(), inf, k, t1);
+    load_be<L>(k, k2s + i * BYTES, BYTES);
+    r = LD::template comb_add<L, COMB_W, COMB_BITS, false, COMB_SIGNED>(r, inf, k, t2);
+    // (an accumulator that ended on O may hold any X, Y beside Z = 0; normalize reads Z alone)
+    store_jac(jac, n, i, r);
+  }
+  // a base before its table is built: x, y < p and on the curve (x || y big-endian at pt)
+  ELL_HD static bool base_ok(const u8* pt) {
+    u32 x[L], y[L], pp[L];
+    load_be<L>(x, pt, BYTES);
+    load_be<L>(y, pt + BYTES, BYTES);
+    ELL_UNROLL
+    for (int l = 0; l < L; l++) {
+      if constexpr (CV::A_KIND == 1) pp[l] = ELL_RT.p[l];
+      else pp[l] = C::p[l];
+    }
+    if (bn_geq<L>(x, pp) || bn_geq<L>(y, pp)) return false;
+    return on_curve(load_affine(pt, 0));
+  }
+
   // ---- point decompression (ShortCurve#pointFromX, short.js:187-204) --------------
   // rhs = x^3 + a x + b  (ShortCurve#validate short.js:205-216 and pointFromX share it)
   ELL_HD static El curve_rhs(const El& x) {

@@ -83,6 +83,7 @@ class Context:
         self._pending_default = None
         self._pbytes = {}                 # p.byteLength() of the user-defined short curves (custom_encode_points)
         self._ed_pbytes = {}              # ... and of the user-defined Edwards curves (custom_ed_encode_points)
+        self._base_curve = {}             # curve of each define_base handle (the width of its scalars)
 
     def group_size(self):
         return self._lib.ellgpu_group_size(self._ctx)
@@ -205,6 +206,91 @@ class Context:
         self._check(self._lib.ellgpu_mul_fixed(self._ctx, self._cid(curve), n, k.ctypes.data,
                                                out.ctypes.data, inf.ctypes.data))
         return out, inf
+
+    # ---- fixed-base tables of caller-chosen points (ellgpu_base_*) -----------
+
+    def define_base(self, curve, xy=None, window_bits=0):
+        """Build the fixed-base table of a point that is used repeatedly (BasePoint#precompute on the
+        device) and return its handle for mul_base / mul_base2.  xy: x || y in the curve's coordinate
+        width (bytes or a uint8 array), or None for the curve's own generator -- the handle then
+        aliases the curve's own table.  window_bits: 0, 4, 8, 12, 16, 22 on secp256k1 and p256
+        (0 = 16), 0 or 8 elsewhere."""
+        cid = self._cid(curve)
+        h = ctypes.c_int(-1)
+        buf = None if xy is None else _u8(xy).reshape(-1)
+        self._check(self._lib.ellgpu_base_define(self._ctx, cid, None if buf is None else buf.ctypes.data,
+                                                 int(window_bits), ctypes.byref(h)))
+        self._base_curve[h.value] = curve
+        return h.value
+
+    def release_base(self, base):
+        self._check(self._lib.ellgpu_base_release(self._ctx, int(base)))
+        self._base_curve.pop(int(base), None)
+
+    def base_info(self, base):
+        """-> (curve id, window width in use, bytes of the table); 0 bits and 0 bytes for a generator
+        alias whose curve has not built its table yet"""
+        c, w, b = ctypes.c_int(-1), ctypes.c_int(0), ctypes.c_uint64(0)
+        self._check(self._lib.ellgpu_base_info(self._ctx, int(base), ctypes.byref(c), ctypes.byref(w), ctypes.byref(b)))
+        return c.value, w.value, b.value
+
+    def _base_width(self, base):
+        curve = self._base_curve.get(int(base))
+        if curve is None:
+            curve = self.base_info(base)[0]
+        return FIELD_BYTES[CURVES[curve] if isinstance(curve, int) and curve < len(CURVES) else curve]
+
+    @staticmethod
+    def _is_tensor(a):
+        return hasattr(a, "data_ptr")
+
+    def _dev_operands(self, base, ks, out):
+        """checks the device tensors of mul_base / mul_base2 before their addresses go to the library"""
+        if out is None or len(out) != 2:
+            raise ValueError("device tensors need out=(xy, inf): uint8 tensors (n, 2 * field_bytes) and (n,)")
+        B = self._base_width(base)
+        n = ks[0].shape[0]
+        import torch
+        for t, shape, name in [(k, (n, B), "k") for k in ks] + [(out[0], (n, 2 * B), "out xy"), (out[1], (n,), "out inf")]:
+            if not self._is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s: a contiguous uint8 tensor of shape %s is needed" % (name, shape))
+            if t.device != torch.device(self.device):
+                raise ValueError("%s is on %s, the context on %s" % (name, t.device, torch.device(self.device)))
+        return n
+
+    def mul_base(self, base, k, out=None):
+        """k * B for the base of a define_base handle -> (xy, inf).  k: (n, field_bytes), used as it
+        stands.  numpy arrays go through host memory; torch device tensors (k and out=(xy, inf), both
+        required then) run on the current stream and return at once."""
+        if self._is_tensor(k):
+            n = self._dev_operands(base, [k], out)
+            out_xy, out_inf = out
+            self._check(self._lib.ellgpu_mul_base(self._ctx, int(base), n, k.data_ptr(), out_xy.data_ptr(),
+                                                  out_inf.data_ptr(), 1, self._stream()))
+            return out_xy, out_inf
+        B = self._base_width(base)
+        k = _u8(k, (-1, B))
+        n = k.shape[0]
+        xy, inf = self._outs(out, [(n, 2 * B), (n,)])
+        self._check(self._lib.ellgpu_mul_base(self._ctx, int(base), n, k.ctypes.data, xy.ctypes.data, inf.ctypes.data, 0, None))
+        return xy, inf
+
+    def mul_base2(self, base1, base2, k1, k2, out=None):
+        """k1 * B1 + k2 * B2 over the tables of two bases of one curve -> (xy, inf); operands as in mul_base"""
+        if self._is_tensor(k1):
+            n = self._dev_operands(base1, [k1, k2], out)
+            out_xy, out_inf = out
+            self._check(self._lib.ellgpu_mul_base2(self._ctx, int(base1), int(base2), n, k1.data_ptr(), k2.data_ptr(),
+                                                   out_xy.data_ptr(), out_inf.data_ptr(), 1, self._stream()))
+            return out_xy, out_inf
+        B = self._base_width(base1)
+        k1 = _u8(k1, (-1, B))
+        n = k1.shape[0]
+        k2 = _u8(k2, (n, B))
+        xy, inf = self._outs(out, [(n, 2 * B), (n,)])
+        self._check(self._lib.ellgpu_mul_base2(self._ctx, int(base1), int(base2), n, k1.ctypes.data, k2.ctypes.data,
+                                               xy.ctypes.data, inf.ctypes.data, 0, None))
+        return xy, inf
 
     def mul_var(self, curve, k, xy, out=None):
         """out: optional (xy, inf) uint8 arrays to write into (reusing result buffers spares a

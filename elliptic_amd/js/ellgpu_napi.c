@@ -50,6 +50,9 @@
  *             (ellgpu_custom_derive / _custom_derive_wire / _custom_validate / _custom_encode_points)
  *             and, on a user-defined Montgomery curve (defineMont(ctx, p, a); ellgpu_custom_mont_ladder /
  *             _validate / _derive), the ops 17..19: Point#mul + getX, MontCurve#validate, KeyPair#derive
+ *           defineBase(ctx, curve, xy|null, windowBits) -> handle, releaseBase(ctx, base), baseInfo(ctx, base) ->
+ *             {curve, windowBits, tableBytes}, mulBase(ctx, base, k) -> {xy, inf}, mulBase2(ctx, base1, base2, k1, k2)
+ *             -> {xy, inf}: fixed-base tables of caller-chosen points (ellgpu_base_*)
  *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
  *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
  *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
@@ -75,6 +78,7 @@
  *             26 customEdVerify(hash, r, s, pub) -> {ok, status}  27 customEdSign (as 11)  28 customEdSignDet (as 12)
  *             (ellgpu_custom_ed_verify / _sign / _sign_det: ECDSA on a user-defined Edwards domain,
  *             defineEdwardsDomain(ctx, p, a, d, n, gx, gy); sync forms customEdVerify, customEdSign, customEdSignDet);
+ *             29 mulBase(k; curve = the base's curve, i0 = base)  30 mulBase2(k1, k2; i0, i1 = the bases) -> {xy, inf};
  *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
@@ -125,6 +129,11 @@ static struct {
                              const uint8_t*, const uint8_t*, int*);
   void (*ctx_destroy)(ellgpu_ctx*);
   int (*mul_fixed)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*);
+  int (*base_define)(ellgpu_ctx*, int, const uint8_t*, int, int*);
+  int (*base_release)(ellgpu_ctx*, int);
+  int (*base_info)(ellgpu_ctx*, int, int*, int*, uint64_t*);
+  int (*mul_base)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*, int, void*);
+  int (*mul_base2)(ellgpu_ctx*, int, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, int, void*);
   int (*mul_var)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
   int (*mul_add2)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, const uint8_t*,
                   const uint8_t*, uint8_t*, uint8_t*);
@@ -217,6 +226,8 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(define_short, "ellgpu_curve_define_short");
   SYM(define_edwards, "ellgpu_curve_define_edwards");
   SYM(define_mont, "ellgpu_curve_define_mont");
+  SYM(base_define, "ellgpu_base_define"); SYM(base_release, "ellgpu_base_release"); SYM(base_info, "ellgpu_base_info");
+  SYM(mul_base, "ellgpu_mul_base"); SYM(mul_base2, "ellgpu_mul_base2");
   SYM(custom_mont_ladder, "ellgpu_custom_mont_ladder");
   SYM(custom_mont_validate, "ellgpu_custom_mont_validate");
   SYM(custom_mont_derive, "ellgpu_custom_mont_derive");
@@ -525,6 +536,81 @@ static napi_value fn_comb_bits(napi_env env, napi_callback_info info) {
   if (v < 0) return lib_error(env);
   napi_value r; CHECK(env, napi_create_int32(env, v, &r)); return r;
 }
+
+/* ---- fixed-base tables of caller-chosen points (ellgpu_base_*): host memory throughout ----
+ * defineBase(ctx, curve, xy|null, windowBits) -> handle; releaseBase(ctx, base);
+ * baseInfo(ctx, base) -> {curve, windowBits, tableBytes}; mulBase(ctx, base, k) -> {xy, inf};
+ * mulBase2(ctx, base1, base2, k1, k2) -> {xy, inf}.  The rows' width is the width of the base's
+ * curve, asked of the library (ellgpu_base_info). */
+static napi_value fn_define_base(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 4; napi_value argv[4];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 4) THROW(env, "defineBase(ctx, curve, xy|null, windowBits)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  int32_t curve, wb;
+  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &wb) != napi_ok)
+    THROW(env, "defineBase(ctx, curve, xy|null, windowBits)");
+  const uint8_t* xy; size_t l;
+  if (!get_buf(env, argv[2], &xy, &l, 1)) return NULL;
+  int B = L.field_bytes(curve);
+  if (xy && B > 0 && l != 2 * (size_t)B) THROW(env, "defineBase: xy is x || y in the curve's coordinate width");
+  int h = -1;
+  if (L.base_define(c, curve, xy, wb, &h) != 0) return lib_error(env);
+  napi_value v; CHECK(env, napi_create_int32(env, h, &v));
+  return v;
+}
+static napi_value fn_release_base(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 2; napi_value argv[2]; int32_t base;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  if (argc < 2 || napi_get_value_int32(env, argv[1], &base) != napi_ok) THROW(env, "releaseBase(ctx, base)");
+  if (L.base_release(c, base) != 0) return lib_error(env);
+  return NULL;
+}
+static napi_value fn_base_info(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 2; napi_value argv[2]; int32_t base;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  if (argc < 2 || napi_get_value_int32(env, argv[1], &base) != napi_ok) THROW(env, "baseInfo(ctx, base)");
+  int curve = -1, bits = 0; uint64_t bytes = 0;
+  if (L.base_info(c, base, &curve, &bits, &bytes) != 0) return lib_error(env);
+  napi_value o, v;
+  CHECK(env, napi_create_object(env, &o));
+  CHECK(env, napi_create_int32(env, curve, &v)); CHECK(env, napi_set_named_property(env, o, "curve", v));
+  CHECK(env, napi_create_int32(env, bits, &v)); CHECK(env, napi_set_named_property(env, o, "windowBits", v));
+  CHECK(env, napi_create_double(env, (double)bytes, &v)); CHECK(env, napi_set_named_property(env, o, "tableBytes", v));
+  return o;
+}
+static napi_value mul_base_with(napi_env env, napi_callback_info info, int two) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 5; napi_value argv[5];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < (two ? 5u : 3u)) THROW(env, two ? "mulBase2(ctx, base1, base2, k1, k2)" : "mulBase(ctx, base, k)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  int32_t b1, b2 = 0;
+  if (napi_get_value_int32(env, argv[1], &b1) != napi_ok || (two && napi_get_value_int32(env, argv[2], &b2) != napi_ok))
+    THROW(env, "base handle expected");
+  int curve = -1;
+  if (L.base_info(c, b1, &curve, NULL, NULL) != 0) return lib_error(env);
+  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
+  const uint8_t *k1, *k2 = NULL; size_t l1, l2 = 0;
+  if (!get_buf(env, argv[two ? 3 : 2], &k1, &l1, 0)) return NULL;
+  if (two && !get_buf(env, argv[4], &k2, &l2, 0)) return NULL;
+  if (l1 % (size_t)B || (two && l2 != l1)) THROW(env, "buffer length mismatch");
+  size_t n = l1 / (size_t)B;
+  napi_value bxy, binf; void *dxy, *dinf;
+  CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
+  CHECK(env, result_buffer(env, n, &dinf, &binf));
+  int rc = two ? L.mul_base2(c, b1, b2, n, k1, k2, (uint8_t*)dxy, (uint8_t*)dinf, 0, NULL)
+               : L.mul_base(c, b1, n, k1, (uint8_t*)dxy, (uint8_t*)dinf, 0, NULL);
+  if (rc != 0) return lib_error(env);
+  return mk_result(env, "xy", bxy, "inf", binf);
+}
+static napi_value fn_mul_base(napi_env e, napi_callback_info i) { return mul_base_with(e, i, 0); }
+static napi_value fn_mul_base2(napi_env e, napi_callback_info i) { return mul_base_with(e, i, 1); }
 
 /* mulFixed / mulVar / mulAdd2 share the output shape */
 static napi_value mul_common(napi_env env, napi_callback_info info, int kind) {
@@ -1017,7 +1103,9 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
 #define ED_OP_VERIFY 26          /* ECDSA on a user-defined Edwards domain: verify (as op 3), sign (as 11), sign_det (as 12) */
 #define ED_OP_SIGN 27
 #define ED_OP_SIGN_DET 28
-#define OP_LAST 28
+#define OP_MUL_BASE 29           /* mulBase(k; curve = the base's curve, i0 = base)  mulBase2(k1, k2; i0, i1 = the bases) */
+#define OP_MUL_BASE2 30
+#define OP_LAST 30
 #define ECDH_ENC_OP(op) ((op) == 16 || (op) == 25)
 static const char* const ECDH_NAMES[13][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
                                               {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0},
@@ -1138,6 +1226,8 @@ static void job_execute(napi_env env, void* data) {
     case 2: j->rc = L.mul_add2(j->ctx, j->curve, j->n, j->in[0], j->in[1], j->in[2], j->in[3], j->out0, j->out1); break;
     case 3: j->rc = L.ecdsa_verify(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2], j->in[3], j->out0, j->out1); break;
     case 4: j->rc = L.x25519(j->ctx, j->n, j->in[0], j->in[1], j->out0, j->out1); break;
+    case OP_MUL_BASE: j->rc = L.mul_base(j->ctx, j->i0, j->n, j->in[0], j->out0, j->out1, 0, NULL); break;
+    case OP_MUL_BASE2: j->rc = L.mul_base2(j->ctx, j->i0, j->i1, j->n, j->in[0], j->in[1], j->out0, j->out1, 0, NULL); break;
     case 5: j->rc = L.ecdsa_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i0,
                                      j->out0, j->out1, j->out2, j->out3); break;
     case 6: j->rc = L.ecdsa_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
@@ -1185,7 +1275,8 @@ static void job_complete(napi_env env, napi_status status, void* data) {
       {"x", "inf", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
       {"xy", "status", 0, 0}, {"xy", "status", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
       {"x", "status", "err", 0}, {"enc", 0, 0, 0},
-      {"ok", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"}};
+      {"ok", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
+      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1248,7 +1339,8 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
       const uint8_t* in2[2] = {j->in[0], j->in[1]};
       ok = ecdh_shape(op, in2, len, i0, i1, &j->n, ecdh_out); break;
     }
-    case 0: j->n = len[0] / B; ok = j->in[0] && len[0] % B == 0; break;
+    case 0: case OP_MUL_BASE: j->n = len[0] / B; ok = j->in[0] && len[0] % B == 0; break;
+    case OP_MUL_BASE2: j->n = len[0] / B; ok = j->in[0] && j->in[1] && len[0] % B == 0 && len[1] == len[0]; break;
     case 1: j->n = len[0] / B; ok = j->in[0] && j->in[1] && len[0] % B == 0 && len[1] == j->n * 2 * B; break;
     case 2: j->n = len[0] / B; ok = j->in[0] && j->in[2] && j->in[3] && len[0] % B == 0 && len[2] == len[0] &&
                                      len[3] == j->n * 2 * B && (!j->in[1] || len[1] == j->n * 2 * B); break;
@@ -1287,6 +1379,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   j->out1_len = op == 5 || op >= 11 ? j->n * NB : j->n;
   j->out2_len = op == 5 || op >= 11 ? j->n : 0;
   j->out3_len = op == 5 || op >= 11 ? j->n : 0;
+  if (op == OP_MUL_BASE || op == OP_MUL_BASE2) { j->out0_len = j->n * 2 * B; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
   if (op == ED_OP_VERIFY) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
   if (op >= 13 && op <= ECDH_OP_LAST) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
   /* (ops 16, 25: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
@@ -1323,6 +1416,8 @@ static napi_value init(napi_env env, napi_value exports) {
     {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
     {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
     {"customEdVerify", fn_custom_ed_verify}, {"customEdSign", fn_custom_ed_sign}, {"customEdSignDet", fn_custom_ed_sign_det}, {"customEcdh", fn_custom_ecdh},
+    {"defineBase", fn_define_base}, {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info},
+    {"mulBase", fn_mul_base}, {"mulBase2", fn_mul_base2},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -638,6 +638,42 @@ Engine.prototype.customEdEncodePointBatchAsync = function(curve, xy, compact, co
   try { pl = this._edEncodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
   return this._async(25, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
 };
+// Fixed-base tables of caller-chosen points (ellgpu_base_*): BasePoint#precompute for any point a
+// caller uses repeatedly.  install() does not route to them.
+// defineBase(curve, xy, windowBits): xy Buffer(2 B) = x || y in the curve's coordinate width, or
+// null for the curve's own generator (an alias of the curve's table) -> handle; windowBits 0, 4, 8,
+// 12, 16, 22 on secp256k1 / p256 (0 = 16), 0 or 8 elsewhere.  At most 16 live bases per context.
+Engine.prototype.defineBase = function defineBase(curve, xy, windowBits) {
+  return this.addon.defineBase(this.ctx, this._id(curve), xy || null, windowBits | 0);
+};
+Engine.prototype.releaseBase = function releaseBase(base) {
+  this.addon.releaseBase(this.ctx, base | 0);
+};
+// -> { curve, windowBits, tableBytes }
+Engine.prototype.baseInfo = function baseInfo(base) {
+  return this.addon.baseInfo(this.ctx, base | 0);
+};
+// mulBaseBatch: k * B per item; ks Buffer(n x B) used as they stand -> { xy: Buffer(n x 2B), inf: Buffer(n) }
+// (B = the width of the base's curve; inf 1 and xy zeroed at infinity)
+Engine.prototype.mulBaseBatch = function mulBaseBatch(base, ks) {
+  this.stats.gpuCalls++; this.stats.gpuItems += ks.length / this.addon.fieldBytes(this.baseInfo(base).curve);
+  return this.addon.mulBase(this.ctx, base | 0, ks);
+};
+// mulBase2Batch: k1 * B1 + k2 * B2 per item over the tables of two bases of one curve
+Engine.prototype.mulBase2Batch = function mulBase2Batch(base1, base2, k1s, k2s) {
+  this.stats.gpuCalls++; this.stats.gpuItems += k1s.length / this.addon.fieldBytes(this.baseInfo(base1).curve);
+  return this.addon.mulBase2(this.ctx, base1 | 0, base2 | 0, k1s, k2s);
+};
+Engine.prototype.mulBaseBatchAsync = function(base, ks) {
+  var curve;
+  try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
+  return this._async(29, curve, 0, 0, ks, null, null, null, base | 0, 0);
+};
+Engine.prototype.mulBase2BatchAsync = function(base1, base2, k1s, k2s) {
+  var curve;
+  try { curve = this.baseInfo(base1).curve; } catch (e) { return Promise.reject(e); }
+  return this._async(30, curve, 0, 0, k1s, k2s, null, null, base1 | 0, base2 | 0);
+};
 Engine.prototype.customMontLadderBatchAsync = function(curve, ks, xs) {
   return this._async(17, curve, 0, 0, ks, xs, null, null, 0, 0);
 };

@@ -842,6 +842,65 @@ int ellgpu_ctx_reserve(ellgpu_ctx* ctx, int curve, size_t n);
  * counterpart is the fixed `doubles` step of BasePoint#precompute (base.js:312-346). */
 int ellgpu_ctx_comb_bits(ellgpu_ctx* ctx, int curve);
 
+/* ---- fixed-base tables for caller-chosen points ---------------------------------------------
+ * BasePoint#precompute (base.js:312-346) for any point a caller uses repeatedly -- the H of a
+ * Pedersen commitment v*G + r*H, a recipient's key in ElGamal / ECIES, a verifier's long-lived
+ * key, a static ECDH key: ellgpu_base_define builds the point's comb on the device once, and
+ * ellgpu_mul_base (P.precompute(); P.mul(k)) and ellgpu_mul_base2 (k1*B1 + k2*B2, _wnafMulAdd on
+ * two precomputed operands) then run the fixed-base kernels over it instead of the variable-base
+ * ladder of ellgpu_mul_var.
+ *
+ * Memory: these calls have ONE form; `mem` says where the batch buffers live and `stream` goes
+ * with it.  ELLGPU_MEM_HOST: host buffers, the call returns with its results back, `stream` must
+ * be NULL.  ELLGPU_MEM_DEVICE: device pointers, the work is enqueued on `stream` (NULL: the
+ * context's own) as in the _dev entry points, and operands and results must not overlap.  Any
+ * other `mem` is ELLGPU_E_ARG.
+ *
+ * ellgpu_base_define
+ *   curve        the six short presets and user-defined short ids, plain and domain.  ed25519,
+ *                curve25519, user-defined Edwards and Montgomery ids: ELLGPU_E_UNSUPPORTED; an
+ *                unknown id: ELLGPU_E_ARG.
+ *   xy           x || y in the curve's coordinate width (ellgpu_curve_field_bytes on presets, 32
+ *                bytes on user-defined ids), host memory.  A coordinate >= p or a point off the
+ *                curve is ELLGPU_E_ARG (tested on the device).  NULL: the curve's own generator
+ *                (presets and domains; ELLGPU_E_ARG on a plain user-defined id) -- window_bits
+ *                must be 0, the handle aliases the curve's own table, which is built at first use
+ *                and which ellgpu_base_release does not free.  This is how v*G + r*H gets its G.
+ *   window_bits  secp256k1 and p256 (signed comb): 0, 4, 8, 12, 16 or 22.  0 means 16 (36 MB, 17
+ *                additions per item) -- not the generator's 22 (1.6 GB): a caller may hold 16
+ *                bases -- and narrows to 12, 8, 4 on ELLGPU_E_NOMEM as the generator's table
+ *                does; an explicit width that does not fit is ELLGPU_E_NOMEM.  The limit of
+ *                ELLGPU_COMB_MAX_BYTES applies per table.  Every other curve has the unsigned
+ *                8-bit comb: 0 or 8.  Anything else is ELLGPU_E_ARG.
+ *   handles      the same (curve, point, width in use) twice gives the same handle; handles are
+ *                never reused within a context; at most ELLGPU_BASE_MAX are live, the next define
+ *                is ELLGPU_E_UNSUPPORTED.  On a group either every member builds the table or none
+ *                does.  Releasing the bases of a user-defined curve is the caller's business.
+ *   order        On the presets every point of the curve has the prime order n, so the table's
+ *                entries ((d << sh) mod n) * P are exact and never the point at infinity.  On a
+ *                user-defined id scalars are not reduced (as for a domain's G) and the base may
+ *                have a small order: a base one of whose table entries is the point at infinity
+ *                is refused, ELLGPU_E_ARG "a multiple of the base inside the table is the point
+ *                at infinity", with nothing left allocated.
+ * ellgpu_base_info reports the curve, the window width in use and the table's bytes (0 and 0 for
+ * a generator alias whose curve has not built its table yet); any out pointer may be NULL.
+ * ellgpu_mul_base: k is field_bytes bytes per item, used as it stands (neither reduced nor
+ *   truncated, as in ellgpu_mul_fixed); out_xy zeroed and out_inf = 1 at infinity.  There is no
+ *   status 2: the base was tested when it was defined.  Sharded over a group (host memory) as
+ *   ellgpu_mul_fixed is; batches of a few items take the lanes-per-item form of ellgpu_mul_fixed.
+ * ellgpu_mul_base2: both bases on one curve (else ELLGPU_E_ARG), base1 == base2 allowed, the two
+ *   tables may have different widths.  Every n runs one item per lane. */
+#define ELLGPU_BASE_MAX   16      /* live bases per context */
+#define ELLGPU_MEM_HOST   0
+#define ELLGPU_MEM_DEVICE 1
+int ellgpu_base_define (ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window_bits, int* out_base);
+int ellgpu_base_release(ellgpu_ctx* ctx, int base);
+int ellgpu_base_info   (ellgpu_ctx* ctx, int base, int* out_curve, int* out_window_bits, uint64_t* out_table_bytes);
+int ellgpu_mul_base (ellgpu_ctx* ctx, int base, size_t n, const uint8_t* k,
+                     uint8_t* out_xy, uint8_t* out_inf, int mem, void* stream);
+int ellgpu_mul_base2(ellgpu_ctx* ctx, int base1, int base2, size_t n, const uint8_t* k1, const uint8_t* k2,
+                     uint8_t* out_xy, uint8_t* out_inf, int mem, void* stream);
+
 /* ---- measurement helper --------------------------------------------------
  * Integer-VALU roofline probe: runs `iters` dependent-free 32x32+64 -> 64 bit
  * multiply-accumulates (v_mad_u64_u32) per lane on `blocks` x 256 lanes and

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Throughput of the fixed-base tables of caller-chosen points (ellgpu_base_define, ellgpu_mul_base,
+ellgpu_mul_base2) on one curve, device-resident buffers, HIP-event timing.  Developer tool (GPU box).
+
+In one process, on the same scalars:
+  mul_base at each table width (a point H that is not G), and on G by coordinates at the width of
+  the curve's own table -- the same kernel over an equally sized table as mul_fixed, so the two
+  must agree within their spread;
+  mul_var with the point repeated (what a caller paid before), mul_fixed;
+  mul_base2(G alias, H) against mul_add2(k1, NULL -> G, k2, H);
+  milliseconds per base_define per width (table build, one shot each).
+Every row is warmed up, then timed for at least --seconds of back-to-back calls, --rounds times;
+the rows alternate inside a round so that drift is shared.  Reported: the median round in items/s
+and the spread (min .. max) over the rounds.  One JSON line per row, also appended to --out.
+
+    python tools/bench_fixed_base.py [--curve secp256k1] [--log2n 20] [--rounds 5] [--seconds 1.0] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--curve", default="secp256k1")
+    ap.add_argument("--log2n", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import elliptic_amd
+    import fixed_base_checks as FB
+    spec = FB.spec_of(a.curve)
+    B, n = spec["B"], 1 << a.log2n
+    ctx = elliptic_amd.Context(0)
+    G, H = FB.bases_of(spec)[0], FB.bases_of(spec)[3]
+    rng = np.random.default_rng(7)
+    k1 = torch.from_numpy(rng.integers(0, 256, (n, B), dtype=np.uint8)).cuda()
+    k2 = torch.from_numpy(rng.integers(0, 256, (n, B), dtype=np.uint8)).cuda()
+    hxy = torch.from_numpy(np.tile(np.frombuffer(FB.xy_bytes(H, B), np.uint8), (n, 1))).cuda()
+    xy = torch.zeros((n, 2 * B), dtype=torch.uint8, device="cuda")
+    inf = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    out = []
+
+    def emit(row):
+        row.update(curve=a.curve, n=n)
+        print(json.dumps(row), flush=True)
+        out.append(row)
+
+    ctx.mul_fixed_dev(a.curve, k1, xy, inf)                     # the curve's own table
+    torch.cuda.synchronize()
+    gbits = ctx.comb_bits(a.curve)
+    widths = [4, 8, 12, 16, 22] if a.curve in FB.SIGNED else [8]
+    bases = {}
+    for w in widths:
+        t = time.perf_counter()
+        bases[w] = ctx.define_base(a.curve, FB.xy_bytes(H, B), w)
+        torch.cuda.synchronize()
+        emit({"row": "base_define", "width": w, "ms": round((time.perf_counter() - t) * 1e3, 2),
+              "table_bytes": ctx.base_info(bases[w])[2]})
+    g_coords = ctx.define_base(a.curve, FB.xy_bytes(G, B), gbits)
+    alias = ctx.define_base(a.curve)
+    dflt = 16 if 16 in bases else widths[0]
+    rows = [("mul_base w=%d" % w, lambda w=w: ctx.mul_base(bases[w], k1, out=(xy, inf))) for w in widths]
+    rows += [("mul_base G by coordinates w=%d" % gbits, lambda: ctx.mul_base(g_coords, k1, out=(xy, inf))),
+             ("mul_fixed (w=%d)" % gbits, lambda: ctx.mul_fixed_dev(a.curve, k1, xy, inf)),
+             ("mul_var, point repeated", lambda: ctx.mul_var_dev(a.curve, k1, hxy, xy, inf)),
+             ("mul_base2(G alias, H w=%d)" % dflt, lambda: ctx.mul_base2(alias, bases[dflt], k1, k2, out=(xy, inf))),
+             ("mul_add2(k1, G, k2, H)", lambda: ctx.mul_add2_dev(a.curve, k1, None, k2, hxy, xy, inf))]
+    reps = {}
+    for name, fn in rows:                                       # warm-up, and calls per timed stretch
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        reps[name] = max(3, int(a.seconds * 1e3 / max(e0.elapsed_time(e1), 1e-3)) + 1)
+    rates = {name: [] for name, _ in rows}
+    for _ in range(a.rounds):
+        for name, fn in rows:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _i in range(reps[name]):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            rates[name].append(n * reps[name] / (e0.elapsed_time(e1) * 1e-3))
+    for name, _ in rows:
+        r = sorted(rates[name])
+        emit({"row": name, "items_per_s": round(r[len(r) // 2]), "min": round(r[0]), "max": round(r[-1]),
+              "rounds": a.rounds, "calls_per_round": reps[name]})
+    ctx.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for row in out:
+                f.write(json.dumps(row) + "\n")
+
+
+if __name__ == "__main__":
+    main()
