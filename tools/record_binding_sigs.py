@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""Records tests/golden/binding_sigs.json: for every key of elliptic_amd/_lib.py's _SIGS the restype
+and the argtypes, by ctypes type name and in argument order, of the tree this is run in.
+
+The fixture pins the prototypes as they stood when every ellgpu_X_dev entry was written out by hand;
+tests/test_binding_sigs.py compares the table under test (whose _dev entries are derived from their
+host entries) with it.  So run this in a checkout of the commit whose table is to be kept -- or
+after a deliberate change of include/ellgpu.h -- never to make a failing test pass.
+
+    python tools/record_binding_sigs.py [--out binding_sigs.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from elliptic_amd import _lib  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "binding_sigs.json")
+
+
+def table(sigs=None):
+    """{symbol: {"res": type name or None, "args": [type names]}}"""
+    sigs = _lib._SIGS if sigs is None else sigs
+    return {name: {"res": None if res is None else res.__name__, "args": [a.__name__ for a in args]}
+            for name, (res, args) in sigs.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=GOLDEN)
+    args = ap.parse_args()
+    data = table()
+    with open(args.out, "w") as f:
+        json.dump(data, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print("%s: %d prototypes" % (args.out, len(data)))
+
+
+if __name__ == "__main__":
+    main()
