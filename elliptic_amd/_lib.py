@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/ellgpu.h.
+"""ctypes binding of the C ABI declared in include/ellgpu.h and include/ellgpu_ext.h.
 
 `load()` opens the in-tree libellgpu.so (built by __graft_entry__.build() /
 elliptic_amd/build.py with hipcc for gfx950).  There is no fallback of any
@@ -107,6 +107,13 @@ for _name, (_res, _args) in _BATCH.items():
 # every symbol include/ellgpu.h declares (tests check the .so exports them all)
 SYMBOLS = sorted(_SIGS)
 
+# the entry points added after that table was recorded: include/ellgpu_ext.h, a table of its own
+# (tests/golden/binding_sigs_ext.json)
+_EXT_SIGS = {
+    "ellgpu_ed_base_define": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_u8p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+}
+EXT_SYMBOLS = sorted(_EXT_SIGS)
+
 # ELLGPU_VERSION of the include/ellgpu.h this table was written against: load() refuses any other
 # library (a prototype changed -- e.g. ellgpu_ecdsa_verify's out_status -- and a stale table would
 # pass garbage for the added arguments)
@@ -131,7 +138,7 @@ def load(path=None, optional=()):
     if got != ABI_VERSION:
         raise ImportError("%s reports ABI version 0x%06x, this binding was written for 0x%06x (include/ellgpu.h "
                           "ELLGPU_VERSION): rebuild the library from this tree" % (path, got, ABI_VERSION))
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_EXT_SIGS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

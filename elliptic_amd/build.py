@@ -54,6 +54,7 @@ def source_files():
     files = sorted(os.path.join("elliptic_amd", "csrc", f) for f in os.listdir(CSRC)
                    if f.endswith((".h", ".hip")) and os.path.isfile(os.path.join(CSRC, f)))
     files.append(os.path.join("include", "ellgpu.h"))
+    files.append(os.path.join("include", "ellgpu_ext.h"))
     return root, files
 
 

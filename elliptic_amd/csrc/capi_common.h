@@ -9,7 +9,7 @@
 // before including this header.
 #pragma once
 
-#include "../../include/ellgpu.h"
+#include "../../include/ellgpu_ext.h"
 #include "engine.h"
 
 #include <mutex>
@@ -330,7 +330,8 @@ int ellgpu_mul_fixed_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* k,
 }
 
 // ---- fixed-base tables of caller-chosen points (Engine::define_base) ----
-int ellgpu_base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window_bits, int* out_base) {
+// (ed: ellgpu_ed_base_define, the Edwards curves' entry point -- the same handles, the same path)
+static int base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window_bits, int* out_base, bool ed) {
   if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
   ELL_LOCK(ctx);
   if (!ctx->members.empty()) {
@@ -346,7 +347,7 @@ int ellgpu_base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window
       ell_enter(*m->eng, nullptr, Mem::host);
       int h = -1;
       bool created = false;
-      rc = finish(m, m->eng->define_base(curve, xy, window_bits, &h, &created));
+      rc = finish(m, m->eng->define_base(curve, xy, window_bits, &h, &created, ed));
       if (rc) { msg = g_last_error; break; }
       if (created) made[i] = h;
       if (i && h != id) { rc = ELLGPU_E_ARG; msg = "group members disagree on the base handle (bases were defined on a member directly)"; }
@@ -365,7 +366,13 @@ int ellgpu_base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window
     *out_base = id;
     return ELLGPU_OK;
   }
-  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem) { return e.define_base(curve, xy, window_bits, out_base); });
+  return ell_call(ctx, nullptr, Mem::host, [=](Eng& e, Mem) { return e.define_base(curve, xy, window_bits, out_base, nullptr, ed); });
+}
+int ellgpu_base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window_bits, int* out_base) {
+  return base_define(ctx, curve, xy, window_bits, out_base, false);
+}
+int ellgpu_ed_base_define(ellgpu_ctx* ctx, int curve, const uint8_t* xy, int window_bits, int* out_base) {
+  return base_define(ctx, curve, xy, window_bits, out_base, true);
 }
 int ellgpu_base_release(ellgpu_ctx* ctx, int base) {
   if (!ctx) return set_err(ELLGPU_E_ARG, "null context");

@@ -9,8 +9,10 @@
 //                                                  on the exceptional inputs of other curves
 //                                                  are whatever these formulas give, here too)
 //   dbl   dbl-2008-bbjlp   3M + 4S + 1a
+//   madd  add-2008-bbjlp with Z2 = 1   9M + 1S + 1a + 1d   (the comb walks: affine table entries)
 // Field: FpMontRT (fp_rt.h), a and d from the curve's parameter block.  Ladder: signed 4-bit
-// fixed windows over the table P..8P, as edwards.h / ladder.h.
+// fixed windows over the table P..8P, as edwards.h / ladder.h.  Fixed-base tables of caller-chosen
+// points (Engine::define_ed_base): an unsigned comb of 8- or 16-bit windows over affine entries.
 #pragma once
 
 #include "fp_rt.h"
@@ -28,6 +30,11 @@ struct EdcWork {
 
   struct P {
     El X, Y, Z;
+  };
+  // an entry of a fixed-base table: affine, Montgomery form.  The slot in front of entry 0 is the
+  // table's header: x.v[0] holds the window width (8 or 16).
+  struct A {
+    El x, y;
   };
 
   ELL_HD static El ca() { return F::curve_a(); }
@@ -78,6 +85,23 @@ struct EdcWork {
     P r;
     r.X = F::mul(F::mul(A, Ff), t);
     r.Y = F::mul(F::mul(A, G), F::sub(D, F::mul(ca(), C)));
+    r.Z = F::mul(Ff, G);
+    return select(do_add, r, p);
+  }
+
+  // p + q for an affine q: `add` with Z2 = 1 written out (A = Z1), one multiplication fewer and the
+  // same values on every input, the exceptional ones included
+  ELL_HD static P madd(const P& p, const A& q, bool do_add = true) {
+    El B = F::sqr(p.Z);
+    El C = F::mul(p.X, q.x);
+    El D = F::mul(p.Y, q.y);
+    El E = F::mul(F::mul(cd(), C), D);
+    El Ff = F::sub(B, E);
+    El G = F::add(B, E);
+    El t = F::sub(F::sub(F::mul(F::add(p.X, p.Y), F::add(q.x, q.y)), C), D);
+    P r;
+    r.X = F::mul(F::mul(p.Z, Ff), t);
+    r.Y = F::mul(F::mul(p.Z, G), F::sub(D, F::mul(ca(), C)));
     r.Z = F::mul(Ff, G);
     return select(do_add, r, p);
   }
@@ -156,6 +180,54 @@ struct EdcWork {
     recode_w4<8, NNIB, true>(k2, ds, 1, 2);
     store_proj(out, n, i, run_w4<2>(ds, tbl));
   }
+  // ---- fixed-base tables of caller-chosen points (BasePoint#precompute; Engine::define_ed_base) ----
+  // acc + k * B over B's table: an unsigned comb of 256 / bits windows x (2^bits - 1) entries,
+  // entry (w, d) = (d << (bits w)) * B, the width read from the header slot (8 or 16: one walk serves
+  // both).  Branch-free: a zero digit adds entry 0 of its window and keeps the accumulator by
+  // select.  The identity and points of small order are ordinary entries of a unified law.
+  ELL_HD static P comb_add(P acc, const u32 (&k)[8], const A* tbl) {
+    const int bits = (int)tbl[-1].x.v[0];
+    const u32 dig = (1u << bits) - 1u;
+    const int nw = 256 / bits;
+    u32 kk[8];
+    bn_copy<8>(kk, k);
+    ELL_NOUNROLL
+    for (int w = 0; w < nw; w++) {
+      const u32 d = kk[0] & dig;
+      ELL_UNROLL
+      for (int i = 0; i < 7; i++) kk[i] = (kk[i] >> bits) | (kk[i + 1] << (32 - bits));
+      kk[7] >>= bits;
+      const u32 e = d ? d - 1 : 0;
+      acc = madd(acc, tbl[(size_t)w * dig + e], d != 0);
+    }
+    return acc;
+  }
+  // P.precompute(); P.mul(k): k as it stands
+  ELL_HD static void mul_base(size_t i, size_t n, const u8* ks, const A* tbl, u32* out) {
+    u32 k[8];
+    load_be<8>(k, ks + i * 32, 32);
+    store_proj(out, n, i, comb_add(identity(), k, tbl));
+  }
+  // k1 * B1 + k2 * B2 (mulAdd on two precomputed operands): two walks, each at its own table's
+  // width, into one accumulator
+  ELL_HD static void mul_base2(size_t i, size_t n, const u8* k1s, const A* t1, const u8* k2s, const A* t2,
+                               u32* out) {
+    u32 k[8];
+    load_be<8>(k, k1s + i * 32, 32);
+    P acc = comb_add(identity(), k, t1);
+    load_be<8>(k, k2s + i * 32, 32);
+    store_proj(out, n, i, comb_add(acc, k, t2));
+  }
+  // a base before its table is built: x, y < p and on the curve (x || y big-endian at pt)
+  ELL_HD static bool base_ok(const u8* pt) {
+    u32 x[8], y[8], pp[8];
+    load_be<8>(x, pt, 32);
+    load_be<8>(y, pt + 32, 32);
+    F::get_p(pp);
+    if (bn_geq<8>(x, pp) || bn_geq<8>(y, pp)) return false;
+    return on_curve(F::from_plain(x), F::from_plain(y));
+  }
+
   // a x^2 + y^2 == 1 + d x^2 y^2 (EdwardsCurve#validate, edwards.js:99-112, c = 1)
   ELL_HD static bool on_curve(const El& x, const El& y) {
     El x2 = F::sqr(x), y2 = F::sqr(y);
@@ -184,9 +256,11 @@ struct EdcWork {
     q = select(inf2 && inf2[i], identity(), q);
     store_proj(out, n, i, add(p, q));
   }
-  // Point#normalize (edwards.js:377-390): x = X / Z, y = Y / Z, one inversion per K items
+  // Point#normalize (edwards.js:377-390): x = X / Z, y = Y / Z, one inversion per K items.
+  // RAW: the affine point goes to raw[i] as a table entry, left in Montgomery form, and nowhere else.
+  template <bool RAW = false>
   ELL_HD static void normalize(size_t t, size_t T, size_t n, int K, const u32* proj, u32* pre,
-                               u8* out_xy, u8* out_inf) {
+                               u8* out_xy, u8* out_inf, A* raw = nullptr) {
     El acc = F::one();
     ELL_NOUNROLL
     for (int j = 0; j < K; j++) {
@@ -220,12 +294,19 @@ struct EdcWork {
       El x = F::mul(X, zinv);
       El y = F::mul(Y, zinv);
       if (zz) { x = F::zero(); y = F::zero(); }
-      u32 w[8];
-      F::to_plain(w, x);
-      store_be<8>(out_xy + i * 64, w, 32);
-      F::to_plain(w, y);
-      store_be<8>(out_xy + i * 64 + 32, w, 32);
-      if (out_inf) out_inf[i] = 0;
+      if constexpr (RAW) {
+        A e;
+        e.x = x;
+        e.y = y;
+        raw[i] = e;
+      } else {
+        u32 w[8];
+        F::to_plain(w, x);
+        store_be<8>(out_xy + i * 64, w, 32);
+        F::to_plain(w, y);
+        store_be<8>(out_xy + i * 64 + 32, w, 32);
+        if (out_inf) out_inf[i] = 0;
+      }
     }
   }
 };

@@ -176,10 +176,10 @@ struct EdWork {
     return acc;
   }
 
-  ELL_HD static P comb_mul(const u32 (&k)[8], const P* comb) {
+  // acc + k * B over the comb of B (the curve's own table, or a caller-chosen base's)
+  ELL_HD static P comb_mul(const u32 (&k)[8], const P* comb, P acc = identity()) {
     u32 kk[8];
     bn_copy<8>(kk, k);
-    P acc = identity();
     ELL_NOUNROLL
     for (int w = 0; w < COMB_W; w++) {
       u32 d = kk[0] & (u32)COMB_DIG;
@@ -207,6 +207,24 @@ struct EdWork {
     u32 k[8];
     load_be<8>(k, ks + i * 32, 32);
     store_ext(ext, n, i, comb_mul(k, comb));
+  }
+  // k1 * B1 + k2 * B2 over the tables of two caller-chosen bases: two comb walks, one accumulator
+  ELL_HD static void mul_base2(size_t i, size_t n, const u8* k1s, const P* t1, const u8* k2s, const P* t2,
+                               u32* ext) {
+    u32 k[8];
+    load_be<8>(k, k1s + i * 32, 32);
+    P acc = comb_mul(k, t1);
+    load_be<8>(k, k2s + i * 32, 32);
+    store_ext(ext, n, i, comb_mul(k, t2, acc));
+  }
+  // a base before its table is built: x, y < p and on the curve (x || y big-endian at pt)
+  ELL_HD static bool base_ok(const u8* pt) {
+    u32 x[8], y[8], pp[8];
+    load_be<8>(x, pt, 32);
+    load_be<8>(y, pt + 32, 32);
+    F::get_p(pp);
+    if (bn_geq<8>(x, pp) || bn_geq<8>(y, pp)) return false;
+    return on_curve(F::from_plain(x), F::from_plain(y));
   }
   ELL_HD static void mul_add_g(size_t i, size_t n, const u8* k1s, const u8* k2s, const u8* xy2,
                                const P* comb, P* tbl_all, const DigitStore& ds, u32* ext) {

@@ -1117,6 +1117,51 @@ struct FnEdMulAdd2 {
     if (i < n) EdWork::mul_add2(i, n, k1, xy1, k2, xy2, tbl, ds, ext);
   }
 };
+// k1 * B1 + k2 * B2 over the tables of two caller-chosen bases (EdWork::mul_base2)
+struct FnEdMulBase2 {
+  static constexpr const char* NAME = "ed_mul_base2";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* k1; const EdWork::P* t1; const u8* k2; const EdWork::P* t2; u32* ext;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdWork::mul_base2(i, n, k1, t1, k2, t2, ext);
+  }
+};
+// the comb of a caller-chosen base on an Edwards curve, ed25519 and user-defined alike (32-byte
+// scalars, 64-byte points): entry idx = (w, d) gets the scalar d << (bits w), as it stands, and the
+// point at pt (x || y big-endian, a device buffer)
+// (RT: the user-defined curves' instance, so that each of the two code objects holds its own kernel)
+template <bool RT>
+struct FnEdBaseCombGen {
+  static constexpr const char* NAME = "ed_base_comb_gen";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; size_t first; const u8* pt; u8* k; u8* xy; int bits;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i >= n) return;
+    const size_t idx = first + i;
+    const size_t per = ((size_t)1 << bits) - 1;
+    const int w = (int)(idx / per);
+    const u32 d = (u32)(idx % per) + 1u;
+    const int byte0 = w * (bits / 8);             // bits is 8 or 16: a window is whole bytes
+    ELL_NOUNROLL
+    for (int b = 0; b < 32; b++) {
+      const int j = 31 - b - byte0;                // byte b counts from the big end
+      k[i * 32 + b] = (j == 0 || (j == 1 && bits == 16)) ? (u8)(d >> (8 * j)) : (u8)0;
+    }
+    ELL_NOUNROLL
+    for (int b = 0; b < 64; b++) xy[i * 64 + b] = pt[b];
+  }
+};
+// the test of a base before its table is built: flag[0] = 1 where a coordinate is >= p or the
+// point is not on the curve
+struct FnEdBaseCheck {
+  static constexpr const char* NAME = "ed_base_check";
+  static constexpr int DS_PER_LANE = 0;
+  const u8* pt; u8* flag;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i) return;
+    flag[0] = EdWork::base_ok(pt) ? 0 : 1;
+  }
+};
 struct FnEdNormalize {
   static constexpr const char* NAME = "ed_normalize";
   static constexpr int DS_PER_LANE = 0;
@@ -1175,6 +1220,43 @@ struct FnEdcNormalize {
   size_t T; size_t n; int K; const u32* proj; u32* pre; u8* out_xy; u8* out_inf;
   ELL_HD void operator()(size_t t, const DigitStore&) const {
     if (t < T) EdcWork::normalize(t, T, n, K, proj, pre, out_xy, out_inf);
+  }
+};
+// fixed-base tables of caller-chosen points on user-defined Edwards curves (EdcWork::comb_add)
+struct FnEdcMulBase {
+  static constexpr const char* NAME = "edc_mul_base";
+  static constexpr int DS_PER_LANE = 0;
+  static constexpr int MIN_WAVES = 3;
+  size_t n; const u8* k; const EdcWork::A* tbl; u32* out;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcWork::mul_base(i, n, k, tbl, out);
+  }
+};
+struct FnEdcMulBase2 {
+  static constexpr const char* NAME = "edc_mul_base2";
+  static constexpr int DS_PER_LANE = 0;
+  static constexpr int MIN_WAVES = 3;
+  size_t n; const u8* k1; const EdcWork::A* t1; const u8* k2; const EdcWork::A* t2; u32* out;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EdcWork::mul_base2(i, n, k1, t1, k2, t2, out);
+  }
+};
+struct FnEdcBaseCheck {
+  static constexpr const char* NAME = "edc_base_check";
+  static constexpr int DS_PER_LANE = 0;
+  const u8* pt; u8* flag;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i) return;
+    flag[0] = EdcWork::base_ok(pt) ? 0 : 1;
+  }
+};
+// the entries of a table under construction: affine, Montgomery form (EdcWork::normalize<true>)
+struct FnEdcBaseNormalize {
+  static constexpr const char* NAME = "edc_base_normalize";
+  static constexpr int DS_PER_LANE = 0;
+  size_t T; size_t n; int K; const u32* proj; u32* pre; EdcWork::A* raw;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) EdcWork::normalize<true>(t, T, n, K, proj, pre, nullptr, nullptr, raw);
   }
 };
 
@@ -1544,6 +1626,19 @@ class Engine {
   template <class CV>
   int mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf,
                     typename Work<CV>::A* raw);
+  // fixed-base tables of caller-chosen points on Edwards curves (define_ed_base): the test of the
+  // base and the build of its table; k1 * B1 (k2 == null) or k1 * B1 + k2 * B2 over built tables, one
+  // item per lane at every n.  ed_*: ed25519, tables in EdWork's cached format; edc_*: user-defined.
+  template <int U = 0>
+  int ed_base_table(const u8* xy, CombTable& out);
+  template <int U = 0>
+  int ed_base_mul_chunk(size_t n, const u8* k1, const EdWork::P* t1, const u8* k2, const EdWork::P* t2,
+                        u8* out_xy, u8* out_inf);
+  template <int U = 0>
+  int edc_base_table(const u8* xy, int window_bits, CombTable& out);
+  template <int U = 0>
+  int edc_base_mul_chunk(size_t n, const u8* k1, const EdcWork::A* t1, const u8* k2, const EdcWork::A* t2,
+                         u8* out_xy, u8* out_inf);
   // (comb: the curve's own table for mul_fixed, a caller-chosen base's for mul_base)
   template <class CV>
   int mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, u8* out_xy, u8* out_inf);
@@ -2280,6 +2375,7 @@ class Engine {
   struct BaseRec {
     int handle, curve, asked;
     bool alias;
+    bool ed = false;           // an Edwards handle (define_ed_base): ed25519 or a user-defined Edwards id
     CombTable t;
     u8 xy[2 * 66];
   };
@@ -2305,6 +2401,19 @@ class Engine {
     ELL_SHORT_DISPATCH(curve, sgn = Work<CV>::COMB_SIGNED);
     return E_OK;
   }
+  // ... and of define_ed_base: ed25519 and user-defined Edwards ids, plain and domain
+  int ed_base_curve_kind(int curve) {
+    if (!curve_info(curve)) return fail(E_ARG, "unknown curve id");
+    if (curve == CURVE_ED25519) return E_OK;
+    if (curve == CURVE_CURVE25519) return fail(E_UNSUPPORTED, "curve25519 is x-only: it has no fixed-base tables");
+    const char* const shorts = "a short Weierstrass curve: its fixed-base tables are ellgpu_base_define's";
+    if (!is_custom(curve)) return fail(E_UNSUPPORTED, shorts);
+    size_t slot = (size_t)(curve - CURVE_CUSTOM0);
+    if (slot >= custom_.size()) return fail(E_ARG, "unknown curve id");
+    if (custom_[slot].kind == 0) return fail(E_UNSUPPORTED, shorts);
+    if (custom_[slot].kind != 1) return fail(E_UNSUPPORTED, "user-defined Montgomery curves are x-only: they have no fixed-base tables");
+    return E_OK;
+  }
   // The kernels of a base on a user-defined id are the domain's (CvCustomDomain: the comb walks
   // read the field alone), so a PLAIN id's block goes to their code object as well: the backend
   // uploads it there for a block marked as a domain, and no kernel reads that mark.
@@ -2314,16 +2423,36 @@ class Engine {
     f.domain = 1;
     bk.rt_upload(f);
   }
-  int define_base(int curve, const u8* xy, int window_bits, int* out_base, bool* created = nullptr) {
+  // ed: the call is define_ed_base (ellgpu_ed_base_define): ed25519 and user-defined Edwards ids,
+  // which this entry point refuses otherwise.  There the identity and points of small order are
+  // ordinary table entries of a unified law (no refusal), scalars are 32 bytes as they stand, and
+  //   xy == null      ed25519: an alias of the curve's own table; an Edwards domain: a table of the
+  //                   domain's G that the handle owns, as if G's coordinates had been passed
+  //   window_bits     ed25519: 0 or EdWork::COMB_BITS (EdWork's cached format, comb_mul as it stands);
+  //                   user-defined: 0 (= 8), 8 or 16 -- 256 / bits windows x (2^bits - 1) affine
+  //                   entries of 64 bytes, the width in the header slot (EdcWork::comb_add)
+  int define_base(int curve, const u8* xy, int window_bits, int* out_base, bool* created = nullptr, bool ed = false) {
     if (created) *created = false;
     if (!out_base) return fail(E_ARG, "null pointer");
     bool sgn = false;
-    if (int rc = base_curve_kind(curve, sgn)) return rc;
-    const bool dom = custom_is_domain(curve);
+    if (int rc = ed ? ed_base_curve_kind(curve) : base_curve_kind(curve, sgn)) return rc;
+    const bool dom = ed ? is_custom(curve) && custom_[(size_t)(curve - CURVE_CUSTOM0)].domain == 1 : custom_is_domain(curve);
     const size_t B = (size_t)curve_info(curve)->field_bytes;
+    u8 gxy[64];
     if (!xy) {
       if (is_custom(curve) && !dom) return fail(E_ARG, "a user-defined curve without a domain has no generator: pass the base's coordinates");
       if (window_bits) return fail(E_ARG, "the curve's own generator comes with its own table: window_bits must be 0");
+      if (ed && dom) {
+        const RtField& f = custom_[(size_t)(curve - CURVE_CUSTOM0)];
+        store_be<8>(gxy, f.gx, 32);
+        store_be<8>(gxy + 32, f.gy, 32);
+        xy = gxy;
+      }
+    } else if (ed) {
+      if (curve == CURVE_ED25519 ? !(window_bits == 0 || window_bits == EdWork::COMB_BITS)
+                                 : !(window_bits == 0 || window_bits == 8 || window_bits == 16))
+        return fail(E_ARG, curve == CURVE_ED25519 ? "window_bits on ed25519: 0 or the width of the curve's own comb"
+                                                  : "window_bits on a user-defined Edwards curve: 0, 8 or 16");
     } else if (sgn ? !(window_bits == 0 || window_bits == 4 || window_bits == 8 || window_bits == 12 ||
                        window_bits == 16 || window_bits == 22)
                    : !(window_bits == 0 || window_bits == 8)) {
@@ -2340,14 +2469,16 @@ class Engine {
     rec.curve = curve;
     rec.asked = window_bits;
     rec.alias = !xy;
+    rec.ed = ed;
     memset(rec.xy, 0, sizeof rec.xy);
     if (xy) {
       memcpy(rec.xy, xy, 2 * B);
       CustomScope sc(this, curve);
       if (sc.rc) return sc.rc;
-      base_upload(curve);
+      if (!ed) base_upload(curve);
       int rc = E_OK;
-      if (is_custom(curve)) rc = base_table<CvCustomDomain>(xy, window_bits, rec.t);
+      if (ed) rc = curve == CURVE_ED25519 ? ed_base_table(xy, rec.t) : edc_base_table(xy, window_bits, rec.t);
+      else if (is_custom(curve)) rc = base_table<CvCustomDomain>(xy, window_bits, rec.t);
       else ELL_SHORT_DISPATCH(curve, rc = base_table<CV>(xy, window_bits, rec.t));
       if (rc) return rc;
       // (a default width that narrowed may have arrived at a table that exists)
@@ -2386,7 +2517,10 @@ class Engine {
     if (!r) return E_ARG;
     int bits = r->t.bits;
     size_t bytes = r->t.bytes;
-    if (r->alias) {
+    if (r->alias && r->ed) {
+      bits = comb_[CURVE_ED25519] ? EdWork::COMB_BITS : 0;
+      bytes = bits ? EdWork::COMB_ENTRIES * sizeof(EdWork::P) : 0;
+    } else if (r->alias) {
       bits = comb_[r->curve] ? (comb_bits_[r->curve] ? comb_bits_[r->curve] : 8) : 0;
       bytes = 0;
       if (bits) {
@@ -2411,6 +2545,11 @@ class Engine {
   // on first use)
   int base_table_ptr(const BaseRec& r, const void*& comb) {
     if (!r.alias) { comb = r.t.comb; return E_OK; }
+    if (r.ed) {                                    // ed25519's own table
+      const int rc = ensure_ed_comb();
+      comb = comb_[CURVE_ED25519];
+      return rc;
+    }
     const int rc = custom_is_domain(r.curve) ? ensure_comb<CvCustomDomain>() : prepare_curve(r.curve);
     comb = comb_[r.curve];
     return rc;
@@ -2427,12 +2566,14 @@ class Engine {
       return fail(E_ARG, "k and the results must not overlap");
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    base_upload(curve);
+    if (!r->ed) base_upload(curve);
     return batch(where, n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto o) {
       const void* t = nullptr;
       int rc = base_table_ptr(*r, t);
       if (rc) return rc;
-      if (is_custom(curve)) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], (const Work<CvCustomDomain>::A*)t, o[0], o[1]);
+      if (r->ed) rc = curve == CURVE_ED25519 ? ed_base_mul_chunk(m, d[0], (const EdWork::P*)t, nullptr, nullptr, o[0], o[1])
+                                             : edc_base_mul_chunk(m, d[0], (const EdcWork::A*)t, nullptr, nullptr, o[0], o[1]);
+      else if (is_custom(curve)) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], (const Work<CvCustomDomain>::A*)t, o[0], o[1]);
       else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], (const typename Work<CV>::A*)t, o[0], o[1]));
       return rc;
     });
@@ -2442,7 +2583,7 @@ class Engine {
     const BaseRec* r1 = base_rec(base1);
     const BaseRec* r2 = r1 ? base_rec(base2) : nullptr;
     if (!r1 || !r2) return E_ARG;
-    if (r1->curve != r2->curve) return fail(E_ARG, "the two bases are on different curves");
+    if (r1->curve != r2->curve || r1->ed != r2->ed) return fail(E_ARG, "the two bases are on different curves");
     if (n && (!k1 || !k2 || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
     const int curve = r1->curve;
     const size_t B = (size_t)curve_info(curve)->field_bytes;
@@ -2452,14 +2593,18 @@ class Engine {
           return fail(E_ARG, "k1 / k2 and the results must not overlap");
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
-    base_upload(curve);
+    if (!r1->ed) base_upload(curve);
     return batch(where, n, {In{k1, B}, In{k2, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto o) {
       const void* t1 = nullptr;
       const void* t2 = nullptr;
       int rc = base_table_ptr(*r1, t1);
       if (rc == E_OK) rc = base_table_ptr(*r2, t2);
       if (rc) return rc;
-      if (is_custom(curve)) {
+      if (r1->ed) {
+        rc = curve == CURVE_ED25519
+                 ? ed_base_mul_chunk(m, d[0], (const EdWork::P*)t1, d[1], (const EdWork::P*)t2, o[0], o[1])
+                 : edc_base_mul_chunk(m, d[0], (const EdcWork::A*)t1, d[1], (const EdcWork::A*)t2, o[0], o[1]);
+      } else if (is_custom(curve)) {
         typedef const Work<CvCustomDomain>::A* T;
         rc = mul_base2_chunk<CvCustomDomain>(m, d[0], (T)t1, d[1], (T)t2, o[0], o[1]);
       } else {
@@ -4032,6 +4177,153 @@ int Engine<BK>::ed_mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u
     bk.launch(g, n);
   }
   return rc;
+}
+
+// ---- fixed-base tables of caller-chosen points on Edwards curves ---------------------------------
+// The test of the base (x, y < p, on the curve) runs on the device, then the table is built by the
+// curve's own variable-base kernel on the scalars d << (bits w), in slices of ELL_COMB_SLICE entries
+// (FnEdBaseCombGen writes a slice's scalars and points).  ELLGPU_COMB_MAX_BYTES applies per table.
+
+template <class BK>
+template <int U>
+int Engine<BK>::ed_base_table(const u8* xy, CombTable& out) {
+  const size_t n = EdWork::COMB_ENTRIES;
+  const size_t bytes = n * sizeof(EdWork::P);
+  const size_t slice = n < (size_t)ELL_COMB_SLICE ? n : (size_t)ELL_COMB_SLICE;
+  u8* dpt = (u8*)bk.alloc(64 + 1);               // the point and, behind it, the test's flag
+  if (!dpt) return fail(E_NOMEM, "scratch allocation failed");
+  u8 flag = 1;
+  bk.h2d(dpt, xy, 64);
+  FnEdBaseCheck chk{dpt, dpt + 64};
+  bk.launch(chk, 1);
+  bk.d2h(&flag, dpt + 64, 1);
+  int rc = bk.sync();
+  if (rc) rc = fail(rc, "testing the base failed on the device");
+  else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
+  if (rc) { bk.free_(dpt); return rc; }
+  EdWork::P* comb = (tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) ? nullptr : (EdWork::P*)bk.alloc(bytes);
+  u8* dk = comb ? (u8*)bk.alloc(slice * 32) : nullptr;
+  u8* dp = dk ? (u8*)bk.alloc(slice * 64) : nullptr;
+  rc = dp ? E_OK : fail(E_NOMEM, "comb table allocation failed");
+  for (size_t first = 0; first < n && rc == E_OK; first += slice) {
+    const size_t m = n - first < slice ? n - first : slice;
+    FnEdBaseCombGen<false> g{m, first, dpt, dk, dp, EdWork::COMB_BITS};
+    bk.launch(g, m);
+    rc = ed_mul_var_chunk(m, dk, dp, nullptr, nullptr, comb + first);
+  }
+  if (dp) {
+    const int src = bk.sync();
+    if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
+  }
+  if (dp) bk.free_(dp);
+  if (dk) bk.free_(dk);
+  bk.free_(dpt);
+  if (rc) {
+    if (comb) bk.free_(comb);
+    return rc;
+  }
+  out.comb = comb;
+  out.base = comb;
+  out.bits = EdWork::COMB_BITS;
+  out.bytes = bytes;
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::ed_base_mul_chunk(size_t n, const u8* k1, const EdWork::P* t1, const u8* k2, const EdWork::P* t2,
+                                  u8* out_xy, u8* out_inf) {
+  u32* ext = (u32*)scratch(S_JAC, n * 4 * 8 * 4);
+  if (!ext) return fail(E_NOMEM, "scratch allocation failed");
+  if (k2) {
+    FnEdMulBase2 f{n, k1, t1, k2, t2, ext};
+    bk.launch(f, n);
+  } else {
+    FnEdMulFixed f{n, k1, t1, ext};
+    bk.launch(f, n);
+  }
+  return ed_normalize_chunk(n, ext, out_xy, out_inf, nullptr);
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edc_base_table(const u8* xy, int window_bits, CombTable& out) {
+  const int bits = window_bits ? window_bits : 8;
+  const size_t n = (size_t)(256 / bits) * (((size_t)1 << bits) - 1);
+  const size_t bytes = (n + 1) * sizeof(EdcWork::A);
+  const size_t slice = n < (size_t)ELL_COMB_SLICE ? n : (size_t)ELL_COMB_SLICE;
+  u8* dpt = (u8*)bk.alloc(64 + 1);
+  if (!dpt) return fail(E_NOMEM, "scratch allocation failed");
+  u8 flag = 1;
+  bk.h2d(dpt, xy, 64);
+  FnEdcBaseCheck chk{dpt, dpt + 64};
+  bk.launch(chk, 1);
+  bk.d2h(&flag, dpt + 64, 1);
+  int rc = bk.sync();
+  if (rc) rc = fail(rc, "testing the base failed on the device");
+  else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
+  if (rc) { bk.free_(dpt); return rc; }
+  EdcWork::A* base = (tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) ? nullptr : (EdcWork::A*)bk.alloc(bytes);
+  u8* dk = base ? (u8*)bk.alloc(slice * 32) : nullptr;
+  u8* dp = dk ? (u8*)bk.alloc(slice * 64) : nullptr;
+  rc = dp ? E_OK : fail(E_NOMEM, "comb table allocation failed");
+  if (rc == E_OK) {
+    u32 hdr[sizeof(EdcWork::A) / 4] = {0};
+    hdr[0] = (u32)bits;
+    bk.h2d(base, hdr, sizeof hdr);
+  }
+  for (size_t first = 0; first < n && rc == E_OK; first += slice) {
+    const size_t m = n - first < slice ? n - first : slice;
+    u32* proj = (u32*)scratch(S_JAC, m * 3 * 8 * 4);
+    u32* pre = (u32*)scratch(S_PRE, m * 8 * 4);
+    EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, m * 8 * sizeof(EdcWork::P));
+    if (!proj || !pre || !tbl) { rc = fail(E_NOMEM, "scratch allocation failed"); break; }
+    FnEdBaseCombGen<true> g{m, first, dpt, dk, dp, bits};
+    bk.launch(g, m);
+    FnEdcMulVar f{m, dk, dp, tbl, proj};
+    bk.launch(f, m);
+    const int K = norm_batch_for(m);
+    const size_t T = (m + K - 1) / K;
+    FnEdcBaseNormalize h{T, m, K, proj, pre, base + 1 + first};
+    bk.launch(h, T);
+  }
+  if (dp) {
+    const int src = bk.sync();
+    if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
+  }
+  if (dp) bk.free_(dp);
+  if (dk) bk.free_(dk);
+  bk.free_(dpt);
+  if (rc) {
+    if (base) bk.free_(base);
+    return rc;
+  }
+  out.comb = base + 1;
+  out.base = base;
+  out.bits = bits;
+  out.bytes = bytes;
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::edc_base_mul_chunk(size_t n, const u8* k1, const EdcWork::A* t1, const u8* k2, const EdcWork::A* t2,
+                                   u8* out_xy, u8* out_inf) {
+  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
+  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
+  if (!proj || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  if (k2) {
+    FnEdcMulBase2 f{n, k1, t1, k2, t2, proj};
+    bk.launch(f, n);
+  } else {
+    FnEdcMulBase f{n, k1, t1, proj};
+    bk.launch(f, n);
+  }
+  const int K = norm_batch_for(n);
+  const size_t T = (n + K - 1) / K;
+  FnEdcNormalize g{T, n, K, proj, pre, out_xy, out_inf};
+  bk.launch(g, T);
+  return E_OK;
 }
 
 template <class BK>

@@ -307,6 +307,20 @@ class Context:
         self._base_curve[h.value] = curve
         return h.value
 
+    def define_ed_base(self, curve, xy=None, window_bits=0):
+        """define_base for ed25519 and user-defined Edwards ids (ellgpu_ed_base_define): the handle goes
+        to mul_base, mul_base2, base_info and release_base like any other; rows are 32 bytes.  xy:
+        x || y, 64 bytes, or None for the curve's own generator (ed25519: an alias of the curve's
+        table; an Edwards domain: a table of its G).  window_bits: 0 or 16 on ed25519; 0 (= 8), 8 or
+        16 on a user-defined id."""
+        cid = self._cid(curve)
+        h = ctypes.c_int(-1)
+        buf = None if xy is None else _u8(xy).reshape(-1)
+        self._check(self._lib.ellgpu_ed_base_define(self._ctx, cid, None if buf is None else buf.ctypes.data,
+                                                    int(window_bits), ctypes.byref(h)))
+        self._base_curve[h.value] = curve
+        return h.value
+
     def release_base(self, base):
         self._check(self._lib.ellgpu_base_release(self._ctx, int(base)))
         self._base_curve.pop(int(base), None)

@@ -50,6 +50,7 @@
  *             (ellgpu_custom_derive / _custom_derive_wire / _custom_validate / _custom_encode_points)
  *             and, on a user-defined Montgomery curve (defineMont(ctx, p, a); ellgpu_custom_mont_ladder /
  *             _validate / _derive), the ops 17..19: Point#mul + getX, MontCurve#validate, KeyPair#derive
+ *           defineEdBase(ctx, curve, xy|null, windowBits) -> handle (Edwards curves, include/ellgpu_ext.h),
  *           defineBase(ctx, curve, xy|null, windowBits) -> handle, releaseBase(ctx, base), baseInfo(ctx, base) ->
  *             {curve, windowBits, tableBytes}, mulBase(ctx, base, k) -> {xy, inf}, mulBase2(ctx, base1, base2, k1, k2)
  *             -> {xy, inf}: fixed-base tables of caller-chosen points (ellgpu_base_*)
@@ -130,6 +131,7 @@ static struct {
   void (*ctx_destroy)(ellgpu_ctx*);
   int (*mul_fixed)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*);
   int (*base_define)(ellgpu_ctx*, int, const uint8_t*, int, int*);
+  int (*ed_base_define)(ellgpu_ctx*, int, const uint8_t*, int, int*);      /* include/ellgpu_ext.h */
   int (*base_release)(ellgpu_ctx*, int);
   int (*base_info)(ellgpu_ctx*, int, int*, int*, uint64_t*);
   int (*mul_base)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*, int, void*);
@@ -226,6 +228,7 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(define_short, "ellgpu_curve_define_short");
   SYM(define_edwards, "ellgpu_curve_define_edwards");
   SYM(define_mont, "ellgpu_curve_define_mont");
+  SYM(ed_base_define, "ellgpu_ed_base_define");
   SYM(base_define, "ellgpu_base_define"); SYM(base_release, "ellgpu_base_release"); SYM(base_info, "ellgpu_base_info");
   SYM(mul_base, "ellgpu_mul_base"); SYM(mul_base2, "ellgpu_mul_base2");
   SYM(custom_mont_ladder, "ellgpu_custom_mont_ladder");
@@ -541,8 +544,10 @@ static napi_value fn_comb_bits(napi_env env, napi_callback_info info) {
  * defineBase(ctx, curve, xy|null, windowBits) -> handle; releaseBase(ctx, base);
  * baseInfo(ctx, base) -> {curve, windowBits, tableBytes}; mulBase(ctx, base, k) -> {xy, inf};
  * mulBase2(ctx, base1, base2, k1, k2) -> {xy, inf}.  The rows' width is the width of the base's
- * curve, asked of the library (ellgpu_base_info). */
-static napi_value fn_define_base(napi_env env, napi_callback_info info) {
+ * curve, asked of the library (ellgpu_base_info).
+ * defineEdBase(ctx, curve, xy|null, windowBits) -> handle: the same for ed25519 and user-defined
+ * Edwards ids (ellgpu_ed_base_define); its handles go to the calls above unchanged. */
+static napi_value define_base_of(napi_env env, napi_callback_info info, int ed) {
   if (!need_lib(env)) return NULL;
   size_t argc = 4; napi_value argv[4];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -556,10 +561,12 @@ static napi_value fn_define_base(napi_env env, napi_callback_info info) {
   int B = L.field_bytes(curve);
   if (xy && B > 0 && l != 2 * (size_t)B) THROW(env, "defineBase: xy is x || y in the curve's coordinate width");
   int h = -1;
-  if (L.base_define(c, curve, xy, wb, &h) != 0) return lib_error(env);
+  if ((ed ? L.ed_base_define : L.base_define)(c, curve, xy, wb, &h) != 0) return lib_error(env);
   napi_value v; CHECK(env, napi_create_int32(env, h, &v));
   return v;
 }
+static napi_value fn_define_base(napi_env env, napi_callback_info info) { return define_base_of(env, info, 0); }
+static napi_value fn_define_ed_base(napi_env env, napi_callback_info info) { return define_base_of(env, info, 1); }
 static napi_value fn_release_base(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
   size_t argc = 2; napi_value argv[2]; int32_t base;
@@ -1416,7 +1423,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
     {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
     {"customEdVerify", fn_custom_ed_verify}, {"customEdSign", fn_custom_ed_sign}, {"customEdSignDet", fn_custom_ed_sign_det}, {"customEcdh", fn_custom_ecdh},
-    {"defineBase", fn_define_base}, {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info},
+    {"defineBase", fn_define_base}, {"defineEdBase", fn_define_ed_base}, {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info},
     {"mulBase", fn_mul_base}, {"mulBase2", fn_mul_base2},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);

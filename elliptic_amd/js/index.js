@@ -646,6 +646,14 @@ Engine.prototype.customEdEncodePointBatchAsync = function(curve, xy, compact, co
 Engine.prototype.defineBase = function defineBase(curve, xy, windowBits) {
   return this.addon.defineBase(this.ctx, this._id(curve), xy || null, windowBits | 0);
 };
+// defineEdBase(curve, xy, windowBits): defineBase for 'ed25519' and user-defined Edwards ids
+// (ellgpu_ed_base_define): xy Buffer(64) = x || y, or null for the curve's own generator (ed25519: an
+// alias of its table; an Edwards domain: a table of its G); windowBits 0 or 16 on ed25519, 0 (= 8), 8
+// or 16 on a user-defined id.  mulBaseBatch, mulBase2Batch and their Async forms take the handle as
+// they take defineBase's; rows are 32 bytes.  install() does not route to them.
+Engine.prototype.defineEdBase = function defineEdBase(curve, xy, windowBits) {
+  return this.addon.defineEdBase(this.ctx, this._id(curve), xy || null, windowBits | 0);
+};
 Engine.prototype.releaseBase = function releaseBase(base) {
   this.addon.releaseBase(this.ctx, base | 0);
 };

@@ -13,7 +13,13 @@ Every row is warmed up, then timed for at least --seconds of back-to-back calls,
 the rows alternate inside a round so that drift is shared.  Reported: the median round in items/s
 and the spread (min .. max) over the rounds.  One JSON line per row, also appended to --out.
 
-    python tools/bench_fixed_base.py [--curve secp256k1] [--log2n 20] [--rounds 5] [--seconds 1.0] [--out FILE]"""
+    python tools/bench_fixed_base.py [--curve secp256k1] [--log2n 20] [--rounds 5] [--seconds 1.0] [--out FILE]
+
+--edwards: the Edwards handles of ellgpu_ed_base_define instead, on ed25519 (a caller's point at the
+comb's own width) and on Curve1174 as a user-defined domain (8 and 16 bits): mul_base per width beside
+mul_var with the point repeated, mul_base2(G, H) beside mul_add2 with both points repeated, and the
+milliseconds per define.  mul_var and mul_add2 on these ids are kernels this feature left as they
+were, so their rows are the earlier commit's figures on the same device, in the same process."""
 import argparse
 import json
 import os
@@ -32,7 +38,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--edwards", action="store_true", help="the Edwards handles (ed25519, Curve1174) instead of --curve")
     a = ap.parse_args()
+    if a.edwards:
+        return main_edwards(a)
     import numpy as np
     import torch
     import elliptic_amd
@@ -74,6 +83,21 @@ def main():
              ("mul_var, point repeated", lambda: ctx.mul_var_dev(a.curve, k1, hxy, xy, inf)),
              ("mul_base2(G alias, H w=%d)" % dflt, lambda: ctx.mul_base2(alias, bases[dflt], k1, k2, out=(xy, inf))),
              ("mul_add2(k1, G, k2, H)", lambda: ctx.mul_add2_dev(a.curve, k1, None, k2, hxy, xy, inf))]
+    measure(rows, n, a, emit)
+    ctx.close()
+    write_out(a, out)
+
+
+def write_out(a, out):
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for row in out:
+                f.write(json.dumps(row) + "\n")
+
+
+def measure(rows, n, a, emit):
+    import torch
     reps = {}
     for name, fn in rows:                                       # warm-up, and calls per timed stretch
         for _ in range(3):
@@ -99,12 +123,53 @@ def main():
         r = sorted(rates[name])
         emit({"row": name, "items_per_s": round(r[len(r) // 2]), "min": round(r[0]), "max": round(r[-1]),
               "rounds": a.rounds, "calls_per_round": reps[name]})
+
+
+def main_edwards(a):
+    import numpy as np
+    import torch
+    import elliptic_amd
+    import fixed_base_checks as FB
+    import fixed_base_ed_checks as FE
+    n = 1 << a.log2n
+    ctx = elliptic_amd.Context(0)
+    rng = np.random.default_rng(7)
+    k1 = torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).cuda()
+    k2 = torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).cuda()
+    xy = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+    inf = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    out = []
+    for name, widths in (("ed25519", [16]), ("curve1174", [8, 16])):
+        spec = FE.spec_of(name)
+        cid = FE.curve_id(ctx, spec)
+        G, H = FE.bases_of(spec)[0], FE.bases_of(spec)[3]
+
+        def emit(row, name=name):
+            row.update(curve=name, n=n)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+
+        gxy = torch.from_numpy(FE.tiled(G, n)).cuda()
+        hxy = torch.from_numpy(FE.tiled(H, n)).cuda()
+        ctx.mul_var_dev(cid, k1, hxy, xy, inf)                  # (ed25519: the curve's own table, once)
+        torch.cuda.synchronize()
+        bh, bg = {}, {}
+        for w in widths:
+            t = time.perf_counter()
+            bh[w] = ctx.define_ed_base(cid, FB.xy_bytes(H, 32), w)
+            torch.cuda.synchronize()
+            emit({"row": "ed_base_define", "width": w, "ms": round((time.perf_counter() - t) * 1e3, 2),
+                  "table_bytes": ctx.base_info(bh[w])[2]})
+            bg[w] = ctx.define_ed_base(cid, FB.xy_bytes(G, 32), w)
+        rows = [("mul_base w=%d" % w, lambda w=w: ctx.mul_base(bh[w], k1, out=(xy, inf))) for w in widths]
+        rows += [("mul_var, point repeated", lambda: ctx.mul_var_dev(cid, k1, hxy, xy, inf))]
+        rows += [("mul_base2(G, H) w=%d" % w, lambda w=w: ctx.mul_base2(bg[w], bh[w], k1, k2, out=(xy, inf))) for w in widths]
+        rows += [("mul_add2(k1, G, k2, H), points repeated", lambda: ctx.mul_add2_dev(cid, k1, gxy, k2, hxy, xy, inf))]
+        measure(rows, n, a, emit)
+        for h in set(list(bh.values()) + list(bg.values())):
+            ctx.release_base(h)
     ctx.close()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for row in out:
-                f.write(json.dumps(row) + "\n")
+    write_out(a, out)
 
 
 if __name__ == "__main__":
