@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -75,7 +76,7 @@
 #ifndef ELL_SPLIT_SMALL_VERIFY
 #define ELL_SPLIT_SMALL_VERIFY 1
 #endif
-// entries per slice of the fixed-base table build (Engine::ensure_comb); the CPU unit-test build
+// entries per slice of the fixed-base table build (Engine::build_table); the CPU unit-test build
 // of these headers passes a small value so that its narrow combs are built in several slices too
 #ifndef ELL_COMB_SLICE
 #define ELL_COMB_SLICE (1u << 20)
@@ -137,59 +138,69 @@ struct FnMulFixed {
     if (i < n) W::mul_fixed(i, n, k, comb, jac);
   }
 };
-// comb construction: entry idx = w * PER + (d - 1) of the fixed-base table is (d << (CB w)) * G;
-// this writes the scalar (reduced mod n) and the generator for entries [first, first + n)
+// comb construction: entry idx = w * PER + (d - 1) of the fixed-base table is (d << (CB w)) * B.
+// comb_entry_scalar gives that scalar for entry idx (cb: window bits of a SIGNED comb, else
+// W::COMB_BITS): reduced mod n on the presets -- every point of a preset has the prime order n, so
+// ((d << sh) mod n) * B is exact and never O -- and left as it stands on a user-defined curve: the
+// unsigned comb's values stay below 2^256, n need not be the order of G (curves.h CvCustomDomain)
+// and a caller's base has no known order (an entry that comes out O refuses the base)
 template <class CV>
-struct FnCombGen {
-  static constexpr const char* NAME = "comb_gen";
+ELL_HD void comb_entry_scalar(size_t idx, int cb, u32* kk) {
   typedef Work<CV> W;
-  static constexpr int DS_PER_LANE = 0;
-  size_t n; size_t first; u8* k; u8* xy; int cb;       // cb: window bits of a SIGNED comb (else W::COMB_BITS)
-  ELL_HD void operator()(size_t i, const DigitStore&) const {
-    if (i >= n) return;
-    const size_t idx = first + i;
-    const size_t per = W::COMB_SIGNED ? ((size_t)1 << (cb - 1)) : (size_t)W::COMB_DIG;
-    const int w = (int)(idx / per);
-    const u32 d = (u32)(idx % per) + 1u;
-    const int sh = w * (W::COMB_SIGNED ? cb : W::COMB_BITS);
-    // (d << sh) mod n: the value can exceed the scalar's byte length in the top window (the
-    // signed recoding's carry window of a narrow comb: 2^256 * G), so it goes through the order
-    // field like any over-long byte string (Work::bytes_mod_n)
-    constexpr int LN = W::LN;
-    u32 v[2 * LN];
+  const size_t per = W::COMB_SIGNED ? ((size_t)1 << (cb - 1)) : (size_t)W::COMB_DIG;
+  const int w = (int)(idx / per);
+  const u32 d = (u32)(idx % per) + 1u;
+  const int sh = w * (W::COMB_SIGNED ? cb : W::COMB_BITS);
+  // (d << sh) mod n: the value can exceed the scalar's byte length in the top window (the
+  // signed recoding's carry window of a narrow comb: 2^256 * G), so it goes through the order
+  // field like any over-long byte string (Work::bytes_mod_n)
+  constexpr int LN = W::LN;
+  u32 v[2 * LN];
+  ELL_UNROLL
+  for (int l = 0; l < 2 * LN; l++) v[l] = 0;
+  const int li = sh >> 5, bs = sh & 31;
+  ELL_UNROLL
+  for (int l = 0; l < 2 * LN; l++) {
+    if (l == li) v[l] = d << bs;
+    if (l == li + 1 && bs) v[l] = d >> (32 - bs);
+  }
+  if constexpr (CV::RT_ORDER) {
     ELL_UNROLL
-    for (int l = 0; l < 2 * LN; l++) v[l] = 0;
-    const int li = sh >> 5, bs = sh & 31;
-    ELL_UNROLL
-    for (int l = 0; l < 2 * LN; l++) {
-      if (l == li) v[l] = d << bs;
-      if (l == li + 1 && bs) v[l] = d >> (32 - bs);
-    }
-    u32 kk[W::L], gx[W::L], gy[W::L];
-    if constexpr (CV::RT_ORDER) {
-      // a user-defined domain: the unsigned comb's values d << sh stay below 2^256, and are NOT
-      // reduced mod n -- n need not be G's order (curves.h CvCustomDomain)
-      W::generator_words(gx, gy);
-      ELL_UNROLL
-      for (int l = 0; l < W::L; l++) kk[l] = v[l];
-    } else {
+    for (int l = 0; l < W::L; l++) kk[l] = v[l];
+  } else {
     u8 vb[8 * LN];
     store_be<2 * LN>(vb, v, 8 * LN);
     typename W::Nl km = W::bytes_mod_n(vb, 8 * LN);
     u32 kn[LN];
     W::Fn::to_plain(kn, km);
     ELL_UNROLL
-    for (int l = 0; l < W::L; l++) { kk[l] = l < LN ? kn[l] : 0u; gx[l] = W::C::gx_plain[l]; gy[l] = W::C::gy_plain[l]; }
+    for (int l = 0; l < W::L; l++) kk[l] = l < LN ? kn[l] : 0u;
+  }
+}
+// the scalars and the generator for entries [first, first + n)
+template <class CV>
+struct FnCombGen {
+  static constexpr const char* NAME = "comb_gen";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; size_t first; u8* k; u8* xy; int cb;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i >= n) return;
+    u32 kk[W::L], gx[W::L], gy[W::L];
+    comb_entry_scalar<CV>(first + i, cb, kk);
+    if constexpr (CV::RT_ORDER) {
+      W::generator_words(gx, gy);
+    } else {
+      ELL_UNROLL
+      for (int l = 0; l < W::L; l++) { gx[l] = W::C::gx_plain[l]; gy[l] = W::C::gy_plain[l]; }
     }
     store_be<W::L>(k + i * W::BYTES, kk, W::BYTES);
     store_be<W::L>(xy + i * 2 * W::BYTES, gx, W::BYTES);
     store_be<W::L>(xy + i * 2 * W::BYTES + W::BYTES, gy, W::BYTES);
   }
 };
-// ... of a caller-chosen base (Engine::define_base): FnCombGen with the point read from a device
-// buffer, x || y big-endian.  The scalar is reduced mod n on the presets -- every point of a preset
-// has the prime order n, so ((d << sh) mod n) * P is exact and never O -- and left as it stands on
-// a user-defined curve, whose bases have no known order (an entry that comes out O refuses the base)
+// ... of a caller-chosen base (Engine::define_base): the point is read from a device buffer,
+// x || y big-endian
 template <class CV>
 struct FnBaseCombGen {
   static constexpr const char* NAME = "base_comb_gen";
@@ -198,34 +209,8 @@ struct FnBaseCombGen {
   size_t n; size_t first; const u8* pt; u8* k; u8* xy; int cb;
   ELL_HD void operator()(size_t i, const DigitStore&) const {
     if (i >= n) return;
-    const size_t idx = first + i;
-    const size_t per = W::COMB_SIGNED ? ((size_t)1 << (cb - 1)) : (size_t)W::COMB_DIG;
-    const int w = (int)(idx / per);
-    const u32 d = (u32)(idx % per) + 1u;
-    const int sh = w * (W::COMB_SIGNED ? cb : W::COMB_BITS);
-    constexpr int LN = W::LN;
-    u32 v[2 * LN];
-    ELL_UNROLL
-    for (int l = 0; l < 2 * LN; l++) v[l] = 0;
-    const int li = sh >> 5, bs = sh & 31;
-    ELL_UNROLL
-    for (int l = 0; l < 2 * LN; l++) {
-      if (l == li) v[l] = d << bs;
-      if (l == li + 1 && bs) v[l] = d >> (32 - bs);
-    }
     u32 kk[W::L];
-    if constexpr (CV::RT_ORDER) {
-      ELL_UNROLL
-      for (int l = 0; l < W::L; l++) kk[l] = v[l];
-    } else {
-      u8 vb[8 * LN];
-      store_be<2 * LN>(vb, v, 8 * LN);
-      typename W::Nl km = W::bytes_mod_n(vb, 8 * LN);
-      u32 kn[LN];
-      W::Fn::to_plain(kn, km);
-      ELL_UNROLL
-      for (int l = 0; l < W::L; l++) kk[l] = l < LN ? kn[l] : 0u;
-    }
+    comb_entry_scalar<CV>(first + i, cb, kk);
     store_be<W::L>(k + i * W::BYTES, kk, W::BYTES);
     ELL_NOUNROLL
     for (int b = 0; b < 2 * W::BYTES; b++) xy[i * 2 * W::BYTES + b] = pt[b];
@@ -1619,6 +1604,98 @@ class Engine {
   // ---- fixed-base comb tables, built on the device with our own kernels ----
   // a built table: entry 0, what was allocated, the window width in use, the allocation's bytes
   struct CombTable { void* comb = nullptr; void* base = nullptr; int bits = 0; size_t bytes = 0; };
+  // what build_table has to know of a table: plain numbers, nothing of the curve
+  struct TablePlan {
+    size_t entries;        // without the header slot
+    size_t entry_bytes;
+    size_t scalar_bytes;   // of a scalar of the build; a point is x || y of as many bytes each
+    int bits;              // the window width
+    bool header;           // a slot in front of entry 0 holds the width
+    bool limit;            // ELLGPU_COMB_MAX_BYTES applies
+    bool check_inf;        // refuse a table that holds the point at infinity
+  };
+  // The one builder of every fixed-base table: the curve's own variable-base kernel on the scalars
+  // d << (bits w) and the base.  gen(m, first, dk, dp) launches the kernel that writes the scalars and
+  // points of the entries [first, first + m); fill(m, dk, dp, out_xy, out_inf, dst) launches the
+  // ladder and the normalisation that writes them to dst, the place of entry `first`.
+  //   Slices.  At most ELL_COMB_SLICE = 2^20 entries at a time: the 22-bit signed comb of the 256-bit
+  // curves has 25 M entries = 1.6 GB, and a slice needs 1 GB of window-table scratch.
+  //   Header slot.  A format that is walked at several widths carries its width in a slot of one
+  // entry's size in front of entry 0 (ladder.h comb_bits_of, EdcWork::comb_add).
+  //   Byte limit.  ELLGPU_COMB_MAX_BYTES (developer / test override, read when the context is created)
+  // refuses a larger table as if its allocation had failed, before anything is allocated.
+  //   check_inf (user-defined short ids, whose bases have no known order): out_xy / out_inf are a
+  // slice's entries as bytes, which nobody reads, and their infinity flags, fetched slice by slice.
+  // One sync at the end surfaces a failed launch (gen's included).  Every temporary is freed on every
+  // way out, and the table itself on failure.
+  typedef std::function<void(size_t, size_t, u8*, u8*)> TableGen;
+  typedef std::function<int(size_t, const u8*, const u8*, u8*, u8*, void*)> TableFill;
+  int build_table(const TablePlan& p, const TableGen& gen, const TableFill& fill, CombTable& out) {
+    const size_t S = p.scalar_bytes;
+    const size_t hdr = p.header ? p.entry_bytes : 0;
+    const size_t bytes = hdr + p.entries * p.entry_bytes;
+    const size_t slice = p.entries < (size_t)ELL_COMB_SLICE ? p.entries : (size_t)ELL_COMB_SLICE;
+    if (p.limit && tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) return fail(E_NOMEM, "comb table allocation failed");
+    u8* base = (u8*)bk.alloc(bytes);
+    u8* dk = base ? (u8*)bk.alloc(slice * S) : nullptr;
+    u8* dp = dk ? (u8*)bk.alloc(slice * 2 * S) : nullptr;
+    u8* dchk = dp && p.check_inf ? (u8*)bk.alloc(slice * (2 * S + 1)) : nullptr;
+    u8* dinf = dchk ? dchk + slice * 2 * S : nullptr;
+    int rc = dp && (dchk || !p.check_inf) ? E_OK : fail(E_NOMEM, "comb table allocation failed");
+    if (rc == E_OK) {
+      std::vector<u32> width(p.entry_bytes / 4, 0);
+      width[0] = (u32)p.bits;
+      if (p.header) bk.h2d(base, width.data(), p.entry_bytes);
+      std::vector<u8> flags(p.check_inf ? slice : 0);
+      bool holds_inf = false;
+      for (size_t first = 0; first < p.entries && rc == E_OK; first += slice) {
+        const size_t m = p.entries - first < slice ? p.entries - first : slice;
+        gen(m, first, dk, dp);
+        rc = fill(m, dk, dp, dchk, dinf, base + hdr + first * p.entry_bytes);
+        if (rc == E_OK && p.check_inf) {
+          bk.d2h(flags.data(), dinf, m);
+          if (bk.sync() == E_OK)
+            for (size_t i = 0; i < m; i++) holds_inf |= flags[i] != 0;
+        }
+      }
+      const int src = bk.sync();
+      if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
+      if (rc == E_OK && holds_inf) rc = fail(E_ARG, "a multiple of the base inside the table is the point at infinity");
+    }
+    if (dchk) bk.free_(dchk);
+    if (dp) bk.free_(dp);
+    if (dk) bk.free_(dk);
+    if (rc) {
+      if (base) bk.free_(base);
+      return rc;
+    }
+    out.comb = base + hdr;
+    out.base = base;
+    out.bits = p.bits;
+    out.bytes = bytes;
+    return E_OK;
+  }
+  // The test of a caller-chosen base before its table is built (Chk: FnBaseCheck<CV>, FnEdBaseCheck
+  // or FnEdcBaseCheck; B: the bytes of a coordinate).  Returns the device copy of x || y for the
+  // table's generator to read, which the caller frees; null with rc set where the base is refused.
+  // test == false (a curve's own generator) only makes the copy.
+  template <class Chk>
+  u8* checked_base(const u8* xy, size_t B, bool test, int& rc) {
+    u8* dpt = (u8*)bk.alloc(2 * B + 1);            // the point and, behind it, the test's flag
+    if (!dpt) { rc = fail(E_NOMEM, "scratch allocation failed"); return nullptr; }
+    u8 flag = test ? 1 : 0;
+    bk.h2d(dpt, xy, 2 * B);
+    if (test) {
+      Chk chk{dpt, dpt + 2 * B};
+      bk.launch(chk, 1);
+      bk.d2h(&flag, dpt + 2 * B, 1);
+    }
+    rc = bk.sync();
+    if (rc) rc = fail(rc, "testing the base failed on the device");
+    else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
+    if (rc) { bk.free_(dpt); dpt = nullptr; }
+    return dpt;
+  }
   template <class CV>
   int ensure_comb();
   template <class CV>
@@ -1628,9 +1705,10 @@ class Engine {
                     typename Work<CV>::A* raw);
   // fixed-base tables of caller-chosen points on Edwards curves (define_ed_base): the test of the
   // base and the build of its table; k1 * B1 (k2 == null) or k1 * B1 + k2 * B2 over built tables, one
-  // item per lane at every n.  ed_*: ed25519, tables in EdWork's cached format; edc_*: user-defined.
+  // item per lane at every n.  ed_*: ed25519, tables in EdWork's cached format (own: the curve's own
+  // comb, ensure_ed_comb); edc_*: user-defined.
   template <int U = 0>
-  int ed_base_table(const u8* xy, CombTable& out);
+  int ed_base_table(const u8* xy, bool own, CombTable& out);
   template <int U = 0>
   int ed_base_mul_chunk(size_t n, const u8* k1, const EdWork::P* t1, const u8* k2, const EdWork::P* t2,
                         u8* out_xy, u8* out_inf);
@@ -1639,21 +1717,18 @@ class Engine {
   template <int U = 0>
   int edc_base_mul_chunk(size_t n, const u8* k1, const EdcWork::A* t1, const u8* k2, const EdcWork::A* t2,
                          u8* out_xy, u8* out_inf);
-  // (comb: the curve's own table for mul_fixed, a caller-chosen base's for mul_base)
+  // k * B over a comb (the curve's own table for mul_fixed, a caller-chosen base's for mul_base), or
+  // with k2: k * B + k2 * B2 over two tables, one item per lane at every n
   template <class CV>
-  int mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, u8* out_xy, u8* out_inf);
-  // the loop that builds a comb: gen(m, first, dk, dp, cb) writes the scalars and points of the
-  // entries [first, first + m), the variable-base kernel turns them into the entries.  cb: the
-  // window width to start from; narrow: go on to narrower signed combs on E_NOMEM; check_inf
-  // (user-defined ids): fetch the entries' infinity flags and refuse a table that holds O
+  int mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, const u8* k2,
+                      const typename Work<CV>::A* t2, u8* out_xy, u8* out_inf);
+  // a short curve's comb through build_table: gen(m, first, dk, dp, cb) at the width cb in use.  cb:
+  // the width to start from; narrow: go on to narrower signed combs on E_NOMEM; check_inf: TablePlan's
   template <class CV, class Gen>
   int build_comb(int cb, bool narrow, bool check_inf, Gen gen, CombTable& out);
   // tests a caller-chosen base on the device and builds its table (define_base)
   template <class CV>
   int base_table(const u8* xy, int window_bits, CombTable& out);
-  template <class CV>
-  int mul_base2_chunk(size_t n, const u8* k1, const typename Work<CV>::A* t1, const u8* k2,
-                      const typename Work<CV>::A* t2, u8* out_xy, u8* out_inf);
   template <class CV>
   int mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                      u8* out_xy, u8* out_inf);
@@ -2272,9 +2347,9 @@ class Engine {
     return batch(where, n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto r) {
       int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
       if (rc) return rc;
-      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], comb_of<CvCustomDomain>(), r[0], r[1]);
+      if (dom) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], comb_of<CvCustomDomain>(), nullptr, nullptr, r[0], r[1]);
       else if (curve == CURVE_ED25519) rc = ed_mul_fixed_chunk(m, d[0], r[0], r[1]);
-      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], comb_of<CV>(), r[0], r[1]));
+      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], comb_of<CV>(), nullptr, nullptr, r[0], r[1]));
       return rc;
     });
   }
@@ -2477,7 +2552,7 @@ class Engine {
       if (sc.rc) return sc.rc;
       if (!ed) base_upload(curve);
       int rc = E_OK;
-      if (ed) rc = curve == CURVE_ED25519 ? ed_base_table(xy, rec.t) : edc_base_table(xy, window_bits, rec.t);
+      if (ed) rc = curve == CURVE_ED25519 ? ed_base_table(xy, false, rec.t) : edc_base_table(xy, window_bits, rec.t);
       else if (is_custom(curve)) rc = base_table<CvCustomDomain>(xy, window_bits, rec.t);
       else ELL_SHORT_DISPATCH(curve, rc = base_table<CV>(xy, window_bits, rec.t));
       if (rc) return rc;
@@ -2554,6 +2629,26 @@ class Engine {
     comb = comb_[r.curve];
     return rc;
   }
+  // One chunk of k1 * B1 (r2 and k2 null) or k1 * B1 + k2 * B2 over the tables of one curve, on the
+  // curve's family: ed25519, a user-defined Edwards id, a user-defined short id, a preset
+  int walk_tables(const BaseRec& r1, const BaseRec* r2, size_t m, const u8* k1, const u8* k2, u8* out_xy, u8* out_inf) {
+    const void* t1 = nullptr;
+    const void* t2 = nullptr;
+    int rc = base_table_ptr(r1, t1);
+    if (rc == E_OK && r2) rc = base_table_ptr(*r2, t2);
+    if (rc) return rc;
+    const int curve = r1.curve;
+    if (r1.ed) return curve == CURVE_ED25519
+                          ? ed_base_mul_chunk(m, k1, (const EdWork::P*)t1, k2, (const EdWork::P*)t2, out_xy, out_inf)
+                          : edc_base_mul_chunk(m, k1, (const EdcWork::A*)t1, k2, (const EdcWork::A*)t2, out_xy, out_inf);
+    if (is_custom(curve)) {
+      typedef const Work<CvCustomDomain>::A* T;
+      return mul_fixed_chunk<CvCustomDomain>(m, k1, (T)t1, k2, (T)t2, out_xy, out_inf);
+    }
+    ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, k1, (const typename Work<CV>::A*)t1, k2,
+                                                        (const typename Work<CV>::A*)t2, out_xy, out_inf));
+    return rc;
+  }
   // P.precompute(); P.mul(k): k as it stands (field_bytes bytes, neither reduced nor truncated, as
   // in mul_fixed), out_inf = 1 and a zeroed result at O.  No status 2: the base was tested when defined.
   int mul_base(Mem where, int base, size_t n, const u8* k, u8* out_xy, u8* out_inf) {
@@ -2568,14 +2663,7 @@ class Engine {
     if (sc.rc) return sc.rc;
     if (!r->ed) base_upload(curve);
     return batch(where, n, {In{k, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto o) {
-      const void* t = nullptr;
-      int rc = base_table_ptr(*r, t);
-      if (rc) return rc;
-      if (r->ed) rc = curve == CURVE_ED25519 ? ed_base_mul_chunk(m, d[0], (const EdWork::P*)t, nullptr, nullptr, o[0], o[1])
-                                             : edc_base_mul_chunk(m, d[0], (const EdcWork::A*)t, nullptr, nullptr, o[0], o[1]);
-      else if (is_custom(curve)) rc = mul_fixed_chunk<CvCustomDomain>(m, d[0], (const Work<CvCustomDomain>::A*)t, o[0], o[1]);
-      else ELL_SHORT_DISPATCH(curve, rc = mul_fixed_chunk<CV>(m, d[0], (const typename Work<CV>::A*)t, o[0], o[1]));
-      return rc;
+      return walk_tables(*r, nullptr, m, d[0], nullptr, o[0], o[1]);
     });
   }
   // k1 * B1 + k2 * B2 (_wnafMulAdd on two precomputed operands); base1 == base2 is allowed
@@ -2595,23 +2683,7 @@ class Engine {
     if (sc.rc) return sc.rc;
     if (!r1->ed) base_upload(curve);
     return batch(where, n, {In{k1, B}, In{k2, B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}}, [&](size_t m, auto d, auto o) {
-      const void* t1 = nullptr;
-      const void* t2 = nullptr;
-      int rc = base_table_ptr(*r1, t1);
-      if (rc == E_OK) rc = base_table_ptr(*r2, t2);
-      if (rc) return rc;
-      if (r1->ed) {
-        rc = curve == CURVE_ED25519
-                 ? ed_base_mul_chunk(m, d[0], (const EdWork::P*)t1, d[1], (const EdWork::P*)t2, o[0], o[1])
-                 : edc_base_mul_chunk(m, d[0], (const EdcWork::A*)t1, d[1], (const EdcWork::A*)t2, o[0], o[1]);
-      } else if (is_custom(curve)) {
-        typedef const Work<CvCustomDomain>::A* T;
-        rc = mul_base2_chunk<CvCustomDomain>(m, d[0], (T)t1, d[1], (T)t2, o[0], o[1]);
-      } else {
-        ELL_SHORT_DISPATCH(curve, rc = mul_base2_chunk<CV>(m, d[0], (const typename Work<CV>::A*)t1, d[1],
-                                                            (const typename Work<CV>::A*)t2, o[0], o[1]));
-      }
-      return rc;
+      return walk_tables(*r1, r2, m, d[0], d[1], o[0], o[1]);
     });
   }
 
@@ -3327,65 +3399,20 @@ template <class BK>
 template <class CV, class Gen>
 int Engine<BK>::build_comb(int cb, bool narrow, bool check_inf, Gen gen, CombTable& out) {
   typedef Work<CV> W;
-  // Built by the engine itself: the variable-base kernel on the scalars d << (COMB_BITS w) and
-  // the base, in slices of at most 2^20 entries (the 22-bit signed comb of the 256-bit
-  // curves has 25 M entries = 1.6 GB; a slice needs 1 GB of window-table scratch).
-  // A SIGNED comb (the 256-bit curves) carries its window width in the slot in front of entry 0
-  // (ladder.h comb_bits_of): when the device cannot hold the default table -- 12 windows x 2^21
-  // entries = 1.6 GB per curve -- the SAME kernels run on a narrower one: 16 bits (17 windows,
-  // 36 MB), 12, 8, 4.  ELLGPU_COMB_MAX_BYTES (developer / test override, read when the context is
-  // created) refuses larger tables as if the allocation had failed.
-  const int B = W::BYTES;
+  // (a domain's entries come from the user-defined curves' own ladder: the same field and points,
+  // no second instantiation of it)
+  typedef typename std::conditional<CV::RT_ORDER, CvCustom, CV>::type CVL;
+  // When the device cannot hold a SIGNED comb (the 256-bit curves: 12 windows x 2^21 entries =
+  // 1.6 GB at the default 22 bits), or the window-table scratch of its build, the SAME kernels run
+  // on a narrower one, whose header slot tells them so: 16 bits (17 windows, 36 MB), 12, 8, 4.
   for (;;) {
-    const size_t n = comb_entries<CV>(cb);
-    const size_t bytes = (n + 1) * sizeof(typename W::A);
-    const size_t slice = n < (size_t)ELL_COMB_SLICE ? n : (size_t)ELL_COMB_SLICE;
-    typename W::A* base = (tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) ? nullptr : (typename W::A*)bk.alloc(bytes);
-    u8* dk = base ? (u8*)bk.alloc(slice * B) : nullptr;
-    u8* dp = dk ? (u8*)bk.alloc(slice * 2 * B) : nullptr;
-    // (check_inf: the entries as bytes, which nobody reads, and their infinity flags behind them)
-    u8* dchk = dp && check_inf ? (u8*)bk.alloc(slice * (2 * B + 1)) : nullptr;
-    int rc = (base && dk && dp && (dchk || !check_inf)) ? E_OK : E_NOMEM;
-    if (rc == E_OK) {
-      typename W::A* comb = base + 1;
-      u32 hdr[sizeof(typename W::A) / 4] = {0};
-      hdr[0] = (u32)cb;
-      bk.h2d(base, hdr, sizeof hdr);
-      std::vector<u8> flags(check_inf ? slice : 0);
-      bool holds_inf = false;
-      for (size_t first = 0; first < n && rc == E_OK; first += slice) {
-        const size_t m = n - first < slice ? n - first : slice;
-        gen(m, first, dk, dp, cb);
-        // (a domain's entries come from the user-defined curves' own ladder: the same field and
-        // points, no second instantiation of it)
-        typedef typename std::conditional<CV::RT_ORDER, CvCustom, CV>::type CVL;
-        rc = mul_var_chunk<CVL>(m, dk, dp, dchk, dchk ? dchk + slice * 2 * B : nullptr, comb + first);
-        if (rc == E_OK && check_inf) {
-          bk.d2h(flags.data(), dchk + slice * 2 * B, m);
-          if (bk.sync() == E_OK)
-            for (size_t i = 0; i < m; i++) holds_inf |= flags[i] != 0;
-        }
-      }
-      const int src = bk.sync();                   // a failed launch (comb_gen included) surfaces here
-      if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
-      if (rc == E_OK && holds_inf) rc = fail(E_ARG, "a multiple of the base inside the table is the point at infinity");
-      if (rc == E_OK) {
-        bk.free_(dk);
-        bk.free_(dp);
-        if (dchk) bk.free_(dchk);
-        out.comb = comb;
-        out.base = base;
-        out.bits = cb;
-        out.bytes = bytes;
-        return E_OK;
-      }
-    }
-    if (dchk) bk.free_(dchk);
-    if (dp) bk.free_(dp);
-    if (dk) bk.free_(dk);
-    if (base) bk.free_(base);
-    // out of memory (the table, or the window-table scratch of its build): a narrower comb
-    if (rc != E_NOMEM || !narrow || !W::COMB_SIGNED || cb <= 4) return rc == E_NOMEM ? fail(E_NOMEM, "comb table allocation failed") : rc;
+    const TablePlan plan{comb_entries<CV>(cb), sizeof(typename W::A), (size_t)W::BYTES, cb, true, true, check_inf};
+    const int rc = build_table(plan, [&](size_t m, size_t first, u8* dk, u8* dp) { gen(m, first, dk, dp, cb); },
+                               [&](size_t m, const u8* dk, const u8* dp, u8* out_xy, u8* out_inf, void* dst) {
+      return mul_var_chunk<CVL>(m, dk, dp, out_xy, out_inf, (typename W::A*)dst);
+    }, out);
+    if (rc != E_NOMEM) return rc;
+    if (!narrow || !W::COMB_SIGNED || cb <= 4) return fail(E_NOMEM, "comb table allocation failed");
     err.clear();
     cb = cb > 16 ? 16 : (cb > 12 ? 12 : (cb > 8 ? 8 : 4));
   }
@@ -3395,26 +3422,16 @@ template <class BK>
 template <class CV>
 int Engine<BK>::base_table(const u8* xy, int window_bits, CombTable& out) {
   typedef Work<CV> W;
-  const size_t B = W::BYTES;
-  u8* dpt = (u8*)bk.alloc(2 * B + 1);            // the point and, behind it, the test's flag
-  if (!dpt) return fail(E_NOMEM, "scratch allocation failed");
-  u8 flag = 1;
-  bk.h2d(dpt, xy, 2 * B);
-  FnBaseCheck<CV> chk{dpt, dpt + 2 * B};
-  bk.launch(chk, 1);
-  bk.d2h(&flag, dpt + 2 * B, 1);
-  int rc = bk.sync();
-  if (rc) rc = fail(rc, "testing the base failed on the device");
-  else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
-  if (rc == E_OK) {
-    // 0: 16 bits (36 MB, 17 additions per item) -- not G's 22 (1.6 GB): a caller may hold 16 bases
-    const int dflt = W::COMB_SIGNED ? (W::COMB_BITS < 16 ? W::COMB_BITS : 16) : W::COMB_BITS;
-    rc = build_comb<CV>(window_bits ? window_bits : dflt, window_bits == 0, CV::RT_ORDER,
-                        [&](size_t m, size_t first, u8* dk, u8* dp, int cb) {
-      FnBaseCombGen<CV> g{m, first, dpt, dk, dp, cb};
-      bk.launch(g, m);
-    }, out);
-  }
+  int rc = E_OK;
+  u8* dpt = checked_base<FnBaseCheck<CV>>(xy, W::BYTES, true, rc);
+  if (!dpt) return rc;
+  // 0: 16 bits (36 MB, 17 additions per item) -- not G's 22 (1.6 GB): a caller may hold 16 bases
+  const int dflt = W::COMB_SIGNED ? (W::COMB_BITS < 16 ? W::COMB_BITS : 16) : W::COMB_BITS;
+  rc = build_comb<CV>(window_bits ? window_bits : dflt, window_bits == 0, CV::RT_ORDER,
+                      [&](size_t m, size_t first, u8* dk, u8* dp, int cb) {
+    FnBaseCombGen<CV> g{m, first, dpt, dk, dp, cb};
+    bk.launch(g, m);
+  }, out);
   bk.free_(dpt);
   return rc;
 }
@@ -3481,14 +3498,15 @@ int Engine<BK>::mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u
 
 template <class BK>
 template <class CV>
-int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, u8* out_xy, u8* out_inf) {
+int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::A* comb, const u8* k2,
+                                const typename Work<CV>::A* t2, u8* out_xy, u8* out_inf) {
   typedef Work<CV> W;
   // a handful of items: the comb and the item's own inversion on a wave, one launch (the scalar is
   // Point#mul's: BYTES bytes as they stand -- coop_sign_point<CW, false>, no _truncateToN)
   constexpr bool row_k256 = CV::ENDO && W::L <= 8 && CoopK256::AVAILABLE;
   constexpr bool row_nist = !CV::ENDO && CoopNist<CV>::AVAILABLE;
   if constexpr ((row_k256 || row_nist) && W::NBYTES == W::BYTES) {
-    if (n <= coop_grid_of<CV>() && out_inf) {
+    if (!k2 && n <= coop_grid_of<CV>() && out_inf) {
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
       FnMulFixedC<CV, CW> fc{n, k, comb, out_xy, out_inf};
       bk.launch_coop(fc, n);
@@ -3497,22 +3515,12 @@ int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::
   }
   u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
   if (!jac) return fail(E_NOMEM, "scratch allocation failed");
-  launch_paired<FnMulFixed, CV>(n, k, comb, jac);
+  // (two tables: one item per lane at every n, and one normalisation for the sum)
+  if (k2) launch_paired<FnMulBase2, CV>(n, k, comb, k2, t2, jac);
+  else launch_paired<FnMulFixed, CV>(n, k, comb, jac);
   return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
 }
 
-
-template <class BK>
-template <class CV>
-int Engine<BK>::mul_base2_chunk(size_t n, const u8* k1, const typename Work<CV>::A* t1, const u8* k2,
-                                const typename Work<CV>::A* t2, u8* out_xy, u8* out_inf) {
-  typedef Work<CV> W;
-  // one item per lane at every n, and one normalisation for the sum
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  if (!jac) return fail(E_NOMEM, "scratch allocation failed");
-  launch_paired<FnMulBase2, CV>(n, k1, t1, k2, t2, jac);
-  return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
-}
 
 
 template <class BK>
@@ -4075,36 +4083,18 @@ template <class BK>
 template <int U>
 int Engine<BK>::ensure_ed_comb() {
   if (comb_[CURVE_ED25519]) return E_OK;
-  const size_t n = EdWork::COMB_ENTRIES;
-  std::vector<u8> ks(n * 32, 0), pts(n * 64, 0);
+  u32 gx[8], gy[8];
+  for (int i = 0; i < 8; i++) { gx[i] = consts::ED25519_C::gx_plain[i]; gy[i] = consts::ED25519_C::gy_plain[i]; }
   u8 g[64];
-  {
-    u32 gx[8], gy[8];
-    for (int i = 0; i < 8; i++) { gx[i] = consts::ED25519_C::gx_plain[i]; gy[i] = consts::ED25519_C::gy_plain[i]; }
-    store_be<8>(g, gx, 32);
-    store_be<8>(g + 32, gy, 32);
-  }
-  for (int w = 0; w < EdWork::COMB_W; w++)
-    for (int d = 1; d <= EdWork::COMB_DIG; d++) {
-      size_t i = (size_t)w * EdWork::COMB_DIG + (d - 1);
-      int byte0 = w * (EdWork::COMB_BITS / 8);
-      for (int bb = 0; bb < EdWork::COMB_BITS / 8; bb++) ks[i * 32 + (31 - (byte0 + bb))] = (u8)(d >> (8 * bb));
-      memcpy(&pts[i * 64], g, 64);
-    }
-  void* comb = bk.alloc(n * sizeof(EdWork::P));
-  u8* dk = (u8*)bk.alloc(ks.size());
-  u8* dp = (u8*)bk.alloc(pts.size());
-  if (!comb || !dk || !dp) return fail(E_NOMEM, "comb table allocation failed");
-  bk.h2d(dk, ks.data(), ks.size());
-  bk.h2d(dp, pts.data(), pts.size());
-  int rc = ed_mul_var_chunk(n, dk, dp, nullptr, nullptr, (EdWork::P*)comb);
-  bk.sync();
-  bk.free_(dk);
-  bk.free_(dp);
-  if (rc) { bk.free_(comb); return rc; }
-  comb_[CURVE_ED25519] = comb;
+  store_be<8>(g, gx, 32);
+  store_be<8>(g + 32, gy, 32);
+  CombTable t;
+  const int rc = ed_base_table(g, true, t);
+  if (rc) return rc;
+  comb_[CURVE_ED25519] = t.comb;
   return E_OK;
 }
+
 
 template <class BK>
 template <int U>
@@ -4180,54 +4170,27 @@ int Engine<BK>::ed_mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u
 }
 
 // ---- fixed-base tables of caller-chosen points on Edwards curves ---------------------------------
-// The test of the base (x, y < p, on the curve) runs on the device, then the table is built by the
-// curve's own variable-base kernel on the scalars d << (bits w), in slices of ELL_COMB_SLICE entries
-// (FnEdBaseCombGen writes a slice's scalars and points).  ELLGPU_COMB_MAX_BYTES applies per table.
+// The test of the base (x, y < p, on the curve) runs on the device (checked_base), then build_table
+// runs the curve's own variable-base kernel on the scalars and points that FnEdBaseCombGen writes.
 
 template <class BK>
 template <int U>
-int Engine<BK>::ed_base_table(const u8* xy, CombTable& out) {
-  const size_t n = EdWork::COMB_ENTRIES;
-  const size_t bytes = n * sizeof(EdWork::P);
-  const size_t slice = n < (size_t)ELL_COMB_SLICE ? n : (size_t)ELL_COMB_SLICE;
-  u8* dpt = (u8*)bk.alloc(64 + 1);               // the point and, behind it, the test's flag
-  if (!dpt) return fail(E_NOMEM, "scratch allocation failed");
-  u8 flag = 1;
-  bk.h2d(dpt, xy, 64);
-  FnEdBaseCheck chk{dpt, dpt + 64};
-  bk.launch(chk, 1);
-  bk.d2h(&flag, dpt + 64, 1);
-  int rc = bk.sync();
-  if (rc) rc = fail(rc, "testing the base failed on the device");
-  else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
-  if (rc) { bk.free_(dpt); return rc; }
-  EdWork::P* comb = (tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) ? nullptr : (EdWork::P*)bk.alloc(bytes);
-  u8* dk = comb ? (u8*)bk.alloc(slice * 32) : nullptr;
-  u8* dp = dk ? (u8*)bk.alloc(slice * 64) : nullptr;
-  rc = dp ? E_OK : fail(E_NOMEM, "comb table allocation failed");
-  for (size_t first = 0; first < n && rc == E_OK; first += slice) {
-    const size_t m = n - first < slice ? n - first : slice;
+int Engine<BK>::ed_base_table(const u8* xy, bool own, CombTable& out) {
+  int rc = E_OK;
+  u8* dpt = checked_base<FnEdBaseCheck>(xy, 32, !own, rc);
+  if (!dpt) return rc;
+  // (the curve's own comb has never been subject to ELLGPU_COMB_MAX_BYTES, and is not now)
+  const TablePlan plan{EdWork::COMB_ENTRIES, sizeof(EdWork::P), 32, EdWork::COMB_BITS, false, !own, false};
+  rc = build_table(plan, [&](size_t m, size_t first, u8* dk, u8* dp) {
     FnEdBaseCombGen<false> g{m, first, dpt, dk, dp, EdWork::COMB_BITS};
     bk.launch(g, m);
-    rc = ed_mul_var_chunk(m, dk, dp, nullptr, nullptr, comb + first);
-  }
-  if (dp) {
-    const int src = bk.sync();
-    if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
-  }
-  if (dp) bk.free_(dp);
-  if (dk) bk.free_(dk);
+  }, [&](size_t m, const u8* dk, const u8* dp, u8*, u8*, void* dst) {
+    return ed_mul_var_chunk(m, dk, dp, nullptr, nullptr, (EdWork::P*)dst);
+  }, out);
   bk.free_(dpt);
-  if (rc) {
-    if (comb) bk.free_(comb);
-    return rc;
-  }
-  out.comb = comb;
-  out.base = comb;
-  out.bits = EdWork::COMB_BITS;
-  out.bytes = bytes;
-  return E_OK;
+  return rc;
 }
+
 
 template <class BK>
 template <int U>
@@ -4249,61 +4212,30 @@ template <class BK>
 template <int U>
 int Engine<BK>::edc_base_table(const u8* xy, int window_bits, CombTable& out) {
   const int bits = window_bits ? window_bits : 8;
-  const size_t n = (size_t)(256 / bits) * (((size_t)1 << bits) - 1);
-  const size_t bytes = (n + 1) * sizeof(EdcWork::A);
-  const size_t slice = n < (size_t)ELL_COMB_SLICE ? n : (size_t)ELL_COMB_SLICE;
-  u8* dpt = (u8*)bk.alloc(64 + 1);
-  if (!dpt) return fail(E_NOMEM, "scratch allocation failed");
-  u8 flag = 1;
-  bk.h2d(dpt, xy, 64);
-  FnEdcBaseCheck chk{dpt, dpt + 64};
-  bk.launch(chk, 1);
-  bk.d2h(&flag, dpt + 64, 1);
-  int rc = bk.sync();
-  if (rc) rc = fail(rc, "testing the base failed on the device");
-  else if (flag) rc = fail(E_ARG, "the base is not a point of the curve (a coordinate >= p, or off the curve)");
-  if (rc) { bk.free_(dpt); return rc; }
-  EdcWork::A* base = (tune_.comb_max_bytes && bytes > tune_.comb_max_bytes) ? nullptr : (EdcWork::A*)bk.alloc(bytes);
-  u8* dk = base ? (u8*)bk.alloc(slice * 32) : nullptr;
-  u8* dp = dk ? (u8*)bk.alloc(slice * 64) : nullptr;
-  rc = dp ? E_OK : fail(E_NOMEM, "comb table allocation failed");
-  if (rc == E_OK) {
-    u32 hdr[sizeof(EdcWork::A) / 4] = {0};
-    hdr[0] = (u32)bits;
-    bk.h2d(base, hdr, sizeof hdr);
-  }
-  for (size_t first = 0; first < n && rc == E_OK; first += slice) {
-    const size_t m = n - first < slice ? n - first : slice;
+  int rc = E_OK;
+  u8* dpt = checked_base<FnEdcBaseCheck>(xy, 32, true, rc);
+  if (!dpt) return rc;
+  const TablePlan plan{(size_t)(256 / bits) * (((size_t)1 << bits) - 1), sizeof(EdcWork::A), 32, bits, true, true, false};
+  rc = build_table(plan, [&](size_t m, size_t first, u8* dk, u8* dp) {
+    FnEdBaseCombGen<true> g{m, first, dpt, dk, dp, bits};
+    bk.launch(g, m);
+  }, [&](size_t m, const u8* dk, const u8* dp, u8*, u8*, void* dst) {
     u32* proj = (u32*)scratch(S_JAC, m * 3 * 8 * 4);
     u32* pre = (u32*)scratch(S_PRE, m * 8 * 4);
     EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, m * 8 * sizeof(EdcWork::P));
-    if (!proj || !pre || !tbl) { rc = fail(E_NOMEM, "scratch allocation failed"); break; }
-    FnEdBaseCombGen<true> g{m, first, dpt, dk, dp, bits};
-    bk.launch(g, m);
+    if (!proj || !pre || !tbl) return fail(E_NOMEM, "scratch allocation failed");
     FnEdcMulVar f{m, dk, dp, tbl, proj};
     bk.launch(f, m);
     const int K = norm_batch_for(m);
     const size_t T = (m + K - 1) / K;
-    FnEdcBaseNormalize h{T, m, K, proj, pre, base + 1 + first};
+    FnEdcBaseNormalize h{T, m, K, proj, pre, (EdcWork::A*)dst};
     bk.launch(h, T);
-  }
-  if (dp) {
-    const int src = bk.sync();
-    if (rc == E_OK && src != E_OK) rc = fail(src, "building the fixed-base table failed on the device");
-  }
-  if (dp) bk.free_(dp);
-  if (dk) bk.free_(dk);
+    return (int)E_OK;
+  }, out);
   bk.free_(dpt);
-  if (rc) {
-    if (base) bk.free_(base);
-    return rc;
-  }
-  out.comb = base + 1;
-  out.base = base;
-  out.bits = bits;
-  out.bytes = bytes;
-  return E_OK;
+  return rc;
 }
+
 
 template <class BK>
 template <int U>

@@ -16,10 +16,9 @@ namespace ell {
                                                           Work<CV>::A*);                           \
   KW template int Engine<HipBackend>::ensure_comb<CV>();
 #define ELL_DECL_G1(KW, CV) \
-  KW template int Engine<HipBackend>::mul_fixed_chunk<CV>(size_t, const u8*, const Work<CV>::A*, u8*, u8*); \
-  KW template int Engine<HipBackend>::base_table<CV>(const u8*, int, Engine<HipBackend>::CombTable&);      \
-  KW template int Engine<HipBackend>::mul_base2_chunk<CV>(size_t, const u8*, const Work<CV>::A*,           \
-                                                          const u8*, const Work<CV>::A*, u8*, u8*);
+  KW template int Engine<HipBackend>::mul_fixed_chunk<CV>(size_t, const u8*, const Work<CV>::A*,           \
+                                                          const u8*, const Work<CV>::A*, u8*, u8*);        \
+  KW template int Engine<HipBackend>::base_table<CV>(const u8*, int, Engine<HipBackend>::CombTable&);
 #define ELL_DECL_G2(KW, CV)                                                                  \
   KW template int Engine<HipBackend>::mul_add2_chunk<CV>(size_t, const u8*, const u8*,       \
                                                          const u8*, const u8*, u8*, u8*);
@@ -110,12 +109,10 @@ namespace ell {
   KW template int Engine<HipBackend>::ensure_comb<CvCustomDomain>();                                 \
   KW template int Engine<HipBackend>::normalize_chunk<CvCustomDomain>(size_t, const u32*, u8*, u8*,  \
                                                                       Work<CvCustomDomain>::A*);     \
-  KW template int Engine<HipBackend>::mul_fixed_chunk<CvCustomDomain>(size_t, const u8*,             \
-                                                                      const Work<CvCustomDomain>::A*, u8*, u8*); \
+  KW template int Engine<HipBackend>::mul_fixed_chunk<CvCustomDomain>(                               \
+      size_t, const u8*, const Work<CvCustomDomain>::A*, const u8*, const Work<CvCustomDomain>::A*, u8*, u8*); \
   KW template int Engine<HipBackend>::base_table<CvCustomDomain>(const u8*, int,                     \
                                                                  Engine<HipBackend>::CombTable&);    \
-  KW template int Engine<HipBackend>::mul_base2_chunk<CvCustomDomain>(                               \
-      size_t, const u8*, const Work<CvCustomDomain>::A*, const u8*, const Work<CvCustomDomain>::A*, u8*, u8*); \
   KW template int Engine<HipBackend>::mul_add_g_chunk<CvCustomDomain>(size_t, const u8*, const u8*,  \
                                                                       const u8*, u8*, u8*);          \
   KW template int Engine<HipBackend>::ecdsa_chunk<CvCustomDomain>(size_t, const u8*, int, int,       \
@@ -154,14 +151,14 @@ namespace ell {
                                                           const u64*, size_t, u8*, u8*);
 
 #define ELL_DECL_ED0(KW)                                                                          \
-  KW template int Engine<HipBackend>::ensure_ed_comb<0>();                                        \
   KW template int Engine<HipBackend>::ed_normalize_chunk<0>(size_t, const u32*, u8*, u8*,         \
                                                             EdWork::P*);                          \
   KW template int Engine<HipBackend>::ed_mul_var_chunk<0>(size_t, const u8*, const u8*, u8*, u8*, \
                                                           EdWork::P*);
 #define ELL_DECL_ED1(KW)                                                                     \
   KW template int Engine<HipBackend>::ed_mul_fixed_chunk<0>(size_t, const u8*, u8*, u8*);    \
-  KW template int Engine<HipBackend>::ed_base_table<0>(const u8*, Engine<HipBackend>::CombTable&); \
+  KW template int Engine<HipBackend>::ensure_ed_comb<0>();                                   \
+  KW template int Engine<HipBackend>::ed_base_table<0>(const u8*, bool, Engine<HipBackend>::CombTable&); \
   KW template int Engine<HipBackend>::ed_base_mul_chunk<0>(size_t, const u8*, const EdWork::P*, \
                                                            const u8*, const EdWork::P*, u8*, u8*); \
   KW template int Engine<HipBackend>::ed_mul_add2_chunk<0>(size_t, const u8*, const u8*,     \

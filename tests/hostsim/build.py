@@ -33,7 +33,7 @@ def build(force=False, lazy_k256=False):
     if not force and os.path.exists(lib) and os.path.exists(stamp) and open(stamp).read() == dig:
         return lib
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fno-strict-aliasing", "-pthread", "-DELL_COMB_BITS_256=8", "-DELL_BOUNDS_CHECK=1",
-           "-DELL_COMB_SLICE=1000"]          # narrow combs built in several slices (ensure_comb's `first` offsets)
+           "-DELL_COMB_SLICE=1000"]          # narrow combs built in several slices (build_table's `first` offsets)
     if lazy_k256:
         cmd.append("-DELL_K256_LAZY=1")
     cmd += ["-o", lib, os.path.join(HERE, "hostsim.cpp")]

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 #include <thread>
 #include <vector>
@@ -21,13 +22,23 @@ namespace ell {
 // launches per kernel name since the last hs_launches_reset (white-box probe: which form of an
 // operation a batch was routed to)
 void hs_note_launch(const char* name);
+// allocations of every LoopBackend that have not been freed (white-box probe: a refused or failed
+// call leaves none behind)
+static std::atomic<long> hs_live_allocs_{0};
 struct LoopBackend {
   void use_stream(void*) {}
   int use_stream_dev(void*) { return 0; }
-  void* alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }
+  void* alloc(size_t bytes) {
+    void* p = malloc(bytes ? bytes : 1);
+    if (p) hs_live_allocs_++;
+    return p;
+  }
   std::vector<unsigned char> pin_;
   void* pinned(size_t bytes) { if (pin_.size() < bytes) pin_.resize(bytes); return pin_.data(); }
-  void free_(void* p) { free(p); }
+  void free_(void* p) {
+    if (p) hs_live_allocs_--;
+    free(p);
+  }
   void h2d(void* d, const void* h, size_t bytes) { memcpy(d, h, bytes); }
   void d2h(void* h, const void* d, size_t bytes) { memcpy(h, d, bytes); }
   int sync() { return 0; }
@@ -235,6 +246,7 @@ int hs_launches(const char* name) {
   auto it = ell::hs_launch_map().find(name);
   return it == ell::hs_launch_map().end() ? 0 : it->second;
 }
+long hs_live_allocs() { return ell::hs_live_allocs_.load(); }
 // field: 0 k256, 1 25519, 2.. mont(curve p): 10+curve -> base field, 20+curve -> order field
 int hs_field_limbs(int field) {
   switch (field) {

@@ -187,7 +187,79 @@ def test_generator_alias_on_ed25519(ctx, tables):
     pa = FB.run_mul2(ctx, alias, g, k, k[::-1], 32)
     pb = FB.run_mul2(ctx, g, g, k, k[::-1], 32)
     assert (pa[0] == pb[0]).all() and (pa[1] == pb[1]).all()
+    # the curve's own table is a table of G by coordinates: the first and the last entry of every
+    # window, 0 and the all-ones scalar through the alias, the handle of G and mul_fixed
+    top = (1 << ED_BITS) - 1
+    ends = [d << (ED_BITS * w) for w in range(256 // ED_BITS) for d in (1, top)] + [0, (1 << 256) - 1]
+    ke = FB.rows(ends, 32)
+    fixed = ctx.mul_fixed("ed25519", ke)
+    for h in (alias, g):
+        xy, inf = FB.run_mul(ctx, h, ke, 32)
+        assert (xy == fixed[0]).all() and (inf == fixed[1]).all()
+    m, G = FE.model_of(spec), FE.bases_of(spec)[0]
+    for i in (0, 1, len(ends) - 4, len(ends) - 3, len(ends) - 1):
+        assert (fixed[0][i] == FE.answer(spec, m.mul(ends[i], G))[0]).all()
     ctx.release_base(alias)
+
+
+def test_last_entry_of_a_sliced_build(ctx, tables):
+    """Curve1174 at 8 bits: 32 x 255 = 8160 entries, built in slices of 1000 with a remainder of
+    160 -- the scalar whose only digit is the last entry of the last window, against the model"""
+    spec = FE.spec_of("curve1174")
+    _, hs_ = tables("curve1174")
+    m, P = FE.model_of(spec), FE.bases_of(spec)[3]
+    k = [255 << 248, 255 << 240, 1 << 248, 254 << 248]
+    xy, inf = FB.run_mul(ctx, hs_[3], FB.rows(k, 32), 32)
+    for i, v in enumerate(k):
+        assert inf[i] == 0 and (xy[i] == FE.answer(spec, m.mul(v, P))[0]).all()
+
+
+def _live(hs):
+    hs.hs_live_allocs.restype = ctypes.c_long
+    return hs.hs_live_allocs()
+
+
+def test_live_allocations_return_to_their_level(hs, monkeypatch):
+    """the CPU backend's count of live allocations after every refused define and after define and
+    release, on ed25519 and on a user-defined Edwards curve"""
+    e222, ed = FE.spec_of("e222"), FE.spec_of("ed25519")
+    xy = FB.xy_bytes(FE.bases_of(e222)[3], 32)
+    x, y = FE.bases_of(e222)[3]
+    exy = FB.xy_bytes(FE.bases_of(ed)[3], 32)
+    ex, ey = FE.bases_of(ed)[3]
+    one = np.ones((1, 32), np.uint8)
+    monkeypatch.setenv("ELLGPU_COMB_MAX_BYTES", "600000")          # 8 bits: 522 304 bytes; ed25519's: 1 044 480
+    c = elliptic_amd.Context(0, lib_path=hs)
+    try:
+        cid = FE.curve_id(c, e222)
+        c.release_base(c.define_ed_base(cid, xy))                   # (the scratch arena has its size from here on)
+        level = _live(hs)
+        assert _code(lambda: c.define_ed_base(cid, xy, 16)) == E_NOMEM and _live(hs) == level
+        assert _code(lambda: c.define_ed_base(cid, FB.xy_bytes((x, y ^ 1), 32))) == E_ARG and _live(hs) == level
+        assert _code(lambda: c.define_ed_base("ed25519", exy)) == E_NOMEM and _live(hs) == level
+        h = c.define_ed_base(cid, xy)
+        assert _live(hs) == level + 1 and c.define_ed_base(cid, xy, 8) == h and _live(hs) == level + 1
+        c.release_base(h)
+        assert _live(hs) == level
+        # the curve's own comb is not subject to the limit (it never was): one more allocation, the table
+        c.mul_fixed("ed25519", one)
+        grown = _live(hs)
+        c.mul_fixed("ed25519", one)
+        assert grown > level and _live(hs) == grown
+    finally:
+        c.close()
+    monkeypatch.delenv("ELLGPU_COMB_MAX_BYTES")
+    c = elliptic_amd.Context(0, lib_path=hs)
+    try:
+        c.release_base(c.define_ed_base("ed25519", exy))
+        level = _live(hs)
+        assert _code(lambda: c.define_ed_base("ed25519", FB.xy_bytes((ex, ey ^ 1), 32))) == E_ARG and _live(hs) == level
+        h = c.define_ed_base("ed25519", exy)
+        assert _live(hs) == level + 1
+        c.release_base(h)
+        assert _live(hs) == level
+    finally:
+        c.close()
 
 
 def test_generator_of_an_edwards_domain(ctx, tables):

@@ -333,6 +333,76 @@ def test_small_order_base_is_refused(hs):
         c.close()
 
 
+def _live(hs):
+    hs.hs_live_allocs.restype = ctypes.c_long
+    return hs.hs_live_allocs()
+
+
+def test_live_allocations_return_to_their_level(hs, monkeypatch):
+    """the CPU backend's count of live allocations after every refused define, after define and
+    release, and after a define that arrives at a live table: a preset and a user-defined domain"""
+    spec = FB.spec_of("secp256k1")
+    pts = [FB.xy_bytes(P, 32) for P in FB.bases_of(spec)]
+    x, y = FB.bases_of(spec)[3]
+    cof = FB.spec_of("cof_p10007")
+    T = FB.xy_bytes(tuple(FB.I(v) for v in cof["refused"][0]), 32)
+    cg = FB.xy_bytes(FB.bases_of(cof)[0], 32)
+    monkeypatch.setenv("ELLGPU_COMB_MAX_BYTES", "100000")          # 8 bits signed: 270 400 bytes, 4 bits: 33 344
+    c = elliptic_amd.Context(0, lib_path=hs)
+    try:
+        cid = FB.curve_id(c, cof)
+        c.release_base(c.define_base("secp256k1", pts[3]))          # (the scratch arena has its size from here on)
+        level = _live(hs)
+        assert _code(lambda: c.define_base("secp256k1", pts[3], 8)) == E_NOMEM and _live(hs) == level
+        assert _code(lambda: c.define_base("secp256k1", FB.xy_bytes((x, y ^ 1), 32))) == E_ARG and _live(hs) == level
+        h = c.define_base("secp256k1", pts[3], 4)
+        assert _live(hs) == level + 1
+        assert c.define_base("secp256k1", pts[3]) == h and _live(hs) == level + 1     # narrowed 16 -> 4: the live table
+        h2 = c.define_base("secp256k1", pts[1])                     # a default width that narrows, then succeeds
+        assert c.base_info(h2)[1] == 4 and _live(hs) == level + 2
+        c.release_base(h)
+        c.release_base(h2)
+        assert _live(hs) == level
+        # the unsigned comb of a user-defined id has one width: refused, explicit or default
+        assert _code(lambda: c.define_base(cid, cg)) == E_NOMEM and _code(lambda: c.define_base(cid, cg, 8)) == E_NOMEM
+        assert _live(hs) == level
+    finally:
+        c.close()
+    monkeypatch.delenv("ELLGPU_COMB_MAX_BYTES")
+    c = elliptic_amd.Context(0, lib_path=hs)
+    try:
+        cid = FB.curve_id(c, cof)
+        c.release_base(c.define_base(cid, cg))
+        level = _live(hs)
+        assert _code(lambda: c.define_base(cid, T)) == E_ARG        # small order: refused after the whole build
+        assert _live(hs) == level
+        gx, gy = FB.bases_of(cof)[0]
+        assert _code(lambda: c.define_base(cid, FB.xy_bytes((gx, gy ^ 1), 32))) == E_ARG and _live(hs) == level
+        h = c.define_base(cid, cg)
+        assert _live(hs) == level + 1
+        c.release_base(h)
+        assert _live(hs) == level
+    finally:
+        c.close()
+
+
+def test_last_entry_of_a_sliced_build(ctx):
+    """p256 at 8 bits: 32 x 255 = 8160 entries, built in slices of 1000 with a remainder of 160 --
+    the scalar whose only digit is the last entry of the last window, against the model"""
+    spec = FB.spec_of("p256")
+    P = FB.bases_of(spec)[3]
+    h = ctx.define_base("p256", FB.xy_bytes(P, 32), 8)
+    try:
+        k = [255 << (8 * 31), 255 << (8 * 30), 1 << (8 * 31), 254 << (8 * 31)]
+        xy, inf = FB.run_mul(ctx, h, FB.rows(k, 32), 32)
+        m = FB.model_of(spec)
+        for i, v in enumerate(k):
+            want = FB.answer(m.mul(v, P), 32)
+            assert inf[i] == want[1] == 0 and (xy[i] == want[0]).all()
+    finally:
+        ctx.release_base(h)
+
+
 def test_group_gives_a_single_contexts_bytes(hs, ctx, batches):
     g = elliptic_amd.Context(lib_path=hs, devices=[0, 0])
     try:
