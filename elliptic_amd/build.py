@@ -55,6 +55,7 @@ def source_files():
                    if f.endswith((".h", ".hip")) and os.path.isfile(os.path.join(CSRC, f)))
     files.append(os.path.join("include", "ellgpu.h"))
     files.append(os.path.join("include", "ellgpu_ext.h"))
+    files.append(os.path.join("include", "ellgpu_ext2.h"))
     return root, files
 
 

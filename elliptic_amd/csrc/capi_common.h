@@ -9,7 +9,7 @@
 // before including this header.
 #pragma once
 
-#include "../../include/ellgpu_ext.h"
+#include "../../include/ellgpu_ext2.h"
 #include "engine.h"
 
 #include <mutex>
@@ -500,6 +500,29 @@ int ellgpu_ecdsa_verify_dev(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t*
                             const uint8_t* pub_xy, uint8_t* out_ok, uint8_t* out_status,
                             void* stream) {
   return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.ecdsa_verify(w, curve, n, hash, hash_len, msg_bits, r, s, pub_xy, out_ok, out_status); });
+}
+// EC#verify against the table of the signer's key (include/ellgpu_ext2.h): one form, `mem` says
+// where the operands live; a group shards a host batch as ellgpu_mul_base2's
+int ellgpu_ecdsa_verify_base(ellgpu_ctx* ctx, int base, size_t n, const uint8_t* hash, int hash_len, int msg_bits,
+                             const uint8_t* r, const uint8_t* s, uint8_t* out_ok, int mem, void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (!ctx->members.empty() && where == Mem::host) {
+    ELL_LOCK(ctx);
+    int curve = -1;
+    if (int rc = ellgpu_base_info(ctx, base, &curve, nullptr, nullptr)) return rc;
+    size_t B, NB;
+    if (curve_widths(curve, B, NB)) return ELLGPU_E_ARG;
+    if (n && (!hash || !r || !s || !out_ok)) return set_err(ELLGPU_E_ARG, "null pointer");
+    if (n && hash_len <= 0) return set_err(ELLGPU_E_ARG, "bad hash_len");
+    if (!n) return ellgpu_ecdsa_verify_base(ctx->members[0], base, 0, hash, hash_len, msg_bits, r, s, out_ok, mem, nullptr);
+    return group_shard(ctx, n, [=](ellgpu_ctx* m, size_t lo, size_t hi) {
+      return ellgpu_ecdsa_verify_base(m, base, hi - lo, hash + lo * (size_t)hash_len, hash_len, msg_bits, r + lo * NB,
+                                      s + lo * NB, out_ok + lo, mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) { return e.ecdsa_verify_base(w, base, n, hash, hash_len, msg_bits, r, s, out_ok); });
 }
 int ellgpu_x25519_ladder(ellgpu_ctx* ctx, size_t n, const uint8_t* k, const uint8_t* in_x,
                          uint8_t* out_x, uint8_t* out_inf) {

@@ -312,6 +312,26 @@ struct FnEcdsaMain {
     if (i < n) W::template ecdsa_main<WIDE>(i, n, u12, valid, r, pub, comb, tbl, ds, ok, st);
   }
 };
+// pass 2 of a verify against a fixed-base table of the signer's key: two comb walks, one item per
+// lane (Work::ecdsa_base_main).  FnMulBase2's register budget where the kernel fits it without
+// scratch (p192, p224, p256: 90 / 102 / 122 VGPRs); secp256k1 and the run-time field do not (the x
+// test with its second candidate behind the two walks: 84 and 112 bytes of scratch per lane at
+// 128 registers) and get ELL_ECDSA_BASE_MIN_WAVES = 3 waves' worth, 168 registers.
+#ifndef ELL_ECDSA_BASE_MIN_WAVES
+#define ELL_ECDSA_BASE_MIN_WAVES 3
+#endif
+template <class CV, int MW = 0>
+struct FnEcdsaBase {
+  static constexpr const char* NAME = "ecdsa_base";
+  typedef Work<CV> W;
+  static constexpr int MIN_WAVES = MW ? MW : (W::L <= 8 ? ((CV::ENDO || CV::RT_ORDER) ? ELL_ECDSA_BASE_MIN_WAVES : ELL_FIXED_MIN_WAVES) : 1);
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u32* u12; const u8* valid; const u8* r;
+  const typename W::A* tg; const typename W::A* tq; u8* ok;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::ecdsa_base_main(i, n, u12, valid, r, tg, tq, ok);
+  }
+};
 // the small-grid verify in two kernels (Work::ecdsa_table / ecdsa_ladder): the tables are built
 // beside ecdsa_prep (FnEcdsaPrepTable), the ladder after both
 template <class CV, bool WIDE = true>
@@ -1738,6 +1758,11 @@ class Engine {
   template <class CV>
   int ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
                   const u8* pub, u8* ok, u8* st);
+  // a verify chunk against the table tq of the signer's key and G's table tg: the scalar-field prep
+  // as ecdsa_chunk's, then the two comb walks, one item per lane at every n
+  template <class CV>
+  int ecdsa_base_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
+                       const typename Work<CV>::A* tg, const typename Work<CV>::A* tq, u8* ok);
   // launch of a scalar-field kernel (ecdsa_prep, sign_finish, recover_prep: batched inversion
   // and Montgomery arithmetic mod n, long dependent chains).  A member of its own so that these
   // kernels are instantiated in their own translation units (inst.hip group 6), which are
@@ -2715,6 +2740,53 @@ class Engine {
       if (rc) return rc;
       if (dom) rc = ecdsa_chunk<CvCustomDomain>(m, d[0], hash_len, shift, d[1], d[2], d[3], o[0], o[1]);
       else ELL_SHORT_DISPATCH(curve, rc = ecdsa_chunk<CV>(m, d[0], hash_len, shift, d[1], d[2], d[3], o[0], o[1]));
+      return rc;
+    });
+  }
+
+  // EC#verify against the fixed-base table of the signer's key: ok[i] is what ecdsa_verify writes
+  // for the same item with the point of `base` as its key, strictly 0 / 1.  Both scalar
+  // multiplications are comb walks (u1 over G's table -- the curve's own, at the width it has --
+  // and u2 over the key's, at the width it was defined with).  No status: the key was tested
+  // against the curve when the handle was defined.  Handles of define_base on the six presets and
+  // on user-defined short DOMAIN ids, the generator alias included (the key with d = 1).
+  int ecdsa_verify_base(Mem where, int base, size_t n, const u8* hash, int hash_len, int msg_bits,
+                        const u8* r, const u8* s, u8* ok) {
+    const BaseRec* rec = base_rec(base);
+    if (!rec) return E_ARG;
+    if (rec->ed)
+      return fail(E_UNSUPPORTED, "ECDSA verify against a key handle is implemented for short Weierstrass curves (an Edwards handle: ellgpu_custom_ed_verify takes the key per item)");
+    const int curve = rec->curve;
+    const bool dom = custom_is_domain(curve);
+    if (is_custom(curve) && !dom)
+      return fail(E_UNSUPPORTED, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (!n) return E_OK;
+    const bool nul = !hash || !r || !s || !ok;
+    if (int rc = host_first(where, nul, hash_len)) return rc;
+    if (nul) return fail(E_ARG, "null pointer");
+    const CurveInfo* ci = curve_info(curve);
+    const size_t NB = ci->order_bytes;
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    int shift = 0;
+    if (int rc = dom ? truncate_shift(hash_len, msg_bits, (int)custom_[(size_t)(curve - CURVE_CUSTOM0)].nbits, 8, shift)
+                     : truncate_shift(hash_len, msg_bits, ci->order_bits, (ci->order_bits + 31) / 32, shift))
+      return rc;
+    if (where == Mem::device)
+      if (overlap2(hash, n * (size_t)hash_len, ok, n) || overlap2(r, n * NB, ok, n) || overlap2(s, n * NB, ok, n))
+        return fail(E_ARG, "hash / r / s and the verdicts must not overlap");
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}}, {Out{ok, 1}}, [&](size_t m, auto d, auto o) {
+      int rc = dom ? ensure_comb<CvCustomDomain>() : prepare_curve(curve);
+      const void* tq = nullptr;
+      if (rc == E_OK) rc = base_table_ptr(*rec, tq);
+      if (rc) return rc;
+      const void* tg = comb_[curve];
+      if (dom) {
+        typedef const Work<CvCustomDomain>::A* T;
+        return ecdsa_base_chunk<CvCustomDomain>(m, d[0], hash_len, shift, d[1], d[2], (T)tg, (T)tq, o[0]);
+      }
+      ELL_SHORT_DISPATCH(curve, rc = ecdsa_base_chunk<CV>(m, d[0], hash_len, shift, d[1], d[2], (const typename Work<CV>::A*)tg,
+                                                           (const typename Work<CV>::A*)tq, o[0]));
       return rc;
     });
   }
@@ -4074,6 +4146,23 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
     }
   }
   launch_paired<FnEcdsaMain, CV>(n, u12, valid, r, pub, comb_of<CV>(), tbl, ok, st);
+  return E_OK;
+}
+
+template <class BK>
+template <class CV>
+int Engine<BK>::ecdsa_base_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
+                                 const typename Work<CV>::A* tg, const typename Work<CV>::A* tq, u8* ok) {
+  typedef Work<CV> W;
+  u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
+  u32* u12 = (u32*)scratch(S_U12, n * 2 * W::LN * 4);
+  u8* valid = (u8*)scratch(S_VALID, n);
+  if (!pre || !u12 || !valid) return fail(E_NOMEM, "scratch allocation failed");
+  const int K = inv_batch_for(n, INV_BATCH_N);
+  const size_t T = (n + K - 1) / K;
+  FnEcdsaPrep<CV> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};
+  launch_fn(f1, T);
+  launch_paired<FnEcdsaBase, CV>(n, u12, valid, r, tg, tq, ok);
   return E_OK;
 }
 

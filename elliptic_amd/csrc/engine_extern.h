@@ -18,7 +18,9 @@ namespace ell {
 #define ELL_DECL_G1(KW, CV) \
   KW template int Engine<HipBackend>::mul_fixed_chunk<CV>(size_t, const u8*, const Work<CV>::A*,           \
                                                           const u8*, const Work<CV>::A*, u8*, u8*);        \
-  KW template int Engine<HipBackend>::base_table<CV>(const u8*, int, Engine<HipBackend>::CombTable&);
+  KW template int Engine<HipBackend>::base_table<CV>(const u8*, int, Engine<HipBackend>::CombTable&); \
+  KW template int Engine<HipBackend>::ecdsa_base_chunk<CV>(size_t, const u8*, int, int, const u8*, const u8*, \
+                                                           const Work<CV>::A*, const Work<CV>::A*, u8*);
 #define ELL_DECL_G2(KW, CV)                                                                  \
   KW template int Engine<HipBackend>::mul_add2_chunk<CV>(size_t, const u8*, const u8*,       \
                                                          const u8*, const u8*, u8*, u8*);
@@ -102,7 +104,8 @@ namespace ell {
                                                          u8*, u8*);                                  \
   KW template int Engine<HipBackend>::rt_validate_chunk<0>(size_t, const u8*, const u8*, bool, u8*); \
   KW template int Engine<HipBackend>::rt_encode_chunk<0>(size_t, const u8*, int, u8*);
-// user-defined ECDSA domains (CvCustomDomain): verify, recovery, sign, k*G, k1*G + k2*Q and the tables of
+// user-defined ECDSA domains (CvCustomDomain): verify (per-item keys, and against a key's table),
+// recovery, sign, k*G, k1*G + k2*Q and the tables of
 // caller-chosen bases (on plain ids too: Engine::base_upload) -- their own translation
 // unit (group 17, with its own parameter block); the window ladder of the comb build is CvCustom's
 #define ELL_DECL_DOMAIN(KW)                                                                          \
@@ -118,6 +121,9 @@ namespace ell {
   KW template int Engine<HipBackend>::ecdsa_chunk<CvCustomDomain>(size_t, const u8*, int, int,       \
                                                                   const u8*, const u8*, const u8*,   \
                                                                   u8*, u8*);                         \
+  KW template int Engine<HipBackend>::ecdsa_base_chunk<CvCustomDomain>(                              \
+      size_t, const u8*, int, int, const u8*, const u8*, const Work<CvCustomDomain>::A*,             \
+      const Work<CvCustomDomain>::A*, u8*);                                                          \
   KW template int Engine<HipBackend>::rt_recover_chunk<0>(size_t, const u8*, int, const u8*,         \
                                                           const u8*, const u8*, u8*, u8*);           \
   KW template int Engine<HipBackend>::rt_sign_chunk<0>(size_t, const u8*, int, int, const u8*,       \

@@ -205,8 +205,10 @@ struct FpMontRTm {
     bn_copy<8>(r, x.v);
   }
   ELL_HD static bool is_odd(const El& a) { u32 r[8]; to_plain(r, a); return r[0] & 1; }
-  // a^(p-2): a^-1, 0 for 0 (the exponent is wave-uniform: a scalar branch per bit)
-  static ELL_HD_NOINLINE El inv(const El& a) {
+  // a^(p-2): a^-1, 0 for 0 (the exponent is wave-uniform: a scalar branch per bit).  inv_inl is
+  // the loop itself, inlined into its caller: a kernel that calls inv pays a call frame in scratch
+  // memory for the two elements passed by reference, one that is to run without scratch takes inv_inl.
+  ELL_HD static El inv_inl(const El& a) {
     El r = one();
     ELL_NOUNROLL
     for (int i = 255; i >= 0; i--) {
@@ -215,6 +217,7 @@ struct FpMontRTm {
     }
     return r;
   }
+  static ELL_HD_NOINLINE El inv(const El& a) { return inv_inl(a); }
   // a^e for the block's square-root exponent (wave-uniform: a scalar branch per bit)
   ELL_HD static El pow_sqrt_e(const El& a) {
     El r = one();

@@ -1576,9 +1576,11 @@ struct Work {
 
   // JPoint#eqXToP (short.js:908-925): X == r*Z^2, retry with r+n while < p.
   // (for every preset p < 2n, so one retry at most)
+  // (INL: on a user-defined domain the one inversion of the rule's rare path is inlined, fp_rt.h inv_inl)
+  template <bool INL = false>
   ELL_HD static bool eq_x_to_p(const J& p, const u32 (&r)[LN]) {
     static_assert(LN <= L, "order wider than field");
-    if constexpr (CV::RT_ORDER) return eq_x_rt(p, r);
+    if constexpr (CV::RT_ORDER) return eq_x_rt<INL>(p, r);
     u32 rx[L], pp[L];
     ELL_UNROLL
     for (int i = 0; i < L; i++) { rx[i] = i < LN ? r[i] : 0u; pp[i] = C::p[i]; }
@@ -1598,11 +1600,14 @@ struct Work {
   // [p, n) matches x = r - p -- then X == (r + k n) Z^2 for k = 1, 2, ... while r + k n < p, i.e.
   // at most floor(p/n) more candidates (eight on a cofactor-8 curve).  Without it (n < p / 100):
   // getX().umod(n) == r, on the affine x (one inversion per item on that rare path).
+  template <bool INL = false>
   ELL_HD static bool eq_x_rt(const J& p, const u32 (&r)[LN]) {
     static_assert(L == 8 && LN == 8, "user-defined domains are 32-byte wide");
     const u32 ncand = ELL_RT.ncand;                        // wave-uniform
     if (ncand == RT_NO_MAXWELL) {
-      El zi = F::inv(p.Z);
+      El zi;
+      if constexpr (INL) zi = F::inv_inl(p.Z);
+      else zi = F::inv(p.Z);
       u32 x[L], xn[LN];
       F::to_plain(x, F::mul(p.X, F::sqr(zi)));
       Fn::to_plain(xn, Fn::from_plain(x));                // x mod n: x R mod n, then out of Montgomery form
@@ -1842,6 +1847,33 @@ struct Work {
 #endif
     const bool on = on_curve(load_affine(pub_xy, i));
     store_verdict(i, valid[i], on, ok, out_ok, out_st);
+  }
+
+  // Pass 2 against a fixed-base table of the signer's key (Engine::ecdsa_verify_base): R = u1*G +
+  // u2*Q as two comb walks into one accumulator, u1 over G's table tG, u2 over the key's table tQ
+  // -- no ladder, no per-item window table, no digit store.  The tables may have different widths
+  // (each walk reads its own table's header).  Q may be +-G: the accumulator meeting +- an entry,
+  // passing through O in the middle of the second walk and ending on O are ordinary paths
+  // (add_mixed_lean's rare branch), as in mul_base2.  u2 and r are loaded where they are used.
+  // The key was tested against the curve when its handle was defined: no status.
+  ELL_HD static void ecdsa_base_main(size_t i, size_t n, const u32* u12, const u8* valid, const u8* rs,
+                                     const A* tG, const A* tQ, u8* out_ok) {
+    u32 u[L], r[LN];
+    ELL_UNROLL
+    for (int l = 0; l < L; l++) u[l] = l < LN ? u12[(size_t)(0 * LN + l) * n + i] : 0u;
+    bool inf = true;
+    J p = LD::template comb_add<L, COMB_W, COMB_BITS, false, COMB_SIGNED>(G::infinity(), inf, u, tG);
+    ELL_UNROLL
+    for (int l = 0; l < L; l++) u[l] = l < LN ? u12[(size_t)(1 * LN + l) * n + i] : 0u;
+    p = LD::template comb_add<L, COMB_W, COMB_BITS, false, COMB_SIGNED>(p, inf, u, tQ);
+#if ELL_LATE_LOADS && defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" ::: "memory");
+#endif
+    load_be<LN>(r, rs + i * NBYTES, NBYTES);
+    // (an accumulator that ended on O may hold any X, Y beside Z = 0: is_inf reads Z alone)
+    bool ok = !G::is_inf(p);
+    ok = ok && eq_x_to_p<true>(p, r);               // (no call in this kernel: it runs without scratch memory)
+    store_verdict(i, valid[i], true, ok, out_ok, nullptr);
   }
 };
 

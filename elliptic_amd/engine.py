@@ -342,36 +342,52 @@ class Context:
     def _is_tensor(a):
         return hasattr(a, "data_ptr")
 
-    def _dev_operands(self, base, ks, out):
-        """checks the device tensors of mul_base / mul_base2 before their addresses go to the library"""
-        if out is None or len(out) != 2:
-            raise ValueError("device tensors need out=(xy, inf): uint8 tensors (n, 2 * field_bytes) and (n,)")
-        B = self._base_width(base)
-        n = ks[0].shape[0]
+    def _dev_operands(self, ins, in_names, out, out_names, shapes):
+        """checks the device tensors of a call on a base handle before their addresses go to the
+        library; shapes: of the inputs, then of the results"""
+        if out is None or len(out) != len(out_names):
+            raise ValueError("device tensors need out=(%s): uint8 tensors of shapes %s"
+                             % (", ".join(out_names), ", ".join(str(sh) for sh in shapes[len(ins):])))
         import torch
-        for t, shape, name in [(k, (n, B), "k") for k in ks] + [(out[0], (n, 2 * B), "out xy"), (out[1], (n,), "out inf")]:
+        for t, shape, name in zip(list(ins) + list(out), shapes, list(in_names) + ["out " + o for o in out_names]):
             if not self._is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError("%s: a contiguous uint8 tensor of shape %s is needed" % (name, shape))
             if t.device != torch.device(self.device):
                 raise ValueError("%s is on %s, the context on %s" % (name, t.device, torch.device(self.device)))
-        return n
+
+    def _base_call(self, name, bases, ins, in_names, widths, ints, out, out_names, out_widths):
+        """ellgpu_mul_base / _base2 / ecdsa_verify_base: one symbol for both kinds of memory, told
+        apart by a flag before the stream -- so the call is made here, beside _call.  The C argument
+        list is (ctx, bases..., n, ins[0], ints..., ins[1:]..., results..., mem, stream).  widths /
+        out_widths: bytes per row of every input / result (None: the first input's own second
+        dimension; 0: a vector of n bytes); a None among ints stands for that dimension too."""
+        dev = self._is_tensor(ins[0])
+        if dev:
+            if ins[0].dim() != 2:
+                raise ValueError("%s: a contiguous uint8 tensor of shape (n, width) is needed" % in_names[0])
+            n, w0 = int(ins[0].shape[0]), int(ins[0].shape[1])
+        else:
+            first = _u8(ins[0]) if widths[0] is None else _u8(ins[0], (-1, widths[0]))
+            if first.ndim != 2:
+                raise ValueError("%s must be (n, width)" % in_names[0])
+            n, w0 = first.shape
+        shapes = [(n, w0 if w is None else w) if w != 0 else (n,) for w in list(widths) + list(out_widths)]
+        if dev:
+            self._dev_operands(ins, in_names, out, out_names, shapes)
+            res = list(out)
+        else:
+            ins = [first] + [_u8(a, sh) for a, sh in zip(ins[1:], shapes[1:])]
+            res = self._outs(out, shapes[len(ins):])
+        addr = [a.data_ptr() if dev else a.ctypes.data for a in list(ins) + res]
+        fn = getattr(self._lib, "ellgpu_" + name)
+        ints = [int(w0) if v is None else v for v in ints]
+        self._check(fn(self._ctx, *[int(b) for b in bases], n, addr[0], *ints, *addr[1:], 1 if dev else 0,
+                       self._stream() if dev else None))
+        return res
 
     def _mul_bases(self, name, bases, ks, out):
-        """ellgpu_mul_base / _base2: one symbol for both kinds of memory, told apart by a flag before
-        the stream -- so the call is made here, beside _call"""
-        dev = self._is_tensor(ks[0])
-        if dev:
-            n = self._dev_operands(bases[0], ks, out)
-            xy, inf = out
-        else:
-            B = self._base_width(bases[0])
-            k0 = _u8(ks[0], (-1, B))
-            n = k0.shape[0]
-            ks = [k0] + [_u8(k, (n, B)) for k in ks[1:]]
-            xy, inf = self._outs(out, [(n, 2 * B), (n,)])
-        ptrs = [a.data_ptr() if dev else a.ctypes.data for a in ks + [xy, inf]]
-        fn = getattr(self._lib, "ellgpu_" + name)
-        self._check(fn(self._ctx, *[int(b) for b in bases], n, *ptrs, 1 if dev else 0, self._stream() if dev else None))
+        B = self._base_width(bases[0])
+        xy, inf = self._base_call(name, bases, ks, ["k"] * len(ks), [B] * len(ks), (), out, ("xy", "inf"), (2 * B, 0))
         return xy, inf
 
     def mul_base(self, base, k, out=None):
@@ -383,6 +399,17 @@ class Context:
     def mul_base2(self, base1, base2, k1, k2, out=None):
         """k1 * B1 + k2 * B2 over the tables of two bases of one curve -> (xy, inf); operands as in mul_base"""
         return self._mul_bases("mul_base2", [base1, base2], [k1, k2], out)
+
+    def ecdsa_verify_base(self, base, hashes, r, s, msg_bits=0, out=None):
+        """EC#verify of n signatures against the key of a define_base handle (ellgpu_ecdsa_verify_base:
+        both scalar multiplications walk fixed-base tables) -> ok, (n,) strictly 0 / 1: what
+        ecdsa_verify gives with the handle's point repeated as the key.  hashes: (n, hash_len); r, s:
+        (n, order_bytes).  The handle: define_base on a preset or on a define_short_domain id, the
+        generator alias included.  numpy arrays go through host memory; torch device tensors
+        (hashes, r, s and out=(ok,), required then) run on the current stream and return at once."""
+        NB = self._base_width(base)               # (order_bytes == field_bytes on every short curve)
+        return self._base_call("ecdsa_verify_base", [base], [hashes, r, s], ["hashes", "r", "s"], [None, NB, NB],
+                               (None, int(msg_bits)), out, ("ok",), (0,))[0]
 
     # ---- point arithmetic: presets, and user-defined ids where the definition allows ---------------
 

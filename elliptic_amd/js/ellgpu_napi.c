@@ -54,6 +54,8 @@
  *           defineBase(ctx, curve, xy|null, windowBits) -> handle, releaseBase(ctx, base), baseInfo(ctx, base) ->
  *             {curve, windowBits, tableBytes}, mulBase(ctx, base, k) -> {xy, inf}, mulBase2(ctx, base1, base2, k1, k2)
  *             -> {xy, inf}: fixed-base tables of caller-chosen points (ellgpu_base_*)
+ *           ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s) -> {ok}: EC#verify against the table of the
+ *             key a defineBase handle stands for (ellgpu_ecdsa_verify_base, include/ellgpu_ext2.h)
  *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
  *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
  *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
@@ -80,6 +82,7 @@
  *             (ellgpu_custom_ed_verify / _sign / _sign_det: ECDSA on a user-defined Edwards domain,
  *             defineEdwardsDomain(ctx, p, a, d, n, gx, gy); sync forms customEdVerify, customEdSign, customEdSignDet);
  *             29 mulBase(k; curve = the base's curve, i0 = base)  30 mulBase2(k1, k2; i0, i1 = the bases) -> {xy, inf};
+ *             31 ecdsaVerifyBase(hashes, r, s; curve = the base's curve, i0 = base) -> {ok};
  *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
@@ -136,6 +139,7 @@ static struct {
   int (*base_info)(ellgpu_ctx*, int, int*, int*, uint64_t*);
   int (*mul_base)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*, int, void*);
   int (*mul_base2)(ellgpu_ctx*, int, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, int, void*);
+  int (*ecdsa_verify_base)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*, uint8_t*, int, void*);
   int (*mul_var)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
   int (*mul_add2)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, const uint8_t*,
                   const uint8_t*, uint8_t*, uint8_t*);
@@ -231,6 +235,7 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(ed_base_define, "ellgpu_ed_base_define");
   SYM(base_define, "ellgpu_base_define"); SYM(base_release, "ellgpu_base_release"); SYM(base_info, "ellgpu_base_info");
   SYM(mul_base, "ellgpu_mul_base"); SYM(mul_base2, "ellgpu_mul_base2");
+  SYM(ecdsa_verify_base, "ellgpu_ecdsa_verify_base");
   SYM(custom_mont_ladder, "ellgpu_custom_mont_ladder");
   SYM(custom_mont_validate, "ellgpu_custom_mont_validate");
   SYM(custom_mont_derive, "ellgpu_custom_mont_derive");
@@ -618,6 +623,33 @@ static napi_value mul_base_with(napi_env env, napi_callback_info info, int two) 
 }
 static napi_value fn_mul_base(napi_env e, napi_callback_info i) { return mul_base_with(e, i, 0); }
 static napi_value fn_mul_base2(napi_env e, napi_callback_info i) { return mul_base_with(e, i, 1); }
+/* ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s) -> {ok}: EC#verify against the table of
+ * the key a handle stands for (ellgpu_ecdsa_verify_base); r and s rows in the width of the base's curve */
+static napi_value fn_verify_base(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 7; napi_value argv[7];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) THROW(env, "ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  int32_t base, hl, mb;
+  if (napi_get_value_int32(env, argv[1], &base) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
+      napi_get_value_int32(env, argv[4], &mb) != napi_ok)
+    THROW(env, "ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s)");
+  int curve = -1;
+  if (L.base_info(c, base, &curve, NULL, NULL) != 0) return lib_error(env);
+  int NB = L.order_bytes(curve); if (NB <= 0) THROW(env, "unknown curve id");
+  const uint8_t *h, *r, *s; size_t lh, lr, ls;
+  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &r, &lr, 0) || !get_buf(env, argv[6], &s, &ls, 0)) return NULL;
+  if (hl <= 0 || lh % (size_t)hl) THROW(env, "buffer length mismatch");
+  size_t n = lh / (size_t)hl;
+  if (lr != n * (size_t)NB || ls != lr) THROW(env, "buffer length mismatch");
+  napi_value bok, o; void* dok;
+  CHECK(env, result_buffer(env, n, &dok, &bok));
+  if (L.ecdsa_verify_base(c, base, n, h, hl, mb, r, s, (uint8_t*)dok, 0, NULL) != 0) return lib_error(env);
+  CHECK(env, napi_create_object(env, &o));
+  CHECK(env, napi_set_named_property(env, o, "ok", bok));
+  return o;
+}
 
 /* mulFixed / mulVar / mulAdd2 share the output shape */
 static napi_value mul_common(napi_env env, napi_callback_info info, int kind) {
@@ -1112,7 +1144,8 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
 #define ED_OP_SIGN_DET 28
 #define OP_MUL_BASE 29           /* mulBase(k; curve = the base's curve, i0 = base)  mulBase2(k1, k2; i0, i1 = the bases) */
 #define OP_MUL_BASE2 30
-#define OP_LAST 30
+#define OP_VERIFY_BASE 31        /* ecdsaVerifyBase(hashes, r, s; curve = the base's curve, i0 = base) -> {ok} */
+#define OP_LAST 31
 #define ECDH_ENC_OP(op) ((op) == 16 || (op) == 25)
 static const char* const ECDH_NAMES[13][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
                                               {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0},
@@ -1235,6 +1268,8 @@ static void job_execute(napi_env env, void* data) {
     case 4: j->rc = L.x25519(j->ctx, j->n, j->in[0], j->in[1], j->out0, j->out1); break;
     case OP_MUL_BASE: j->rc = L.mul_base(j->ctx, j->i0, j->n, j->in[0], j->out0, j->out1, 0, NULL); break;
     case OP_MUL_BASE2: j->rc = L.mul_base2(j->ctx, j->i0, j->i1, j->n, j->in[0], j->in[1], j->out0, j->out1, 0, NULL); break;
+    case OP_VERIFY_BASE: j->rc = L.ecdsa_verify_base(j->ctx, j->i0, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2],
+                                                     j->out0, 0, NULL); break;
     case 5: j->rc = L.ecdsa_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i0,
                                      j->out0, j->out1, j->out2, j->out3); break;
     case 6: j->rc = L.ecdsa_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
@@ -1283,7 +1318,7 @@ static void job_complete(napi_env env, napi_status status, void* data) {
       {"xy", "status", 0, 0}, {"xy", "status", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
       {"x", "status", "err", 0}, {"enc", 0, 0, 0},
       {"ok", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
-      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}};
+      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", 0, 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1355,6 +1390,10 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
             ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB && len[2] == j->n * NB && len[3] == j->n * 2 * B; break;
+    case OP_VERIFY_BASE:
+            ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && !j->in[3] && len[0] % (size_t)hl == 0;
+            j->n = ok ? len[0] / (size_t)hl : 0;
+            ok = ok && len[1] == j->n * NB && len[2] == j->n * NB; break;
     case 4: j->n = len[0] / 32; ok = j->in[0] && j->in[1] && len[0] % 32 == 0 && len[1] == len[0]; break;
     case 5: ok = hl > 0 && j->in[0] && j->in[1] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
@@ -1388,6 +1427,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   j->out3_len = op == 5 || op >= 11 ? j->n : 0;
   if (op == OP_MUL_BASE || op == OP_MUL_BASE2) { j->out0_len = j->n * 2 * B; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
   if (op == ED_OP_VERIFY) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
+  if (op == OP_VERIFY_BASE) { j->out0_len = j->n; j->out1_len = 0; j->out2_len = 0; j->out3_len = 0; }
   if (op >= 13 && op <= ECDH_OP_LAST) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
   /* (ops 16, 25: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
   j->out0 = (uint8_t*)malloc(ECDH_ENC_OP(op) ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
@@ -1424,7 +1464,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
     {"customEdVerify", fn_custom_ed_verify}, {"customEdSign", fn_custom_ed_sign}, {"customEdSignDet", fn_custom_ed_sign_det}, {"customEcdh", fn_custom_ecdh},
     {"defineBase", fn_define_base}, {"defineEdBase", fn_define_ed_base}, {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info},
-    {"mulBase", fn_mul_base}, {"mulBase2", fn_mul_base2},
+    {"mulBase", fn_mul_base}, {"mulBase2", fn_mul_base2}, {"ecdsaVerifyBase", fn_verify_base},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

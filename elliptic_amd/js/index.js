@@ -672,6 +672,21 @@ Engine.prototype.mulBase2Batch = function mulBase2Batch(base1, base2, k1s, k2s) 
   this.stats.gpuCalls++; this.stats.gpuItems += k1s.length / this.addon.fieldBytes(this.baseInfo(base1).curve);
   return this.addon.mulBase2(this.ctx, base1 | 0, base2 | 0, k1s, k2s);
 };
+// ecdsaVerifyBaseBatch: EC#verify of n signatures against the key a defineBase handle stands for
+// (ellgpu_ecdsa_verify_base: both scalar multiplications walk fixed-base tables) -> { ok: Buffer(n) },
+// strictly 0 / 1: what ecdsaVerifyBatch gives with the handle's point repeated as the key.
+// b = { hashes: Buffer(n x hashLen), hashLen, r, s: Buffer(n x order bytes of the base's curve), msgBits }.
+// The handle: defineBase on a preset or on a defineShortDomain id, the generator alias included.
+// install() does not route to it.
+Engine.prototype.ecdsaVerifyBaseBatch = function ecdsaVerifyBaseBatch(base, b) {
+  this.stats.gpuCalls++; this.stats.gpuItems += b.hashLen > 0 ? b.hashes.length / b.hashLen : 0;
+  return this.addon.ecdsaVerifyBase(this.ctx, base | 0, b.hashes, b.hashLen | 0, b.msgBits | 0, b.r, b.s);
+};
+Engine.prototype.ecdsaVerifyBaseBatchAsync = function(base, b) {
+  var curve;
+  try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
+  return this._async(31, curve, b.hashLen | 0, b.msgBits | 0, b.hashes, b.r, b.s, null, base | 0, 0);
+};
 Engine.prototype.mulBaseBatchAsync = function(base, ks) {
   var curve;
   try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }

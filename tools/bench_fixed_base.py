@@ -19,7 +19,16 @@ and the spread (min .. max) over the rounds.  One JSON line per row, also append
 comb's own width) and on Curve1174 as a user-defined domain (8 and 16 bits): mul_base per width beside
 mul_var with the point repeated, mul_base2(G, H) beside mul_add2 with both points repeated, and the
 milliseconds per define.  mul_var and mul_add2 on these ids are kernels this feature left as they
-were, so their rows are the earlier commit's figures on the same device, in the same process."""
+were, so their rows are the earlier commit's figures on the same device, in the same process.
+
+--verify: ellgpu_ecdsa_verify_base.  On secp256k1 and p256 the key's table at 8, 16 and 22 bits
+(G's table as it stands), beside ellgpu_ecdsa_verify on the same items with the key repeated per item
+(the baseline: the variable-base ladder) and mul_base2 over the same two tables (the ceiling the two
+walks set: no scalar-field prep, but a normalisation); on p384 and brainpoolP256r1 (a user-defined
+domain) the one width they have.  The items are random hashes with random r and s below 2^(bits - 1),
+so every item is in range and walks both tables; almost every verdict is 0, which costs the x test
+its second candidate.  After the timed rows, per curve: the share of ecdsa_prep in the device time of
+one more ecdsa_verify_base call (ellgpu_ctx_get_timing)."""
 import argparse
 import json
 import os
@@ -39,9 +48,12 @@ def main():
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--edwards", action="store_true", help="the Edwards handles (ed25519, Curve1174) instead of --curve")
+    ap.add_argument("--verify", action="store_true", help="ellgpu_ecdsa_verify_base beside ecdsa_verify and mul_base2")
     a = ap.parse_args()
     if a.edwards:
         return main_edwards(a)
+    if a.verify:
+        return main_verify(a)
     import numpy as np
     import torch
     import elliptic_amd
@@ -168,6 +180,70 @@ def main_edwards(a):
         measure(rows, n, a, emit)
         for h in set(list(bh.values()) + list(bg.values())):
             ctx.release_base(h)
+    ctx.close()
+    write_out(a, out)
+
+
+def main_verify(a):
+    import numpy as np
+    import torch
+    import elliptic_amd
+    import verify_base_checks as VB
+    ctx = elliptic_amd.Context(0)
+    rng = np.random.default_rng(11)
+    out = []
+    for name, widths, log2n in (("secp256k1", [8, 16, 22], a.log2n), ("p256", [8, 16, 22], a.log2n),
+                                ("p384", [8], min(a.log2n, 18)), ("brainpoolP256r1", [8], a.log2n)):
+        spec = VB.spec_of(name)
+        B, n = spec["B"], 1 << log2n
+        cid = VB.curve_id(ctx, spec)
+        Q = VB.keys_of(spec)[3][1]
+
+        def emit(row, name=name, n=n):
+            row.update(curve=name, n=n)
+            print(json.dumps(row), flush=True)
+            out.append(row)
+
+        def scalars():
+            v = rng.integers(0, 256, (n, B), dtype=np.uint8)
+            v[:, 0] &= 0x7F                                    # below 2^(8 B - 1) < n: in range
+            return torch.from_numpy(v).cuda()
+
+        h = torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).cuda()
+        r, s, k1, k2 = scalars(), scalars(), scalars(), scalars()
+        pub = torch.from_numpy(np.tile(np.frombuffer(VB.xy_bytes(Q, B), np.uint8), (n, 1))).cuda()
+        ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        ok2 = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        xy = torch.zeros((n, 2 * B), dtype=torch.uint8, device="cuda")
+        inf = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        alias = ctx.define_base(cid)
+        keys = {w: ctx.define_base(cid, VB.xy_bytes(Q, B), w) for w in widths}
+        ctx.ecdsa_verify_dev(cid, h, r, s, pub, ok2)
+        for w in widths:                                        # the same verdicts, before anything is timed
+            ctx.ecdsa_verify_base(keys[w], h, r, s, out=(ok,))
+            torch.cuda.synchronize()
+            assert torch.equal(ok, ok2), (name, w)
+        gbits = ctx.base_info(alias)[1]
+        rows = [("ecdsa_verify_base key w=%d (G w=%d)" % (w, gbits), lambda w=w: ctx.ecdsa_verify_base(keys[w], h, r, s, out=(ok,)))
+                for w in widths]
+        rows += [("ecdsa_verify, key repeated", lambda: ctx.ecdsa_verify_dev(cid, h, r, s, pub, ok2))]
+        rows += [("mul_base2(G alias, key w=%d)" % w, lambda w=w: ctx.mul_base2(alias, keys[w], k1, k2, out=(xy, inf))) for w in widths]
+        measure(rows, n, a, emit)
+        base = next(x["items_per_s"] for x in out if x["curve"] == name and x["row"].startswith("ecdsa_verify,"))
+        for x in out:
+            if x["curve"] == name and x["row"].startswith("ecdsa_verify_base"):
+                x["ratio_to_ecdsa_verify"] = round(x["items_per_s"] / base, 3)
+        dflt = 16 if 16 in keys else widths[0]
+        ctx.set_timing(True)
+        ctx.ecdsa_verify_base(keys[dflt], h, r, s, out=(ok,))
+        torch.cuda.synchronize()
+        t = ctx.get_timing()
+        ctx.set_timing(False)
+        prep, walk = t.get("ecdsa_prep", (0, 0.0))[1], t.get("ecdsa_base", (0, 0.0))[1]
+        emit({"row": "kernel times of one ecdsa_verify_base call, key w=%d" % dflt, "ecdsa_prep_ms": round(prep, 4),
+              "ecdsa_base_ms": round(walk, 4), "prep_share": round(prep / (prep + walk), 3) if prep + walk else None})
+        for hdl in list(keys.values()) + [alias]:
+            ctx.release_base(hdl)
     ctx.close()
     write_out(a, out)
 

@@ -8,6 +8,10 @@ host entries) with it.  So run this in a checkout of the commit whose table is t
 after a deliberate change of include/ellgpu.h -- never to make a failing test pass.
 
     python tools/record_binding_sigs.py [--out binding_sigs.json]
+
+--table ext / ext2 records one of the later tables instead (_EXT_SIGS of include/ellgpu_ext.h into
+binding_sigs_ext.json, _EXT2_SIGS of include/ellgpu_ext2.h into binding_sigs_ext2.json): once, when
+the table is introduced.
 """
 import argparse
 import json
@@ -20,6 +24,8 @@ sys.path.insert(0, ROOT)
 from elliptic_amd import _lib  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "binding_sigs.json")
+TABLES = {"sigs": ("_SIGS", GOLDEN), "ext": ("_EXT_SIGS", GOLDEN.replace(".json", "_ext.json")),
+          "ext2": ("_EXT2_SIGS", GOLDEN.replace(".json", "_ext2.json"))}
 
 
 def table(sigs=None):
@@ -31,9 +37,12 @@ def table(sigs=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=GOLDEN)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--table", choices=sorted(TABLES), default="sigs")
     args = ap.parse_args()
-    data = table()
+    attr, default_out = TABLES[args.table]
+    args.out = args.out or default_out
+    data = table(getattr(_lib, attr))
     with open(args.out, "w") as f:
         json.dump(data, f, indent=0, sort_keys=True)
         f.write("\n")
