@@ -9,7 +9,7 @@
 // before including this header.
 #pragma once
 
-#include "../../include/ellgpu_ext2.h"
+#include "../../include/ellgpu_ext3.h"
 #include "engine.h"
 
 #include <mutex>
@@ -904,6 +904,28 @@ int ellgpu_eddsa_verify_dev(ellgpu_ctx* ctx, size_t n, const uint8_t* msgs, cons
                             size_t msg_len, const uint8_t* sigs, const uint8_t* pubs,
                             uint8_t* out_ok, uint8_t* out_err, void* stream) {
   return ell_call(ctx, stream, Mem::device, [=](Eng& e, Mem w) { return e.eddsa_verify(w, n, msgs, (const ell::u64*)msg_off, msg_len, sigs, pubs, out_ok, out_err); });
+}
+// EDDSA#verify against the table of the signer's key (include/ellgpu_ext3.h): one form, `mem` says
+// where the operands live.  A group shards a host batch of uniform stride as ellgpu_ecdsa_verify_base
+// shards its batch (handles are defined on every member); with offsets the call runs on the first member
+int ellgpu_eddsa_verify_base(ellgpu_ctx* ctx, int base, size_t n, const uint8_t* msgs, const uint64_t* msg_off,
+                             size_t msg_len, const uint8_t* sigs, uint8_t* out_ok, uint8_t* out_err, int mem,
+                             void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (!ctx->members.empty() && where == Mem::host && !msg_off && n) {
+    ELL_LOCK(ctx);
+    if (int rc = ellgpu_base_info(ctx, base, nullptr, nullptr, nullptr)) return rc;
+    if (!sigs || !out_ok || (!msgs && msg_len)) return set_err(ELLGPU_E_ARG, "null pointer");
+    return group_shard(ctx, n, [=](ellgpu_ctx* m, size_t lo, size_t hi) {
+      return ellgpu_eddsa_verify_base(m, base, hi - lo, msgs ? msgs + lo * msg_len : nullptr, nullptr, msg_len,
+                                      sigs + lo * 64, out_ok + lo, out_err ? out_err + lo : nullptr, mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) {
+    return e.eddsa_verify_base(w, base, n, msgs, (const ell::u64*)msg_off, msg_len, sigs, out_ok, out_err);
+  });
 }
 int ellgpu_eddsa_sign(ellgpu_ctx* ctx, size_t n, const uint8_t* secrets, const uint8_t* msgs,
                       const uint64_t* msg_off, size_t msg_len, uint8_t* out_sig, uint8_t* out_pub) {

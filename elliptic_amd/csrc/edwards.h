@@ -177,6 +177,9 @@ struct EdWork {
   }
 
   // acc + k * B over the comb of B (the curve's own table, or a caller-chosen base's)
+  // (NEG: acc - k * B, every entry negated as it is loaded -- not (n - k) * B, which differs from
+  // -k * B where B has a torsion component)
+  template <bool NEG = false>
   ELL_HD static P comb_mul(const u32 (&k)[8], const P* comb, P acc = identity()) {
     u32 kk[8];
     bn_copy<8>(kk, k);
@@ -187,7 +190,8 @@ struct EdWork {
       for (int i = 0; i < 7; i++) kk[i] = (kk[i] >> COMB_BITS) | (kk[i + 1] << (32 - COMB_BITS));
       kk[7] >>= COMB_BITS;
       u32 e = d ? d - 1 : 0;
-      acc = add(acc, comb[(size_t)w * COMB_DIG + e], d != 0);
+      if constexpr (NEG) acc = add(acc, cached_cneg(comb[(size_t)w * COMB_DIG + e], true), d != 0);
+      else acc = add(acc, comb[(size_t)w * COMB_DIG + e], d != 0);
     }
     return acc;
   }
@@ -302,6 +306,8 @@ struct EdWork {
 
   // decodePoint (eddsa/index.js:99-109) of a 32-byte little-endian encoding: y with the
   // top bit cleared (reduced mod p like BN#toRed), the top bit is x's parity.
+  // (INL: the exponentiation of the square root inlined, fp.h pow22523_inl)
+  template <bool INL = false>
   ELL_HD static bool decode_point(P& out, const u8* enc) {
     u32 t[8];
     ELL_UNROLL
@@ -318,7 +324,7 @@ struct EdWork {
     El u = F::sub(y2, F::one());
     El v = F::add(F::mul(y2, d), F::one());
     El x;
-    bool ok = F::sqrt_ratio(x, u, v);
+    bool ok = F::template sqrt_ratio<INL>(x, u, v);
     ok = ok && !F::is_zero(v) && !(F::is_zero(x) && want_odd);
     bool is_odd = (x.v[0] & 1u) != 0;
     El xn = F::neg(x);
@@ -542,6 +548,54 @@ struct EdWork {
     bool bad = s_ok && !(a_ok && r_ok);
     out_ok[i] = (s_ok && a_ok && r_ok && same) ? 1 : 0;
     if (out_err) out_err[i] = bad ? 1 : 0;
+  }
+
+  // EDDSA#verify against the comb of the signer's key (Engine::eddsa_verify_base): A is the point of
+  // a define_ed_base handle, tq its table and aw encodePoint(A) as the four big-endian words
+  // sha512_prefixed takes; tg is G's table.  S < n, h = hashInt(R bytes || encodePoint(A) || M), R
+  // decoded, then h over the key's table and S over G's: no decode of A, no window table, no
+  // ladder.  The law is unified, so A may be the identity, of small order or carry a torsion
+  // component (the verdict then depends on h mod 8).  No a_ok term: the key was tested against the
+  // curve when its handle was defined.
+  // ONE_ACC: S*G - h*A in one accumulator, the key's entries negated as they are loaded, compared
+  // with the affine R; otherwise the two sides as the reference writes them, R + h*A against S*G.
+  ELL_HD static void load_le(u32 (&t)[8], const u8* p) {
+    ELL_UNROLL
+    for (int l = 0; l < 8; l++)
+      t[l] = (u32)p[4 * l] | ((u32)p[4 * l + 1] << 8) | ((u32)p[4 * l + 2] << 16) | ((u32)p[4 * l + 3] << 24);
+  }
+  template <bool ONE_ACC>
+  ELL_HD static void eddsa_verify_base(size_t i, const u8* msg, u64 msg_len, const u8* sig, const u64 (&aw)[4],
+                                       const P* tg, const P* tq, u8* out_ok, u8* out_err) {
+    u32 S[8], nn[8], h[8];
+    {
+      u64 pre[8], st[8];
+      bytes_to_words(pre, sig);
+      ELL_UNROLL
+      for (int k = 0; k < 4; k++) pre[4 + k] = aw[k];
+      sha512_prefixed<8>(st, pre, msg, msg_len);
+      hash_int(h, st);
+    }
+    P R;
+    const bool r_ok = decode_point<true>(R, sig);     // (no call in this kernel: it runs without scratch memory)
+    bool same;
+    if constexpr (ONE_ACC) {
+      P acc = comb_mul<true>(h, tq);
+      load_le(S, sig + 32);
+      acc = comb_mul(S, tg, acc);
+      same = F::eq(acc.a, F::mul(R.a, acc.c)) && F::eq(acc.b, F::mul(R.b, acc.c));
+    } else {
+      const P lhs = add(comb_mul(h, tq), to_cached(R));
+      load_le(S, sig + 32);
+      const P SG = comb_mul(S, tg);
+      // projective equality (Point#eq compares the normalized coordinates, edwards.js:409-413)
+      same = F::eq(F::mul(lhs.a, SG.c), F::mul(SG.a, lhs.c)) && F::eq(F::mul(lhs.b, SG.c), F::mul(SG.b, lhs.c));
+    }
+    ELL_UNROLL
+    for (int l = 0; l < 8; l++) nn[l] = C::n[l];
+    const bool s_ok = !bn_geq<8>(S, nn);
+    out_ok[i] = (s_ok && r_ok && same) ? 1 : 0;
+    if (out_err) out_err[i] = (s_ok && !r_ok) ? 1 : 0;
   }
 
   // the comparison of EDDSA#verify for the items whose two sides came from the lanes-per-item layer

@@ -997,6 +997,29 @@ struct FnEddsaVerify {
   }
 };
 
+// EDDSA#verify against the comb of the signer's key (EdWork::eddsa_verify_base): one item per lane
+// at every n, no digit store, no scratch memory.  aw: encodePoint(A) as sha512_prefixed's words,
+// computed once per call on the host -- the kernel never loads a key per item.  Launch bounds as
+// FnEdMulBase2's (none of its own): 158 VGPRs, three waves per SIMD, no scratch memory.
+// ELL_EDDSA_BASE_ONE_ACC: S*G - h*A in one accumulator against the affine R (1), or R + h*A against
+// S*G as the reference writes it (0: 166 VGPRs) -- the same bytes, the first 3 % faster
+// (docs/EXPERIMENTS.md A10d).
+#ifndef ELL_EDDSA_BASE_ONE_ACC
+#define ELL_EDDSA_BASE_ONE_ACC 1
+#endif
+struct FnEddsaBase {
+  static constexpr const char* NAME = "eddsa_base";
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* msgs; const u64* off; size_t msg_len; const u8* sigs; u64 aw[4];
+  const EdWork::P* tg; const EdWork::P* tq; u8* ok; u8* err;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i >= n) return;
+    const u8* m = off ? msgs + off[i] : msgs + i * msg_len;
+    u64 len = off ? off[i + 1] - off[i] : (u64)msg_len;
+    EdWork::eddsa_verify_base<ELL_EDDSA_BASE_ONE_ACC != 0>(i, m, len, sigs + i * 64, aw, tg, tq, ok, err);
+  }
+};
+
 // EDDSA#verify for a handful of items: the two sides of the equation on a wave each (coop_ed.h),
 // then the one-lane comparison
 struct FnEddsaPartsC {
@@ -1874,6 +1897,10 @@ class Engine {
   template <int U = 0>
   int eddsa_chunk(size_t n, size_t o, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
                   const u8* pubs, u8* ok, u8* err);
+  // a verify chunk against the comb tq of the signer's key, whose encoding is aw, and G's comb tg
+  template <int U = 0>
+  int eddsa_base_chunk(size_t n, size_t o, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
+                       const u64 (&aw)[4], const EdWork::P* tg, const EdWork::P* tq, u8* ok, u8* err);
   template <int U = 0>
   int eddsa_sign_chunk(size_t n, size_t o, const u8* secrets, const u8* msgs, const u64* off,
                        size_t msg_len, u8* sig, u8* pub);
@@ -2877,6 +2904,65 @@ class Engine {
                             In{sigs, n * 64}, In{pubs, n * 32}},
                         {Out{ok, n}, Out{err, n}}, [&](auto d, auto r) {
       return run(d[0], (const u64*)d[1], d[2], d[3], r[0], r[1]);
+    });
+  }
+  // EDDSA#verify(msg, sig, A) with A the point of a define_ed_base handle on ed25519: ok and err are
+  // what eddsa_verify writes for the same items with encodePoint(A) repeated as the key.  h walks
+  // the key's comb and S the curve's own (the generator alias: both walks read that one).  The
+  // handle is looked up before n is: the refusals hold for an empty batch too.
+  int eddsa_verify_base(Mem where, int base, size_t n, const u8* msgs, const u64* off, size_t msg_len,
+                        const u8* sigs, u8* ok, u8* err) {
+    const BaseRec* rec = base_rec(base);
+    if (!rec) return E_ARG;
+    if (!rec->ed)
+      return fail(E_UNSUPPORTED, "EdDSA verify against a key handle takes a handle of ellgpu_ed_base_define on ed25519 (a short Weierstrass handle: ellgpu_ecdsa_verify_base)");
+    if (rec->curve != CURVE_ED25519)
+      return fail(E_UNSUPPORTED, "the engine has no EdDSA on a user-defined Edwards curve: EdDSA verify against a key handle is ed25519's");
+    if (!rec->alias && rec->t.bits != EdWork::COMB_BITS)
+      return fail(E_UNSUPPORTED, "the key's table does not have the width of ed25519's own comb");
+    if (!n) return E_OK;
+    if (!sigs || !ok) return fail(E_ARG, "null pointer");
+    // encodePoint(A), once per call: the generator alias keeps no coordinates of its own
+    u8 axy[64], enc[32];
+    if (rec->alias) {
+      u32 gx[8], gy[8];
+      for (int i = 0; i < 8; i++) { gx[i] = consts::ED25519_C::gx_plain[i]; gy[i] = consts::ED25519_C::gy_plain[i]; }
+      store_be<8>(axy, gx, 32);
+      store_be<8>(axy + 32, gy, 32);
+    } else {
+      memcpy(axy, rec->xy, 64);
+    }
+    EdWork::encode_affine(enc, axy);
+    u64 aw[4];
+    EdWork::bytes_to_words(aw, enc);
+    auto run = [&](const u8* dm, const u64* doff, const u8* ds, u8* dok, u8* derr) {
+      if (!dm && (doff || msg_len)) return fail(E_ARG, "null pointer");
+      return for_chunks(n, CHUNK, [&](size_t o, size_t m) {
+        if (int rc = prepare_curve(CURVE_ED25519)) return rc;
+        const void* tq = nullptr;
+        if (int rc = base_table_ptr(*rec, tq)) return rc;
+        return eddsa_base_chunk(m, o, dm, doff, msg_len, ds, aw, (const EdWork::P*)comb_[CURVE_ED25519],
+                                (const EdWork::P*)tq, dok, derr);
+      });
+    };
+    if (where == Mem::device) {
+      // (with offsets in device memory the host does not know where the messages end: their extent
+      // is then taken as the offsets' own array and the first message byte)
+      const size_t mlen = off ? 1 : n * msg_len;
+      const u8* ins[3] = {sigs, msgs, (const u8*)off};
+      const size_t lens[3] = {n * 64, mlen, off ? (n + 1) * sizeof(u64) : 0};
+      for (int k = 0; k < 3; k++)
+        if (overlap2(ins[k], lens[k], ok, n) || overlap2(ins[k], lens[k], err, n))
+          return fail(E_ARG, "sigs / msgs / msg_off and the results must not overlap");
+      if (overlap2(ok, n, err, n)) return fail(E_ARG, "out_ok and out_err must not overlap");
+      return run(msgs, off, sigs, ok, err);
+    }
+    size_t total;
+    if (int rc = check_eddsa_messages(n, msgs, off, msg_len, total)) return rc;
+    return staged_whole(n, {In{msgs ? msgs : (const u8*)"", total}, In{off, off ? (n + 1) * sizeof(u64) : 0, true},
+                            In{sigs, n * 64}},
+                        {Out{ok, n}, Out{err, n}}, [&](auto d, auto r) {
+      return run(d[0], (const u64*)d[1], d[2], r[0], r[1]);
     });
   }
   // EDDSA#sign with KeyPair.fromSecret, from 32-byte secrets; pub (n x 32, the encoded public
@@ -4577,6 +4663,16 @@ int Engine<BK>::eddsa_chunk(size_t n, size_t o, const u8* msgs, const u64* off, 
   FnEddsaVerify f{n, off ? msgs : msgs + o * msg_len, off ? off + o : nullptr, msg_len,
                   sigs + o * 64, pubs + o * 32, (const EdWork::P*)comb_[CURVE_ED25519], tbl,
                   ok + o, err ? err + o : nullptr};
+  bk.launch(f, n);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+int Engine<BK>::eddsa_base_chunk(size_t n, size_t o, const u8* msgs, const u64* off, size_t msg_len, const u8* sigs,
+                                 const u64 (&aw)[4], const EdWork::P* tg, const EdWork::P* tq, u8* ok, u8* err) {
+  FnEddsaBase f{n, off ? msgs : msgs + o * msg_len, off ? off + o : nullptr, msg_len, sigs + o * 64,
+                {aw[0], aw[1], aw[2], aw[3]}, tg, tq, ok + o, err ? err + o : nullptr};
   bk.launch(f, n);
   return E_OK;
 }

@@ -151,7 +151,10 @@ namespace ell {
                                                             const u8*, u8*, u8*);
 #define ELL_DECL_ED3(KW)                                                                          \
   KW template int Engine<HipBackend>::eddsa_chunk<0>(size_t, size_t, const u8*, const u64*, size_t, \
-                                                     const u8*, const u8*, u8*, u8*);
+                                                     const u8*, const u8*, u8*, u8*);               \
+  KW template int Engine<HipBackend>::eddsa_base_chunk<0>(size_t, size_t, const u8*, const u64*, size_t, \
+                                                          const u8*, const u64 (&)[4], const EdWork::P*,  \
+                                                          const EdWork::P*, u8*, u8*);
 #define ELL_DECL_ED4(KW)                                                                          \
   KW template int Engine<HipBackend>::eddsa_sign_chunk<0>(size_t, size_t, const u8*, const u8*,   \
                                                           const u64*, size_t, u8*, u8*);

@@ -628,8 +628,11 @@ struct Fp25519 {
     SafeGcd<consts::P25519_P>::inv(r.v, z.v);
     return r;
   }
-  // z^((p-5)/8) = z^(2^252 - 3): the building block of the square root of a ratio
-  static ELL_HD_NOINLINE El pow22523(const El& z) {
+  // z^((p-5)/8) = z^(2^252 - 3): the building block of the square root of a ratio.  pow22523_inl is
+  // the chain itself, inlined into its caller: a kernel that calls pow22523 pays a call frame in
+  // scratch memory for the elements passed by reference, one that is to run without scratch takes
+  // pow22523_inl (sqrt_ratio<true>).
+  ELL_HD static El pow22523_inl(const El& z) {
     El z2 = sqr(z);
     El z9 = mul(sqr_n(z2, 2), z);
     El z11 = mul(z9, z2);
@@ -643,6 +646,7 @@ struct Fp25519 {
     El z2_250_0 = mul(sqr_n(z2_200_0, 50), z2_50_0);
     return mul(sqr_n(z2_250_0, 2), z);
   }
+  static ELL_HD_NOINLINE El pow22523(const El& z) { return pow22523_inl(z); }
   // sqrt(-1) = 2^((p-1)/4)
   ELL_HD static El sqrt_m1() {
     El r;
@@ -654,10 +658,14 @@ struct Fp25519 {
   }
   // x with v*x^2 == u, if one exists (p = 5 mod 8): candidate u v^3 (u v^7)^((p-5)/8),
   // multiplied by sqrt(-1) when v x^2 == -u.  Returns false when u/v is not a square.
+  template <bool INL = false>
   ELL_HD static bool sqrt_ratio(El& x, const El& u, const El& v) {
     El v3 = mul(sqr(v), v);
     El v7 = mul(sqr(v3), v);
-    El r = mul(mul(u, v3), pow22523(mul(u, v7)));
+    El e;
+    if constexpr (INL) e = pow22523_inl(mul(u, v7));
+    else e = pow22523(mul(u, v7));
+    El r = mul(mul(u, v3), e);
     El chk = mul(v, sqr(r));
     bool ok1 = eq(chk, u);
     bool ok2 = eq(chk, neg(u));

@@ -991,6 +991,56 @@ class Context:
     def eddsa_verify_dev(self, msgs, msg_len, sigs, pubs, out_ok, out_err=None, msg_off=None):
         self._c_eddsa_verify(True, msgs, msg_off, msg_len, sigs, pubs, out_ok, out_err)
 
+    def eddsa_verify_base(self, base, msgs, sigs, msg_off=None, out=None):
+        """EDDSA#verify(msg, sig, A) of n signatures against the key A of a define_ed_base handle on
+        ed25519 (ellgpu_eddsa_verify_base: h walks the key's table, S the curve's own) -> (ok, err):
+        what eddsa_verify gives with encodePoint(A) repeated as the key.  The handle:
+        define_ed_base("ed25519", xy), the generator alias included.  numpy: msgs as for eddsa_verify
+        (a list of bytes objects or an (n, len) array), sigs (n, 64), through host memory.  torch
+        device tensors run on the current stream and return at once: msgs (n, len) uint8, or a flat
+        uint8 tensor with msg_off a device tensor of n + 1 64-bit offsets; out=(ok,) or (ok, err),
+        (n,) uint8, is required then (with out=(ok,) the second result is None)."""
+        fn = self._lib.ellgpu_eddsa_verify_base
+        if not self._is_tensor(sigs):
+            if msg_off is not None:
+                raise ValueError("msg_off goes with device tensors: host messages are a list of bytes objects or an (n, len) array")
+            sigs = _u8(sigs, (-1, 64))
+            n = sigs.shape[0]
+            ok, err = self._outs(out, [(n,), (n,)])
+            m, off, msg_len = self._messages(msgs, n)
+            self._check(fn(self._ctx, int(base), n, m.ctypes.data, None if off is None else off.ctypes.data, int(msg_len),
+                           sigs.ctypes.data, ok.ctypes.data, err.ctypes.data, 0, None))
+            return ok, err
+        import torch
+        if sigs.dim() != 2 or sigs.shape[1] != 64:
+            raise ValueError("sigs: a contiguous uint8 tensor of shape (n, 64) is needed")
+        n = int(sigs.shape[0])
+        if out is None or len(out) not in (1, 2):
+            raise ValueError("device tensors need out=(ok,) or out=(ok, err): uint8 tensors of shape (%d,)" % n)
+        here = torch.device(self.device)
+        ops = [(sigs, (n, 64), torch.uint8, "sigs")] + [(o, (n,), torch.uint8, "out " + nm) for o, nm in zip(out, ("ok", "err"))]
+        if msg_off is None:
+            if not self._is_tensor(msgs) or msgs.dim() != 2:
+                raise ValueError("msgs: a contiguous uint8 tensor of shape (n, len) is needed (or a flat one with msg_off)")
+            ops.append((msgs, (n, int(msgs.shape[1])), torch.uint8, "msgs"))
+        else:
+            if not self._is_tensor(msgs) or msgs.dim() != 1:
+                raise ValueError("msgs: with msg_off a flat contiguous uint8 tensor is needed")
+            ops.append((msgs, tuple(msgs.shape), torch.uint8, "msgs"))
+            if not self._is_tensor(msg_off) or msg_off.dtype not in (torch.int64, torch.uint64):
+                raise ValueError("msg_off: a contiguous tensor of %d 64-bit offsets is needed" % (n + 1))
+            ops.append((msg_off, (n + 1,), msg_off.dtype, "msg_off"))
+        for t, shape, dtype, name in ops:
+            if not self._is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s: a contiguous %s tensor of shape %s is needed" % (name, str(dtype).replace("torch.", ""), shape))
+            if t.device != here:
+                raise ValueError("%s is on %s, the context on %s" % (name, t.device, here))
+        msg_len = 0 if msg_off is not None else int(msgs.shape[1])
+        self._check(fn(self._ctx, int(base), n, msgs.data_ptr() if msgs.numel() else None,
+                       None if msg_off is None else msg_off.data_ptr(), msg_len, sigs.data_ptr(), out[0].data_ptr(),
+                       out[1].data_ptr() if len(out) == 2 else None, 1, self._stream()))
+        return out[0], (out[1] if len(out) == 2 else None)
+
     def eddsa_sign(self, msgs, secrets):
         """ed25519 EdDSA sign from 32-byte secrets (EDDSA#sign with keyFromSecret).  msgs as for
         eddsa_verify.  -> (sig (n, 64), pub (n, 32)) uint8 arrays"""

@@ -56,6 +56,8 @@
  *             -> {xy, inf}: fixed-base tables of caller-chosen points (ellgpu_base_*)
  *           ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s) -> {ok}: EC#verify against the table of the
  *             key a defineBase handle stands for (ellgpu_ecdsa_verify_base, include/ellgpu_ext2.h)
+ *           eddsaVerifyBase(ctx, base, msgs, offsets|null, msgLen, sigs) -> {ok, err}: EDDSA#verify against the table
+ *             of the key a defineEdBase handle on ed25519 stands for (ellgpu_eddsa_verify_base, include/ellgpu_ext3.h)
  *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
  *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
  *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
@@ -83,6 +85,7 @@
  *             defineEdwardsDomain(ctx, p, a, d, n, gx, gy); sync forms customEdVerify, customEdSign, customEdSignDet);
  *             29 mulBase(k; curve = the base's curve, i0 = base)  30 mulBase2(k1, k2; i0, i1 = the bases) -> {xy, inf};
  *             31 ecdsaVerifyBase(hashes, r, s; curve = the base's curve, i0 = base) -> {ok};
+ *             32 eddsaVerifyBase(msgs, offsets, sigs; curve = the base's curve, i0 = base) -> {ok, err};
  *             runs on a libuv worker
  *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
  *             same value the synchronous form returns.  One call per context at a time:
@@ -140,6 +143,8 @@ static struct {
   int (*mul_base)(ellgpu_ctx*, int, size_t, const uint8_t*, uint8_t*, uint8_t*, int, void*);
   int (*mul_base2)(ellgpu_ctx*, int, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, int, void*);
   int (*ecdsa_verify_base)(ellgpu_ctx*, int, size_t, const uint8_t*, int, int, const uint8_t*, const uint8_t*, uint8_t*, int, void*);
+  int (*eddsa_verify_base)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint64_t*, size_t, const uint8_t*, uint8_t*,
+                           uint8_t*, int, void*);
   int (*mul_var)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*);
   int (*mul_add2)(ellgpu_ctx*, int, size_t, const uint8_t*, const uint8_t*, const uint8_t*,
                   const uint8_t*, uint8_t*, uint8_t*);
@@ -236,6 +241,7 @@ static napi_value fn_open(napi_env env, napi_callback_info info) {
   SYM(base_define, "ellgpu_base_define"); SYM(base_release, "ellgpu_base_release"); SYM(base_info, "ellgpu_base_info");
   SYM(mul_base, "ellgpu_mul_base"); SYM(mul_base2, "ellgpu_mul_base2");
   SYM(ecdsa_verify_base, "ellgpu_ecdsa_verify_base");
+  SYM(eddsa_verify_base, "ellgpu_eddsa_verify_base");
   SYM(custom_mont_ladder, "ellgpu_custom_mont_ladder");
   SYM(custom_mont_validate, "ellgpu_custom_mont_validate");
   SYM(custom_mont_derive, "ellgpu_custom_mont_derive");
@@ -1097,6 +1103,41 @@ static napi_value fn_eddsa_verify(napi_env env, napi_callback_info info) {
   return mk_result(env, "ok", bok, "err", berr);
 }
 
+/* offsets of n messages in a buffer of lm bytes: an aligned Buffer of n + 1 non-decreasing uint64 (NULL if fine) */
+static const char* bad_offsets(const uint8_t* off, size_t loff, size_t n, size_t lm) {
+  if (loff != (n + 1) * 8 || ((uintptr_t)off & 7)) return "offsets must be an aligned Buffer of n+1 uint64";
+  if (((const uint64_t*)off)[n] > lm) return "offsets exceed the message buffer";
+  for (size_t i = 0; i < n; i++)        /* the kernels take len = off[i+1] - off[i]: must not wrap */
+    if (((const uint64_t*)off)[i] > ((const uint64_t*)off)[i + 1]) return "offsets must be non-decreasing";
+  return NULL;
+}
+/* eddsaVerifyBase(ctx, base, msgs, offsets|null, msgLen, sigs) -> {ok, err}: EDDSA#verify against the table
+ * of the key a handle stands for (ellgpu_eddsa_verify_base) */
+static napi_value fn_eddsa_verify_base(napi_env env, napi_callback_info info) {
+  if (!need_lib(env)) return NULL;
+  size_t argc = 6; napi_value argv[6];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 6) THROW(env, "eddsaVerifyBase(ctx, base, msgs, offsets, msgLen, sigs)");
+  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
+  int32_t base, mlen = 0;
+  if (napi_get_value_int32(env, argv[1], &base) != napi_ok) THROW(env, "eddsaVerifyBase(ctx, base, msgs, offsets, msgLen, sigs)");
+  const uint8_t *m, *off, *sg; size_t lm, loff, lsg;
+  if (!get_buf(env, argv[2], &m, &lm, 1) || !get_buf(env, argv[3], &off, &loff, 1) || !get_buf(env, argv[5], &sg, &lsg, 0)) return NULL;
+  napi_get_value_int32(env, argv[4], &mlen);
+  if (lsg % 64) THROW(env, "buffer length mismatch");
+  size_t n = lsg / 64;
+  if (off) {
+    const char* bad = bad_offsets(off, loff, n, lm);
+    if (bad) THROW(env, bad);
+  } else if (mlen < 0 || (size_t)mlen * n > lm) THROW(env, "message buffer too short");
+  napi_value bok, berr; void *dok, *derr;
+  CHECK(env, result_buffer(env, n, &dok, &bok));
+  CHECK(env, result_buffer(env, n, &derr, &berr));
+  if (L.eddsa_verify_base(c, base, n, m, (const uint64_t*)off, (size_t)mlen, sg, (uint8_t*)dok, (uint8_t*)derr, 0, NULL) != 0)
+    return lib_error(env);
+  return mk_result(env, "ok", bok, "err", berr);
+}
+
 /* eddsaSign(ctx, msgs, offsets|null, msgLen, secrets) -> {sig: Buffer(n*64), pub: Buffer(n*32)} */
 static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
@@ -1145,7 +1186,8 @@ static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
 #define OP_MUL_BASE 29           /* mulBase(k; curve = the base's curve, i0 = base)  mulBase2(k1, k2; i0, i1 = the bases) */
 #define OP_MUL_BASE2 30
 #define OP_VERIFY_BASE 31        /* ecdsaVerifyBase(hashes, r, s; curve = the base's curve, i0 = base) -> {ok} */
-#define OP_LAST 31
+#define OP_EDDSA_VERIFY_BASE 32  /* eddsaVerifyBase(msgs, offsets, sigs; curve = the base's curve, i0 = base) -> {ok, err} */
+#define OP_LAST 32
 #define ECDH_ENC_OP(op) ((op) == 16 || (op) == 25)
 static const char* const ECDH_NAMES[13][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
                                               {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0},
@@ -1270,6 +1312,8 @@ static void job_execute(napi_env env, void* data) {
     case OP_MUL_BASE2: j->rc = L.mul_base2(j->ctx, j->i0, j->i1, j->n, j->in[0], j->in[1], j->out0, j->out1, 0, NULL); break;
     case OP_VERIFY_BASE: j->rc = L.ecdsa_verify_base(j->ctx, j->i0, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2],
                                                      j->out0, 0, NULL); break;
+    case OP_EDDSA_VERIFY_BASE: j->rc = L.eddsa_verify_base(j->ctx, j->i0, j->n, j->in[0], (const uint64_t*)j->in[1], 0, j->in[2],
+                                                           j->out0, j->out1, 0, NULL); break;
     case 5: j->rc = L.ecdsa_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i0,
                                      j->out0, j->out1, j->out2, j->out3); break;
     case 6: j->rc = L.ecdsa_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
@@ -1318,7 +1362,7 @@ static void job_complete(napi_env env, napi_status status, void* data) {
       {"xy", "status", 0, 0}, {"xy", "status", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
       {"x", "status", "err", 0}, {"enc", 0, 0, 0},
       {"ok", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
-      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", 0, 0, 0}};
+      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", 0, 0, 0}, {"ok", "err", 0, 0}};
     uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
     size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
     napi_create_object(env, &result);
@@ -1394,6 +1438,10 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
             ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && !j->in[3] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
             ok = ok && len[1] == j->n * NB && len[2] == j->n * NB; break;
+    case OP_EDDSA_VERIFY_BASE:
+            ok = j->in[1] && j->in[2] && !j->in[3] && len[2] % 64 == 0;
+            j->n = ok ? len[2] / 64 : 0;
+            ok = ok && !bad_offsets(j->in[1], len[1], j->n, len[0]); break;
     case 4: j->n = len[0] / 32; ok = j->in[0] && j->in[1] && len[0] % 32 == 0 && len[1] == len[0]; break;
     case 5: ok = hl > 0 && j->in[0] && j->in[1] && len[0] % (size_t)hl == 0;
             j->n = ok ? len[0] / (size_t)hl : 0;
@@ -1428,6 +1476,7 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   if (op == OP_MUL_BASE || op == OP_MUL_BASE2) { j->out0_len = j->n * 2 * B; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
   if (op == ED_OP_VERIFY) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
   if (op == OP_VERIFY_BASE) { j->out0_len = j->n; j->out1_len = 0; j->out2_len = 0; j->out3_len = 0; }
+  if (op == OP_EDDSA_VERIFY_BASE) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
   if (op >= 13 && op <= ECDH_OP_LAST) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
   /* (ops 16, 25: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
   j->out0 = (uint8_t*)malloc(ECDH_ENC_OP(op) ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
@@ -1465,6 +1514,7 @@ static napi_value init(napi_env env, napi_value exports) {
     {"customEdVerify", fn_custom_ed_verify}, {"customEdSign", fn_custom_ed_sign}, {"customEdSignDet", fn_custom_ed_sign_det}, {"customEcdh", fn_custom_ecdh},
     {"defineBase", fn_define_base}, {"defineEdBase", fn_define_ed_base}, {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info},
     {"mulBase", fn_mul_base}, {"mulBase2", fn_mul_base2}, {"ecdsaVerifyBase", fn_verify_base},
+    {"eddsaVerifyBase", fn_eddsa_verify_base},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

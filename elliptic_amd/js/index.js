@@ -687,6 +687,29 @@ Engine.prototype.ecdsaVerifyBaseBatchAsync = function(base, b) {
   try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
   return this._async(31, curve, b.hashLen | 0, b.msgBits | 0, b.hashes, b.r, b.s, null, base | 0, 0);
 };
+// eddsaVerifyBaseBatch: EDDSA#verify(msg, sig, A) of n signatures against the key A a defineEdBase handle on
+// ed25519 stands for (ellgpu_eddsa_verify_base: h walks the key's table, S the curve's own) ->
+// { ok: Buffer(n), err: Buffer(n) }: what eddsaVerifyBatch gives with encodePoint(A) repeated as the key
+// (err = 1 where the reference throws: R is not a curve point).  msgs: array of Buffers (any lengths);
+// sigs: Buffer(n x 64) of R||S.  The handle: defineEdBase('ed25519', xy), the generator alias included.
+// install() does not route to it.
+Engine.prototype._msgOffsets = function _msgOffsets(msgs) {
+  var n = msgs.length, off = Buffer.alloc((n + 1) * 8), pos = 0;
+  for (var i = 0; i <= n; i++) {
+    off.writeUInt32LE(pos >>> 0, i * 8); off.writeUInt32LE(Math.floor(pos / 4294967296), i * 8 + 4);
+    if (i < n) pos += msgs[i].length;
+  }
+  return off;
+};
+Engine.prototype.eddsaVerifyBaseBatch = function eddsaVerifyBaseBatch(base, msgs, sigs) {
+  this.stats.gpuCalls++; this.stats.gpuItems += msgs.length;
+  return this.addon.eddsaVerifyBase(this.ctx, base | 0, Buffer.concat(msgs), this._msgOffsets(msgs), 0, sigs);
+};
+Engine.prototype.eddsaVerifyBaseBatchAsync = function(base, msgs, sigs) {
+  var curve;
+  try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
+  return this._async(32, curve, 0, 0, Buffer.concat(msgs), this._msgOffsets(msgs), sigs, null, base | 0, 0);
+};
 Engine.prototype.mulBaseBatchAsync = function(base, ks) {
   var curve;
   try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }

@@ -28,7 +28,15 @@ walks set: no scalar-field prep, but a normalisation); on p384 and brainpoolP256
 domain) the one width they have.  The items are random hashes with random r and s below 2^(bits - 1),
 so every item is in range and walks both tables; almost every verdict is 0, which costs the x test
 its second candidate.  After the timed rows, per curve: the share of ecdsa_prep in the device time of
-one more ecdsa_verify_base call (ellgpu_ctx_get_timing)."""
+one more ecdsa_verify_base call (ellgpu_ctx_get_timing).
+
+--eddsa: ellgpu_eddsa_verify_base on ed25519.  Signatures of one signer over 32-byte messages at a
+uniform stride (made by the engine's own eddsa_sign), about one item in 16 tampered with; beside
+ellgpu_eddsa_verify_dev on the same items with the encoded key repeated per item (the baseline: the
+decode of A, the window table and the ladder per item) and ed25519 mul_base2 over the same two tables
+(the ceiling the two walks set: no hash, no decode of R, but a normalisation).  The verdicts of the
+two verifies are compared before anything is timed.  Then the same two verifies at 200-byte messages:
+what the longer hash costs."""
 import argparse
 import json
 import os
@@ -49,7 +57,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--edwards", action="store_true", help="the Edwards handles (ed25519, Curve1174) instead of --curve")
     ap.add_argument("--verify", action="store_true", help="ellgpu_ecdsa_verify_base beside ecdsa_verify and mul_base2")
+    ap.add_argument("--eddsa", action="store_true", help="ellgpu_eddsa_verify_base beside eddsa_verify and ed25519 mul_base2")
     a = ap.parse_args()
+    if a.eddsa:
+        return main_eddsa(a)
     if a.edwards:
         return main_edwards(a)
     if a.verify:
@@ -244,6 +255,65 @@ def main_verify(a):
               "ecdsa_base_ms": round(walk, 4), "prep_share": round(prep / (prep + walk), 3) if prep + walk else None})
         for hdl in list(keys.values()) + [alias]:
             ctx.release_base(hdl)
+    ctx.close()
+    write_out(a, out)
+
+
+def main_eddsa(a):
+    import numpy as np
+    import torch
+    import elliptic_amd
+    from oracle import ec_oracle as O
+    n = 1 << a.log2n
+    ctx = elliptic_amd.Context(0)
+    rng = np.random.default_rng(13)
+    out = []
+
+    def emit(row):
+        row.update(curve="ed25519", n=n)
+        print(json.dumps(row), flush=True)
+        out.append(row)
+
+    secret = bytes(rng.integers(0, 256, 32, dtype=np.uint8))
+    A = O.get_curve("ed25519").g.mul(O.eddsa_keypair(O.get_curve("ed25519"), secret)[0])
+    x, y = A.normalized()
+    enc = O.ed_encode_point(A)
+    key = ctx.define_ed_base("ed25519", x.to_bytes(32, "big") + y.to_bytes(32, "big"))
+    alias = ctx.define_ed_base("ed25519")
+    secrets = torch.from_numpy(np.tile(np.frombuffer(secret, np.uint8), (n, 1))).cuda()
+    pubs = torch.from_numpy(np.tile(np.frombuffer(enc, np.uint8), (n, 1))).cuda()
+    k1 = torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).cuda()
+    k2 = torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).cuda()
+    xy = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+    inf = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    ok, err, ok2, err2 = (torch.zeros(n, dtype=torch.uint8, device="cuda") for _ in range(4))
+    rates = {}
+    for mlen in (32, 200):
+        msgs = torch.from_numpy(rng.integers(0, 256, (n, mlen), dtype=np.uint8)).cuda()
+        sigs = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+        ctx.eddsa_sign_dev(secrets, msgs, mlen, sigs)
+        torch.cuda.synchronize()
+        sigs[::16, 33] ^= 1                                     # about one item in 16: a bit of S
+        ctx.eddsa_verify_dev(msgs, mlen, sigs, pubs, ok2, err2)
+        ctx.eddsa_verify_base(key, msgs, sigs, out=(ok, err))
+        torch.cuda.synchronize()
+        assert torch.equal(ok, ok2) and torch.equal(err, err2), mlen
+        accepted = int(ok.sum())
+        assert accepted == n - (n + 15) // 16 and not bool(err.any()), (accepted, n)
+        rows = [("eddsa_verify_base, %d-byte messages" % mlen, lambda: ctx.eddsa_verify_base(key, msgs, sigs, out=(ok, err))),
+                ("eddsa_verify, key repeated, %d-byte messages" % mlen, lambda: ctx.eddsa_verify_dev(msgs, mlen, sigs, pubs, ok2, err2))]
+        if mlen == 32:
+            rows.append(("mul_base2(G alias, key)", lambda: ctx.mul_base2(alias, key, k1, k2, out=(xy, inf))))
+        measure(rows, n, a, emit)
+        for x in out:
+            rates[x["row"]] = x.get("items_per_s")
+    b32, v32 = rates["eddsa_verify_base, 32-byte messages"], rates["eddsa_verify, key repeated, 32-byte messages"]
+    b200, v200 = rates["eddsa_verify_base, 200-byte messages"], rates["eddsa_verify, key repeated, 200-byte messages"]
+    emit({"row": "ratios", "base_to_verify_32": round(b32 / v32, 3), "base_to_mul_base2_32": round(b32 / rates["mul_base2(G alias, key)"], 3),
+          "base_to_verify_200": round(b200 / v200, 3),
+          "share_of_the_longer_hash_in_a_200_byte_call": round(1 - b200 / b32, 3)})
+    ctx.release_base(key)
+    ctx.release_base(alias)
     ctx.close()
     write_out(a, out)
 
