@@ -10,8 +10,10 @@
 //                  carry chain), 8-entry table {1..8}P per lane in HBM/L2
 //                  scratch, one add per window, every lane adds at the same
 //                  step (a zero digit is a select, not a branch);
-//   secp256k1      GLV first (k = k1 + k2*lambda, |k1|,|k2| < 2^129), two
-//                  33-window ladders sharing the doublings
+//   secp256k1      GLV first (k = k1 + k2*lambda, both halves odd; |k1|,|k2| < 2^128
+//                  where the table is built after the split -- glv_split's ROT form --
+//                  and < 2^130 otherwise), two 32-window (4 bits) or 26-window (5 bits)
+//                  ladders sharing the doublings
 //                  (replaces _endoSplit/_endoWnafMulAdd, short.js:168-249);
 //   fixed base     unsigned 8-bit comb over a table of d*2^(8w)*G, no
 //                  doublings at all (replaces _fixedNafMul, base.js:52-84).
@@ -417,7 +419,8 @@ struct Ladder {
 // lib/elliptic/curve/short.js:168-185).  c1 = round(b2*k/n), c2 =
 // round(-b1*k/n) are taken as the top 128 bits of k*g with g = round(2^384 *
 // b/n); an off-by-one in c only moves (k1,k2) by one lattice vector, so
-// k1 + k2*lambda == k (mod n) holds exactly and |k1|,|k2| < 2^129.
+// k1 + k2*lambda == k (mod n) holds exactly; |k1|,|k2| < 0.64 * 2^128 before the halves are made
+// odd (the bound is worked out above glv_split).
 // --------------------------------------------------------------------------
 ELL_HD void glv_mul_shift384(u32 (&c)[4], const u32 (&k)[8], const u32 (&g)[8]) {
   u32 t[16];
@@ -450,11 +453,34 @@ ELL_HD bool abs9(u32 (&r)[9]) {
 // ODD = true: both halves come back odd.  (k1, k2) may be moved by any lattice vector
 // (a_i, b_i) -- a_i + b_i * lambda == 0 (mod n) -- and the basis' parities, (a1, b1) = (1, 1) and
 // (a2, b2) = (0, 1) mod 2, span all four cases: one conditional add / subtract of each vector fixes
-// both parities, |k1|, |k2| stay below 2^130 (the 33-window odd recoding takes < 2^132), and the
+// both parities, |k1|, |k2| stay below 2^130 (what the 26-window five-bit odd recoding takes), and the
 // ladder needs no "k was even: subtract P once more" additions at its end (two mixed additions
 // that every wave executed, 1 % of a verify).  Signs are chosen towards zero.
-template <bool ODD = false>
-ELL_HD void glv_split(const u32 (&k)[8], u32 (&k1)[5], bool& neg1, u32 (&k2)[5], bool& neg2) {
+//
+// ROT = true: both halves odd AND below 2^128, for every k in [0, 2^256), for a caller that can still
+// choose the point (the table of P is built after the split: Work::var_ladder).  Translations
+// alone cannot do it: k = 1 + 2 lambda has the reduced pair (1, 2), and every lattice vector with
+// the parities (0, 1) -- m1 v1 + m2 v2, m1 even, m2 odd -- has a component of at least a2 > 2^128.
+// The units of Z[lambda] can.  Write z = k1 + k2 lambda; lambda^2 + lambda + 1 = 0, so
+//     z lambda   = -k2 + (k1 - k2) lambda         z lambda^2 = (k2 - k1) - k1 lambda
+// and k P = z P = (z u) (u^-1 P) for a unit u: u = lambda^2 goes with P' = lambda P = (beta x, y),
+// u = lambda with P' = lambda^2 P = (beta^2 x, y) (beta^3 = 1).  Modulo 2 the pair (k1, k2) is an
+// element of F_4 = Z[lambda] / 2, whose three non-zero classes the units permute:
+//     (1, 1): as it is, P' = P                (1, 0) = 1:      z lambda^2 = (k2 - k1, -k1), both odd, P' = lambda P
+//     (0, 0): -+ v1 = (1, 1) mod 2, P' = P    (0, 1) = lambda: z lambda   = (-k2, k1 - k2), both odd, P' = lambda^2 P
+// The bound.  (k, 0) = x1 v1 + x2 v2 with x1 = k b2 / n, x2 = -k b1 / n (a1 b2 - a2 b1 = n), and
+// c_i = floor(k g_i / 2^384 + 1/2) with |g_i - 2^384 b / n| <= 1/2 and k < 2^256 is the rounding
+// of x_i + e, |e| < 2^-129: (k1, k2) = t1 v1 + t2 v2 with |t_i| <= h = 1/2 + 2^-129.  With
+// a1 = b2 = 0.1896, |b1| = 0.8917, a2 = 1.0812 (units of 2^128), over that parallelogram
+//     |k1| <= h (a1 + a2) = 0.6354    |k2| <= h (|b1| + b2) = 0.5407
+//     |k1 - k2| = |t1 (a1 + |b1|) + t2 (a2 - b2)| <= h (|b1| + a2) = 0.9865   (a1 = b2)
+// so the rotated pairs, whose components are k1, k2 and k1 - k2 up to sign, stay below 0.9865 * 2^128;
+// and (0, 0) -+ v1, minus where k2 >= 0: |k2'| = |b1| - |k2| <= 0.8917, |k1'| <= 0.6354 + a1 = 0.8250.
+// The slack, 0.0135 * 2^128, is 2^121 times what the 2^-129 in h moves a component by.
+// *rot comes back as the exponent of beta for P', 0 / 1 / 2.  (tests/test_glv_split_bound.py holds
+// the integer model.)
+template <bool ODD = false, bool ROT = false>
+ELL_HD void glv_split(const u32 (&k)[8], u32 (&k1)[5], bool& neg1, u32 (&k2)[5], bool& neg2, int* rot = nullptr) {
   typedef consts::SECP256K1_C C;
   u32 g1[8], g2[8], a1[4], mb1[4], a2[5], b2[4];
   ELL_UNROLL
@@ -500,19 +526,52 @@ ELL_HD void glv_split(const u32 (&k)[8], u32 (&k1)[5], bool& neg1, u32 (&k2)[5],
       br = (u32)(t >> 63);
     }
   }
-  if constexpr (ODD) {
-    // 9-limb two's complement x += sign * v (v >= 0, nv limbs), sign = +1 / -1, only where `on`
-    auto addv = [](u32 (&x)[9], const u32* v, int nv, bool minus, bool on) {
-      u64 c = (on && minus) ? 1 : 0;                      // x - v = x + ~v + 1 over all nine limbs
+  // 9-limb two's complement x += sign * v (v >= 0, nv limbs), sign = +1 / -1, only where `on`
+  auto addv = [](u32 (&x)[9], const u32* v, int nv, bool minus, bool on) {
+    u64 c = (on && minus) ? 1 : 0;                        // x - v = x + ~v + 1 over all nine limbs
+    ELL_UNROLL
+    for (int i = 0; i < 9; i++) {
+      const u32 vi = i < nv ? v[i] : 0u;
+      const u32 w = on ? (minus ? ~vi : vi) : 0u;
+      c += (u64)x[i] + w;
+      x[i] = (u32)c;
+      c >>= 32;
+    }
+  };
+  (void)addv;
+  if constexpr (ROT) {
+    const bool e1 = (r[0] & 1u) == 0, e2 = (r2[0] & 1u) == 0;
+    // z = 0 (mod 2): -+ v1, towards zero in k2, v1's large component
+    const bool both = e1 && e2;
+    const bool k2pos = (r2[8] >> 31) == 0;
+    addv(r, a1, 4, !k2pos, both);
+    addv(r2, mb1, 4, k2pos, both);
+    const bool ra = !e1 && e2;                            // z = 1 (mod 2): z lambda^2 = (k2 - k1, -k1), P' = lambda P
+    const bool rb = e1 && !e2;                            // z = lambda:    z lambda   = (-k2, k1 - k2), P' = lambda^2 P
+    u32 d[9];
+    {
+      u32 br = 0;
       ELL_UNROLL
       for (int i = 0; i < 9; i++) {
-        const u32 vi = i < nv ? v[i] : 0u;
-        const u32 w = on ? (minus ? ~vi : vi) : 0u;
-        c += (u64)x[i] + w;
-        x[i] = (u32)c;
-        c >>= 32;
+        u64 t = (u64)r[i] - r2[i] - br;
+        d[i] = (u32)t;
+        br = (u32)(t >> 63);
       }
-    };
+    }
+    // the negations are taken on the sign flags, after abs9
+    ELL_UNROLL
+    for (int i = 0; i < 9; i++) {
+      const u32 x1 = r[i], x2 = r2[i];
+      r[i] = ra ? d[i] : (rb ? x2 : x1);                  // ra: -(k1 - k2),  rb: -k2
+      r2[i] = ra ? x1 : (rb ? d[i] : x2);                 // ra: -k1,         rb: k1 - k2
+    }
+    *rot = ra ? 1 : (rb ? 2 : 0);
+    neg1 = abs9(r) != (ra || rb);
+    neg2 = abs9(r2) != ra;
+    ELL_UNROLL
+    for (int i = 0; i < 5; i++) { k1[i] = r[i]; k2[i] = r2[i]; }
+    return;
+  } else if constexpr (ODD) {
     // v1 = (a1, -|b1|): fixes k1's parity; towards zero in its large component, k2
     const bool x1 = (r[0] & 1u) == 0;
     const bool k2pos = (r2[8] >> 31) == 0;

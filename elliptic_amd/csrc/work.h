@@ -76,9 +76,12 @@ struct Work {
   static constexpr int NWIN = NNIB + (TOP ? 1 : 0);
   // variable-base window table: 8 affine odd multiples per digit string (16 entries per item:
   // P and lambda*P for secp256k1; the second half is build_table_odd8's scratch otherwise)
-  // The secp256k1 odd-digit ladder (GLV halves below 2^130): WB-bit windows over the 2^(WB-1)
-  // odd multiples.  4 bits = 33 windows (128 doublings, 65 additions) over 8 entries; 5 bits = 26
-  // windows (125 doublings, 51 additions) over 16.  Since the table's entries cost a co-Z addition
+  // The secp256k1 odd-digit ladder: WB-bit windows over the 2^(WB-1) odd multiples of the GLV
+  // halves, which are below 2^128 where the split may still choose among P, lambda P and lambda^2 P
+  // (var_ladder's full-grid tuning: glv_split's ROT form, ladder.h) and below 2^130 where the table
+  // was built without the scalar (the small-grid, parted and row forms).  4 bits over 128 = 32
+  // windows (124 doublings, 63 additions) over 8 entries; 5 bits over 130 = 26 windows (125
+  // doublings, 51 additions) over 16.  Since the table's entries cost a co-Z addition
   // and a rescaling each (1.7 k instructions; they were 2.6 k) the 5-bit form executes 3 % fewer
   // instructions -- and writes twice the table bytes: on a full grid (4 waves/SIMD) the two
   // measure the same (7.98 against 7.94 ms per 2^20), where only two or three waves per SIMD are
@@ -87,7 +90,9 @@ struct Work {
   template <bool WIDE>
   struct Endo {
     static constexpr int WB = ENDO ? (WIDE ? ELL_ENDO_WBITS_WIDE : ELL_ENDO_WBITS) : 4;
-    static constexpr int NW = (130 + WB - 1) / WB;                     // 26 (5 bits) / 33 (4 bits)
+    static constexpr bool ROT = ENDO && !WIDE;                         // var_ladder splits with glv_split<true, true>
+    static constexpr int BITS = ROT ? 128 : 130;                       // bound on the odd GLV halves
+    static constexpr int NW = (BITS + WB - 1) / WB;                    // 26 (5 bits) / 32 (4 bits)
     static constexpr int NE = 1 << (WB - 1);                           // table entries
     static constexpr int TBL = 2 * NE > 16 ? 2 * NE : 16;             // slots per item: entries + the build's ratios
     static_assert(!ENDO || NW * 2 <= NWIN * NSV, "digit store too small for the odd ladder");
@@ -208,13 +213,23 @@ struct Work {
       typedef Endo<WIDE> E;
       u32 k1[5], k2[5];
       bool n1, n2;
-      glv_split<true>(k, k1, n1, k2, n2);           // both halves odd: no correction at the end
+      int rot = 0;
+      glv_split<true, E::ROT>(k, k1, n1, k2, n2, &rot);   // both halves odd: no correction at the end
       const u32 evenmask = 0u;
       recode_odd_w4<5, E::NW, E::WB>(k1, ds, 0, 2);
       recode_odd_w4<5, E::NW, E::WB>(k2, ds, 1, 2);
       u32 negmask = (n1 ? 1u : 0u) | (n2 ? 2u : 0u);
       El zg;
-      LD::template build_table_odd8<E::NE>(tbl, p, zg);
+      if constexpr (E::ROT) {
+        // the halves are those of k against P' = lambda^rot P = (beta^rot x, y): the table is P''s
+        const El b1 = load_beta();
+        const El f = fe_select<F>(rot == 1, b1, fe_select<F>(rot == 2, F::sqr(b1), F::one()));
+        A pr = p;
+        pr.x = F::mul(p.x, f);
+        LD::template build_table_odd8<E::NE>(tbl, pr, zg);
+      } else {
+        LD::template build_table_odd8<E::NE>(tbl, p, zg);
+      }
       // lambda*P table: (beta*x, y)   (short.js:282-310 _getBeta); beta commutes with the
       // isomorphisms, which only scale x and y
       El beta = load_beta();
@@ -1663,6 +1678,7 @@ struct Work {
     const VT* tbl = tbl_all + i * stride<WIDE>();
     u32 k1[5], k2[5];
     bool n1, n2;
+    static_assert(!E::ROT, "the table was built without u2: the split cannot choose the point");
     glv_split<true>(u2, k1, n1, k2, n2);
     recode_odd_w4<5, E::NW, E::WB>(k1, ds, 0, 2);
     recode_odd_w4<5, E::NW, E::WB>(k2, ds, 1, 2);
@@ -1702,6 +1718,7 @@ struct Work {
     for (int l = 0; l < L; l++) u2[l] = l < LN ? u12[(size_t)(1 * LN + l) * n + i] : 0u;
     u32 k1[5], k2[5];
     bool n1, n2;
+    static_assert(!E::ROT, "the table was built without u2: the split cannot choose the point");
     glv_split<true>(u2, k1, n1, k2, n2);
     const bool lam = half != 0;
     ELL_UNROLL
@@ -1764,6 +1781,7 @@ struct Work {
     load_be<L>(k, ks + i * BYTES, BYTES);
     u32 k1[5], k2[5];
     bool n1, n2;
+    static_assert(!E::ROT, "the halves run over one table of P itself");
     glv_split<true>(k, k1, n1, k2, n2);
     const bool lam = half != 0;
     ELL_UNROLL
