@@ -9,89 +9,19 @@
  *
  *   gcc -shared -fPIC -I/usr/include/node -o ellgpu.node ellgpu_napi.c -ldl
  *
- * Exports:  open(path) -> true
- *           createContext(device) -> external
- *           destroyContext(ctx)
- *           combBits(ctx, curve) -> width of the fixed-base table in use (ellgpu_ctx_comb_bits)
- *           defer(ctx): the next few-item call on ctx returns once it is enqueued (ellgpu_ctx_defer);
- *           collect(ctx): waits for it and fills the result Buffers that call returned
- *             (ellgpu_ctx_collect; throws the library's error) -- index.js validates the
- *             reference's precomputed tables in between, while the device works
- *           curveId(name), fieldBytes(id), orderBytes(id), deviceCount(), defineShort(ctx, p, a, b), defineEdwards(ctx, p, a, d)
- *           mulFixed(ctx, curve, k) -> {xy, inf}
- *           mulVar(ctx, curve, k, xy) -> {xy, inf}
- *           mulAdd2(ctx, curve, k1, p1|null, k2, p2) -> {xy, inf}
- *           ecdsaVerify(ctx, curve, hash, hashLen, msgBits, r, s, pub) -> {ok, status}
- *           x25519(ctx, k, x) -> {x, inf}
- *           x25519Derive(ctx, k, x) -> {x, status}   (KeyPair#derive: validate + ladder, one call)
- *           decompress(ctx, curve, v, odd) -> {xy, ok}
- *           ecdsaSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical)
- *             -> {r, s, recid, ok}
- *           eddsaVerify(ctx, msgs, offsets|null, msgLen, sigs, pubs) -> {ok, err}
- *           eddsaSign(ctx, msgs, offsets|null, msgLen, secrets) -> {sig, pub}
- *           ecdsaRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy, status}
- *           ecdsaSignDet(ctx, curve, hash, hashLen, msgBits, priv, canonical) -> {r, s, recid, ok}
- *           decodePoints(ctx, curve, enc, encLen) -> {xy, status}
- *           encodePoints(ctx, curve, xy, compact) -> Buffer
- *           validate(ctx, curve, xy, inf|null, checkOrder) -> Buffer (status bytes)
- *           pointAdd(ctx, curve, xy1, inf1|null, xy2, inf2|null) -> {xy, inf}
- *           sigFromDer(ctx, curve, der, stride, lens) -> {r, s, status}
- *           sigToDer(ctx, curve, r, s) -> {der, lens}     (stride = der.length / n)
- *           ecdsaVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)
- *             -> {ok, err};  lens: Buffer of n little-endian uint32
- *           customDecompress(ctx, curve, x, odd) -> {xy, status}
- *           customDecodePoints(ctx, curve, enc, encLen) -> {xy, status}
- *           customVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)
- *             -> {ok, err}: the same three on a user-defined short curve / domain (ellgpu_custom_*)
- *           customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy, status}: EC#recoverPubKey on a
- *             user-defined domain (ellgpu_custom_recover; 32-byte r, s and coordinates, hashLen 1..64)
- *           customEcdh(ctx, op, curve, b0, b1, i0, i1): the key side on a user-defined short curve, the ops
- *             13..16 of callAsync below -- KeyPair#derive, #validate and BasePoint#encode
- *             (ellgpu_custom_derive / _custom_derive_wire / _custom_validate / _custom_encode_points)
- *             and, on a user-defined Montgomery curve (defineMont(ctx, p, a); ellgpu_custom_mont_ladder /
- *             _validate / _derive), the ops 17..19: Point#mul + getX, MontCurve#validate, KeyPair#derive
- *           defineEdBase(ctx, curve, xy|null, windowBits) -> handle (Edwards curves, include/ellgpu_ext.h),
- *           defineBase(ctx, curve, xy|null, windowBits) -> handle, releaseBase(ctx, base), baseInfo(ctx, base) ->
- *             {curve, windowBits, tableBytes}, mulBase(ctx, base, k) -> {xy, inf}, mulBase2(ctx, base1, base2, k1, k2)
- *             -> {xy, inf}: fixed-base tables of caller-chosen points (ellgpu_base_*)
- *           ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s) -> {ok}: EC#verify against the table of the
- *             key a defineBase handle stands for (ellgpu_ecdsa_verify_base, include/ellgpu_ext2.h)
- *           eddsaVerifyBase(ctx, base, msgs, offsets|null, msgLen, sigs) -> {ok, err}: EDDSA#verify against the table
- *             of the key a defineEdBase handle on ed25519 stands for (ellgpu_eddsa_verify_base, include/ellgpu_ext3.h)
- *           customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok}
- *           customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok}:
- *             EC#sign on a user-defined domain (ellgpu_custom_sign / _custom_sign_det; 32-byte priv,
- *             nonces, r and s; drbgHash 0 sha256, 1 sha384, 2 sha512)
- *             offsets: Buffer of n+1 little-endian uint64 byte offsets into msgs
- *           callAsync(op, ctx, curve, hashLen, msgBits, b0, b1, b2, b3) -> Promise
- *             op 0 mulFixed(b0=k) 1 mulVar(k, xy) 2 mulAdd2(k1, p1|null, k2, p2)
- *             3 ecdsaVerify(hash, r, s, pub) 4 x25519(k, x) 5 ecdsaSignDet(hash, priv; i0 = canonical)
- *             6 ecdsaRecover(hash, r, s, recid) 7 ecdsaVerifyWire(hash, der, lens, keys; i0 = der
- *             stride, i1 = key length) 8 decodePoints(enc; i0 = encoding length) 9 customVerifyWire (as 7); 10 customRecover (as 6);
- *             13 customDerive(priv, pubXY) -> {x, status}  14 customDeriveWire(priv, enc; i0 = key length) ->
- *             {x, status, err}  15 customValidate(xy, inf or null; i0 = checkOrder) -> {status}
- *             16 customEncodePoints(xy; i0 = compact, i1 = p.byteLength()) -> {enc};
- *             17 customMontLadder(k, x) -> {x, inf}  18 customMontValidate(x) -> {status}
- *             19 customMontDerive(priv, x) -> {x, status};
- *             20 customEdDecompress(v, odd; i0 = fromY) -> {xy, status}  21 customEdDecodePoints(enc; i0 = row
- *             length) -> {xy, status}  22 customEdValidate(xy, order or null) -> {status}  23 customEdDerive(priv,
- *             pubXY) -> {x, status}  24 customEdDeriveWire(priv, enc; i0 = key length) -> {x, status, err}
- *             25 customEdEncodePoints(xy; i0 = compact, i1 = p.byteLength()) -> {enc}
- *             (ellgpu_custom_ed_*: the key side of a user-defined Edwards curve);
- *             11 customSign(hash, priv, nonces; i0 = canonical) 12 customSignDet(hash, priv; i0 = canonical,
- *             i1 = drbgHash);
- *             26 customEdVerify(hash, r, s, pub) -> {ok, status}  27 customEdSign (as 11)  28 customEdSignDet (as 12)
- *             (ellgpu_custom_ed_verify / _sign / _sign_det: ECDSA on a user-defined Edwards domain,
- *             defineEdwardsDomain(ctx, p, a, d, n, gx, gy); sync forms customEdVerify, customEdSign, customEdSignDet);
- *             29 mulBase(k; curve = the base's curve, i0 = base)  30 mulBase2(k1, k2; i0, i1 = the bases) -> {xy, inf};
- *             31 ecdsaVerifyBase(hashes, r, s; curve = the base's curve, i0 = base) -> {ok};
- *             32 eddsaVerifyBase(msgs, offsets, sigs; curve = the base's curve, i0 = base) -> {ok, err};
- *             runs on a libuv worker
- *             thread (napi_async_work) so the JS thread is not blocked; resolves to the
- *             same value the synchronous form returns.  One call per context at a time:
- *             index.js serialises them.
- * Errors from the library are thrown as plain `Error(message)`, the
- * reference's convention (minimalistic-assert, dist/elliptic.js:8832-8835).
+ * Conventions:
+ *   - open(path) first; createContext(device | [devices]) -> the external every other call takes first;
+ *     destroyContext(ctx) releases it.  The context, curve-definition and base-table calls have a
+ *     comment each where they stand.
+ *   - Every batch operation is one row of the table ops[] (its signature stands on its row): operands
+ *     and results are flat Buffers of n fixed-width big-endian rows; an operand written `x|null` may
+ *     be null or undefined; counts (lens) are little-endian uint32, offsets little-endian uint64.
+ *   - A batch operation returns an object of result Buffers named as its row says (two return the
+ *     bare Buffer).  callAsync(op, ...) is its Promise form, op = ops.<name>.
+ *   - Errors -- a refused argument, or the library's own message -- are thrown as plain
+ *     `Error(message)`, the reference's convention (minimalistic-assert, dist/elliptic.js:8832-8835);
+ *     a Promise-form call that fails in the library rejects with that Error.
+ *   - One call per context at a time: index.js serialises the Promise forms.
  */
 #include <dlfcn.h>
 #include <node_api.h>
@@ -415,18 +345,13 @@ static napi_status result_buffer(napi_env env, size_t size, void** data, napi_va
   return st;
 }
 
-static napi_value mk_result(napi_env env, const char* k1, napi_value a, const char* k2, napi_value b) {
-  napi_value o; CHECK(env, napi_create_object(env, &o));
-  CHECK(env, napi_set_named_property(env, o, k1, a));
-  CHECK(env, napi_set_named_property(env, o, k2, b));
-  return o;
-}
+static int curve_id_of(const char* name) { return L.curve_id(name); }
 static napi_value fn_curve_id(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
   size_t argc = 1; napi_value argv[1]; char name[64]; size_t len;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (napi_get_value_string_utf8(env, argv[0], name, sizeof name, &len) != napi_ok) THROW(env, "curveId(name)");
-  napi_value r; CHECK(env, napi_create_int32(env, L.curve_id(name), &r)); return r;
+  napi_value r; CHECK(env, napi_create_int32(env, curve_id_of(name), &r)); return r;
 }
 static napi_value int_fn(napi_env env, napi_callback_info info, int which) {
   if (!need_lib(env)) return NULL;
@@ -602,507 +527,77 @@ static napi_value fn_base_info(napi_env env, napi_callback_info info) {
   CHECK(env, napi_create_double(env, (double)bytes, &v)); CHECK(env, napi_set_named_property(env, o, "tableBytes", v));
   return o;
 }
-static napi_value mul_base_with(napi_env env, napi_callback_info info, int two) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 5; napi_value argv[5];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (two ? 5u : 3u)) THROW(env, two ? "mulBase2(ctx, base1, base2, k1, k2)" : "mulBase(ctx, base, k)");
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t b1, b2 = 0;
-  if (napi_get_value_int32(env, argv[1], &b1) != napi_ok || (two && napi_get_value_int32(env, argv[2], &b2) != napi_ok))
-    THROW(env, "base handle expected");
-  int curve = -1;
-  if (L.base_info(c, b1, &curve, NULL, NULL) != 0) return lib_error(env);
-  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
-  const uint8_t *k1, *k2 = NULL; size_t l1, l2 = 0;
-  if (!get_buf(env, argv[two ? 3 : 2], &k1, &l1, 0)) return NULL;
-  if (two && !get_buf(env, argv[4], &k2, &l2, 0)) return NULL;
-  if (l1 % (size_t)B || (two && l2 != l1)) THROW(env, "buffer length mismatch");
-  size_t n = l1 / (size_t)B;
-  napi_value bxy, binf; void *dxy, *dinf;
-  CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
-  CHECK(env, result_buffer(env, n, &dinf, &binf));
-  int rc = two ? L.mul_base2(c, b1, b2, n, k1, k2, (uint8_t*)dxy, (uint8_t*)dinf, 0, NULL)
-               : L.mul_base(c, b1, n, k1, (uint8_t*)dxy, (uint8_t*)dinf, 0, NULL);
-  if (rc != 0) return lib_error(env);
-  return mk_result(env, "xy", bxy, "inf", binf);
-}
-static napi_value fn_mul_base(napi_env e, napi_callback_info i) { return mul_base_with(e, i, 0); }
-static napi_value fn_mul_base2(napi_env e, napi_callback_info i) { return mul_base_with(e, i, 1); }
-/* ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s) -> {ok}: EC#verify against the table of
- * the key a handle stands for (ellgpu_ecdsa_verify_base); r and s rows in the width of the base's curve */
-static napi_value fn_verify_base(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 7; napi_value argv[7];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 7) THROW(env, "ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s)");
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t base, hl, mb;
-  if (napi_get_value_int32(env, argv[1], &base) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &mb) != napi_ok)
-    THROW(env, "ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s)");
-  int curve = -1;
-  if (L.base_info(c, base, &curve, NULL, NULL) != 0) return lib_error(env);
-  int NB = L.order_bytes(curve); if (NB <= 0) THROW(env, "unknown curve id");
-  const uint8_t *h, *r, *s; size_t lh, lr, ls;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &r, &lr, 0) || !get_buf(env, argv[6], &s, &ls, 0)) return NULL;
-  if (hl <= 0 || lh % (size_t)hl) THROW(env, "buffer length mismatch");
-  size_t n = lh / (size_t)hl;
-  if (lr != n * (size_t)NB || ls != lr) THROW(env, "buffer length mismatch");
-  napi_value bok, o; void* dok;
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  if (L.ecdsa_verify_base(c, base, n, h, hl, mb, r, s, (uint8_t*)dok, 0, NULL) != 0) return lib_error(env);
-  CHECK(env, napi_create_object(env, &o));
-  CHECK(env, napi_set_named_property(env, o, "ok", bok));
-  return o;
-}
+/* ---- batch operations: one descriptor each ---------------------------------------------
+ * An operation is stated once: a row of ops[] below -- its names, the argument list of its
+ * synchronous export, its result properties -- with a `shape` (item count and result lengths from
+ * the operands, or the refusal) and a `call` (the one place that names its C ABI entry).  The
+ * synchronous exports are one callback, op_sync, which gets the row through napi_create_function's
+ * data pointer; callAsync(op, ...) looks the row up by id and runs the same shape and call, the
+ * call on a worker thread. */
+typedef struct op_desc op_desc;
+typedef struct {
+  const op_desc* d;
+  ellgpu_ctx* ctx;
+  int curve, B, NB;            /* the curve id, its coordinate and scalar widths in bytes */
+  int hl, mb, i0, i1;          /* hashLen, msgBits and the operation's two integers */
+  int promise;                 /* 1 in callAsync: the few places where the two forms differ ask */
+  const uint8_t* in[4]; size_t len[4];
+  size_t n, ol[4];             /* set by shape: the item count, the result lengths */
+  uint8_t* out[4];
+} op_call;
+enum {
+  F_OWN_OUT = 1,      /* the synchronous form takes trailing (xy, inf) result Buffers of the caller's */
+  F_BARE = 2,         /* the synchronous form returns its one Buffer, not an object */
+  F_BASE_CURVE = 4,   /* the synchronous form has no curve argument: the curve is the base handle's (i0) */
+  F_X25519 = 8,       /* callAsync ignores its curve argument: curve25519 */
+  F_WIDE_ENC = 16,    /* result rows at the curve's own width: written through rows of ECDH_ENC_MAX bytes */
+  F_ECDH = 32,        /* reachable through customEcdh(ctx, op, ...) */
+  F_BY_OP = 64,       /* customEcdh itself: the row is chosen by its op argument */
+  F_NONCES = 128,     /* a signing call with supplied nonces (operand 2) */
+  F_WIRE = 256,       /* a derive call whose peer keys are encodings of i0 bytes */
+};
+struct op_desc {
+  const char* name;               /* key of addon.ops and, where `args` is set, the synchronous export */
+  int id;                         /* callAsync's op; -1: no Promise form */
+  const char* args;               /* the synchronous export's arguments after ctx, one letter each:
+                                   *   c curve  h hashLen  m msgBits  i, j the integers i0, i1  b a boolean into i0
+                                   *   k, l base handles into i0, i1  o customEcdh's op  0..3 the operand Buffers
+                                   * a '?' after a letter: null / undefined allowed (Buffers), or read leniently
+                                   * (a value of another type leaves 0).  NULL: no export of its own. */
+  const char* names[5];           /* the result properties, in output order */
+  const char* (*shape)(op_call*); /* NULL, or the refusal's message */
+  int (*call)(const op_call*);
+  int flags;
+  int min_argc;                   /* fewer arguments than this throw `usage` */
+  const char* usage;              /* thrown too for an integer argument that is none, unless `badint` is set */
+  const char* badint;
+};
 
-/* mulFixed / mulVar / mulAdd2 share the output shape */
-static napi_value mul_common(napi_env env, napi_callback_info info, int kind) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 8; napi_value argv[8];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve; if (napi_get_value_int32(env, argv[1], &curve) != napi_ok) THROW(env, "curve id expected");
-  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
-  const uint8_t *k1 = 0, *p1 = 0, *k2 = 0, *p2 = 0; size_t l1 = 0, lp1 = 0, l2 = 0, lp2 = 0;
-  if (!get_buf(env, argv[2], &k1, &l1, 0)) return NULL;
-  if (l1 % (size_t)B) THROW(env, "scalar buffer length is not a multiple of the field width");
-  size_t n = l1 / (size_t)B;
-  if (kind == 1) { if (!get_buf(env, argv[3], &p1, &lp1, 0)) return NULL; if (lp1 != n * 2 * (size_t)B) THROW(env, "point buffer length mismatch"); }
-  if (kind == 2) {
-    if (!get_buf(env, argv[3], &p1, &lp1, 1)) return NULL;
-    if (!get_buf(env, argv[4], &k2, &l2, 0)) return NULL;
-    if (!get_buf(env, argv[5], &p2, &lp2, 0)) return NULL;
-    if ((p1 && lp1 != n * 2 * (size_t)B) || l2 != l1 || lp2 != n * 2 * (size_t)B) THROW(env, "buffer length mismatch");
-  }
-  napi_value bxy, binf; void *dxy, *dinf;
-  /* optional trailing (xy, inf) result Buffers supplied by the caller */
-  size_t oi = kind == 0 ? 3 : kind == 1 ? 4 : 6;
-  bool own = false;
-  if (argc >= oi + 2) {
-    bool is0 = false, is1 = false;
-    napi_is_buffer(env, argv[oi], &is0); napi_is_buffer(env, argv[oi + 1], &is1);
-    own = is0 && is1;
-  }
-  if (own) {
-    size_t lx, li;
-    CHECK(env, napi_get_buffer_info(env, argv[oi], &dxy, &lx));
-    CHECK(env, napi_get_buffer_info(env, argv[oi + 1], &dinf, &li));
-    if (lx != n * 2 * (size_t)B || li != n) THROW(env, "result buffer length mismatch");
-    bxy = argv[oi]; binf = argv[oi + 1];
-  } else {
-    CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
-    CHECK(env, result_buffer(env, n, &dinf, &binf));
-  }
-  int rc = kind == 0 ? L.mul_fixed(c, curve, n, k1, (uint8_t*)dxy, (uint8_t*)dinf)
-         : kind == 1 ? L.mul_var(c, curve, n, k1, p1, (uint8_t*)dxy, (uint8_t*)dinf)
-                     : L.mul_add2(c, curve, n, k1, p1, k2, p2, (uint8_t*)dxy, (uint8_t*)dinf);
-  if (rc != 0) return lib_error(env);
-  return mk_result(env, "xy", bxy, "inf", binf);
+#define MISMATCH "buffer length mismatch"
+#define XY(c) ((c)->n * 2 * (size_t)(c)->B)
+static const char* outs(op_call* c, size_t l0, size_t l1, size_t l2, size_t l3) {
+  c->ol[0] = l0; c->ol[1] = l1; c->ol[2] = l2; c->ol[3] = l3;
+  return NULL;
 }
-static napi_value fn_mul_fixed(napi_env e, napi_callback_info i) { return mul_common(e, i, 0); }
-static napi_value fn_mul_var(napi_env e, napi_callback_info i) { return mul_common(e, i, 1); }
-static napi_value fn_mul_add2(napi_env e, napi_callback_info i) { return mul_common(e, i, 2); }
-
-static napi_value verify_with(napi_env env, napi_callback_info info, int ed) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 8; napi_value argv[8];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, hl, mb;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &mb) != napi_ok) THROW(env, "ecdsaVerify(ctx, curve, hash, hashLen, msgBits, r, s, pub)");
-  int B = L.field_bytes(curve), NB = L.order_bytes(curve);
-  if (B <= 0 || hl <= 0) THROW(env, "bad curve / hashLen");
-  const uint8_t *h, *r, *s, *q; size_t lh, lr, ls, lq;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &r, &lr, 0) ||
-      !get_buf(env, argv[6], &s, &ls, 0) || !get_buf(env, argv[7], &q, &lq, 0)) return NULL;
-  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
-  size_t n = lh / (size_t)hl;
-  if (lr != n * (size_t)NB || ls != n * (size_t)NB || lq != n * 2 * (size_t)B) THROW(env, "buffer length mismatch");
-  napi_value bok, bst; void *dok, *dst;
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  CHECK(env, result_buffer(env, n, &dst, &bst));
-  if ((ed ? L.custom_ed_verify : L.ecdsa_verify)(c, curve, n, h, hl, mb, r, s, q, (uint8_t*)dok, (uint8_t*)dst) != 0) return lib_error(env);
-  return mk_result(env, "ok", bok, "status", bst);
+/* n from operand 0: hashes of hashLen bytes (hashLen > 0 is the caller's check) */
+static const char* per_hash(op_call* c) {
+  if (!c->in[0] || c->len[0] % (size_t)c->hl) return "hash buffer length is not a multiple of hashLen";
+  c->n = c->len[0] / (size_t)c->hl;
+  return NULL;
 }
-static napi_value fn_verify(napi_env env, napi_callback_info info) { return verify_with(env, info, 0); }
-/* customEdVerify(ctx, curve, hash, hashLen, msgBits, r, s, pub) -> {ok, status} (ellgpu_custom_ed_verify) */
-static napi_value fn_custom_ed_verify(napi_env env, napi_callback_info info) { return verify_with(env, info, 1); }
-static napi_value fn_x25519(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 3; napi_value argv[3];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  const uint8_t *k, *x; size_t lk, lx;
-  if (!get_buf(env, argv[1], &k, &lk, 0) || !get_buf(env, argv[2], &x, &lx, 0)) return NULL;
-  if (lk % 32 || lx != lk) THROW(env, "buffer length mismatch");
-  size_t n = lk / 32;
-  napi_value bx, binf; void *dx, *dinf;
-  CHECK(env, result_buffer(env, n * 32, &dx, &bx));
-  CHECK(env, result_buffer(env, n, &dinf, &binf));
-  if (L.x25519(c, n, k, x, (uint8_t*)dx, (uint8_t*)dinf) != 0) return lib_error(env);
-  return mk_result(env, "x", bx, "inf", binf);
+/* n from operand 0: scalars of B bytes */
+static const char* per_scalar(op_call* c) {
+  if (c->B <= 0) return "unknown curve id";
+  if (!c->in[0] || c->len[0] % (size_t)c->B) return "scalar buffer length is not a multiple of the field width";
+  c->n = c->len[0] / (size_t)c->B;
+  return NULL;
 }
-
-/* x25519Derive(ctx, k, x) -> {x, status}: KeyPair#derive on curve25519 (ellgpu_x25519_derive) */
-static napi_value fn_x25519_derive(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 3; napi_value argv[3];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  const uint8_t *k, *x; size_t lk, lx;
-  if (!get_buf(env, argv[1], &k, &lk, 0) || !get_buf(env, argv[2], &x, &lx, 0)) return NULL;
-  if (lk % 32 || lx != lk) THROW(env, "buffer length mismatch");
-  size_t n = lk / 32;
-  napi_value bx, bst; void *dx, *dst;
-  CHECK(env, result_buffer(env, n * 32, &dx, &bx));
-  CHECK(env, result_buffer(env, n, &dst, &bst));
-  if (L.x25519_derive(c, n, k, x, (uint8_t*)dx, (uint8_t*)dst) != 0) return lib_error(env);
-  return mk_result(env, "x", bx, "status", bst);
+/* n from operand 0: points of 2 * w bytes */
+static const char* per_point(op_call* c, size_t w, const char* msg) {
+  if (!c->in[0] || c->len[0] % (2 * w)) return msg;
+  c->n = c->len[0] / (2 * w);
+  return NULL;
 }
-
-/* decompress / customDecompress: the preset form reports ok (1 = point), the user-defined-curve
- * form a status (0 = point) */
-static napi_value decompress_with(napi_env env, napi_callback_info info, int custom) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 4; napi_value argv[4];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve; if (napi_get_value_int32(env, argv[1], &curve) != napi_ok) THROW(env, "curve id expected");
-  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
-  const uint8_t *v, *odd; size_t lv, lo;
-  if (!get_buf(env, argv[2], &v, &lv, 0) || !get_buf(env, argv[3], &odd, &lo, 0)) return NULL;
-  if (lv % (size_t)B || lo != lv / (size_t)B) THROW(env, "buffer length mismatch");
-  size_t n = lo;
-  napi_value bxy, bok; void *dxy, *dok;
-  CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  if ((custom ? L.custom_decompress : L.decompress)(c, curve, n, v, odd, (uint8_t*)dxy, (uint8_t*)dok) != 0)
-    return lib_error(env);
-  return mk_result(env, "xy", bxy, custom ? "status" : "ok", bok);
-}
-static napi_value fn_decompress(napi_env env, napi_callback_info info) { return decompress_with(env, info, 0); }
-static napi_value fn_custom_decompress(napi_env env, napi_callback_info info) { return decompress_with(env, info, 1); }
-
-static napi_value fn_sign(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 8; napi_value argv[8];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, hl, mb; bool canon = 0;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &mb) != napi_ok) THROW(env, "ecdsaSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical)");
-  napi_get_value_bool(env, argv[7], &canon);
-  int NB = L.order_bytes(curve);
-  if (NB <= 0 || hl <= 0) THROW(env, "bad curve / hashLen");
-  const uint8_t *h, *d, *k; size_t lh, ld, lk;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &d, &ld, 0) || !get_buf(env, argv[6], &k, &lk, 0)) return NULL;
-  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
-  size_t n = lh / (size_t)hl;
-  if (ld != n * (size_t)NB || lk != ld) THROW(env, "buffer length mismatch");
-  napi_value br, bs, brec, bok, o; void *dr, *dsg, *drec, *dok;
-  CHECK(env, result_buffer(env, n * (size_t)NB, &dr, &br));
-  CHECK(env, result_buffer(env, n * (size_t)NB, &dsg, &bs));
-  CHECK(env, result_buffer(env, n, &drec, &brec));
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  if (L.ecdsa_sign(c, curve, n, h, hl, mb, d, k, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg, (uint8_t*)drec, (uint8_t*)dok) != 0)
-    return lib_error(env);
-  CHECK(env, napi_create_object(env, &o));
-  CHECK(env, napi_set_named_property(env, o, "r", br));
-  CHECK(env, napi_set_named_property(env, o, "s", bs));
-  CHECK(env, napi_set_named_property(env, o, "recid", brec));
-  CHECK(env, napi_set_named_property(env, o, "ok", bok));
-  return o;
-}
-
-/* ecdsaSignDet(ctx, curve, hash, hashLen, msgBits, priv, canonical) -> {r, s, recid, ok} */
-static napi_value fn_sign_det(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 7; napi_value argv[7];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, hl, mb; bool canon = 0;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &mb) != napi_ok) THROW(env, "ecdsaSignDet(ctx, curve, hash, hashLen, msgBits, priv, canonical)");
-  napi_get_value_bool(env, argv[6], &canon);
-  int NB = L.order_bytes(curve);
-  if (NB <= 0 || hl <= 0) THROW(env, "bad curve / hashLen");
-  const uint8_t *h, *d; size_t lh, ld;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &d, &ld, 0)) return NULL;
-  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
-  size_t n = lh / (size_t)hl;
-  if (ld != n * (size_t)NB) THROW(env, "buffer length mismatch");
-  napi_value br, bs, brec, bok, o; void *dr, *dsg, *drec, *dok;
-  CHECK(env, result_buffer(env, n * (size_t)NB, &dr, &br));
-  CHECK(env, result_buffer(env, n * (size_t)NB, &dsg, &bs));
-  CHECK(env, result_buffer(env, n, &drec, &brec));
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  if (L.ecdsa_sign_det(c, curve, n, h, hl, mb, d, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg, (uint8_t*)drec, (uint8_t*)dok) != 0)
-    return lib_error(env);
-  CHECK(env, napi_create_object(env, &o));
-  CHECK(env, napi_set_named_property(env, o, "r", br));
-  CHECK(env, napi_set_named_property(env, o, "s", bs));
-  CHECK(env, napi_set_named_property(env, o, "recid", brec));
-  CHECK(env, napi_set_named_property(env, o, "ok", bok));
-  return o;
-}
-
-/* customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) and
- * customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) -> {r, s, recid, ok} */
-static napi_value custom_sign_with(napi_env env, napi_callback_info info, int det, int ed) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 8; napi_value argv[8];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, hl, mb, dh = 0; bool canon = 0;
-  if (argc < 8 || napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &mb) != napi_ok || (det && napi_get_value_int32(env, argv[6], &dh) != napi_ok))
-    THROW(env, det ? "customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical)"
-                   : "customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical)");
-  napi_get_value_bool(env, argv[7], &canon);
-  if (hl <= 0) THROW(env, "bad hashLen");
-  const uint8_t *h, *d, *k = NULL; size_t lh, ld, lk = 0;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &d, &ld, 0)) return NULL;
-  if (!det && !get_buf(env, argv[6], &k, &lk, 0)) return NULL;
-  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
-  size_t n = lh / (size_t)hl;
-  if (ld != n * 32 || (!det && lk != ld)) THROW(env, "buffer length mismatch");
-  napi_value br, bs, brec, bok, o; void *dr, *dsg, *drec, *dok;
-  CHECK(env, result_buffer(env, n * 32, &dr, &br));
-  CHECK(env, result_buffer(env, n * 32, &dsg, &bs));
-  CHECK(env, result_buffer(env, n, &drec, &brec));
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  int rc = det ? (ed ? L.custom_ed_sign_det : L.custom_sign_det)(c, curve, n, h, hl, mb, d, dh, canon ? 1 : 0, (uint8_t*)dr,
-                                                                 (uint8_t*)dsg, (uint8_t*)drec, (uint8_t*)dok)
-               : (ed ? L.custom_ed_sign : L.custom_sign)(c, curve, n, h, hl, mb, d, k, canon ? 1 : 0, (uint8_t*)dr, (uint8_t*)dsg,
-                                                         (uint8_t*)drec, (uint8_t*)dok);
-  if (rc != 0) return lib_error(env);
-  CHECK(env, napi_create_object(env, &o));
-  CHECK(env, napi_set_named_property(env, o, "r", br));
-  CHECK(env, napi_set_named_property(env, o, "s", bs));
-  CHECK(env, napi_set_named_property(env, o, "recid", brec));
-  CHECK(env, napi_set_named_property(env, o, "ok", bok));
-  return o;
-}
-static napi_value fn_custom_sign(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 0, 0); }
-static napi_value fn_custom_sign_det(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 1, 0); }
-/* customEdSign / customEdSignDet: the same argument lists on a user-defined Edwards domain (ellgpu_custom_ed_sign / _sign_det) */
-static napi_value fn_custom_ed_sign(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 0, 1); }
-static napi_value fn_custom_ed_sign_det(napi_env env, napi_callback_info info) { return custom_sign_with(env, info, 1, 1); }
-
-/* ecdsaRecover / customRecover(ctx, curve, hash, hashLen, r, s, recid) -> {xy: Buffer(n*2B), status: Buffer(n)} */
-static napi_value recover_with(napi_env env, napi_callback_info info, int custom) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 7; napi_value argv[7];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, hl;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok)
-    THROW(env, "ecdsaRecover(ctx, curve, hash, hashLen, r, s, recid)");
-  int B = L.field_bytes(curve), NB = L.order_bytes(curve);
-  if (B <= 0 || NB <= 0 || hl <= 0) THROW(env, "bad curve / hashLen");
-  const uint8_t *h, *r, *sg, *j; size_t lh, lr, ls, lj;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[4], &r, &lr, 0) ||
-      !get_buf(env, argv[5], &sg, &ls, 0) || !get_buf(env, argv[6], &j, &lj, 0)) return NULL;
-  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
-  size_t n = lh / (size_t)hl;
-  if (lr != n * (size_t)NB || ls != lr || lj != n) THROW(env, "buffer length mismatch");
-  napi_value bxy, bst; void *dxy, *dst;
-  CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
-  CHECK(env, result_buffer(env, n, &dst, &bst));
-  if ((custom ? L.custom_recover : L.ecdsa_recover)(c, curve, n, h, hl, r, sg, j, (uint8_t*)dxy, (uint8_t*)dst) != 0)
-    return lib_error(env);
-  return mk_result(env, "xy", bxy, "status", bst);
-}
-static napi_value fn_recover(napi_env env, napi_callback_info info) { return recover_with(env, info, 0); }
-static napi_value fn_custom_recover(napi_env env, napi_callback_info info) { return recover_with(env, info, 1); }
-
-static napi_value decode_points_with(napi_env env, napi_callback_info info, int custom) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 4; napi_value argv[4];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, el;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &el) != napi_ok)
-    THROW(env, "decodePoints(ctx, curve, enc, encLen)");
-  int B = L.field_bytes(curve); if (B <= 0 || el <= 0) THROW(env, "bad curve / encLen");
-  const uint8_t* enc; size_t le;
-  if (!get_buf(env, argv[2], &enc, &le, 0)) return NULL;
-  if (le % (size_t)el) THROW(env, "enc buffer length is not a multiple of encLen");
-  size_t n = le / (size_t)el;
-  napi_value bxy, bst; void *dxy, *dst;
-  CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
-  CHECK(env, result_buffer(env, n, &dst, &bst));
-  if ((custom ? L.custom_decode_points : L.decode_points)(c, curve, n, enc, (size_t)el, (uint8_t*)dxy,
-                                                          (uint8_t*)dst) != 0) return lib_error(env);
-  return mk_result(env, "xy", bxy, "status", bst);
-}
-static napi_value fn_decode_points(napi_env env, napi_callback_info info) { return decode_points_with(env, info, 0); }
-static napi_value fn_custom_decode_points(napi_env env, napi_callback_info info) { return decode_points_with(env, info, 1); }
-
-static napi_value fn_encode_points(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 4; napi_value argv[4];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve; bool compact = 0;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_bool(env, argv[3], &compact) != napi_ok)
-    THROW(env, "encodePoints(ctx, curve, xy, compact)");
-  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
-  const uint8_t* xy; size_t lx;
-  if (!get_buf(env, argv[2], &xy, &lx, 0)) return NULL;
-  if (lx % (2 * (size_t)B)) THROW(env, "xy buffer length is not a multiple of 2 * fieldBytes");
-  size_t n = lx / (2 * (size_t)B);
-  /* the library's rule for the encoded length: SEC1 for the short curves, 32 bytes for ed25519 */
-  size_t el = compact ? 1 + (size_t)B : 1 + 2 * (size_t)B;
-  if (L.curve_id("ed25519") == curve) el = 32;
-  napi_value be; void* de;
-  CHECK(env, result_buffer(env, n * el, &de, &be));
-  if (L.encode_points(c, curve, n, xy, compact ? 1 : 0, (uint8_t*)de) != 0) return lib_error(env);
-  return be;
-}
-
-static napi_value fn_validate(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 5; napi_value argv[5];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve; bool order = 1;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_bool(env, argv[4], &order) != napi_ok)
-    THROW(env, "validate(ctx, curve, xy, inf|null, checkOrder)");
-  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
-  const uint8_t *xy, *inf; size_t lx, li;
-  if (!get_buf(env, argv[2], &xy, &lx, 0) || !get_buf(env, argv[3], &inf, &li, 1)) return NULL;
-  if (lx % (2 * (size_t)B)) THROW(env, "xy buffer length is not a multiple of 2 * fieldBytes");
-  size_t n = lx / (2 * (size_t)B);
-  if (inf && li != n) THROW(env, "buffer length mismatch");
-  napi_value bst; void* dst;
-  CHECK(env, result_buffer(env, n, &dst, &bst));
-  if (L.validate(c, curve, n, xy, inf, order ? 1 : 0, (uint8_t*)dst) != 0) return lib_error(env);
-  return bst;
-}
-
-static napi_value fn_point_add(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 6; napi_value argv[6];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok) THROW(env, "pointAdd(ctx, curve, xy1, inf1|null, xy2, inf2|null)");
-  int B = L.field_bytes(curve); if (B <= 0) THROW(env, "unknown curve id");
-  const uint8_t *p1, *i1, *p2, *i2; size_t l1, li1, l2, li2;
-  if (!get_buf(env, argv[2], &p1, &l1, 0) || !get_buf(env, argv[3], &i1, &li1, 1) ||
-      !get_buf(env, argv[4], &p2, &l2, 0) || !get_buf(env, argv[5], &i2, &li2, 1)) return NULL;
-  if (l1 % (2 * (size_t)B) || l2 != l1) THROW(env, "buffer length mismatch");
-  size_t n = l1 / (2 * (size_t)B);
-  if ((i1 && li1 != n) || (i2 && li2 != n)) THROW(env, "buffer length mismatch");
-  napi_value bxy, binf; void *dxy, *dinf;
-  CHECK(env, result_buffer(env, n * 2 * (size_t)B, &dxy, &bxy));
-  CHECK(env, result_buffer(env, n, &dinf, &binf));
-  if (L.point_add(c, curve, n, p1, i1, p2, i2, (uint8_t*)dxy, (uint8_t*)dinf) != 0) return lib_error(env);
-  return mk_result(env, "xy", bxy, "inf", binf);
-}
-
-static napi_value fn_sig_from_der(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 5; napi_value argv[5];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, stride;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &stride) != napi_ok)
-    THROW(env, "sigFromDer(ctx, curve, der, stride, lens)");
-  int NB = L.order_bytes(curve); if (NB <= 0 || stride <= 0) THROW(env, "bad curve / stride");
-  const uint8_t *der, *lens; size_t ld, ll;
-  if (!get_buf(env, argv[2], &der, &ld, 0) || !get_buf(env, argv[4], &lens, &ll, 0)) return NULL;
-  if (ll % 4 || ((uintptr_t)lens & 3)) THROW(env, "lens must be an aligned Buffer of uint32");
-  size_t n = ll / 4;
-  if (ld != n * (size_t)stride) THROW(env, "buffer length mismatch");
-  napi_value br, bs, bst, o; void *dr, *ds, *dst;
-  CHECK(env, result_buffer(env, n * (size_t)NB, &dr, &br));
-  CHECK(env, result_buffer(env, n * (size_t)NB, &ds, &bs));
-  CHECK(env, result_buffer(env, n, &dst, &bst));
-  if (L.sig_from_der(c, curve, n, der, (size_t)stride, (const uint32_t*)lens, (uint8_t*)dr, (uint8_t*)ds,
-                     (uint8_t*)dst) != 0) return lib_error(env);
-  o = mk_result(env, "r", br, "s", bs); if (!o) return NULL;
-  CHECK(env, napi_set_named_property(env, o, "status", bst));
-  return o;
-}
-
-static napi_value fn_sig_to_der(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 4; napi_value argv[4];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok) THROW(env, "sigToDer(ctx, curve, r, s)");
-  int NB = L.order_bytes(curve); if (NB <= 0) THROW(env, "unknown curve id");
-  const uint8_t *r, *s; size_t lr, ls;
-  if (!get_buf(env, argv[2], &r, &lr, 0) || !get_buf(env, argv[3], &s, &ls, 0)) return NULL;
-  if (lr % (size_t)NB || ls != lr) THROW(env, "buffer length mismatch");
-  size_t n = lr / (size_t)NB, stride = 2 * (size_t)NB + 9;
-  napi_value bd, bl; void *dd, *dl;
-  CHECK(env, result_buffer(env, n * stride, &dd, &bd));
-  CHECK(env, result_buffer(env, n * 4, &dl, &bl));
-  if (L.sig_to_der(c, curve, n, r, s, (uint8_t*)dd, stride, (uint32_t*)dl) != 0) return lib_error(env);
-  return mk_result(env, "der", bd, "lens", bl);
-}
-
-static napi_value verify_wire_with(napi_env env, napi_callback_info info, int custom) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 10; napi_value argv[10];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t curve, hl, mb, stride, kl;
-  if (napi_get_value_int32(env, argv[1], &curve) != napi_ok || napi_get_value_int32(env, argv[3], &hl) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &mb) != napi_ok || napi_get_value_int32(env, argv[6], &stride) != napi_ok ||
-      napi_get_value_int32(env, argv[9], &kl) != napi_ok)
-    THROW(env, "ecdsaVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)");
-  if (hl <= 0 || stride <= 0 || kl <= 0) THROW(env, "bad hashLen / stride / keyLen");
-  const uint8_t *h, *der, *lens, *keys; size_t lh, ld, ll, lk;
-  if (!get_buf(env, argv[2], &h, &lh, 0) || !get_buf(env, argv[5], &der, &ld, 0) ||
-      !get_buf(env, argv[7], &lens, &ll, 0) || !get_buf(env, argv[8], &keys, &lk, 0)) return NULL;
-  if (lh % (size_t)hl) THROW(env, "hash buffer length is not a multiple of hashLen");
-  size_t n = lh / (size_t)hl;
-  if (ll != n * 4 || ((uintptr_t)lens & 3)) THROW(env, "lens must be an aligned Buffer of n uint32");
-  if (ld != n * (size_t)stride || lk != n * (size_t)kl) THROW(env, "buffer length mismatch");
-  napi_value bok, berr; void *dok, *derr;
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  CHECK(env, result_buffer(env, n, &derr, &berr));
-  if ((custom ? L.custom_verify_wire : L.verify_wire)(c, curve, n, h, hl, mb, der, (size_t)stride,
-                                                      (const uint32_t*)lens, keys, (size_t)kl, (uint8_t*)dok,
-                                                      (uint8_t*)derr) != 0) return lib_error(env);
-  return mk_result(env, "ok", bok, "err", berr);
-}
-static napi_value fn_verify_wire(napi_env env, napi_callback_info info) { return verify_wire_with(env, info, 0); }
-static napi_value fn_custom_verify_wire(napi_env env, napi_callback_info info) { return verify_wire_with(env, info, 1); }
-
-static napi_value fn_eddsa_verify(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 6; napi_value argv[6];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  const uint8_t *m, *off, *sg, *pk; size_t lm, loff, lsg, lpk; int32_t mlen = 0;
-  if (!get_buf(env, argv[1], &m, &lm, 1) || !get_buf(env, argv[2], &off, &loff, 1) ||
-      !get_buf(env, argv[4], &sg, &lsg, 0) || !get_buf(env, argv[5], &pk, &lpk, 0)) return NULL;
-  napi_get_value_int32(env, argv[3], &mlen);
-  if (lsg % 64 || lpk != lsg / 2) THROW(env, "buffer length mismatch");
-  size_t n = lsg / 64;
-  if (off) {
-    if (loff != (n + 1) * 8 || ((uintptr_t)off & 7)) THROW(env, "offsets must be an aligned Buffer of n+1 uint64");
-    if (((const uint64_t*)off)[n] > lm) THROW(env, "offsets exceed the message buffer");
-    for (size_t i = 0; i < n; i++)        /* the kernels take len = off[i+1] - off[i]: must not wrap */
-      if (((const uint64_t*)off)[i] > ((const uint64_t*)off)[i + 1]) THROW(env, "offsets must be non-decreasing");
-  } else if ((size_t)mlen * n > lm) THROW(env, "message buffer too short");
-  napi_value bok, berr; void *dok, *derr;
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  CHECK(env, result_buffer(env, n, &derr, &berr));
-  if (L.eddsa_verify(c, n, m, (const uint64_t*)off, (size_t)mlen, sg, pk, (uint8_t*)dok, (uint8_t*)derr) != 0)
-    return lib_error(env);
-  return mk_result(env, "ok", bok, "err", berr);
-}
-
 /* offsets of n messages in a buffer of lm bytes: an aligned Buffer of n + 1 non-decreasing uint64 (NULL if fine) */
 static const char* bad_offsets(const uint8_t* off, size_t loff, size_t n, size_t lm) {
   if (loff != (n + 1) * 8 || ((uintptr_t)off & 7)) return "offsets must be an aligned Buffer of n+1 uint64";
@@ -1111,190 +606,495 @@ static const char* bad_offsets(const uint8_t* off, size_t loff, size_t n, size_t
     if (((const uint64_t*)off)[i] > ((const uint64_t*)off)[i + 1]) return "offsets must be non-decreasing";
   return NULL;
 }
-/* eddsaVerifyBase(ctx, base, msgs, offsets|null, msgLen, sigs) -> {ok, err}: EDDSA#verify against the table
- * of the key a handle stands for (ellgpu_eddsa_verify_base) */
-static napi_value fn_eddsa_verify_base(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 6; napi_value argv[6];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 6) THROW(env, "eddsaVerifyBase(ctx, base, msgs, offsets, msgLen, sigs)");
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t base, mlen = 0;
-  if (napi_get_value_int32(env, argv[1], &base) != napi_ok) THROW(env, "eddsaVerifyBase(ctx, base, msgs, offsets, msgLen, sigs)");
-  const uint8_t *m, *off, *sg; size_t lm, loff, lsg;
-  if (!get_buf(env, argv[2], &m, &lm, 1) || !get_buf(env, argv[3], &off, &loff, 1) || !get_buf(env, argv[5], &sg, &lsg, 0)) return NULL;
-  napi_get_value_int32(env, argv[4], &mlen);
-  if (lsg % 64) THROW(env, "buffer length mismatch");
-  size_t n = lsg / 64;
-  if (off) {
-    const char* bad = bad_offsets(off, loff, n, lm);
-    if (bad) THROW(env, bad);
-  } else if (mlen < 0 || (size_t)mlen * n > lm) THROW(env, "message buffer too short");
-  napi_value bok, berr; void *dok, *derr;
-  CHECK(env, result_buffer(env, n, &dok, &bok));
-  CHECK(env, result_buffer(env, n, &derr, &berr));
-  if (L.eddsa_verify_base(c, base, n, m, (const uint64_t*)off, (size_t)mlen, sg, (uint8_t*)dok, (uint8_t*)derr, 0, NULL) != 0)
-    return lib_error(env);
-  return mk_result(env, "ok", bok, "err", berr);
+/* the n messages of an EdDSA call: operand 0 cut by the offsets in operand 1, or into rows of i1 bytes */
+static const char* messages(const op_call* c) {
+  if (c->in[1]) return bad_offsets(c->in[1], c->len[1], c->n, c->len[0]);
+  return (size_t)c->i1 * c->n > c->len[0] ? "message buffer too short" : NULL;
 }
 
-/* eddsaSign(ctx, msgs, offsets|null, msgLen, secrets) -> {sig: Buffer(n*64), pub: Buffer(n*32)} */
-static napi_value fn_eddsa_sign(napi_env env, napi_callback_info info) {
-  if (!need_lib(env)) return NULL;
-  size_t argc = 5; napi_value argv[5];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  const uint8_t *m, *off, *sec; size_t lm, loff, lsec; int32_t mlen = 0;
-  if (!get_buf(env, argv[1], &m, &lm, 1) || !get_buf(env, argv[2], &off, &loff, 1) ||
-      !get_buf(env, argv[4], &sec, &lsec, 0)) return NULL;
-  napi_get_value_int32(env, argv[3], &mlen);
-  if (lsec % 32) THROW(env, "secrets must be n x 32 bytes");
-  size_t n = lsec / 32;
-  if (off) {
-    if (loff != (n + 1) * 8 || ((uintptr_t)off & 7)) THROW(env, "offsets must be an aligned Buffer of n+1 uint64");
-    if (((const uint64_t*)off)[n] > lm) THROW(env, "offsets exceed the message buffer");
-    for (size_t i = 0; i < n; i++)        /* the kernels take len = off[i+1] - off[i]: must not wrap */
-      if (((const uint64_t*)off)[i] > ((const uint64_t*)off)[i + 1]) THROW(env, "offsets must be non-decreasing");
-  } else if ((size_t)mlen * n > lm) THROW(env, "message buffer too short");
-  napi_value bsig, bpub; void *dsig, *dpub;
-  CHECK(env, result_buffer(env, n * 64, &dsig, &bsig));
-  CHECK(env, result_buffer(env, n * 32, &dpub, &bpub));
-  if (L.eddsa_sign(c, n, sec, m, (const uint64_t*)off, (size_t)mlen, (uint8_t*)dsig, (uint8_t*)dpub) != 0)
-    return lib_error(env);
-  return mk_result(env, "sig", bsig, "pub", bpub);
+static const char* shape_mul_fixed(op_call* c) {
+  const char* bad = per_scalar(c);
+  return bad ? bad : outs(c, XY(c), c->n, 0, 0);
 }
-
-/* ---- the key side on user-defined short curves: KeyPair#derive / #validate, BasePoint#encode ----
- * ops 13 derive(priv, pubXY)  14 deriveWire(priv, enc; i0 = key length)  15 validate(xy, inf or
- * null; i0 = checkOrder)  16 encodePoints(xy; i0 = compact, i1 = p.byteLength()).  Scalars and
- * coordinates are 32 bytes.  ecdh_shape: the item count and the result lengths from the input
- * lengths (0 = mismatch); ecdh_call: the C ABI call.  Shared by customEcdh and callAsync.
- * The library writes encodePoints' rows at the CURVE's width, which this addon cannot ask it for
+static const char* shape_mul_var(op_call* c) {
+  const char* bad = per_scalar(c); if (bad) return bad;
+  if (!c->in[1] || c->len[1] != XY(c)) return "point buffer length mismatch";
+  return outs(c, XY(c), c->n, 0, 0);
+}
+static const char* shape_mul_add2(op_call* c) {
+  const char* bad = per_scalar(c); if (bad) return bad;
+  if ((c->in[1] && c->len[1] != XY(c)) || !c->in[2] || c->len[2] != c->len[0] || !c->in[3] || c->len[3] != XY(c)) return MISMATCH;
+  return outs(c, XY(c), c->n, 0, 0);
+}
+static const char* shape_mul_base(op_call* c) {
+  if (c->B <= 0) return "unknown curve id";
+  if (!c->in[0] || c->len[0] % (size_t)c->B) return MISMATCH;
+  c->n = c->len[0] / (size_t)c->B;
+  return outs(c, XY(c), c->n, 0, 0);
+}
+static const char* shape_mul_base2(op_call* c) {
+  const char* bad = shape_mul_base(c); if (bad) return bad;
+  return c->in[1] && c->len[1] == c->len[0] ? NULL : MISMATCH;
+}
+static const char* shape_verify(op_call* c) {
+  if (c->B <= 0 || c->hl <= 0) return "bad curve / hashLen";
+  const char* bad = per_hash(c); if (bad) return bad;
+  if (!c->in[1] || !c->in[2] || !c->in[3] || c->len[1] != c->n * (size_t)c->NB || c->len[2] != c->len[1] || c->len[3] != XY(c))
+    return MISMATCH;
+  return outs(c, c->n, c->n, 0, 0);
+}
+static const char* shape_verify_base(op_call* c) {
+  if (c->NB <= 0) return "unknown curve id";
+  if (c->hl <= 0 || per_hash(c)) return MISMATCH;
+  if (!c->in[1] || !c->in[2] || c->in[3] || c->len[1] != c->n * (size_t)c->NB || c->len[2] != c->len[1]) return MISMATCH;
+  return outs(c, c->n, 0, 0, 0);
+}
+static const char* shape_x25519(op_call* c) {
+  if (!c->in[0] || !c->in[1] || c->len[0] % 32 || c->len[1] != c->len[0]) return MISMATCH;
+  c->n = c->len[0] / 32;
+  return outs(c, c->n * 32, c->n, 0, 0);
+}
+static const char* shape_decompress(op_call* c) {
+  if (c->B <= 0) return "unknown curve id";
+  if (!c->in[0] || !c->in[1] || c->len[0] % (size_t)c->B || c->len[1] != c->len[0] / (size_t)c->B) return MISMATCH;
+  c->n = c->len[1];
+  return outs(c, XY(c), c->n, 0, 0);
+}
+/* private keys (and, with F_NONCES, nonces) of w bytes per hash -> r, s, recid, ok */
+static const char* sign_rows(op_call* c, size_t w) {
+  const char* bad = per_hash(c); if (bad) return bad;
+  if (!c->in[1] || c->len[1] != c->n * w) return MISMATCH;
+  if ((c->d->flags & F_NONCES) && (!c->in[2] || c->len[2] != c->len[1])) return MISMATCH;
+  return outs(c, c->n * w, c->n * w, c->n, c->n);
+}
+static const char* shape_sign(op_call* c) {
+  if (c->NB <= 0 || c->hl <= 0) return "bad curve / hashLen";
+  return sign_rows(c, (size_t)c->NB);
+}
+static const char* shape_custom_sign(op_call* c) {      /* 32-byte rows; callAsync asks the library for the width */
+  if (c->hl <= 0) return "bad hashLen";
+  return sign_rows(c, c->promise ? (size_t)c->NB : 32);
+}
+static const char* shape_recover(op_call* c) {
+  if (c->B <= 0 || c->NB <= 0 || c->hl <= 0) return "bad curve / hashLen";
+  const char* bad = per_hash(c); if (bad) return bad;
+  if (!c->in[1] || !c->in[2] || !c->in[3] || c->len[1] != c->n * (size_t)c->NB || c->len[2] != c->len[1] || c->len[3] != c->n)
+    return MISMATCH;
+  return outs(c, XY(c), c->n, 0, 0);
+}
+static const char* shape_decode(op_call* c) {
+  if (c->B <= 0 || c->i0 <= 0) return "bad curve / encLen";
+  if (!c->in[0] || c->len[0] % (size_t)c->i0) return "enc buffer length is not a multiple of encLen";
+  c->n = c->len[0] / (size_t)c->i0;
+  return outs(c, XY(c), c->n, 0, 0);
+}
+static const char* shape_encode(op_call* c) {
+  if (c->B <= 0) return "unknown curve id";
+  const char* bad = per_point(c, (size_t)c->B, "xy buffer length is not a multiple of 2 * fieldBytes"); if (bad) return bad;
+  /* the library's rule for the encoded length: SEC1 for the short curves, 32 bytes for ed25519 */
+  size_t el = 1 + (c->i0 ? 1 : 2) * (size_t)c->B;
+  if (curve_id_of("ed25519") == c->curve) el = 32;
+  return outs(c, c->n * el, 0, 0, 0);
+}
+static const char* shape_validate(op_call* c) {
+  if (c->B <= 0) return "unknown curve id";
+  const char* bad = per_point(c, (size_t)c->B, "xy buffer length is not a multiple of 2 * fieldBytes"); if (bad) return bad;
+  if (c->in[1] && c->len[1] != c->n) return MISMATCH;
+  return outs(c, c->n, 0, 0, 0);
+}
+static const char* shape_point_add(op_call* c) {
+  if (c->B <= 0) return "unknown curve id";
+  if (per_point(c, (size_t)c->B, MISMATCH) || !c->in[2] || c->len[2] != c->len[0]) return MISMATCH;
+  if ((c->in[1] && c->len[1] != c->n) || (c->in[3] && c->len[3] != c->n)) return MISMATCH;
+  return outs(c, XY(c), c->n, 0, 0);
+}
+static const char* shape_sig_from_der(op_call* c) {
+  if (c->NB <= 0 || c->i0 <= 0) return "bad curve / stride";
+  if (!c->in[1] || c->len[1] % 4 || ((uintptr_t)c->in[1] & 3)) return "lens must be an aligned Buffer of uint32";
+  c->n = c->len[1] / 4;
+  if (!c->in[0] || c->len[0] != c->n * (size_t)c->i0) return MISMATCH;
+  return outs(c, c->n * (size_t)c->NB, c->n * (size_t)c->NB, c->n, 0);
+}
+static const char* shape_sig_to_der(op_call* c) {
+  if (c->NB <= 0) return "unknown curve id";
+  if (!c->in[0] || !c->in[1] || c->len[0] % (size_t)c->NB || c->len[1] != c->len[0]) return MISMATCH;
+  c->n = c->len[0] / (size_t)c->NB;
+  return outs(c, c->n * (2 * (size_t)c->NB + 9), c->n * 4, 0, 0);
+}
+static const char* shape_verify_wire(op_call* c) {
+  if (c->hl <= 0 || c->i0 <= 0 || c->i1 <= 0) return "bad hashLen / stride / keyLen";
+  const char* bad = per_hash(c); if (bad) return bad;
+  if (!c->in[2] || c->len[2] != c->n * 4 || ((uintptr_t)c->in[2] & 3)) return "lens must be an aligned Buffer of n uint32";
+  if (!c->in[1] || !c->in[3] || c->len[1] != c->n * (size_t)c->i0 || c->len[3] != c->n * (size_t)c->i1) return MISMATCH;
+  return outs(c, c->n, c->n, 0, 0);
+}
+static const char* shape_eddsa_verify(op_call* c) {
+  if (!c->in[2] || !c->in[3] || c->len[2] % 64 || c->len[3] != c->len[2] / 2) return MISMATCH;
+  c->n = c->len[2] / 64;
+  const char* bad = messages(c);
+  return bad ? bad : outs(c, c->n, c->n, 0, 0);
+}
+static const char* shape_eddsa_sign(op_call* c) {
+  if (!c->in[2] || c->len[2] % 32) return "secrets must be n x 32 bytes";
+  c->n = c->len[2] / 32;
+  const char* bad = messages(c);
+  return bad ? bad : outs(c, c->n * 64, c->n * 32, 0, 0);
+}
+static const char* shape_eddsa_verify_base(op_call* c) {
+  if (!c->in[2] || c->in[3] || c->len[2] % 64 || (c->promise && !c->in[1])) return MISMATCH;
+  c->n = c->len[2] / 64;
+  if (!c->in[1] && c->i1 < 0) return "message buffer too short";
+  const char* bad = messages(c);
+  return bad ? bad : outs(c, c->n, c->n, 0, 0);
+}
+/* The key side on user-defined short, Montgomery and Edwards curves (reached synchronously through
+ * customEcdh): scalars and coordinates are 32 bytes. */
+static const char* shape_derive(op_call* c) {
+  const int wire = c->d->flags & F_WIRE;
+  if (!c->in[0] || !c->in[1] || c->len[0] % 32 || (wire && c->i0 <= 0)) return MISMATCH;
+  c->n = c->len[0] / 32;
+  if (c->len[1] != c->n * (wire ? (size_t)c->i0 : 64)) return MISMATCH;
+  return outs(c, c->n * 32, c->n, wire ? c->n : 0, 0);
+}
+static const char* shape_custom_validate(op_call* c) {
+  if (per_point(c, 32, MISMATCH) || (c->in[1] && c->len[1] != c->n)) return MISMATCH;
+  return outs(c, c->n, 0, 0, 0);
+}
+static const char* shape_ed_validate(op_call* c) {      /* operand 1: the order, 32 bytes, or null */
+  if (per_point(c, 32, MISMATCH) || (c->in[1] && c->len[1] != 32)) return MISMATCH;
+  return outs(c, c->n, 0, 0, 0);
+}
+/* The library writes the encoders' rows at the CURVE's width, which this addon cannot ask it for
  * (index.js records it when the curve is defined and refuses another): so the call never gets the
  * caller-sized result buffer.  It writes into n rows of ECDH_ENC_MAX bytes -- the widest a curve
- * below 2^256 has -- and the result is cut from those: a wrong i1 gives wrong bytes, never a write
- * past the end. */
+ * below 2^256 has -- and the result is cut from those (F_WIDE_ENC): a wrong i1 gives wrong bytes,
+ * never a write past the end. */
 #define ECDH_ENC_MAX 65
-/* 17 montLadder(k, x)  18 montValidate(x)  19 montDerive(priv, x): 32-byte rows.
- * The key side of a user-defined Edwards curve (ellgpu_custom_ed_*): 20 edDecompress(v, odd; i0 = fromY)
- * 21 edDecodePoints(enc; i0 = row length)  22 edValidate(xy, order: 32 bytes or null)  23 edDerive(priv, pubXY)
- * 24 edDeriveWire(priv, enc; i0 = key length)  25 edEncodePoints(xy; i0 = compact, i1 = p.byteLength(); as 16) */
-#define ECDH_OP_LAST 25
-#define ED_OP_VERIFY 26          /* ECDSA on a user-defined Edwards domain: verify (as op 3), sign (as 11), sign_det (as 12) */
-#define ED_OP_SIGN 27
-#define ED_OP_SIGN_DET 28
-#define OP_MUL_BASE 29           /* mulBase(k; curve = the base's curve, i0 = base)  mulBase2(k1, k2; i0, i1 = the bases) */
-#define OP_MUL_BASE2 30
-#define OP_VERIFY_BASE 31        /* ecdsaVerifyBase(hashes, r, s; curve = the base's curve, i0 = base) -> {ok} */
-#define OP_EDDSA_VERIFY_BASE 32  /* eddsaVerifyBase(msgs, offsets, sigs; curve = the base's curve, i0 = base) -> {ok, err} */
-#define OP_LAST 32
-#define ECDH_ENC_OP(op) ((op) == 16 || (op) == 25)
-static const char* const ECDH_NAMES[13][3] = {{"x", "status", 0}, {"x", "status", "err"}, {"status", 0, 0}, {"enc", 0, 0},
-                                              {"x", "inf", 0}, {"status", 0, 0}, {"x", "status", 0},
-                                              {"xy", "status", 0}, {"xy", "status", 0}, {"status", 0, 0}, {"x", "status", 0},
-                                              {"x", "status", "err"}, {"enc", 0, 0}};
-static int ecdh_shape(int op, const uint8_t* const in[2], const size_t len[2], int i0, int i1, size_t* n, size_t out[3]) {
-  out[0] = out[1] = out[2] = 0;
-  if (!in[0]) return 0;
-  if (op == 13 || op == 14 || op == 23 || op == 24) {
-    const int wire = op == 14 || op == 24;
-    if (!in[1] || len[0] % 32 || (wire && i0 <= 0)) return 0;
-    *n = len[0] / 32;
-    if (len[1] != *n * (wire ? (size_t)i0 : 64)) return 0;
-    out[0] = *n * 32; out[1] = *n; out[2] = wire ? *n : 0;
-  } else if (op == 15 || op == 16 || op == 22 || op == 25) {
-    if (len[0] % 64) return 0;
-    *n = len[0] / 64;
-    if (op == 15) { if (in[1] && len[1] != *n) return 0; out[0] = *n; }
-    else if (op == 22) { if (in[1] && len[1] != 32) return 0; out[0] = *n; }
-    else { if (i1 <= 0 || i1 > 32) return 0; out[0] = *n * (1 + (i0 ? 1 : 2) * (size_t)i1); }
-  } else if (op == 20) {
-    if (!in[1] || len[0] % 32) return 0;
-    *n = len[0] / 32;
-    if (len[1] != *n) return 0;
-    out[0] = *n * 64; out[1] = *n;
-  } else if (op == 21) {
-    if (in[1] || i0 <= 0 || len[0] % (size_t)i0) return 0;
-    *n = len[0] / (size_t)i0;
-    out[0] = *n * 64; out[1] = *n;
-  } else if (op == 17 || op == 18 || op == 19) {
-    if (len[0] % 32) return 0;
-    *n = len[0] / 32;
-    if (op == 18) { if (in[1]) return 0; out[0] = *n; }
-    else { if (!in[1] || len[1] != len[0]) return 0; out[0] = *n * 32; out[1] = *n; }
-  } else return 0;
-  return 1;
+static const char* shape_custom_encode(op_call* c) {
+  /* the row width is the curve's: not a caller's choice to get wrong silently */
+  if (c->i1 <= 0 || c->i1 > 32) return "customEncodePoints: coordBytes must be 1..32";
+  if (per_point(c, 32, MISMATCH)) return MISMATCH;
+  return outs(c, c->n * (1 + (c->i0 ? 1 : 2) * (size_t)c->i1), 0, 0, 0);
 }
-static int ecdh_call(int op, ellgpu_ctx* c, int curve, size_t n, const uint8_t* const in[2], int i0, uint8_t* const out[3]) {
-  switch (op) {
-    case 13: return L.custom_derive(c, curve, n, in[0], in[1], out[0], out[1]);
-    case 14: return L.custom_derive_wire(c, curve, n, in[0], in[1], (size_t)i0, out[0], out[1], out[2]);
-    case 15: return L.custom_validate(c, curve, n, in[0], in[1], i0, out[0]);
-    case 17: return L.custom_mont_ladder(c, curve, n, in[0], in[1], out[0], out[1]);
-    case 18: return L.custom_mont_validate(c, curve, n, in[0], out[0]);
-    case 19: return L.custom_mont_derive(c, curve, n, in[0], in[1], out[0], out[1]);
-    case 20: return L.custom_ed_decompress(c, curve, n, in[0], in[1], i0, out[0], out[1]);
-    case 21: return L.custom_ed_decode_points(c, curve, n, in[0], (size_t)i0, out[0], out[1]);
-    case 22: return L.custom_ed_validate(c, curve, n, in[0], in[1], out[0]);
-    case 23: return L.custom_ed_derive(c, curve, n, in[0], in[1], out[0], out[1]);
-    case 24: return L.custom_ed_derive_wire(c, curve, n, in[0], in[1], (size_t)i0, out[0], out[1], out[2]);
-    case 25: return L.custom_ed_encode_points(c, curve, n, in[0], i0, out[0]);
-    default: return L.custom_encode_points(c, curve, n, in[0], i0, out[0]);
-  }
+static const char* shape_ed_decompress(op_call* c) {
+  if (!c->in[0] || !c->in[1] || c->len[0] % 32 || c->len[1] != c->len[0] / 32) return MISMATCH;
+  c->n = c->len[1];
+  return outs(c, c->n * 64, c->n, 0, 0);
 }
-/* customEcdh(ctx, op, curve, b0, b1, i0, i1) -> the op's result object */
-static napi_value fn_custom_ecdh(napi_env env, napi_callback_info info) {
+static const char* shape_ed_decode(op_call* c) {
+  if (!c->in[0] || c->in[1] || c->i0 <= 0 || c->len[0] % (size_t)c->i0) return MISMATCH;
+  c->n = c->len[0] / (size_t)c->i0;
+  return outs(c, c->n * 64, c->n, 0, 0);
+}
+static const char* shape_mont_pair(op_call* c) {
+  if (!c->in[0] || !c->in[1] || c->len[0] % 32 || c->len[1] != c->len[0]) return MISMATCH;
+  c->n = c->len[0] / 32;
+  return outs(c, c->n * 32, c->n, 0, 0);
+}
+static const char* shape_mont_validate(op_call* c) {
+  if (!c->in[0] || c->in[1] || c->len[0] % 32) return MISMATCH;
+  c->n = c->len[0] / 32;
+  return outs(c, c->n, 0, 0, 0);
+}
+
+static int call_mul_fixed(const op_call* c) { return L.mul_fixed(c->ctx, c->curve, c->n, c->in[0], c->out[0], c->out[1]); }
+static int call_mul_var(const op_call* c) { return L.mul_var(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_mul_add2(const op_call* c) {
+  return L.mul_add2(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_mul_base(const op_call* c) { return L.mul_base(c->ctx, c->i0, c->n, c->in[0], c->out[0], c->out[1], 0, NULL); }
+static int call_mul_base2(const op_call* c) {
+  return L.mul_base2(c->ctx, c->i0, c->i1, c->n, c->in[0], c->in[1], c->out[0], c->out[1], 0, NULL);
+}
+static int call_verify(const op_call* c) {
+  return L.ecdsa_verify(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_custom_ed_verify(const op_call* c) {
+  return L.custom_ed_verify(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_verify_base(const op_call* c) {
+  return L.ecdsa_verify_base(c->ctx, c->i0, c->n, c->in[0], c->hl, c->mb, c->in[1], c->in[2], c->out[0], 0, NULL);
+}
+static int call_x25519(const op_call* c) { return L.x25519(c->ctx, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_x25519_derive(const op_call* c) { return L.x25519_derive(c->ctx, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_decompress(const op_call* c) { return L.decompress(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_custom_decompress(const op_call* c) {
+  return L.custom_decompress(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]);
+}
+static int call_sign(const op_call* c) {
+  return L.ecdsa_sign(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->in[2], c->i0, c->out[0], c->out[1], c->out[2], c->out[3]);
+}
+static int call_sign_det(const op_call* c) {
+  return L.ecdsa_sign_det(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->i0, c->out[0], c->out[1], c->out[2], c->out[3]);
+}
+static int call_custom_sign(const op_call* c) {
+  return L.custom_sign(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->in[2], c->i0, c->out[0], c->out[1], c->out[2], c->out[3]);
+}
+static int call_custom_sign_det(const op_call* c) {
+  return L.custom_sign_det(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->i1, c->i0, c->out[0], c->out[1], c->out[2], c->out[3]);
+}
+static int call_custom_ed_sign(const op_call* c) {
+  return L.custom_ed_sign(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->in[2], c->i0, c->out[0], c->out[1], c->out[2], c->out[3]);
+}
+static int call_custom_ed_sign_det(const op_call* c) {
+  return L.custom_ed_sign_det(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], c->i1, c->i0, c->out[0], c->out[1], c->out[2], c->out[3]);
+}
+static int call_recover(const op_call* c) {
+  return L.ecdsa_recover(c->ctx, c->curve, c->n, c->in[0], c->hl, c->in[1], c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_custom_recover(const op_call* c) {
+  return L.custom_recover(c->ctx, c->curve, c->n, c->in[0], c->hl, c->in[1], c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_decode_points(const op_call* c) { return L.decode_points(c->ctx, c->curve, c->n, c->in[0], (size_t)c->i0, c->out[0], c->out[1]); }
+static int call_custom_decode_points(const op_call* c) {
+  return L.custom_decode_points(c->ctx, c->curve, c->n, c->in[0], (size_t)c->i0, c->out[0], c->out[1]);
+}
+static int call_encode_points(const op_call* c) { return L.encode_points(c->ctx, c->curve, c->n, c->in[0], c->i0, c->out[0]); }
+static int call_validate(const op_call* c) { return L.validate(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->i0, c->out[0]); }
+static int call_point_add(const op_call* c) {
+  return L.point_add(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_sig_from_der(const op_call* c) {
+  return L.sig_from_der(c->ctx, c->curve, c->n, c->in[0], (size_t)c->i0, (const uint32_t*)c->in[1], c->out[0], c->out[1], c->out[2]);
+}
+static int call_sig_to_der(const op_call* c) {
+  return L.sig_to_der(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], 2 * (size_t)c->NB + 9, (uint32_t*)c->out[1]);
+}
+static int call_verify_wire(const op_call* c) {
+  return L.verify_wire(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], (size_t)c->i0, (const uint32_t*)c->in[2], c->in[3],
+                       (size_t)c->i1, c->out[0], c->out[1]);
+}
+static int call_custom_verify_wire(const op_call* c) {
+  return L.custom_verify_wire(c->ctx, c->curve, c->n, c->in[0], c->hl, c->mb, c->in[1], (size_t)c->i0, (const uint32_t*)c->in[2],
+                              c->in[3], (size_t)c->i1, c->out[0], c->out[1]);
+}
+static int call_eddsa_verify(const op_call* c) {
+  return L.eddsa_verify(c->ctx, c->n, c->in[0], (const uint64_t*)c->in[1], (size_t)c->i1, c->in[2], c->in[3], c->out[0], c->out[1]);
+}
+static int call_eddsa_sign(const op_call* c) {
+  return L.eddsa_sign(c->ctx, c->n, c->in[2], c->in[0], (const uint64_t*)c->in[1], (size_t)c->i1, c->out[0], c->out[1]);
+}
+static int call_eddsa_verify_base(const op_call* c) {
+  return L.eddsa_verify_base(c->ctx, c->i0, c->n, c->in[0], (const uint64_t*)c->in[1], (size_t)c->i1, c->in[2], c->out[0], c->out[1], 0, NULL);
+}
+static int call_custom_derive(const op_call* c) { return L.custom_derive(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_custom_derive_wire(const op_call* c) {
+  return L.custom_derive_wire(c->ctx, c->curve, c->n, c->in[0], c->in[1], (size_t)c->i0, c->out[0], c->out[1], c->out[2]);
+}
+static int call_custom_validate(const op_call* c) { return L.custom_validate(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->i0, c->out[0]); }
+static int call_custom_encode_points(const op_call* c) { return L.custom_encode_points(c->ctx, c->curve, c->n, c->in[0], c->i0, c->out[0]); }
+static int call_custom_mont_ladder(const op_call* c) { return L.custom_mont_ladder(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_custom_mont_validate(const op_call* c) { return L.custom_mont_validate(c->ctx, c->curve, c->n, c->in[0], c->out[0]); }
+static int call_custom_mont_derive(const op_call* c) { return L.custom_mont_derive(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_custom_ed_decompress(const op_call* c) {
+  return L.custom_ed_decompress(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->i0, c->out[0], c->out[1]);
+}
+static int call_custom_ed_decode_points(const op_call* c) {
+  return L.custom_ed_decode_points(c->ctx, c->curve, c->n, c->in[0], (size_t)c->i0, c->out[0], c->out[1]);
+}
+static int call_custom_ed_validate(const op_call* c) { return L.custom_ed_validate(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0]); }
+static int call_custom_ed_derive(const op_call* c) { return L.custom_ed_derive(c->ctx, c->curve, c->n, c->in[0], c->in[1], c->out[0], c->out[1]); }
+static int call_custom_ed_derive_wire(const op_call* c) {
+  return L.custom_ed_derive_wire(c->ctx, c->curve, c->n, c->in[0], c->in[1], (size_t)c->i0, c->out[0], c->out[1], c->out[2]);
+}
+static int call_custom_ed_encode_points(const op_call* c) { return L.custom_ed_encode_points(c->ctx, c->curve, c->n, c->in[0], c->i0, c->out[0]); }
+
+/* The table.  Above each row: the synchronous export and, after `|`, callAsync's operands
+ * (b0..b3; i0, i1) where the operation has a Promise form; then the result.
+ * Where the two forms differ (tests/golden/addon_forms.json pins each):
+ *   - only mulFixed / mulVar / mulAdd2 take caller-supplied result Buffers, and only synchronously;
+ *   - synchronous mulBase, mulBase2 and ecdsaVerifyBase take the curve from ellgpu_base_info (and
+ *     eddsaVerifyBase takes none); callAsync uses the curve argument index.js passes;
+ *   - callAsync x25519 forces curve 7;
+ *   - a refusal of the operands is thrown with its own message synchronously, and as the one
+ *     `callAsync: buffer length mismatch` by callAsync;
+ *   - callAsync eddsaVerifyBase needs the offsets; the synchronous form takes null and msgLen;
+ *   - customSign / customSignDet / customEdSign / customEdSignDet rows are 32 bytes synchronously and
+ *     the width ellgpu_curve_order_bytes reports in callAsync (32 on every id they accept);
+ *   - encodePoints and validate return a bare Buffer. */
+#define VERIFY_USAGE "ecdsaVerify(ctx, curve, hash, hashLen, msgBits, r, s, pub)"
+#define RECOVER_USAGE "ecdsaRecover(ctx, curve, hash, hashLen, r, s, recid)"
+#define WIRE_USAGE "ecdsaVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen)"
+#define CUSTOM_SIGN_USAGE "customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical)"
+#define CUSTOM_SIGN_DET_USAGE "customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical)"
+static const op_desc ops[] = {
+  /* mulFixed(ctx, curve, k[, xy, inf]) | k -> {xy, inf} */
+  {"mulFixed", 0, "c0", {"xy", "inf"}, shape_mul_fixed, call_mul_fixed, F_OWN_OUT, 0, "curve id expected", 0},
+  /* mulVar(ctx, curve, k, xy[, xy, inf]) | k, xy -> {xy, inf} */
+  {"mulVar", 1, "c01", {"xy", "inf"}, shape_mul_var, call_mul_var, F_OWN_OUT, 0, "curve id expected", 0},
+  /* mulAdd2(ctx, curve, k1, p1|null, k2, p2[, xy, inf]) | k1, p1|null, k2, p2 -> {xy, inf}; p1 null: the generator */
+  {"mulAdd2", 2, "c01?23", {"xy", "inf"}, shape_mul_add2, call_mul_add2, F_OWN_OUT, 0, "curve id expected", 0},
+  /* ecdsaVerify(ctx, curve, hash, hashLen, msgBits, r, s, pub) | hash, r, s, pub -> {ok, status} */
+  {"ecdsaVerify", 3, "c0hm123", {"ok", "status"}, shape_verify, call_verify, 0, 0, VERIFY_USAGE, 0},
+  /* x25519(ctx, k, x) | k, x -> {x, inf} */
+  {"x25519", 4, "01", {"x", "inf"}, shape_x25519, call_x25519, F_X25519, 0, 0, 0},
+  /* x25519Derive(ctx, k, x) -> {x, status}: KeyPair#derive on curve25519, validate + ladder in one call */
+  {"x25519Derive", -1, "01", {"x", "status"}, shape_x25519, call_x25519_derive, 0, 0, 0, 0},
+  /* ecdsaSignDet(ctx, curve, hash, hashLen, msgBits, priv, canonical) | hash, priv; i0 = canonical -> {r, s, recid, ok} */
+  {"ecdsaSignDet", 5, "c0hm1b?", {"r", "s", "recid", "ok"}, shape_sign, call_sign_det, 0, 0,
+   "ecdsaSignDet(ctx, curve, hash, hashLen, msgBits, priv, canonical)", 0},
+  /* ecdsaSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) -> {r, s, recid, ok} */
+  {"ecdsaSign", -1, "c0hm12b?", {"r", "s", "recid", "ok"}, shape_sign, call_sign, F_NONCES, 0,
+   "ecdsaSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical)", 0},
+  /* ecdsaRecover(ctx, curve, hash, hashLen, r, s, recid) | hash, r, s, recid -> {xy, status} */
+  {"ecdsaRecover", 6, "c0h123", {"xy", "status"}, shape_recover, call_recover, 0, 0, RECOVER_USAGE, 0},
+  /* ecdsaVerifyWire(ctx, curve, hash, hashLen, msgBits, der, stride, lens, keys, keyLen) | hash, der, lens, keys;
+   * i0 = stride, i1 = keyLen -> {ok, err}; lens: n little-endian uint32 */
+  {"ecdsaVerifyWire", 7, "c0hm1i23j", {"ok", "err"}, shape_verify_wire, call_verify_wire, 0, 0, WIRE_USAGE, 0},
+  /* decodePoints(ctx, curve, enc, encLen) | enc; i0 = encLen -> {xy, status} */
+  {"decodePoints", 8, "c0i", {"xy", "status"}, shape_decode, call_decode_points, 0, 0, "decodePoints(ctx, curve, enc, encLen)", 0},
+  /* the same three, and decompress, on a user-defined short curve / domain (ellgpu_custom_*) */
+  {"customVerifyWire", 9, "c0hm1i23j", {"ok", "err"}, shape_verify_wire, call_custom_verify_wire, 0, 0, WIRE_USAGE, 0},
+  {"customRecover", 10, "c0h123", {"xy", "status"}, shape_recover, call_custom_recover, 0, 0, RECOVER_USAGE, 0},
+  {"customDecodePoints", -1, "c0i", {"xy", "status"}, shape_decode, call_custom_decode_points, 0, 0, "decodePoints(ctx, curve, enc, encLen)", 0},
+  /* decompress(ctx, curve, v, odd) -> {xy, ok} (ok 1 = point); customDecompress -> {xy, status} (status 0 = point) */
+  {"decompress", -1, "c01", {"xy", "ok"}, shape_decompress, call_decompress, 0, 0, "curve id expected", 0},
+  {"customDecompress", -1, "c01", {"xy", "status"}, shape_decompress, call_custom_decompress, 0, 0, "curve id expected", 0},
+  /* customSign(ctx, curve, hash, hashLen, msgBits, priv, nonces, canonical) | hash, priv, nonces; i0 = canonical
+   * customSignDet(ctx, curve, hash, hashLen, msgBits, priv, drbgHash, canonical) | hash, priv; i0 = canonical, i1 = drbgHash
+   * (0 sha256, 1 sha384, 2 sha512) -> {r, s, recid, ok}: EC#sign on a user-defined domain */
+  {"customSign", 11, "c0hm12b?", {"r", "s", "recid", "ok"}, shape_custom_sign, call_custom_sign, F_NONCES, 8, CUSTOM_SIGN_USAGE, 0},
+  {"customSignDet", 12, "c0hm1jb?", {"r", "s", "recid", "ok"}, shape_custom_sign, call_custom_sign_det, 0, 8, CUSTOM_SIGN_DET_USAGE, 0},
+  /* The key side on a user-defined short curve, synchronously through customEcdh:
+   * 13 customDerive | priv, pubXY -> {x, status}      14 customDeriveWire | priv, enc; i0 = key length -> {x, status, err}
+   * 15 customValidate | xy, inf|null; i0 = checkOrder -> {status}
+   * 16 customEncodePoints | xy; i0 = compact, i1 = p.byteLength() -> {enc} */
+  {"customDerive", 13, 0, {"x", "status"}, shape_derive, call_custom_derive, F_ECDH, 0, 0, 0},
+  {"customDeriveWire", 14, 0, {"x", "status", "err"}, shape_derive, call_custom_derive_wire, F_ECDH | F_WIRE, 0, 0, 0},
+  {"customValidate", 15, 0, {"status"}, shape_custom_validate, call_custom_validate, F_ECDH, 0, 0, 0},
+  {"customEncodePoints", 16, 0, {"enc"}, shape_custom_encode, call_custom_encode_points, F_ECDH | F_WIDE_ENC, 0, 0, 0},
+  /* on a user-defined Montgomery curve: 17 customMontLadder | k, x -> {x, inf}  18 customMontValidate | x -> {status}
+   * 19 customMontDerive | priv, x -> {x, status} */
+  {"customMontLadder", 17, 0, {"x", "inf"}, shape_mont_pair, call_custom_mont_ladder, F_ECDH, 0, 0, 0},
+  {"customMontValidate", 18, 0, {"status"}, shape_mont_validate, call_custom_mont_validate, F_ECDH, 0, 0, 0},
+  {"customMontDerive", 19, 0, {"x", "status"}, shape_mont_pair, call_custom_mont_derive, F_ECDH, 0, 0, 0},
+  /* on a user-defined Edwards curve: 20 customEdDecompress | v, odd; i0 = fromY -> {xy, status}
+   * 21 customEdDecodePoints | enc; i0 = row length -> {xy, status}  22 customEdValidate | xy, order|null -> {status}
+   * 23 customEdDerive, 24 customEdDeriveWire, 25 customEdEncodePoints: as 13, 14, 16 */
+  {"customEdDecompress", 20, 0, {"xy", "status"}, shape_ed_decompress, call_custom_ed_decompress, F_ECDH, 0, 0, 0},
+  {"customEdDecodePoints", 21, 0, {"xy", "status"}, shape_ed_decode, call_custom_ed_decode_points, F_ECDH, 0, 0, 0},
+  {"customEdValidate", 22, 0, {"status"}, shape_ed_validate, call_custom_ed_validate, F_ECDH, 0, 0, 0},
+  {"customEdDerive", 23, 0, {"x", "status"}, shape_derive, call_custom_ed_derive, F_ECDH, 0, 0, 0},
+  {"customEdDeriveWire", 24, 0, {"x", "status", "err"}, shape_derive, call_custom_ed_derive_wire, F_ECDH | F_WIRE, 0, 0, 0},
+  {"customEdEncodePoints", 25, 0, {"enc"}, shape_custom_encode, call_custom_ed_encode_points, F_ECDH | F_WIDE_ENC, 0, 0, 0},
+  /* customEcdh(ctx, op, curve, b0, b1|null, i0, i1) -> the result of op 13..25 */
+  {"customEcdh", -1, "oc01?ij", {0}, 0, 0, F_BY_OP, 7, "customEcdh(ctx, op, curve, b0, b1, i0, i1)", 0},
+  /* ECDSA on a user-defined Edwards domain: customEdVerify, customEdSign, customEdSignDet as ecdsaVerify, customSign, customSignDet */
+  {"customEdVerify", 26, "c0hm123", {"ok", "status"}, shape_verify, call_custom_ed_verify, 0, 0, VERIFY_USAGE, 0},
+  {"customEdSign", 27, "c0hm12b?", {"r", "s", "recid", "ok"}, shape_custom_sign, call_custom_ed_sign, F_NONCES, 8, CUSTOM_SIGN_USAGE, 0},
+  {"customEdSignDet", 28, "c0hm1jb?", {"r", "s", "recid", "ok"}, shape_custom_sign, call_custom_ed_sign_det, 0, 8, CUSTOM_SIGN_DET_USAGE, 0},
+  /* Fixed-base tables of caller-chosen points (handles of defineBase / defineEdBase); rows in the width of the base's curve.
+   * mulBase(ctx, base, k) | k; i0 = base      mulBase2(ctx, base1, base2, k1, k2) | k1, k2; i0, i1 = the bases -> {xy, inf} */
+  {"mulBase", 29, "k0", {"xy", "inf"}, shape_mul_base, call_mul_base, F_BASE_CURVE, 3, "mulBase(ctx, base, k)", "base handle expected"},
+  {"mulBase2", 30, "kl01", {"xy", "inf"}, shape_mul_base2, call_mul_base2, F_BASE_CURVE, 5, "mulBase2(ctx, base1, base2, k1, k2)",
+   "base handle expected"},
+  /* ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s) | hashes, r, s; i0 = base -> {ok}: EC#verify against the key's table */
+  {"ecdsaVerifyBase", 31, "k0hm12", {"ok"}, shape_verify_base, call_verify_base, F_BASE_CURVE, 7,
+   "ecdsaVerifyBase(ctx, base, hashes, hashLen, msgBits, r, s)", 0},
+  /* eddsaVerifyBase(ctx, base, msgs, offsets|null, msgLen, sigs) | msgs, offsets, sigs; i0 = base -> {ok, err}: EDDSA#verify against
+   * the table of a defineEdBase handle on ed25519; offsets: n + 1 little-endian uint64 byte offsets into msgs */
+  {"eddsaVerifyBase", 32, "i0?1?j?2", {"ok", "err"}, shape_eddsa_verify_base, call_eddsa_verify_base, 0, 6,
+   "eddsaVerifyBase(ctx, base, msgs, offsets, msgLen, sigs)", 0},
+  /* eddsaVerify(ctx, msgs, offsets|null, msgLen, sigs, pubs) -> {ok, err}      eddsaSign(ctx, msgs, offsets|null, msgLen, secrets)
+   * -> {sig: n x 64, pub: n x 32} */
+  {"eddsaVerify", -1, "0?1?j?23", {"ok", "err"}, shape_eddsa_verify, call_eddsa_verify, 0, 0, 0, 0},
+  {"eddsaSign", -1, "0?1?j?2", {"sig", "pub"}, shape_eddsa_sign, call_eddsa_sign, 0, 0, 0, 0},
+  /* encodePoints(ctx, curve, xy, compact) -> Buffer      validate(ctx, curve, xy, inf|null, checkOrder) -> Buffer (status bytes) */
+  {"encodePoints", -1, "c0b", {"enc"}, shape_encode, call_encode_points, F_BARE, 0, "encodePoints(ctx, curve, xy, compact)", 0},
+  {"validate", -1, "c01?b", {"status"}, shape_validate, call_validate, F_BARE, 0, "validate(ctx, curve, xy, inf|null, checkOrder)", 0},
+  /* pointAdd(ctx, curve, xy1, inf1|null, xy2, inf2|null) -> {xy, inf} */
+  {"pointAdd", -1, "c01?23?", {"xy", "inf"}, shape_point_add, call_point_add, 0, 0, "pointAdd(ctx, curve, xy1, inf1|null, xy2, inf2|null)", 0},
+  /* sigFromDer(ctx, curve, der, stride, lens) -> {r, s, status}      sigToDer(ctx, curve, r, s) -> {der, lens} (stride = der.length / n) */
+  {"sigFromDer", -1, "c0i1", {"r", "s", "status"}, shape_sig_from_der, call_sig_from_der, 0, 0, "sigFromDer(ctx, curve, der, stride, lens)", 0},
+  {"sigToDer", -1, "c01", {"der", "lens"}, shape_sig_to_der, call_sig_to_der, 0, 0, "sigToDer(ctx, curve, r, s)", 0},
+};
+#define N_OPS (sizeof ops / sizeof ops[0])
+static const op_desc* op_by_id(int id) {
+  for (size_t i = 0; id >= 0 && i < N_OPS; i++) if (ops[i].id == id) return &ops[i];
+  return NULL;
+}
+
+/* every synchronous export of the table: fetch the arguments, shape, allocate the results, call */
+static napi_value op_sync(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
-  size_t argc = 7; napi_value argv[7];
-  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 7) THROW(env, "customEcdh(ctx, op, curve, b0, b1, i0, i1)");
-  ellgpu_ctx* c = get_ctx(env, argv[0]); if (!c) return NULL;
-  int32_t op, curve, i0, i1;
-  if (napi_get_value_int32(env, argv[1], &op) != napi_ok || napi_get_value_int32(env, argv[2], &curve) != napi_ok ||
-      napi_get_value_int32(env, argv[5], &i0) != napi_ok || napi_get_value_int32(env, argv[6], &i1) != napi_ok)
-    THROW(env, "customEcdh(ctx, op, curve, b0, b1, i0, i1)");
-  const uint8_t* in[2]; size_t len[2], n = 0, ol[3];
-  if (!get_buf(env, argv[3], &in[0], &len[0], 0) || !get_buf(env, argv[4], &in[1], &len[1], 1)) return NULL;
-  if (ECDH_ENC_OP(op)) {                 /* the row width is the curve's: not a caller's choice to get wrong silently */
-    if (i1 <= 0 || i1 > 32) THROW(env, "customEncodePoints: coordBytes must be 1..32");
+  size_t argc = 12; napi_value argv[12]; void* data = NULL;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, &data));
+  const op_desc* d = (const op_desc*)data;
+  if (argc < (size_t)d->min_argc) THROW(env, d->usage);
+  op_call c; memset(&c, 0, sizeof c);
+  c.ctx = get_ctx(env, argv[0]); if (!c.ctx) return NULL;
+  int32_t op = -1; size_t a = 1;
+  for (const char* s = d->args; *s; s++, a++) {
+    const int lenient = s[1] == '?';
+    if (*s >= '0' && *s <= '3') {
+      if (!get_buf(env, argv[a], &c.in[*s - '0'], &c.len[*s - '0'], lenient)) return NULL;
+    } else {
+      int32_t v = 0; bool flag = 0;
+      if ((*s == 'b' ? napi_get_value_bool(env, argv[a], &flag) : napi_get_value_int32(env, argv[a], &v)) != napi_ok && !lenient)
+        THROW(env, d->badint ? d->badint : d->usage);
+      switch (*s) {
+        case 'c': c.curve = v; break;
+        case 'h': c.hl = v; break;
+        case 'm': c.mb = v; break;
+        case 'b': c.i0 = flag ? 1 : 0; break;
+        case 'i': case 'k': c.i0 = v; break;
+        case 'j': case 'l': c.i1 = v; break;
+        default: op = v; break;
+      }
+    }
+    if (lenient) s++;
   }
-  if (op < 13 || op > ECDH_OP_LAST) THROW(env, "customEcdh: bad op");
-  if (!ecdh_shape(op, in, len, i0, i1, &n, ol)) THROW(env, "buffer length mismatch");
-  napi_value b[3] = {NULL, NULL, NULL}; void* d[3] = {NULL, NULL, NULL};
-  for (int k = 0; k < 3 && ECDH_NAMES[op - 13][k]; k++) CHECK(env, result_buffer(env, ol[k], &d[k], &b[k]));
-  uint8_t* out[3] = {(uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2]};
+  if (d->flags & F_BY_OP) {
+    d = op_by_id(op);
+    if (!d || !(d->flags & F_ECDH)) THROW(env, "customEcdh: bad op");
+  }
+  if ((d->flags & F_BASE_CURVE) && L.base_info(c.ctx, c.i0, &c.curve, NULL, NULL) != 0) return lib_error(env);
+  c.d = d; c.B = L.field_bytes(c.curve); c.NB = L.order_bytes(c.curve);
+  const char* bad = d->shape(&c);
+  if (bad) THROW(env, bad);
+  napi_value b[4] = {NULL, NULL, NULL, NULL}; void* p[4] = {NULL, NULL, NULL, NULL};
+  bool own = false;              /* optional trailing (xy, inf) result Buffers supplied by the caller */
+  if ((d->flags & F_OWN_OUT) && argc >= a + 2) {
+    bool is0 = false, is1 = false;
+    napi_is_buffer(env, argv[a], &is0); napi_is_buffer(env, argv[a + 1], &is1);
+    own = is0 && is1;
+  }
+  if (own) {
+    size_t l[2];
+    for (int k = 0; k < 2; k++) { CHECK(env, napi_get_buffer_info(env, argv[a + k], &p[k], &l[k])); b[k] = argv[a + k]; }
+    if (l[0] != c.ol[0] || l[1] != c.ol[1]) THROW(env, "result buffer length mismatch");
+  } else {
+    for (int k = 0; k < 4 && d->names[k]; k++) CHECK(env, result_buffer(env, c.ol[k], &p[k], &b[k]));
+  }
+  for (int k = 0; k < 4; k++) c.out[k] = (uint8_t*)p[k];
   uint8_t* wide = NULL;
-  if (ECDH_ENC_OP(op)) {
-    wide = (uint8_t*)malloc(n * ECDH_ENC_MAX + 1);
+  if (d->flags & F_WIDE_ENC) {
+    wide = (uint8_t*)malloc(c.n * ECDH_ENC_MAX + 1);
     if (!wide) THROW(env, "customEcdh: out of memory");
-    out[0] = wide;
+    c.out[0] = wide;
   }
-  int rc = ecdh_call(op, c, curve, n, in, i0, out);
+  int rc = d->call(&c);
   if (wide) {
-    if (rc == 0) memcpy(d[0], wide, ol[0]);
+    if (rc == 0) memcpy(p[0], wide, c.ol[0]);
     free(wide);
   }
   if (rc != 0) return lib_error(env);
+  if (d->flags & F_BARE) return b[0];
   napi_value o; CHECK(env, napi_create_object(env, &o));
-  for (int k = 0; k < 3 && ECDH_NAMES[op - 13][k]; k++) CHECK(env, napi_set_named_property(env, o, ECDH_NAMES[op - 13][k], b[k]));
+  for (int k = 0; k < 4 && d->names[k]; k++) CHECK(env, napi_set_named_property(env, o, d->names[k], b[k]));
   return o;
 }
 
-/* ---- asynchronous form: napi_async_work + Promise ---------------------------------- */
+/* ---- asynchronous form: napi_async_work + Promise ----------------------------------
+ * callAsync(op, ctx, curve, hashLen, msgBits, b0, b1, b2, b3[, i0, i1]) -> Promise of what the synchronous
+ * form returns.  The call runs on a libuv worker thread, so the JS thread is not blocked.  One call per
+ * context at a time: index.js serialises them. */
 typedef struct {
   napi_async_work work;
   napi_deferred deferred;
   napi_ref refs[5];          /* four input Buffers + the context external */
   int nrefs;
-  int op, curve, hash_len, msg_bits, B, NB;
-  ellgpu_ctx* ctx;
-  const uint8_t* in[4];
-  size_t n;
-  uint8_t* out0; size_t out0_len;      /* xy / ok / x */
-  uint8_t* out1; size_t out1_len;      /* inf */
-  uint8_t* out2; size_t out2_len;      /* ops 5..: third / fourth result */
-  uint8_t* out3; size_t out3_len;
-  int i0, i1;                          /* op 5: canonical; op 7: der stride, key length; op 8: encoding length */
+  op_call c;
   int rc;
   char err[512];
 } async_job;
@@ -1302,75 +1102,31 @@ typedef struct {
 static void job_execute(napi_env env, void* data) {
   (void)env;
   async_job* j = (async_job*)data;
-  switch (j->op) {
-    case 0: j->rc = L.mul_fixed(j->ctx, j->curve, j->n, j->in[0], j->out0, j->out1); break;
-    case 1: j->rc = L.mul_var(j->ctx, j->curve, j->n, j->in[0], j->in[1], j->out0, j->out1); break;
-    case 2: j->rc = L.mul_add2(j->ctx, j->curve, j->n, j->in[0], j->in[1], j->in[2], j->in[3], j->out0, j->out1); break;
-    case 3: j->rc = L.ecdsa_verify(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2], j->in[3], j->out0, j->out1); break;
-    case 4: j->rc = L.x25519(j->ctx, j->n, j->in[0], j->in[1], j->out0, j->out1); break;
-    case OP_MUL_BASE: j->rc = L.mul_base(j->ctx, j->i0, j->n, j->in[0], j->out0, j->out1, 0, NULL); break;
-    case OP_MUL_BASE2: j->rc = L.mul_base2(j->ctx, j->i0, j->i1, j->n, j->in[0], j->in[1], j->out0, j->out1, 0, NULL); break;
-    case OP_VERIFY_BASE: j->rc = L.ecdsa_verify_base(j->ctx, j->i0, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2],
-                                                     j->out0, 0, NULL); break;
-    case OP_EDDSA_VERIFY_BASE: j->rc = L.eddsa_verify_base(j->ctx, j->i0, j->n, j->in[0], (const uint64_t*)j->in[1], 0, j->in[2],
-                                                           j->out0, j->out1, 0, NULL); break;
-    case 5: j->rc = L.ecdsa_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i0,
-                                     j->out0, j->out1, j->out2, j->out3); break;
-    case 6: j->rc = L.ecdsa_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
-                                    j->out0, j->out1); break;
-    case 7: j->rc = L.verify_wire(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], (size_t)j->i0,
-                                  (const uint32_t*)j->in[2], j->in[3], (size_t)j->i1, j->out0, j->out1); break;
-    case 9: j->rc = L.custom_verify_wire(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1],
-                                         (size_t)j->i0, (const uint32_t*)j->in[2], j->in[3], (size_t)j->i1, j->out0,
-                                         j->out1); break;
-    case 10: j->rc = L.custom_recover(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->in[1], j->in[2], j->in[3],
-                                      j->out0, j->out1); break;
-    case 11: j->rc = L.custom_sign(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2], j->i0,
-                                   j->out0, j->out1, j->out2, j->out3); break;
-    case 12: j->rc = L.custom_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1, j->i0,
-                                       j->out0, j->out1, j->out2, j->out3); break;
-    case ED_OP_VERIFY: j->rc = L.custom_ed_verify(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2],
-                                                  j->in[3], j->out0, j->out1); break;
-    case ED_OP_SIGN: j->rc = L.custom_ed_sign(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->in[2], j->i0,
-                                              j->out0, j->out1, j->out2, j->out3); break;
-    case ED_OP_SIGN_DET: j->rc = L.custom_ed_sign_det(j->ctx, j->curve, j->n, j->in[0], j->hash_len, j->msg_bits, j->in[1], j->i1,
-                                                      j->i0, j->out0, j->out1, j->out2, j->out3); break;
-    case 13: case 14: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: {
-      const uint8_t* in[2] = {j->in[0], j->in[1]};
-      uint8_t* out[3] = {j->out0, j->out1, j->out2};
-      j->rc = ecdh_call(j->op, j->ctx, j->curve, j->n, in, j->i0, out); break;
-    }
-    default: j->rc = L.decode_points(j->ctx, j->curve, j->n, j->in[0], (size_t)j->i0, j->out0, j->out1); break;
-  }
+  j->rc = j->c.d->call(&j->c);
   if (j->rc != 0) {               /* last_error is thread-local: read it on this thread */
     const char* m = L.last_error();
     snprintf(j->err, sizeof j->err, "%s", m && *m ? m : "ellgpu error");
   }
 }
 static void free_cb(napi_env env, void* data, void* hint) { (void)env; (void)hint; free(data); }
+/* every exit of a job: release its references (the context external first of all -- a leaked
+ * reference keeps the external from ever being collected) and what it still owns */
+static void job_free(napi_env env, async_job* j) {
+  for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
+  for (int k = 0; k < 4; k++) free(j->c.out[k]);
+  free(j);
+}
 static void job_complete(napi_env env, napi_status status, void* data) {
   async_job* j = (async_job*)data;
   napi_value result = NULL;
   if (status == napi_ok && j->rc == 0) {
-    /* result property names per op, in output order */
-    static const char* const names[OP_LAST + 1][4] = {
-      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", "status", 0, 0}, {"x", "inf", 0, 0},
-      {"r", "s", "recid", "ok"}, {"xy", "status", 0, 0}, {"ok", "err", 0, 0}, {"xy", "status", 0, 0},
-      {"ok", "err", 0, 0}, {"xy", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
-      {"x", "status", 0, 0}, {"x", "status", "err", 0}, {"status", 0, 0, 0}, {"enc", 0, 0, 0},
-      {"x", "inf", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
-      {"xy", "status", 0, 0}, {"xy", "status", 0, 0}, {"status", 0, 0, 0}, {"x", "status", 0, 0},
-      {"x", "status", "err", 0}, {"enc", 0, 0, 0},
-      {"ok", "status", 0, 0}, {"r", "s", "recid", "ok"}, {"r", "s", "recid", "ok"},
-      {"xy", "inf", 0, 0}, {"xy", "inf", 0, 0}, {"ok", 0, 0, 0}, {"ok", "err", 0, 0}};
-    uint8_t** outs[4] = {&j->out0, &j->out1, &j->out2, &j->out3};
-    size_t lens[4] = {j->out0_len, j->out1_len, j->out2_len, j->out3_len};
+    const char* const* names = j->c.d->names;
     napi_create_object(env, &result);
-    for (int k = 0; k < 4 && names[j->op][k]; k++) {
+    for (int k = 0; k < 4 && names[k]; k++) {
       napi_value b;
-      napi_create_external_buffer(env, lens[k], *outs[k], free_cb, NULL, &b);
-      *outs[k] = NULL;
-      napi_set_named_property(env, result, names[j->op][k], b);
+      napi_create_external_buffer(env, j->c.ol[k], j->c.out[k], free_cb, NULL, &b);
+      j->c.out[k] = NULL;
+      napi_set_named_property(env, result, names[k], b);
     }
     napi_resolve_deferred(env, j->deferred, result);
   } else {
@@ -1379,16 +1135,9 @@ static void job_complete(napi_env env, napi_status status, void* data) {
     napi_create_error(env, NULL, msg, &errv);
     napi_reject_deferred(env, j->deferred, errv);
   }
-  for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
   g_jobs_in_flight--;
   napi_delete_async_work(env, j->work);
-  free(j->out0); free(j->out1); free(j->out2); free(j->out3); free(j);
-}
-/* every early exit of fn_call_async: release the references taken so far (the context external
- * first of all -- a leaked reference keeps ctx_finalize / ellgpu_ctx_destroy from ever running) */
-static void drop_job_refs(napi_env env, async_job* j) {
-  for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
-  j->nrefs = 0;
+  job_free(env, j);
 }
 static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   if (!need_lib(env)) return NULL;
@@ -1396,97 +1145,33 @@ static napi_value fn_call_async(napi_env env, napi_callback_info info) {
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < 9) THROW(env, "callAsync(op, ctx, curve, hashLen, msgBits, b0, b1, b2, b3[, i0, i1])");
   async_job* j = (async_job*)calloc(1, sizeof *j);
-  int32_t op, curve, hl, mb;
-  napi_get_value_int32(env, argv[0], &op);
   if (!j) THROW(env, "callAsync: out of memory");
-  j->ctx = get_ctx(env, argv[1]);
-  if (!j->ctx) { free(j); return NULL; }
-  /* the worker thread uses the context after this call returns: hold its external so that the
-   * GC finalizer (ctx_finalize -> ellgpu_ctx_destroy) cannot run under the job */
+  op_call* c = &j->c;
+  int32_t op = -1, curve = 0, hl = 0, mb = 0, i0 = 0, i1 = 0;
+  napi_get_value_int32(env, argv[0], &op);
+  c->ctx = get_ctx(env, argv[1]);
+  if (!c->ctx) { free(j); return NULL; }
+  /* the worker thread uses the context after this call returns: hold its external so that it
+   * cannot be collected under the job */
   napi_create_reference(env, argv[1], 1, &j->refs[j->nrefs++]);
   napi_get_value_int32(env, argv[2], &curve); napi_get_value_int32(env, argv[3], &hl); napi_get_value_int32(env, argv[4], &mb);
-  j->op = op; j->curve = op == 4 ? 7 : curve; j->hash_len = hl; j->msg_bits = mb;
-  j->B = L.field_bytes(j->curve); j->NB = L.order_bytes(j->curve);
-  if (op < 0 || op > OP_LAST || j->B <= 0) { drop_job_refs(env, j); free(j); THROW(env, "callAsync: bad op / curve"); }
-  int32_t i0 = 0, i1 = 0;
   if (argc > 9) napi_get_value_int32(env, argv[9], &i0);
   if (argc > 10) napi_get_value_int32(env, argv[10], &i1);
-  j->i0 = i0; j->i1 = i1;
-  size_t len[4] = {0, 0, 0, 0};
+  c->d = op_by_id(op);
+  c->curve = c->d && (c->d->flags & F_X25519) ? 7 : curve;
+  c->hl = hl; c->mb = mb; c->i0 = i0; c->i1 = i1; c->promise = 1;
+  c->B = L.field_bytes(c->curve); c->NB = L.order_bytes(c->curve);
+  if (!c->d || c->B <= 0) { job_free(env, j); THROW(env, "callAsync: bad op / curve"); }
   for (int i = 0; i < 4; i++) {
-    if (!get_buf(env, argv[5 + i], &j->in[i], &len[i], 1)) { drop_job_refs(env, j); free(j); return NULL; }
-    if (j->in[i]) napi_create_reference(env, argv[5 + i], 1, &j->refs[j->nrefs++]);   /* keep alive */
+    if (!get_buf(env, argv[5 + i], &c->in[i], &c->len[i], 1)) { job_free(env, j); return NULL; }
+    if (c->in[i]) napi_create_reference(env, argv[5 + i], 1, &j->refs[j->nrefs++]);   /* keep alive */
   }
-  size_t B = (size_t)j->B, NB = (size_t)j->NB;
-  int ok = 1;
-  size_t ecdh_out[3] = {0, 0, 0};
-  switch (op) {
-    case 13: case 14: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: {
-      const uint8_t* in2[2] = {j->in[0], j->in[1]};
-      ok = ecdh_shape(op, in2, len, i0, i1, &j->n, ecdh_out); break;
-    }
-    case 0: case OP_MUL_BASE: j->n = len[0] / B; ok = j->in[0] && len[0] % B == 0; break;
-    case OP_MUL_BASE2: j->n = len[0] / B; ok = j->in[0] && j->in[1] && len[0] % B == 0 && len[1] == len[0]; break;
-    case 1: j->n = len[0] / B; ok = j->in[0] && j->in[1] && len[0] % B == 0 && len[1] == j->n * 2 * B; break;
-    case 2: j->n = len[0] / B; ok = j->in[0] && j->in[2] && j->in[3] && len[0] % B == 0 && len[2] == len[0] &&
-                                     len[3] == j->n * 2 * B && (!j->in[1] || len[1] == j->n * 2 * B); break;
-    case 3: case ED_OP_VERIFY:
-            ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
-            j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * NB && len[2] == j->n * NB && len[3] == j->n * 2 * B; break;
-    case OP_VERIFY_BASE:
-            ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && !j->in[3] && len[0] % (size_t)hl == 0;
-            j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * NB && len[2] == j->n * NB; break;
-    case OP_EDDSA_VERIFY_BASE:
-            ok = j->in[1] && j->in[2] && !j->in[3] && len[2] % 64 == 0;
-            j->n = ok ? len[2] / 64 : 0;
-            ok = ok && !bad_offsets(j->in[1], len[1], j->n, len[0]); break;
-    case 4: j->n = len[0] / 32; ok = j->in[0] && j->in[1] && len[0] % 32 == 0 && len[1] == len[0]; break;
-    case 5: ok = hl > 0 && j->in[0] && j->in[1] && len[0] % (size_t)hl == 0;
-            j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * NB; break;
-    case 11: case 12: case ED_OP_SIGN: case ED_OP_SIGN_DET: {
-            const int det = op == 12 || op == ED_OP_SIGN_DET;
-            ok = hl > 0 && j->in[0] && j->in[1] && (det || j->in[2]) && len[0] % (size_t)hl == 0;
-            j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * NB && (det || len[2] == j->n * NB); break;
-    }
-    case 6: case 10:
-            ok = hl > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
-            j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * NB && len[2] == j->n * NB && len[3] == j->n; break;
-    case 7: case 9:
-            ok = hl > 0 && i0 > 0 && i1 > 0 && j->in[0] && j->in[1] && j->in[2] && j->in[3] && len[0] % (size_t)hl == 0;
-            j->n = ok ? len[0] / (size_t)hl : 0;
-            ok = ok && len[1] == j->n * (size_t)i0 && len[2] == j->n * 4 && !((uintptr_t)j->in[2] & 3) &&
-                 len[3] == j->n * (size_t)i1; break;
-    default: ok = i0 > 0 && j->in[0] && len[0] % (size_t)i0 == 0;
-             j->n = ok ? len[0] / (size_t)i0 : 0; break;
-  }
-  if (!ok) {
-    for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
-    free(j);
-    THROW(env, "callAsync: buffer length mismatch");
-  }
-  j->out0_len = op == 3 || op == 7 || op == 9 ? j->n : op == 4 ? j->n * 32 : op == 5 || op >= 11 ? j->n * NB : j->n * 2 * B;
-  j->out1_len = op == 5 || op >= 11 ? j->n * NB : j->n;
-  j->out2_len = op == 5 || op >= 11 ? j->n : 0;
-  j->out3_len = op == 5 || op >= 11 ? j->n : 0;
-  if (op == OP_MUL_BASE || op == OP_MUL_BASE2) { j->out0_len = j->n * 2 * B; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
-  if (op == ED_OP_VERIFY) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
-  if (op == OP_VERIFY_BASE) { j->out0_len = j->n; j->out1_len = 0; j->out2_len = 0; j->out3_len = 0; }
-  if (op == OP_EDDSA_VERIFY_BASE) { j->out0_len = j->n; j->out1_len = j->n; j->out2_len = 0; j->out3_len = 0; }
-  if (op >= 13 && op <= ECDH_OP_LAST) { j->out0_len = ecdh_out[0]; j->out1_len = ecdh_out[1]; j->out2_len = ecdh_out[2]; j->out3_len = 0; }
-  /* (ops 16, 25: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is out0_len long) */
-  j->out0 = (uint8_t*)malloc(ECDH_ENC_OP(op) ? j->n * ECDH_ENC_MAX + 1 : j->out0_len ? j->out0_len : 1);
-  j->out1 = (uint8_t*)malloc(j->out1_len ? j->out1_len : 1);
-  j->out2 = (uint8_t*)malloc(j->out2_len ? j->out2_len : 1);
-  j->out3 = (uint8_t*)malloc(j->out3_len ? j->out3_len : 1);
-  if (!j->out0 || !j->out1 || !j->out2 || !j->out3) {
-    for (int i = 0; i < j->nrefs; i++) napi_delete_reference(env, j->refs[i]);
-    free(j->out0); free(j->out1); free(j->out2); free(j->out3); free(j);
-    THROW(env, "callAsync: out of memory");
+  if (c->d->shape(c)) { job_free(env, j); THROW(env, "callAsync: buffer length mismatch"); }
+  for (int k = 0; k < 4; k++) {
+    /* (F_WIDE_ENC: rows of the widest encoding, see ECDH_ENC_MAX; the Buffer handed back is ol[0] long) */
+    size_t cap = k == 0 && (c->d->flags & F_WIDE_ENC) ? c->n * ECDH_ENC_MAX + 1 : c->ol[k];
+    c->out[k] = (uint8_t*)malloc(cap ? cap : 1);
+    if (!c->out[k]) { job_free(env, j); THROW(env, "callAsync: out of memory"); }
   }
   napi_value promise, name;
   CHECK(env, napi_create_promise(env, &j->deferred, &promise));
@@ -1502,19 +1187,10 @@ static napi_value init(napi_env env, napi_value exports) {
     {"open", fn_open}, {"createContext", fn_create}, {"destroyContext", fn_destroy},
     {"defer", fn_defer}, {"collect", fn_collect}, {"combBits", fn_comb_bits},
     {"curveId", fn_curve_id}, {"fieldBytes", fn_field_bytes}, {"orderBytes", fn_order_bytes},
-    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short}, {"defineEdwards", fn_define_edwards}, {"defineMont", fn_define_mont}, {"defineShortDomain", fn_define_short_domain}, {"defineEdwardsDomain", fn_define_edwards_domain}, {"mulFixed", fn_mul_fixed}, {"mulVar", fn_mul_var},
-    {"mulAdd2", fn_mul_add2}, {"ecdsaVerify", fn_verify}, {"x25519", fn_x25519}, {"x25519Derive", fn_x25519_derive},
-    {"callAsync", fn_call_async}, {"decompress", fn_decompress},
-    {"eddsaVerify", fn_eddsa_verify}, {"eddsaSign", fn_eddsa_sign}, {"ecdsaSign", fn_sign}, {"ecdsaRecover", fn_recover}, {"ecdsaSignDet", fn_sign_det},
-    {"decodePoints", fn_decode_points}, {"encodePoints", fn_encode_points}, {"validate", fn_validate},
-    {"pointAdd", fn_point_add}, {"sigFromDer", fn_sig_from_der}, {"sigToDer", fn_sig_to_der}, {"ecdsaVerifyWire", fn_verify_wire},
-    {"customDecompress", fn_custom_decompress}, {"customDecodePoints", fn_custom_decode_points},
-    {"customVerifyWire", fn_custom_verify_wire}, {"customRecover", fn_custom_recover},
-    {"customSign", fn_custom_sign}, {"customSignDet", fn_custom_sign_det},
-    {"customEdVerify", fn_custom_ed_verify}, {"customEdSign", fn_custom_ed_sign}, {"customEdSignDet", fn_custom_ed_sign_det}, {"customEcdh", fn_custom_ecdh},
-    {"defineBase", fn_define_base}, {"defineEdBase", fn_define_ed_base}, {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info},
-    {"mulBase", fn_mul_base}, {"mulBase2", fn_mul_base2}, {"ecdsaVerifyBase", fn_verify_base},
-    {"eddsaVerifyBase", fn_eddsa_verify_base},
+    {"deviceCount", fn_device_count}, {"groupSize", fn_group_size}, {"defineShort", fn_define_short},
+    {"defineEdwards", fn_define_edwards}, {"defineMont", fn_define_mont}, {"defineShortDomain", fn_define_short_domain},
+    {"defineEdwardsDomain", fn_define_edwards_domain}, {"defineBase", fn_define_base}, {"defineEdBase", fn_define_ed_base},
+    {"releaseBase", fn_release_base}, {"baseInfo", fn_base_info}, {"callAsync", fn_call_async},
   };
   napi_add_env_cleanup_hook(env, on_env_cleanup, NULL);
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {
@@ -1522,6 +1198,17 @@ static napi_value init(napi_env env, napi_value exports) {
     if (napi_create_function(env, fns[i].name, NAPI_AUTO_LENGTH, fns[i].fn, NULL, &f) != napi_ok) return NULL;
     if (napi_set_named_property(env, exports, fns[i].name, f) != napi_ok) return NULL;
   }
+  /* the batch operations: their synchronous exports, and ops = {name: callAsync's id} */
+  napi_value ids;
+  if (napi_create_object(env, &ids) != napi_ok) return NULL;
+  for (size_t i = 0; i < N_OPS; i++) {
+    napi_value f, id;
+    if (ops[i].args && (napi_create_function(env, ops[i].name, NAPI_AUTO_LENGTH, op_sync, (void*)&ops[i], &f) != napi_ok ||
+                        napi_set_named_property(env, exports, ops[i].name, f) != napi_ok)) return NULL;
+    if (ops[i].id >= 0 && (napi_create_int32(env, ops[i].id, &id) != napi_ok ||
+                           napi_set_named_property(env, ids, ops[i].name, id) != napi_ok)) return NULL;
+  }
+  if (napi_set_named_property(env, exports, "ops", ids) != napi_ok) return NULL;
   return exports;
 }
 NAPI_MODULE(NODE_GYP_MODULE_NAME, init)

@@ -37,6 +37,7 @@ function Engine(options) {
     path.join(__dirname, 'ellgpu.node'));
   this.addon.open(options.libPath || process.env.ELLGPU_LIB ||
     path.join(__dirname, '..', 'lib', 'libellgpu.so'));
+  this.OPS = this.addon.ops;   // {name: id} of the operations that have a Promise form (callAsync) or go through customEcdh
   // options.devices = [d0, d1, ...]: a device GROUP -- mulBatch / mulAddBatch / ecdsaVerifyBatch
   // (and their Promise forms) shard every batch over the listed GPUs, one host thread per
   // device, results written straight into the result Buffers; everything else (and the
@@ -433,21 +434,21 @@ Engine.prototype.eddsaSignBatch = function eddsaSignBatch(msgs, secrets) {
 // 2 the product is the point at infinity (getX throws)
 Engine.prototype.customDeriveBatch = function customDeriveBatch(curve, privs, pubs) {
   this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
-  return this.addon.customEcdh(this.ctx, 13, this._id(curve), privs, pubs, 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customDerive, this._id(curve), privs, pubs, 0, 0);
 };
 // customDeriveWireBatch: the same with the peer keys as SEC1 encodings of pubLen bytes each
 // (keyFromPublic -> decodePoint) -> { x, status, err }; status 3 = the key did not decode, err the
 // statuses of customDecodePointBatch
 Engine.prototype.customDeriveWireBatch = function customDeriveWireBatch(curve, privs, pubs, pubLen) {
   this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
-  return this.addon.customEcdh(this.ctx, 14, this._id(curve), privs, pubs, pubLen | 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customDeriveWire, this._id(curve), privs, pubs, pubLen | 0, 0);
 };
 // customValidateBatch: KeyPair#validate; xy Buffer(n x 64), inf Buffer(n) or null -> { status }:
 // 0 ok, 1 'Invalid public key', 2 'Public key is not a point', 3 'Public key * N != O' (checkOrder:
 // a domain id only)
 Engine.prototype.customValidateBatch = function customValidateBatch(curve, xy, inf, checkOrder) {
   this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
-  return this.addon.customEcdh(this.ctx, 15, this._id(curve), xy, inf || null, checkOrder === false ? 0 : 1, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customValidate, this._id(curve), xy, inf || null, checkOrder === false ? 0 : 1, 0);
 };
 // User-defined Montgomery curves (an id from defineMont), x-only, on the device.  install() does
 // not route Point#mul / validate / KeyPair#derive of such a curve to these (ladderDomain() answers
@@ -457,19 +458,19 @@ Engine.prototype.customValidateBatch = function customValidateBatch(curve, xy, i
 // Z = 0 -- the reference's getX() returns 0 there (redInvm of 0 is 0), the engine flags it; x zeroed
 Engine.prototype.customMontLadderBatch = function customMontLadderBatch(curve, ks, xs) {
   this.stats.gpuCalls++; this.stats.gpuItems += ks.length / 32;
-  return this.addon.customEcdh(this.ctx, 17, this._id(curve), ks, xs, 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customMontLadder, this._id(curve), ks, xs, 0, 0);
 };
 // customMontValidateBatch: MontCurve#validate -> { status }: 0 true, 1 false (a non-residue where
 // p = 3 mod 4), 3 'Assertion failed' (a non-residue where p = 1 mod 4: bn.js's Tonelli-Shanks loop)
 Engine.prototype.customMontValidateBatch = function customMontValidateBatch(curve, xs) {
   this.stats.gpuCalls++; this.stats.gpuItems += xs.length / 32;
-  return this.addon.customEcdh(this.ctx, 18, this._id(curve), xs, null, 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customMontValidate, this._id(curve), xs, null, 0, 0);
 };
 // customMontDeriveBatch: KeyPair#derive -> { x, status }: 0 shared secret, 1 'public point not
 // validated', 3 'Assertion failed', 2 Z = 0; validation first (x = 0 is valid: 2); x zeroed unless 0
 Engine.prototype.customMontDeriveBatch = function customMontDeriveBatch(curve, privs, xs) {
   this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
-  return this.addon.customEcdh(this.ctx, 19, this._id(curve), privs, xs, 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customMontDerive, this._id(curve), privs, xs, 0, 0);
 };
 // customEncodePointBatch: BasePoint#encode at the curve's own width PL = p.byteLength() ->
 // { enc: Buffer(n x (1 + PL)) } for compact, else n x (1 + 2 PL).  PL is what defineShort /
@@ -486,7 +487,7 @@ Engine.prototype._encodeWidth = function _encodeWidth(curve, coordBytes) {
 Engine.prototype.customEncodePointBatch = function customEncodePointBatch(curve, xy, compact, coordBytes) {
   var pl = this._encodeWidth(curve, coordBytes);
   this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
-  return this.addon.customEcdh(this.ctx, 16, this._id(curve), xy, null, compact ? 1 : 0, pl);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEncodePoints, this._id(curve), xy, null, compact ? 1 : 0, pl);
 };
 // The key side of a user-defined Edwards curve (an id from defineEdwards), on the device
 // (ellgpu_custom_ed_*).  install() does not route pointFromX / pointFromY / decodePoint /
@@ -498,12 +499,12 @@ Engine.prototype.customEncodePointBatch = function customEncodePointBatch(curve,
 // pointFromY with x^2 = 0 returns (0, y) for an even request, 'invalid point' for an odd one
 Engine.prototype.customEdDecompressBatch = function customEdDecompressBatch(curve, vs, odds, fromY) {
   this.stats.gpuCalls++; this.stats.gpuItems += vs.length / 32;
-  return this.addon.customEcdh(this.ctx, 20, this._id(curve), vs, odds, fromY ? 1 : 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEdDecompress, this._id(curve), vs, odds, fromY ? 1 : 0, 0);
 };
 // customEdDecodePointBatch: decodePoint per row of encLen bytes -> { xy, status } as customDecodePointBatch
 Engine.prototype.customEdDecodePointBatch = function customEdDecodePointBatch(curve, enc, encLen) {
   this.stats.gpuCalls++; this.stats.gpuItems += encLen > 0 ? enc.length / encLen : 0;
-  return this.addon.customEcdh(this.ctx, 21, this._id(curve), enc, null, encLen, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEdDecodePoints, this._id(curve), enc, null, encLen, 0);
 };
 // customEdValidateBatch: KeyPair#validate -> { status }: 0 ok, 1 'Invalid public key' ((0, 1)),
 // 2 'Public key is not a point', 3 'Public key * N != O'; order a 32-byte Buffer or a BN-like, or
@@ -514,19 +515,19 @@ function orderBuf(order) {
 }
 Engine.prototype.customEdValidateBatch = function customEdValidateBatch(curve, xy, order) {
   this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
-  return this.addon.customEcdh(this.ctx, 22, this._id(curve), xy, orderBuf(order), 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEdValidate, this._id(curve), xy, orderBuf(order), 0, 0);
 };
 // customEdDeriveBatch: KeyPair#derive -> { x, status }: 0 shared secret (the identity is a legal peer and
 // result: x = 0), 1 'public point not validated', 2 Z = 0 (incomplete addition laws only); privs as they stand
 Engine.prototype.customEdDeriveBatch = function customEdDeriveBatch(curve, privs, pubXY) {
   this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
-  return this.addon.customEcdh(this.ctx, 23, this._id(curve), privs, pubXY, 0, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEdDerive, this._id(curve), privs, pubXY, 0, 0);
 };
 // customEdDeriveWireBatch: the same with SEC1 keys of keyLen bytes -> { x, status, err }: status 3 the key
 // did not decode, err the statuses of customEdDecodePointBatch
 Engine.prototype.customEdDeriveWireBatch = function customEdDeriveWireBatch(curve, privs, enc, keyLen) {
   this.stats.gpuCalls++; this.stats.gpuItems += privs.length / 32;
-  return this.addon.customEcdh(this.ctx, 24, this._id(curve), privs, enc, keyLen, 0);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEdDeriveWire, this._id(curve), privs, enc, keyLen, 0);
 };
 // customEdEncodePointBatch: Point#encode at PL = p.byteLength(), recorded by defineEdwards; the
 // contract of customEncodePointBatch
@@ -540,14 +541,14 @@ Engine.prototype._edEncodeWidth = function _edEncodeWidth(curve, coordBytes) {
 Engine.prototype.customEdEncodePointBatch = function customEdEncodePointBatch(curve, xy, compact, coordBytes) {
   var pl = this._edEncodeWidth(curve, coordBytes);
   this.stats.gpuCalls++; this.stats.gpuItems += xy.length / 64;
-  return this.addon.customEcdh(this.ctx, 25, this._id(curve), xy, null, compact ? 1 : 0, pl);
+  return this.addon.customEcdh(this.ctx, this.OPS.customEdEncodePoints, this._id(curve), xy, null, compact ? 1 : 0, pl);
 };
 // ---- asynchronous batch API: same arguments, returns a Promise; the work runs on a
 // libuv worker thread (napi_async_work), so the JS thread stays responsive during a large
 // batch.  A context processes one call at a time, so calls are chained.
 Engine.prototype._async = function _async(op, curve, hashLen, msgBits, b0, b1, b2, b3, i0, i1) {
   var self = this;
-  var id = op === 4 ? 7 : this._id(curve);
+  var id = op === this.OPS.x25519 ? 7 : this._id(curve);
   var run = function() {
     self.stats.gpuCalls++;
     return self.addon.callAsync(op, self.ctx, id, hashLen | 0, msgBits | 0, b0 || null,
@@ -561,82 +562,82 @@ Engine.prototype._async = function _async(op, curve, hashLen, msgBits, b0, b1, b
   return p;
 };
 Engine.prototype.mulBatchAsync = function(curve, scalars, points) {
-  return points ? this._async(1, curve, 0, 0, scalars, points) : this._async(0, curve, 0, 0, scalars);
+  return points ? this._async(this.OPS.mulVar, curve, 0, 0, scalars, points) : this._async(this.OPS.mulFixed, curve, 0, 0, scalars);
 };
 Engine.prototype.mulAddBatchAsync = function(curve, k1, points1, k2, points2) {
-  return this._async(2, curve, 0, 0, k1, points1 || null, k2, points2);
+  return this._async(this.OPS.mulAdd2, curve, 0, 0, k1, points1 || null, k2, points2);
 };
 Engine.prototype.ecdsaVerifyBatchAsync = function(curve, o) {
-  return this._async(3, curve, o.hashLen, o.msgBits | 0, o.hashes, o.r, o.s, o.pub).then(function(res) {
+  return this._async(this.OPS.ecdsaVerify, curve, o.hashLen, o.msgBits | 0, o.hashes, o.r, o.s, o.pub).then(function(res) {
     if (o.status) res.status.copy(o.status);
     return res.ok;
   });
 };
 Engine.prototype.ecdsaSignDetBatchAsync = function(curve, o) {
-  return this._async(5, curve, o.hashLen, o.msgBits | 0, o.hashes, o.priv, null, null, o.canonical ? 1 : 0, 0);
+  return this._async(this.OPS.ecdsaSignDet, curve, o.hashLen, o.msgBits | 0, o.hashes, o.priv, null, null, o.canonical ? 1 : 0, 0);
 };
 Engine.prototype.ecdsaRecoverBatchAsync = function(curve, o) {
-  return this._async(6, curve, o.hashLen, 0, o.hashes, o.r, o.s, o.recid);
+  return this._async(this.OPS.ecdsaRecover, curve, o.hashLen, 0, o.hashes, o.r, o.s, o.recid);
 };
 Engine.prototype.ecdsaVerifyWireBatchAsync = function(curve, o) {
   var p = packRecords(o.sigs);
-  return this._async(7, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
+  return this._async(this.OPS.ecdsaVerifyWire, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
 };
 Engine.prototype.customVerifyWireBatchAsync = function(curve, o) {
   var p = packRecords(o.sigs);
-  return this._async(9, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
+  return this._async(this.OPS.customVerifyWire, curve, o.hashLen, o.msgBits | 0, o.hashes, p.buf, p.lens, o.keys, p.stride, o.keyLen);
 };
 Engine.prototype.customRecoverBatchAsync = function(curve, hashes, hashLen, r, s, recid) {
-  return this._async(10, curve, hashLen, 0, hashes, r, s, recid);
+  return this._async(this.OPS.customRecover, curve, hashLen, 0, hashes, r, s, recid);
 };
 Engine.prototype.customSignBatchAsync = function(curve, hashes, hashLen, msgBits, priv, nonces, canonical) {
-  return this._async(11, curve, hashLen, msgBits | 0, hashes, priv, nonces, null, canonical ? 1 : 0, 0);
+  return this._async(this.OPS.customSign, curve, hashLen, msgBits | 0, hashes, priv, nonces, null, canonical ? 1 : 0, 0);
 };
 Engine.prototype.customSignDetBatchAsync = function(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
-  return this._async(12, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
+  return this._async(this.OPS.customSignDet, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
 };
 Engine.prototype.customEdVerifyBatchAsync = function(curve, hashes, hashLen, msgBits, r, s, pub) {
-  return this._async(26, curve, hashLen, msgBits | 0, hashes, r, s, pub);
+  return this._async(this.OPS.customEdVerify, curve, hashLen, msgBits | 0, hashes, r, s, pub);
 };
 Engine.prototype.customEdSignBatchAsync = function(curve, hashes, hashLen, msgBits, priv, nonces, canonical) {
-  return this._async(27, curve, hashLen, msgBits | 0, hashes, priv, nonces, null, canonical ? 1 : 0, 0);
+  return this._async(this.OPS.customEdSign, curve, hashLen, msgBits | 0, hashes, priv, nonces, null, canonical ? 1 : 0, 0);
 };
 Engine.prototype.customEdSignDetBatchAsync = function(curve, hashes, hashLen, msgBits, priv, drbgHash, canonical) {
-  return this._async(28, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
+  return this._async(this.OPS.customEdSignDet, curve, hashLen, msgBits | 0, hashes, priv, null, null, canonical ? 1 : 0, drbgHashId(drbgHash));
 };
 Engine.prototype.customDeriveBatchAsync = function(curve, privs, pubs) {
-  return this._async(13, curve, 0, 0, privs, pubs, null, null, 0, 0);
+  return this._async(this.OPS.customDerive, curve, 0, 0, privs, pubs, null, null, 0, 0);
 };
 Engine.prototype.customDeriveWireBatchAsync = function(curve, privs, pubs, pubLen) {
-  return this._async(14, curve, 0, 0, privs, pubs, null, null, pubLen | 0, 0);
+  return this._async(this.OPS.customDeriveWire, curve, 0, 0, privs, pubs, null, null, pubLen | 0, 0);
 };
 Engine.prototype.customValidateBatchAsync = function(curve, xy, inf, checkOrder) {
-  return this._async(15, curve, 0, 0, xy, inf || null, null, null, checkOrder === false ? 0 : 1, 0);
+  return this._async(this.OPS.customValidate, curve, 0, 0, xy, inf || null, null, null, checkOrder === false ? 0 : 1, 0);
 };
 Engine.prototype.customEncodePointBatchAsync = function(curve, xy, compact, coordBytes) {
   var pl;
   try { pl = this._encodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
-  return this._async(16, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
+  return this._async(this.OPS.customEncodePoints, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
 };
 Engine.prototype.customEdDecompressBatchAsync = function(curve, vs, odds, fromY) {
-  return this._async(20, curve, 0, 0, vs, odds, null, null, fromY ? 1 : 0, 0);
+  return this._async(this.OPS.customEdDecompress, curve, 0, 0, vs, odds, null, null, fromY ? 1 : 0, 0);
 };
 Engine.prototype.customEdDecodePointBatchAsync = function(curve, enc, encLen) {
-  return this._async(21, curve, 0, 0, enc, null, null, null, encLen, 0);
+  return this._async(this.OPS.customEdDecodePoints, curve, 0, 0, enc, null, null, null, encLen, 0);
 };
 Engine.prototype.customEdValidateBatchAsync = function(curve, xy, order) {
-  return this._async(22, curve, 0, 0, xy, orderBuf(order), null, null, 0, 0);
+  return this._async(this.OPS.customEdValidate, curve, 0, 0, xy, orderBuf(order), null, null, 0, 0);
 };
 Engine.prototype.customEdDeriveBatchAsync = function(curve, privs, pubXY) {
-  return this._async(23, curve, 0, 0, privs, pubXY, null, null, 0, 0);
+  return this._async(this.OPS.customEdDerive, curve, 0, 0, privs, pubXY, null, null, 0, 0);
 };
 Engine.prototype.customEdDeriveWireBatchAsync = function(curve, privs, enc, keyLen) {
-  return this._async(24, curve, 0, 0, privs, enc, null, null, keyLen, 0);
+  return this._async(this.OPS.customEdDeriveWire, curve, 0, 0, privs, enc, null, null, keyLen, 0);
 };
 Engine.prototype.customEdEncodePointBatchAsync = function(curve, xy, compact, coordBytes) {
   var pl;
   try { pl = this._edEncodeWidth(curve, coordBytes); } catch (e) { return Promise.reject(e); }
-  return this._async(25, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
+  return this._async(this.OPS.customEdEncodePoints, curve, 0, 0, xy, null, null, null, compact ? 1 : 0, pl);
 };
 // Fixed-base tables of caller-chosen points (ellgpu_base_*): BasePoint#precompute for any point a
 // caller uses repeatedly.  install() does not route to them.
@@ -685,7 +686,7 @@ Engine.prototype.ecdsaVerifyBaseBatch = function ecdsaVerifyBaseBatch(base, b) {
 Engine.prototype.ecdsaVerifyBaseBatchAsync = function(base, b) {
   var curve;
   try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
-  return this._async(31, curve, b.hashLen | 0, b.msgBits | 0, b.hashes, b.r, b.s, null, base | 0, 0);
+  return this._async(this.OPS.ecdsaVerifyBase, curve, b.hashLen | 0, b.msgBits | 0, b.hashes, b.r, b.s, null, base | 0, 0);
 };
 // eddsaVerifyBaseBatch: EDDSA#verify(msg, sig, A) of n signatures against the key A a defineEdBase handle on
 // ed25519 stands for (ellgpu_eddsa_verify_base: h walks the key's table, S the curve's own) ->
@@ -708,32 +709,32 @@ Engine.prototype.eddsaVerifyBaseBatch = function eddsaVerifyBaseBatch(base, msgs
 Engine.prototype.eddsaVerifyBaseBatchAsync = function(base, msgs, sigs) {
   var curve;
   try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
-  return this._async(32, curve, 0, 0, Buffer.concat(msgs), this._msgOffsets(msgs), sigs, null, base | 0, 0);
+  return this._async(this.OPS.eddsaVerifyBase, curve, 0, 0, Buffer.concat(msgs), this._msgOffsets(msgs), sigs, null, base | 0, 0);
 };
 Engine.prototype.mulBaseBatchAsync = function(base, ks) {
   var curve;
   try { curve = this.baseInfo(base).curve; } catch (e) { return Promise.reject(e); }
-  return this._async(29, curve, 0, 0, ks, null, null, null, base | 0, 0);
+  return this._async(this.OPS.mulBase, curve, 0, 0, ks, null, null, null, base | 0, 0);
 };
 Engine.prototype.mulBase2BatchAsync = function(base1, base2, k1s, k2s) {
   var curve;
   try { curve = this.baseInfo(base1).curve; } catch (e) { return Promise.reject(e); }
-  return this._async(30, curve, 0, 0, k1s, k2s, null, null, base1 | 0, base2 | 0);
+  return this._async(this.OPS.mulBase2, curve, 0, 0, k1s, k2s, null, null, base1 | 0, base2 | 0);
 };
 Engine.prototype.customMontLadderBatchAsync = function(curve, ks, xs) {
-  return this._async(17, curve, 0, 0, ks, xs, null, null, 0, 0);
+  return this._async(this.OPS.customMontLadder, curve, 0, 0, ks, xs, null, null, 0, 0);
 };
 Engine.prototype.customMontValidateBatchAsync = function(curve, xs) {
-  return this._async(18, curve, 0, 0, xs, null, null, null, 0, 0);
+  return this._async(this.OPS.customMontValidate, curve, 0, 0, xs, null, null, null, 0, 0);
 };
 Engine.prototype.customMontDeriveBatchAsync = function(curve, privs, xs) {
-  return this._async(19, curve, 0, 0, privs, xs, null, null, 0, 0);
+  return this._async(this.OPS.customMontDerive, curve, 0, 0, privs, xs, null, null, 0, 0);
 };
 Engine.prototype.decodePointBatchAsync = function(curve, enc, encLen) {
-  return this._async(8, curve, 0, 0, enc, null, null, null, encLen, 0);
+  return this._async(this.OPS.decodePoints, curve, 0, 0, enc, null, null, null, encLen, 0);
 };
 Engine.prototype.x25519BatchAsync = function(scalars, xs) {
-  return this._async(4, 7, 0, 0, scalars, xs);
+  return this._async(this.OPS.x25519, 7, 0, 0, scalars, xs);
 };
 
 // ---- install(): prototype patch on a user-supplied elliptic instance ----------
