@@ -41,6 +41,23 @@
 #ifndef ELL_COZ_TABLE
 #define ELL_COZ_TABLE 1
 #endif
+// FpK256 (the saturated secp256k1 field): 1 = the field offers pair products, a difference of two
+// wide products folded once (FpK256::mul_sub_mul / mul_sub_sqr); 0 = the group law below does not
+// see them.  Which operation uses them is decided per operation, each on its own A/B
+// (docs/EXPERIMENTS.md H):
+//   ELL_K256_PAIR_DBL   ShortOps::dbl: 1 = the 3M + 4S doubling with L = 3/2 X^2 whose Y3 is one
+//                       pair product, 0 = dbl-2009-l (2M + 5S)
+//   ELL_K256_PAIR_MADD  the mixed additions: 1 = Y3 = rr (v - X3) - Y1 hhh as one pair product,
+//                       0 = two reduced products and a field subtraction
+#ifndef ELL_K256_PAIR
+#define ELL_K256_PAIR 1
+#endif
+#ifndef ELL_K256_PAIR_DBL
+#define ELL_K256_PAIR_DBL 1
+#endif
+#ifndef ELL_K256_PAIR_MADD
+#define ELL_K256_PAIR_MADD 0
+#endif
 #ifndef ELL_P224_TS_WINDOW
 #define ELL_P224_TS_WINDOW 1      // p224 square root: windowed Tonelli-Shanks (fp.h)
 #endif

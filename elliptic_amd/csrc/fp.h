@@ -411,6 +411,71 @@ struct FpK256 {
     fe_sqr_wide<8>(t, a.v);
     return reduce_wide(t);
   }
+  // PAIR PRODUCTS with one fold (ELL_K256_PAIR, common.h): Y3 = rr (v - X3) - Y1 hhh of the mixed
+  // addition and Y3 = L (T - X3) - S^2 of the doubling (short.h) are a difference of two wide
+  // products, folded once instead of twice.  The 512-bit difference t - s is taken with one borrow
+  // chain; where it borrows, the words hold 2^512 - m with m = s - t in (0, (p - 1)^2], and the
+  // multiple p 2^256 = 2^512 - delta 2^256 of p is added by subtracting delta = 2^32 + 977 from
+  // words 8 and 9:
+  //     2^512 - m - delta 2^256 = p 2^256 - m >= p 2^256 - (p - 1)^2 = p delta + 2p - 1 > 0,
+  // so that subtraction never borrows out of word 15, and the value handed to reduce_wide lies in
+  // [0, p 2^256) in both cases -- below 2^512 like a single product, so reduce_wide, fold4's
+  // carry-out path (hi_i >= 2^32 - 977) and fold_top's bounds (T < 2^34, t2 <= 4) hold as they
+  // stand and no seventeenth word exists.  A borrow out of word 9 needs (t[9], t[8]) < delta, i.e.
+  // word 9 of a negative difference to be 0 or 1: rare for every lane of a wave, the ripple
+  // through words 10..15 sits behind a branch as in sub.
+  static constexpr bool PAIR = ELL_K256_PAIR != 0;
+  ELL_HD static El reduce_wide_diff(u32 (&t)[16], const u32 (&s)[16]) {
+    u32 bw = 0;
+    ELL_UNROLL
+    for (int i = 0; i < 16; i++) t[i] = subb32(t[i], s[i], bw, bw);
+    u32 d0 = bw ? C0 : 0u, d1 = bw;
+    u32 bb = 0;
+    t[8] = subb32(t[8], d0, bb, bb);
+    t[9] = subb32(t[9], d1, bb, bb);
+    if (ELL_UNLIKELY(bb != 0)) {
+      ELL_UNROLL
+      for (int i = 10; i < 16; i++) t[i] = subb32(t[i], 0, bb, bb);
+    }
+    return reduce_wide(t);
+  }
+  // a * b - c * d
+  ELL_HD static El mul_sub_mul(const El& a, const El& b, const El& c, const El& d) {
+    u32 t[16], s[16];
+    fe_mul_wide<8>(s, c.v, d.v);
+    fe_mul_wide<8>(t, a.v, b.v);
+    return reduce_wide_diff(t, s);
+  }
+  // a * b - c^2
+  ELL_HD static El mul_sub_sqr(const El& a, const El& b, const El& c) {
+    u32 t[16], s[16];
+    fe_mul_wide<8>(t, a.v, b.v);
+    fe_sqr_wide<8>(s, c.v);
+    return reduce_wide_diff(t, s);
+  }
+  // a / 2: for odd a, (a + p) / 2 = (a >> 1) + (p + 1) / 2 with (p + 1) / 2 = 2^255 - (2^31 + 488):
+  // the shift, bit 255 set (a >> 1 is below it) and 2^31 + 488 taken off word 0; a borrow out of
+  // word 1 (needs word 1 = 0) is rare and ripples behind a branch, never out of word 7 (bit 255 is
+  // set then).  Canonical: (a + p) / 2 < p.
+  ELL_HD static El half(const El& a) {
+    const u32 odd = a.v[0] & 1u;
+    u32 s[8];
+    ELL_UNROLL
+    for (int i = 0; i < 7; i++) s[i] = (a.v[i] >> 1) | (a.v[i + 1] << 31);
+    s[7] = (a.v[7] >> 1) | (odd << 31);
+    u32 d0 = odd ? 0x80000000u + (C0 - 1u) / 2u : 0u;
+    u32 bb = 0;
+    El r;
+    r.v[0] = subb32(s[0], d0, bb, bb);
+    r.v[1] = subb32(s[1], 0, bb, bb);
+    ELL_UNROLL
+    for (int i = 2; i < 8; i++) r.v[i] = s[i];
+    if (ELL_UNLIKELY(bb != 0)) {
+      ELL_UNROLL
+      for (int i = 2; i < 8; i++) r.v[i] = subb32(s[i], 0, bb, bb);
+    }
+    return r;
+  }
   ELL_HD static El sqr_n(El a, int n) {
     ELL_NOUNROLL
     for (int i = 0; i < n; i++) a = sqr(a);

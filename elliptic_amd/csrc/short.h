@@ -43,12 +43,18 @@ struct is_lazy { static constexpr bool value = false; };
 template <class F>
 struct is_lazy<F, decltype((void)F::LAZY)> { static constexpr bool value = F::LAZY; };
 
-// F::PAIR (fp.h FpSolinas): the field folds a difference of two wide products once
-// (mul_sub_mul / mul_sub_sqr8); the doubling and the additions below form their Y3 that way
+// F::PAIR (fp.h FpSolinas, FpK256): the field folds a difference of two wide products once
+// (mul_sub_mul, and mul_sub_sqr8 / mul_sub_sqr); the doubling and the additions below form their
+// Y3 that way
 template <class F, class = void>
 struct has_pair { static constexpr bool value = false; };
 template <class F>
 struct has_pair<F, decltype((void)F::PAIR)> { static constexpr bool value = F::PAIR; };
+
+// a = 0 doubling with Y3 as one pair product (F::mul_sub_sqr, F::half: FpK256); ELL_K256_PAIR_DBL
+// (common.h) switches it off by itself
+template <class F>
+struct pair_dbl { static constexpr bool value = has_pair<F>::value && !is_lazy<F>::value && ELL_K256_PAIR_DBL != 0; };
 
 // F::QUAD (coop.h): a wave holds four field elements side by side and multiplies them in one
 // instruction stream (F::mulq over F::pack* / F::unpack*); the lazy doubling and mixed addition
@@ -142,6 +148,19 @@ struct ShortOps {
       r.Z = F::sub(F::sub(F::sqr(F::add(p.Y, p.Z)), yy), zz);
       r.Y = F::sub(F::mul(m, F::sub(s, r.X)), F::template mul_pow2<3>(yyyy));
       return r;
+    } else if constexpr (CV::A_KIND == 0 && pair_dbl<F>::value) {
+      // a = 0 over a saturated field with pair products (secp256k1 over FpK256): the formulas of
+      // dbl_lazy above, 3M + 4S of which S^2 only enters Y3 -- one pair product, one fold -- and five
+      // linear operations where dbl-2009-l below has twelve.  The triple is that one's scaled by
+      // 1/2 (same affine point); Z3 = Y Z is 0 for O and for Y = 0.  Statement order = shortest
+      // live ranges (Y and Z die first, then X).
+      El s = F::sqr(p.Y);
+      r.Z = F::mul(p.Y, p.Z);
+      El a = F::sqr(p.X);
+      El t = F::mul(p.X, s);
+      El l = F::add(a, F::half(a));
+      r.X = F::sub(F::sqr(l), F::template mul_pow2<1>(t));
+      r.Y = F::mul_sub_sqr(l, F::sub(t, r.X), s);
     } else if (CV::A_KIND == 0) {
       // dbl-2009-l, a = 0: 2M + 5S.  Statement order = shortest live ranges (Y and Z die
       // first, then X): at most five field elements are live next to a product's own words.
@@ -178,7 +197,7 @@ struct ShortOps {
       r.X = F::sub(F::sqr(alpha), F::template mul_pow2<1>(beta4));
       El yz = F::sqr(F::add(p.Y, p.Z));
       r.Z = F::sub(F::sub(yz, gamma), delta);
-      if constexpr (has_pair<F>::value) {
+      if constexpr (has_pair<F>::value && CV::A_KIND != 0) {
         r.Y = F::mul_sub_sqr8(alpha, F::sub(beta4, r.X), gamma);
       } else {
         El g2 = F::sqr(gamma);
@@ -187,6 +206,16 @@ struct ShortOps {
       }
     }
     return r;
+  }
+
+  // the mixed addition's Y3 = rr (v - X3) - Y1 hhh as one pair product: the Solinas fields' choice is
+  // their prime's (F::PAIR); over FpK256 (a = 0) it is ELL_K256_PAIR_MADD (common.h: measured, off)
+  static constexpr bool PAIR_ADD = has_pair<F>::value && (CV::A_KIND != 0 || ELL_K256_PAIR_MADD != 0);
+  // Y3 of add_mixed / add_mixed_zr: over FpK256 the same form as add_mixed_lean's; the other curves'
+  // forms stay as they are
+  ELL_HD static El y3_pair(const El& rr, const El& w, const El& y1, const El& hhh) {
+    if constexpr (PAIR_ADD && CV::A_KIND == 0) return F::mul_sub_mul(rr, w, y1, hhh);
+    else return F::sub(F::mul(rr, w), F::mul(y1, hhh));
   }
 
   // P + Q, Q affine and finite; if !do_add returns P unchanged.  8M + 3S.
@@ -201,7 +230,7 @@ struct ShortOps {
     El v = F::mul(p.X, hh);
     J r;
     r.X = F::sub(F::sub(F::sqr(rr), hhh), F::template mul_pow2<1>(v));
-    r.Y = F::sub(F::mul(rr, F::sub(v, r.X)), F::mul(p.Y, hhh));
+    r.Y = y3_pair(rr, F::sub(v, r.X), p.Y, hhh);
     r.Z = F::mul(p.Z, h);          // h == 0, rr != 0  ->  Z3 = 0: infinity
     // Every exceptional input (P = O, P = Q, P = -Q) gives Z3 = Z1 * h = 0: one zero test on
     // the common path, the case analysis behind a branch that is almost never taken.
@@ -320,7 +349,7 @@ struct ShortOps {
       El hhh = F::mul(h, hh);
       El v = F::mul(p.X, hh);
       r.X = F::sub(F::sub(F::sqr(rr), hhh), F::template mul_pow2<1>(v));
-      if constexpr (has_pair<F>::value) {
+      if constexpr (PAIR_ADD) {
         r.Y = F::mul_sub_mul(rr, F::sub(v, r.X), p.Y, hhh);
       } else {
         El yh = F::mul(p.Y, hhh);
@@ -357,7 +386,7 @@ struct ShortOps {
     El v = F::mul(p.X, hh);
     J r;
     r.X = F::sub(F::sub(F::sqr(rr), hhh), F::template mul_pow2<1>(v));
-    r.Y = F::sub(F::mul(rr, F::sub(v, r.X)), F::mul(p.Y, hhh));
+    r.Y = y3_pair(rr, F::sub(v, r.X), p.Y, hhh);
     r.Z = F::mul(p.Z, h);
     return r;
   }
