@@ -1608,6 +1608,16 @@ class Engine {
     while (k > 1 && n / (size_t)k < 2 * tune_.wave_round) k >>= 1;
     return k;
   }
+  // The geometry of a shared-inversion kernel on n items: K items per inversion, hence T threads.
+  // field_inv: the kernels that invert in the base field (the normalisations ...); scalar_inv: those
+  // that invert mod the order (ecdsa_prep, sign_finish, recover_prep).  launch_inv() takes one.
+  struct InvBatch {
+    int K;
+    size_t T;
+    InvBatch(size_t n, int k) : K(k), T((n + K - 1) / K) {}
+  };
+  InvBatch field_inv(size_t n) const { return InvBatch(n, norm_batch_for(n)); }
+  InvBatch scalar_inv(size_t n) const { return InvBatch(n, inv_batch_for(n, INV_BATCH_N)); }
   static constexpr size_t CHUNK = 1u << 21;   // max items per launch (bounds the scratch arena)
 
   explicit Engine(const BK& b) : bk(b) {
@@ -1641,6 +1651,21 @@ class Engine {
     return b.p;
   }
   void* scratch(int which, size_t bytes) { return grow(scratch_[lane_][which], bytes); }
+  // How a chunk body claims its scratch: every buffer once (slot, element type, bytes), in the order
+  // in which they are to be allocated, then claimed() once behind the last of them -- E_NOMEM if
+  // any of the grows failed.  The only caller of scratch().
+  template <class T>
+  T* claim(int which, size_t bytes) {
+    T* p = (T*)scratch(which, bytes);
+    claim_failed_ |= !p;
+    return p;
+  }
+  int claimed() {
+    if (!claim_failed_) return E_OK;
+    claim_failed_ = false;
+    return no_scratch();
+  }
+  int no_scratch() { return fail(E_NOMEM, "scratch allocation failed"); }
 
   int fail(int code, const char* msg) { err = msg; return code; }
 
@@ -1725,7 +1750,7 @@ class Engine {
   template <class Chk>
   u8* checked_base(const u8* xy, size_t B, bool test, int& rc) {
     u8* dpt = (u8*)bk.alloc(2 * B + 1);            // the point and, behind it, the test's flag
-    if (!dpt) { rc = fail(E_NOMEM, "scratch allocation failed"); return nullptr; }
+    if (!dpt) { rc = no_scratch(); return nullptr; }
     u8 flag = test ? 1 : 0;
     bk.h2d(dpt, xy, 2 * B);
     if (test) {
@@ -1786,13 +1811,38 @@ class Engine {
   template <class CV>
   int ecdsa_base_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
                        const typename Work<CV>::A* tg, const typename Work<CV>::A* tq, u8* ok);
-  // launch of a scalar-field kernel (ecdsa_prep, sign_finish, recover_prep: batched inversion
-  // and Montgomery arithmetic mod n, long dependent chains).  A member of its own so that these
-  // kernels are instantiated in their own translation units (inst.hip group 6), which are
-  // compiled with LLVM's max-ILP scheduling strategy: measured ecdsa_prep 0.334 -> 0.234 ms per
-  // 2^20, while the ladder kernels are 0.4-1.3 % slower under it and keep the default.
+  // The two routes of a launch.  They run the same code on the host and are NOT interchangeable:
+  //   bk.launch(f, n)   compiles the kernel where the calling chunk body is compiled;
+  //   launch_fn(f, n)   compiles it in the translation unit whose group lists launch_fn<Fn> in
+  //                     engine_extern.h -- a member of its own, not inline, for that reason alone.
+  // The unit fixes the kernel's compile flags (group 6, the scalar-field kernels ecdsa_prep,
+  // sign_finish, recover_prep: LLVM's max-ILP scheduling, measured ecdsa_prep 0.334 -> 0.234 ms per
+  // 2^20, while the ladder kernels are 0.4-1.3 % slower under it and keep the default) and, on
+  // user-defined curves, the parameter block it reads: g_rt (group 16), g_rt_dom (17) or g_rt_ed (18,
+  // inst.hip).  The Edwards domain's chunk bodies are compiled in group 18 and are correct only
+  // because the short domain's scalar-field kernels they launch (ecdsa_prep, rt_sign_nonce,
+  // rt_sign_finish) go through the launch_fn of group 17, where n is.  Moving a launch from one
+  // route to the other moves its kernel: check the per-unit kernel lists of a --remarks build.
+  // (An Fn that engine_extern.h does not list is compiled where launch_fn is called, as by bk.launch.)
   template <class Fn>
   int launch_fn(const Fn& f, size_t nthreads);
+  // The one launch of a shared-inversion kernel: Fn{T, n, K, rest...} on T threads, on the route
+  // that the call names.
+  enum class Route { here, unit };      // bk.launch / launch_fn
+  template <Route R, class Fn, class... A>
+  int launch_inv(InvBatch g, size_t n, A... rest) {
+    Fn f{g.T, n, g.K, rest...};
+    if constexpr (R == Route::unit) return launch_fn(f, g.T);
+    else bk.launch(f, g.T);         // (else: the branch not taken must not be instantiated)
+    return E_OK;
+  }
+  // the HmacDRBG nonces of a sign chunk on a user-defined domain, short or Edwards, over the hash
+  // drbg_hash (ELLGPU_HASH_*): the short domain's kernels (group 17)
+  int draw_nonces(int drbg_hash, size_t n, const u8* hash, int hash_len, int shift, const u8* priv, u8* drawn) {
+    if (drbg_hash == 0) return launch_fn(FnRtSignNonce<Sha256>{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn}, n);
+    if (drbg_hash == 1) return launch_fn(FnRtSignNonce<Sha384>{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn}, n);
+    return launch_fn(FnRtSignNonce<Sha512>{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn}, n);
+  }
   template <int U = 0>
   int ensure_ed_comb();
   template <int U = 0>
@@ -1817,6 +1867,11 @@ class Engine {
   // KeyPair#validate, order == null without the order test.
   template <int U = 0>
   int edk_point_chunk(size_t n, const u8* a, const u8* b, int from_y, size_t len, u8* out_xy, u8* out_st, u8* valid);
+  // edk_point_chunk's three passes over buffers that the caller holds: pts n x 64 bytes, flags 3 n
+  // (the status, what the root pass owes each item; the third n are the caller's), nd n x 24 words
+  template <int U = 0>
+  void edk_point_passes(size_t n, const u8* a, const u8* b, int from_y, size_t len, u8* pts, u8* flags, u32* nd,
+                        u8* out_xy, u8* out_st, u8* valid);
   template <int U = 0>
   int edk_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len, u8* out_x, u8* status, u8* err);
   template <int U = 0>
@@ -3133,15 +3188,15 @@ class Engine {
   // the scratch of a wire verify of m items: r, s (NB bytes each), the decoded key (2 B), and the
   // statuses of the key, the signature and the verify
   struct WireTmp { u8 *r, *s, *xy, *kst, *sst, *vst; };
-  bool wire_tmp(size_t m, size_t B, size_t NB, WireTmp& t) {
-    t.r = (u8*)scratch(S_WIRE, m * (2 * NB + 2 * B + 3));
-    if (!t.r) return false;
+  int wire_tmp(size_t m, size_t B, size_t NB, WireTmp& t) {
+    t.r = claim<u8>(S_WIRE, m * (2 * NB + 2 * B + 3));
+    if (int rc = claimed()) return rc;
     t.s = t.r + m * NB;
     t.xy = t.s + m * NB;
     t.kst = t.xy + m * 2 * B;
     t.sst = t.kst + m;
     t.vst = t.sst + m;
-    return true;
+    return E_OK;
   }
   // EC#verify(msg, derSignature, encodedKey) (ec/index.js:188-229 with keyFromPublic ->
   // decodePoint and new Signature(der)): decode, parse and verify on the device -- the three
@@ -3160,7 +3215,7 @@ class Engine {
     return batch(where, n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
                  {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto o) {
       WireTmp t;
-      if (!wire_tmp(m, B, NB, t)) return fail(E_NOMEM, "scratch allocation failed");
+      if ((rc = wire_tmp(m, B, NB, t))) return rc;
       rc = decode_points(Mem::device, curve, m, d[3], pub_len, t.xy, t.kst);
       if (rc) return rc;
       rc = sig_from_der(Mem::device, curve, m, d[1], der_stride, (const u32*)d[2], t.r, t.s, t.sst);
@@ -3179,25 +3234,28 @@ class Engine {
   // out are 32 bytes; a SEC1 coordinate is p.byteLength() bytes, the block's pbytes.
   // The checks of the custom_* operations are the same in both forms, in the same order.
   enum { OP_RT_DECOMPRESS = 0, OP_RT_DECODE = 1, OP_RT_FROM_DER = 2, OP_RT_WIRE_STATUS = 3 };
-  int check_custom_short(int curve, bool need_domain) {
-    if (!is_custom(curve))
-      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (the presets have ellgpu_decompress, ellgpu_decode_points and ellgpu_ecdsa_verify_wire)")
-                               : fail(E_ARG, "unknown curve id");
+  // The id check of every custom_* operation: a user-defined id of this context whose curve is of
+  // `kind` (0 short, 1 Edwards, 2 Montgomery) and, with no_domain, has an ECDSA domain.  A preset
+  // or unknown id is an argument error, the rest unsupported.  The messages: what to say to a preset
+  // id, to another kind (a Montgomery id has one of its own where `mont` is set) and to a plain id.
+  struct CustomIdMsgs { const char *preset, *kind, *mont, *no_domain; };
+  int check_custom(int curve, u32 kind, const CustomIdMsgs& m) {
+    if (!is_custom(curve)) return fail(E_ARG, curve_info(curve) ? m.preset : "unknown curve id");
     const RtField* f = custom_block(curve);
     if (!f) return fail(E_ARG, "unknown curve id");
-    if (f->kind == 2) return fail(E_UNSUPPORTED, "not available on user-defined Montgomery curves (x-only: ellgpu_custom_mont_ladder, _validate, _derive)");
-    if (f->kind != 0) return fail(E_UNSUPPORTED, "not available on user-defined Edwards curves");
-    if (need_domain && !f->domain)
-      return fail(E_UNSUPPORTED, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    if (f->kind != kind) return fail(E_UNSUPPORTED, f->kind == 2 && m.mont ? m.mont : m.kind);
+    if (m.no_domain && !f->domain) return fail(E_UNSUPPORTED, m.no_domain);
     return E_OK;
   }
-  // ... and a domain on it, for the operations that need n and G (msg: what to say to a plain id)
-  int check_custom_short_domain(int curve, const char* msg) {
-    const int rc = check_custom_short(curve, false);
-    return rc || custom_is_domain(curve) ? rc : fail(E_UNSUPPORTED, msg);
+  // a short curve; with no_domain: ... and a domain on it, for the operations that need n and G
+  int check_custom_short(int curve, const char* no_domain = nullptr) {
+    return check_custom(curve, 0, {"not a user-defined curve id (the presets have ellgpu_decompress, ellgpu_decode_points and ellgpu_ecdsa_verify_wire)",
+                                   "not available on user-defined Edwards curves",
+                                   "not available on user-defined Montgomery curves (x-only: ellgpu_custom_mont_ladder, _validate, _derive)",
+                                   no_domain});
   }
   int custom_decompress(Mem where, int curve, size_t n, const u8* x, const u8* odd, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
+    int rc = check_custom_short(curve);
     if (rc) return rc;
     if (n && (!x || !odd || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve);
@@ -3209,7 +3267,7 @@ class Engine {
   // enc_len other than 1 + pbytes and 1 + 2 pbytes is no error of the call: every item is then
   // 'Unknown point format', as in the reference
   int custom_decode_points(Mem where, int curve, size_t n, const u8* enc, size_t enc_len, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short(curve, false);
+    int rc = check_custom_short(curve);
     if (rc) return rc;
     if (n && (!enc || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     if (enc_len == 0) return fail(E_ARG, "enc_len must be positive");
@@ -3223,7 +3281,7 @@ class Engine {
   // composed like ecdsa_verify_wire
   int custom_verify_wire(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* der,
                          size_t der_stride, const u32* der_len, const u8* pub_enc, size_t pub_len, u8* ok, u8* err) {
-    int rc = check_custom_short(curve, true);
+    int rc = check_custom_short(curve, "ECDSA verify on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
     if (rc) return rc;
     if (n && (!hash || !der || !der_len || !pub_enc || !ok)) return fail(E_ARG, "null pointer");
     if (hash_len <= 0 || der_stride == 0 || pub_len == 0) return fail(E_ARG, "bad hash_len / stride / pub_len");
@@ -3232,7 +3290,7 @@ class Engine {
     return batch(where, n, {In{hash, (size_t)hash_len}, In{der, der_stride}, In{der_len, 4}, In{pub_enc, pub_len}},
                  {Out{ok, 1}, Out{err, 1}}, [&](size_t m, auto d, auto o) {
       WireTmp t;
-      if (!wire_tmp(m, 32, 32, t)) return fail(E_NOMEM, "scratch allocation failed");
+      if ((rc = wire_tmp(m, 32, 32, t))) return rc;
       rc = rt_wire_chunk(OP_RT_DECODE, m, d[3], nullptr, pub_len, nullptr, t.xy, t.kst, nullptr);
       if (rc) return rc;
       rc = rt_wire_chunk(OP_RT_FROM_DER, m, d[1], nullptr, der_stride, (const u32*)d[2], t.r, t.s, t.sst);
@@ -3248,7 +3306,7 @@ class Engine {
   // truncated, only reduced mod n; s is not range-checked (the reference reduces it).
   int custom_recover(Mem where, int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
                      const u8* recid, u8* out_xy, u8* out_status) {
-    int rc = check_custom_short_domain(curve, "public-key recovery on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
+    int rc = check_custom_short(curve, "public-key recovery on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
     if (rc) return rc;
     if (n && (!hash || !r || !s || !recid || !out_xy || !out_status)) return fail(E_ARG, "null pointer");
     if (hash_len < 1 || hash_len > 64) return fail(E_ARG, "hash_len must be 1 .. 64");
@@ -3284,7 +3342,7 @@ class Engine {
                   const u8* nonces, bool det, int drbg_hash, int canonical, u8* out_r, u8* out_s,
                   u8* out_recid, u8* out_ok) {
     int shift;
-    int rc = check_custom_sign(check_custom_short_domain(curve, "ECDSA sign on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"),
+    int rc = check_custom_sign(check_custom_short(curve, "ECDSA sign on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)"),
                                curve, n, hash, hash_len, msg_bits, priv, nonces, det, drbg_hash, out_r, out_s, out_recid, out_ok, shift);
     if (rc) return rc;
     CustomScope sc(this, curve);
@@ -3314,7 +3372,7 @@ class Engine {
   }
   int custom_derive(Mem where, int curve, size_t n, const u8* priv, const u8* pub, bool wire, size_t pub_len, u8* out_x,
                     u8* out_status, u8* out_err) {
-    int rc = check_custom_derive(check_custom_short(curve, false), n, priv, pub, wire, pub_len, out_x, out_status);
+    int rc = check_custom_derive(check_custom_short(curve), n, priv, pub, wire, pub_len, out_x, out_status);
     if (rc) return rc;
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
@@ -3325,10 +3383,8 @@ class Engine {
   }
   // statuses as validate's; check_order on a plain id: it has no n
   int custom_validate(Mem where, int curve, size_t n, const u8* xy, const u8* inf, int check_order, u8* out_status) {
-    int rc = check_custom_short(curve, false);
+    int rc = check_custom_short(curve, check_order ? "the order test on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)" : nullptr);
     if (rc) return rc;
-    if (check_order && !custom_is_domain(curve))
-      return fail(E_UNSUPPORTED, "the order test on a user-defined curve needs its domain (ellgpu_curve_define_short_domain)");
     if (n && (!xy || !out_status)) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve);
     if (sc.rc) return sc.rc;
@@ -3338,7 +3394,7 @@ class Engine {
   }
   // rows of 1 + pbytes (compact) or 1 + 2 pbytes bytes
   int custom_encode_points(Mem where, int curve, size_t n, const u8* xy, int compact, u8* out_enc) {
-    int rc = check_custom_short(curve, false);
+    int rc = check_custom_short(curve);
     if (rc) return rc;
     if (n && (!xy || !out_enc)) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve);
@@ -3354,12 +3410,9 @@ class Engine {
   // user-defined id is unsupported.
   enum { OP_MONTC_LADDER = 0, OP_MONTC_VALIDATE = 1, OP_MONTC_DERIVE = 2 };
   int custom_mont(Mem where, int curve, int op, size_t n, const u8* k, const u8* x, u8* out_x, u8* out_flag) {
-    if (!is_custom(curve))
-      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (curve25519 has ellgpu_x25519_ladder and ellgpu_x25519_derive)")
-                               : fail(E_ARG, "unknown curve id");
-    const RtField* f = custom_block(curve);
-    if (!f) return fail(E_ARG, "unknown curve id");
-    if (f->kind != 2) return fail(E_UNSUPPORTED, "not a user-defined Montgomery curve (ellgpu_curve_define_mont)");
+    int rc = check_custom(curve, 2, {"not a user-defined curve id (curve25519 has ellgpu_x25519_ladder and ellgpu_x25519_derive)",
+                                     "not a user-defined Montgomery curve (ellgpu_curve_define_mont)", nullptr, nullptr});
+    if (rc) return rc;
     const bool v = op == OP_MONTC_VALIDATE;        // (k and out_x unused: absent operands)
     if (n && (!x || !out_flag || (!v && (!k || !out_x)))) return fail(E_ARG, "null pointer");
     CustomScope sc(this, curve, true);
@@ -3376,13 +3429,8 @@ class Engine {
   // p.byteLength() of the Edwards curve of the call in progress: from the augmented copy (the registered block's is zero)
   int custom_ed_pbytes() const { return (int)custom_aug_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].pbytes; }
   int check_custom_ed(int curve) {
-    if (!is_custom(curve))
-      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (ed25519 has ellgpu_decompress, ellgpu_decode_points, ellgpu_validate and ellgpu_ecdh_derive)")
-                               : fail(E_ARG, "unknown curve id");
-    const RtField* f = custom_block(curve);
-    if (!f) return fail(E_ARG, "unknown curve id");
-    if (f->kind != 1) return fail(E_UNSUPPORTED, "not a user-defined Edwards curve (ellgpu_curve_define_edwards)");
-    return E_OK;
+    return check_custom(curve, 1, {"not a user-defined curve id (ed25519 has ellgpu_decompress, ellgpu_decode_points, ellgpu_validate and ellgpu_ecdh_derive)",
+                                   "not a user-defined Edwards curve (ellgpu_curve_define_edwards)", nullptr, nullptr});
   }
   int custom_ed_decompress(Mem where, int curve, size_t n, const u8* v, const u8* odd, int from_y, u8* out_xy, u8* out_status) {
     int rc = check_custom_ed(curve);
@@ -3446,14 +3494,9 @@ class Engine {
   // EC#verify and EC#sign over a define_edwards_domain id (edcecdsa.h).  A preset or unknown id is
   // an argument error; a short id, a Montgomery id and an Edwards id without a domain are unsupported.
   int check_custom_ed_domain(int curve) {
-    if (!is_custom(curve))
-      return curve_info(curve) ? fail(E_ARG, "not a user-defined curve id (the presets have ellgpu_ecdsa_verify and ellgpu_ecdsa_sign)")
-                               : fail(E_ARG, "unknown curve id");
-    const RtField* f = custom_block(curve);
-    if (!f) return fail(E_ARG, "unknown curve id");
-    if (f->kind != 1 || !f->domain)
-      return fail(E_UNSUPPORTED, "ECDSA on a user-defined Edwards curve needs its domain (ellgpu_curve_define_edwards_domain)");
-    return E_OK;
+    const char* need = "ECDSA on a user-defined Edwards curve needs its domain (ellgpu_curve_define_edwards_domain)";
+    return check_custom(curve, 1, {"not a user-defined curve id (the presets have ellgpu_ecdsa_verify and ellgpu_ecdsa_sign)",
+                                   need, nullptr, need});
   }
   int custom_ed_verify(Mem where, int curve, size_t n, const u8* hash, int hash_len, int msg_bits, const u8* r,
                        const u8* s, const u8* pub, u8* ok, u8* st) {
@@ -3503,16 +3546,17 @@ class Engine {
     size_t L = (size_t)(ci->field_bytes + 3) / 4 + 1;       // +1: the 29-bit secp256k1 field stores 9 limbs
     size_t ent = (curve == CURVE_ED25519) ? 16 * 4 * L * 4 : 32 * 3 * L * 4;
     // both lanes: a caller that alternates two streams works in both arenas
-    for (int l = 0; l < 2; l++) {
+    for (int l = 0; l < 2 && rc == E_OK; l++) {
       lane_ = l;
-      if (!scratch(S_TBL, m * ent) || !scratch(S_JAC, m * 4 * L * 4) || !scratch(S_PRE, m * L * 4) ||
-          !scratch(S_U12, m * 2 * L * 4) || !scratch(S_VALID, m)) {
-        lane_ = 0;
-        return fail(E_NOMEM, "scratch allocation failed");
-      }
+      claim<void>(S_TBL, m * ent);
+      claim<void>(S_JAC, m * 4 * L * 4);
+      claim<void>(S_PRE, m * L * 4);
+      claim<void>(S_U12, m * 2 * L * 4);
+      claim<void>(S_VALID, m);
+      rc = claimed();
     }
     lane_ = 0;
-    return E_OK;
+    return rc;
   }
 
  private:
@@ -3525,6 +3569,7 @@ class Engine {
   int next_base_ = 0;                        // handles are never reused
   Buf scratch_[2][S_COUNT];   // one scratch arena per compute lane (see pipelined())
   int lane_ = 0;
+  bool claim_failed_ = false;   // a claim() since the last claimed() got no memory
   Buf staging_[2 * STAGED_MAX];   // the host-buffer calls' device copies: inputs, then outputs (stage())
   std::vector<RtField> custom_;  // user-defined curves of this context (id = CURVE_CUSTOM0 + index)
   std::vector<RtPmodN> custom_pmn_;  // p mod n of each (zero for a curve without a domain): rt_recover_prep's argument
@@ -3599,13 +3644,9 @@ template <class BK>
 template <class CV>
 int Engine<BK>::normalize_chunk(size_t n, const u32* jac, u8* out_xy, u8* out_inf, typename Work<CV>::A* raw) {
   typedef Work<CV> W;
-  u32* pre = (u32*)scratch(S_PRE, n * W::NS * 4);
-  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
-  const int K = norm_batch_for(n);
-  size_t T = (n + K - 1) / K;
-  FnNormalize<CV> f{T, n, K, jac, pre, out_xy, out_inf, raw};
-  bk.launch(f, T);
-  return E_OK;
+  u32* pre = claim<u32>(S_PRE, n * W::NS * 4);
+  if (int rc = claimed()) return rc;
+  return launch_inv<Route::here, FnNormalize<CV>>(field_inv(n), n, jac, pre, out_xy, out_inf, raw);
 }
 
 
@@ -3620,9 +3661,9 @@ int Engine<BK>::mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u
   // table and a result per half
   const size_t slots = form != Form::FULL ? (size_t)W::template stride<true>() : (size_t)W::template stride<false>();
   const size_t halves = parted(form) ? 2 : 1;
-  typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, halves * n * slots * sizeof(typename W::VT));
-  u32* jac = (u32*)scratch(S_JAC, halves * n * 3 * W::NS * 4);
-  if (!tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
+  auto* tbl = claim<typename W::VT>(S_TBL, halves * n * slots * sizeof(typename W::VT));
+  u32* jac = claim<u32>(S_JAC, halves * n * 3 * W::NS * 4);
+  if (int rc = claimed()) return rc;
   bool launched = false;
   if constexpr (CV::ENDO && W::L <= 8) {
     if (parted(form)) {                     // most SIMDs would idle: the halves of every item apart, then the join
@@ -3671,8 +3712,8 @@ int Engine<BK>::mul_fixed_chunk(size_t n, const u8* k, const typename Work<CV>::
       return E_OK;
     }
   }
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  if (!jac) return fail(E_NOMEM, "scratch allocation failed");
+  u32* jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
+  if (int rc = claimed()) return rc;
   // (two tables: one item per lane at every n, and one normalisation for the sum)
   if (k2) launch_paired<FnMulBase2, CV>(n, k, comb, k2, t2, jac);
   else launch_paired<FnMulFixed, CV>(n, k, comb, jac);
@@ -3686,9 +3727,9 @@ template <class CV>
 int Engine<BK>::mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                    u8* out_xy, u8* out_inf) {
   typedef Work<CV> W;
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  typename W::J* tbl = (typename W::J*)scratch(S_TBL, n * 2 * W::TBLJ * sizeof(typename W::J));
-  if (!tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
+  u32* jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
+  auto* tbl = claim<typename W::J>(S_TBL, n * 2 * W::TBLJ * sizeof(typename W::J));
+  if (int rc = claimed()) return rc;
   FnMulAdd2<CV> f{n, k1, xy1, k2, xy2, tbl, jac};
   bk.launch(f, n);
   int rc = normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
@@ -3708,9 +3749,9 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
     const Form form = form_for<CV>(n);
     // (k1*G + k2*P has no WIDE kernel: a wide batch that is not parted runs the ordinary mul_add_g below)
     if (parted(form)) {                     // most SIMDs would idle: k2's halves and k1's comb apart, then the join
-      u32* pj = (u32*)scratch(S_JAC, 3 * n * 3 * W::NS * 4);
-      typename W::VT* pt = (typename W::VT*)scratch(S_TBL, 2 * n * (size_t)W::template stride<true>() * sizeof(typename W::VT));
-      if (!pt || !pj) return fail(E_NOMEM, "scratch allocation failed");
+      u32* pj = claim<u32>(S_JAC, 3 * n * 3 * W::NS * 4);
+      auto* pt = claim<typename W::VT>(S_TBL, 2 * n * (size_t)W::template stride<true>() * sizeof(typename W::VT));
+      if (int rc = claimed()) return rc;
       launch_mul_parts<CV>(form, n, k2, xy2, pt, pj, k1);
       FnMulJoin<CV> fj{n, pj, true, xy2, out_xy, out_inf, nullptr};
       return launch_fn(fj, n);
@@ -3718,17 +3759,17 @@ int Engine<BK>::mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* 
   }
   if constexpr (!CV::ENDO && CoopNist<CV>::AVAILABLE) {
     if (n <= coop_grid_of<CV>()) {                 // the ladder of k2 and the comb of k1 on a wave each, joined on one lane
-      u32* pj = (u32*)scratch(S_JAC, 2 * n * 3 * W::NS * 4);
-      if (!pj) return fail(E_NOMEM, "scratch allocation failed");
+      u32* pj = claim<u32>(S_JAC, 2 * n * 3 * W::NS * 4);
+      if (int rc = claimed()) return rc;
       FnMulPartsN<CV> fc{n, k2, xy2, pj, k1, comb_of<CV>()};
       bk.launch_coop(fc, 2 * n);
       FnMulJoin<CV> fj{n, pj, false, xy2, out_xy, out_inf, nullptr};
       return launch_fn(fj, n);
     }
   }
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
-  if (!tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
+  u32* jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
+  auto* tbl = claim<typename W::VT>(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
+  if (int rc = claimed()) return rc;
   launch_paired<FnMulAddG, CV>(n, k1, k2, xy2, comb_of<CV>(), tbl, jac);
   int rc = normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
   if (rc == E_OK && out_inf) {
@@ -3773,19 +3814,18 @@ int Engine<BK>::rt_ecdh_ladder(size_t n, const u8* k, const u8* pub, size_t len,
   typedef Work<CvCustom> W;
   // the points, the order as scalars and the flags live across the ladder kernel, which uses
   // S_TBL / S_JAC only (as in rt_recover_chunk)
-  flags = (u8*)scratch(S_VALID, 2 * n);
-  if (!flags) return fail(E_NOMEM, "scratch allocation failed");
+  flags = claim<u8>(S_VALID, 2 * n);
   u8* pts = nullptr;
   u8* scal = nullptr;
   typename W::VT* tbl = nullptr;
   jac = nullptr;
   if (ladder) {
-    pts = (u8*)scratch(S_U12, n * (size_t)(k ? 64 : 96));
-    tbl = (typename W::VT*)scratch(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
-    jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-    if (!pts || !tbl || !jac) return fail(E_NOMEM, "scratch allocation failed");
-    if (!k) scal = pts + n * 64;
+    pts = claim<u8>(S_U12, n * (size_t)(k ? 64 : 96));
+    tbl = claim<typename W::VT>(S_TBL, n * (size_t)W::template stride<false>() * sizeof(typename W::VT));
+    jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
   }
+  if (int rc = claimed()) return rc;
+  if (ladder && !k) scal = pts + n * 64;
   FnRtEcdhFront f0{n, pub, len, custom_pbytes(), pts, flags + n, flags, scal};
   bk.launch(f0, n);
   if (ladder) launch_paired<FnMulVar, CvCustom>(n, k ? k : (const u8*)scal, (const u8*)pts, tbl, jac);   // form_for<CvCustom>: FULL
@@ -3800,13 +3840,9 @@ int Engine<BK>::rt_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len
   u32* jac;
   int rc = rt_ecdh_ladder(n, k, pub, len, true, flags, jac);
   if (rc) return rc;
-  u32* pre = (u32*)scratch(S_PRE, n * W::NS * 4);
-  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
-  const int K = norm_batch_for(n);
-  const size_t T = (n + K - 1) / K;
-  FnRtDeriveFinish f1{T, n, K, jac, flags + n, flags, pre, out_x, status, err};
-  bk.launch(f1, T);
-  return E_OK;
+  u32* pre = claim<u32>(S_PRE, n * W::NS * 4);
+  if ((rc = claimed())) return rc;
+  return launch_inv<Route::here, FnRtDeriveFinish>(field_inv(n), n, jac, flags + n, flags, pre, out_x, status, err);
 }
 
 template <class BK>
@@ -3828,10 +3864,10 @@ int Engine<BK>::rt_recover_chunk(size_t n, const u8* hash, int hash_len, const u
   typedef Work<CvCustomDomain> W;
   // the scalars, the x-coordinates and the points R live across the ladder kernels, which use
   // S_TBL / S_JAC / S_PRE only (as in recover_chunk)
-  u8* buf = (u8*)scratch(S_U12, n * (2 * 32 + 3 * 32));
-  u8* flags = (u8*)scratch(S_VALID, 3 * n);
-  u32* pre = (u32*)scratch(S_PRE, n * W::LN * 4);
-  if (!buf || !flags || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  u8* buf = claim<u8>(S_U12, n * (2 * 32 + 3 * 32));
+  u8* flags = claim<u8>(S_VALID, 3 * n);
+  u32* pre = claim<u32>(S_PRE, n * W::LN * 4);
+  if (int rc = claimed()) return rc;
   u8* s1 = buf;
   u8* s2 = s1 + n * 32;
   u8* xs = s2 + n * 32;
@@ -3839,11 +3875,8 @@ int Engine<BK>::rt_recover_chunk(size_t n, const u8* hash, int hash_len, const u
   u8* odd = flags;
   u8* dec_st = flags + n;
   u8* inf = flags + 2 * n;
-  const int Kr = inv_batch_for(n, INV_BATCH_N);
-  const size_t T = (n + Kr - 1) / Kr;
-  FnRtRecoverPrep f1{T, n, Kr, custom_pmn_[(size_t)(custom_curve_ - CURVE_CUSTOM0)], hash, hash_len, r, s, recid,
-                     pre, xs, odd, s1, s2, out_status};
-  bk.launch(f1, T);
+  launch_inv<Route::here, FnRtRecoverPrep>(scalar_inv(n), n, custom_pmn_[(size_t)(custom_curve_ - CURVE_CUSTOM0)], hash,
+                                           hash_len, r, s, recid, pre, xs, odd, s1, s2, out_status);
   int rc = rt_wire_chunk(OP_RT_DECOMPRESS, n, xs, odd, 0, nullptr, rxy, dec_st, nullptr);
   if (rc) return rc;
   rc = mul_add_g_chunk<CvCustomDomain>(n, s1, s2, rxy, out_xy, inf);           // s1 * G + s2 * R
@@ -3859,47 +3892,33 @@ int Engine<BK>::rt_sign_chunk(size_t n, const u8* hash, int hash_len, int shift,
                               const u8* nonces, int drbg_hash, int canonical, u8* out_r, u8* out_s,
                               u8* out_recid, u8* out_ok) {
   typedef Work<CvCustomDomain> W;
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  u8* kg = (u8*)scratch(S_U12, n * (2 * W::BYTES + 1));          // k*G affine + infinity flags
-  if (!jac || !kg) return fail(E_NOMEM, "scratch allocation failed");
+  u32* jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
+  u8* kg = claim<u8>(S_U12, n * (2 * W::BYTES + 1));             // k*G affine + infinity flags
+  u8* drawn = nonces ? nullptr : claim<u8>(S_TBL, n * W::NBYTES);   // the passes below use S_JAC / S_U12 / S_PRE
+  if (int rc = claimed()) return rc;
   u8* kg_inf = kg + n * 2 * W::BYTES;
   if (!nonces) {
-    u8* drawn = (u8*)scratch(S_TBL, n * W::NBYTES);       // the passes below use S_JAC / S_U12 / S_PRE
-    if (!drawn) return fail(E_NOMEM, "scratch allocation failed");
-    if (drbg_hash == 0) {
-      FnRtSignNonce<Sha256> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
-      bk.launch(f, n);
-    } else if (drbg_hash == 1) {
-      FnRtSignNonce<Sha384> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
-      bk.launch(f, n);
-    } else {
-      FnRtSignNonce<Sha512> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
-      bk.launch(f, n);
-    }
+    draw_nonces(drbg_hash, n, hash, hash_len, shift, priv, drawn);   // (group 17 is this body's own unit too)
     nonces = drawn;
   }
   FnRtSignMul f1{n, nonces, comb_of<CvCustomDomain>(), jac};
   bk.launch(f1, n);
   int rc = normalize_chunk<CvCustomDomain>(n, jac, kg, kg_inf, nullptr);
   if (rc) return rc;
-  u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
-  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
-  const int Kf = inv_batch_for(n, INV_BATCH_N);
-  const size_t T = (n + Kf - 1) / Kf;
-  FnRtSignFinish f2{T, n, Kf, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre,
-                    out_r, out_s, out_recid, out_ok};
-  bk.launch(f2, T);
-  return E_OK;
+  u32* pre = claim<u32>(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
+  if ((rc = claimed())) return rc;
+  return launch_inv<Route::here, FnRtSignFinish>(scalar_inv(n), n, hash, hash_len, shift, priv, nonces, kg, kg_inf,
+                                                 canonical, pre, out_r, out_s, out_recid, out_ok);
 }
 
 template <class BK>
 template <int U>
 int Engine<BK>::edc_chunk(int op, size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                           const u8* a, const u8* b, u8* out_xy, u8* out_inf) {
-  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, n * 16 * sizeof(EdcWork::P));
-  if (!proj || !pre || !tbl) return fail(E_NOMEM, "scratch allocation failed");
+  u32* proj = claim<u32>(S_JAC, n * 3 * 8 * 4);
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  auto* tbl = claim<EdcWork::P>(S_TBL, n * 16 * sizeof(EdcWork::P));
+  if (int rc = claimed()) return rc;
   if (op == 0) {
     FnEdcMulVar f{n, k1, xy1, tbl, proj};
     bk.launch(f, n);
@@ -3910,10 +3929,7 @@ int Engine<BK>::edc_chunk(int op, size_t n, const u8* k1, const u8* xy1, const u
     FnEdcPointAdd f{n, xy1, a, xy2, b, proj};
     bk.launch(f, n);
   }
-  const int K = norm_batch_for(n);
-  size_t T = (n + K - 1) / K;
-  FnEdcNormalize g{T, n, K, proj, pre, out_xy, out_inf};
-  bk.launch(g, T);
+  launch_inv<Route::here, FnEdcNormalize>(field_inv(n), n, proj, pre, out_xy, out_inf);
   if (op != 2 && out_inf) {                       // Point#add is one formula: the reference's own
     FnEdcDomainMark h{n, xy1, op == 1 ? xy2 : nullptr, out_xy, out_inf};
     bk.launch(h, n);
@@ -3929,21 +3945,17 @@ int Engine<BK>::montc_chunk(int op, size_t n, const u8* k, const u8* x, u8* out_
     bk.launch(fv, n);
     return E_OK;
   }
-  u32* xz = (u32*)scratch(S_JAC, n * 2 * 8 * 4);
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  u8* vst = op == OP_MONTC_DERIVE ? (u8*)scratch(S_VALID, n) : nullptr;
-  if (!xz || !pre || (op == OP_MONTC_DERIVE && !vst)) return fail(E_NOMEM, "scratch allocation failed");
+  u32* xz = claim<u32>(S_JAC, n * 2 * 8 * 4);
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  u8* vst = op == OP_MONTC_DERIVE ? claim<u8>(S_VALID, n) : nullptr;
+  if (int rc = claimed()) return rc;
   if (vst) {
     FnMontcValidate fv{n, x, vst};
     bk.launch(fv, n);
   }
   FnMontcLadder f{n, k, x, xz};
   bk.launch(f, n);
-  const int K = norm_batch_for(n);
-  const size_t T = (n + K - 1) / K;
-  FnMontcNormalize g{T, n, K, xz, pre, vst, out_x, out_flag};
-  bk.launch(g, T);
-  return E_OK;
+  return launch_inv<Route::here, FnMontcNormalize>(field_inv(n), n, xz, pre, vst, out_x, out_flag);
 }
 
 template <class BK>
@@ -3952,10 +3964,18 @@ int Engine<BK>::edk_point_chunk(size_t n, const u8* a, const u8* b, int from_y, 
                                 u8* valid) {
   // the point under construction, the decoder's status and what the root pass owes each item live
   // across the three passes; out_xy == null: the finished point stays in S_U12 for the ladder
-  u8* pts = (u8*)scratch(S_U12, n * 64);
-  u8* flags = (u8*)scratch(S_VALID, 3 * n);
-  u32* nd = (u32*)scratch(S_PRE, n * 24 * 4);                    // numerator, denominator, prefix products
-  if (!pts || !flags || !nd) return fail(E_NOMEM, "scratch allocation failed");
+  u8* pts = claim<u8>(S_U12, n * 64);
+  u8* flags = claim<u8>(S_VALID, 3 * n);
+  u32* nd = claim<u32>(S_PRE, n * 24 * 4);                       // numerator, denominator, prefix products
+  if (int rc = claimed()) return rc;
+  edk_point_passes(n, a, b, from_y, len, pts, flags, nd, out_xy, out_st, valid);
+  return E_OK;
+}
+
+template <class BK>
+template <int U>
+void Engine<BK>::edk_point_passes(size_t n, const u8* a, const u8* b, int from_y, size_t len, u8* pts, u8* flags,
+                                  u32* nd, u8* out_xy, u8* out_st, u8* valid) {
   u8* st = flags;
   u8* need = flags + n;
   u32* pre = nd + n * 16;
@@ -3966,40 +3986,32 @@ int Engine<BK>::edk_point_chunk(size_t n, const u8* a, const u8* b, int from_y, 
     FnEdcKeyFrontCoord f{n, a, b, from_y, pts, st, need, nd};
     bk.launch(f, n);
   }
-  const int K = norm_batch_for(n);
-  const size_t T = (n + K - 1) / K;
-  FnEdcKeyQuotient q{T, n, K, nd, pre};
-  bk.launch(q, T);
+  launch_inv<Route::here, FnEdcKeyQuotient>(field_inv(n), n, nd, pre);
   FnEdcKeyRoot r{n, nd, pts, st, need, out_xy ? out_xy : pts, out_st, valid};
   bk.launch(r, n);
-  return E_OK;
 }
 
 template <class BK>
 template <int U>
 int Engine<BK>::edk_derive_chunk(size_t n, const u8* k, const u8* pub, size_t len, u8* out_x, u8* status, u8* err) {
-  u8* pts = (u8*)scratch(S_U12, n * 64);
-  u8* flags = (u8*)scratch(S_VALID, 3 * n);
-  u32* pre = (u32*)scratch(S_PRE, n * 24 * 4);
-  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
-  EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, n * 8 * sizeof(EdcWork::P));
-  if (!pts || !flags || !pre || !proj || !tbl) return fail(E_NOMEM, "scratch allocation failed");
+  u8* pts = claim<u8>(S_U12, n * 64);
+  u8* flags = claim<u8>(S_VALID, 3 * n);
+  u32* pre = claim<u32>(S_PRE, n * 24 * 4);
+  u32* proj = claim<u32>(S_JAC, n * 3 * 8 * 4);
+  auto* tbl = claim<EdcWork::P>(S_TBL, n * 8 * sizeof(EdcWork::P));
+  if (int rc = claimed()) return rc;
   u8* dec_st = flags;
   u8* valid = flags + 2 * n;
-  if (len) {
-    int rc = edk_point_chunk(n, pub, nullptr, 0, len, nullptr, dec_st, valid);   // the same buffers, already sized
-    if (rc) return rc;
+  if (len) {                                    // decodePoint into pts, in the buffers held here
+    edk_point_passes(n, pub, nullptr, 0, len, pts, flags, pre, nullptr, dec_st, valid);
   } else {
     FnEdcKeyFrontXy f0{n, pub, pts, valid, nullptr, nullptr, EdcKey::Scalar{}};
     bk.launch(f0, n);
   }
   FnEdcMulVar lad{n, k, pts, tbl, proj};
   bk.launch(lad, n);
-  const int K = norm_batch_for(n);
-  const size_t T = (n + K - 1) / K;
-  FnEdcKeyDeriveFinish f1{T, n, K, proj, len ? dec_st : nullptr, valid, pre, out_x, status, err};
-  bk.launch(f1, T);
-  return E_OK;
+  return launch_inv<Route::here, FnEdcKeyDeriveFinish>(field_inv(n), n, proj, len ? dec_st : nullptr, valid, pre, out_x,
+                                                       status, err);
 }
 
 template <class BK>
@@ -4013,18 +4025,19 @@ int Engine<BK>::edk_encode_chunk(size_t n, const u8* xy, int compact, u8* out_en
 template <class BK>
 template <int U>
 int Engine<BK>::edk_validate_chunk(size_t n, const u8* xy, const u8* order, u8* status) {
-  u8* flags = (u8*)scratch(S_VALID, 3 * n);
-  if (!flags) return fail(E_NOMEM, "scratch allocation failed");
+  u8* flags = claim<u8>(S_VALID, 3 * n);
   u8* pts = nullptr;
   u8* scal = nullptr;
   u32* proj = nullptr;
   EdcWork::P* tbl = nullptr;
   EdcKey::Scalar ord{};
   if (order) {
-    pts = (u8*)scratch(S_U12, n * 96);                           // the points, then `order` once per item
-    proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
-    tbl = (EdcWork::P*)scratch(S_TBL, n * 8 * sizeof(EdcWork::P));
-    if (!pts || !proj || !tbl) return fail(E_NOMEM, "scratch allocation failed");
+    pts = claim<u8>(S_U12, n * 96);                              // the points, then `order` once per item
+    proj = claim<u32>(S_JAC, n * 3 * 8 * 4);
+    tbl = claim<EdcWork::P>(S_TBL, n * 8 * sizeof(EdcWork::P));
+  }
+  if (int rc = claimed()) return rc;
+  if (order) {
     scal = pts + n * 64;
     memcpy(ord.b, order, 32);
   }
@@ -4066,70 +4079,48 @@ template <class BK>
 template <int U>
 int Engine<BK>::edc_verify_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
                                  const u8* pub, u8* ok, u8* st) {
-  EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, n * 8 * sizeof(EdcWork::P));
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  u32* u12 = (u32*)scratch(S_U12, n * 2 * 8 * 4);
-  u8* flags = (u8*)scratch(S_VALID, 2 * n);
-  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
-  if (!tbl || !pre || !u12 || !flags || !proj) return fail(E_NOMEM, "scratch allocation failed");
+  auto* tbl = claim<EdcWork::P>(S_TBL, n * 8 * sizeof(EdcWork::P));
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  u32* u12 = claim<u32>(S_U12, n * 2 * 8 * 4);
+  u8* flags = claim<u8>(S_VALID, 2 * n);
+  u32* proj = claim<u32>(S_JAC, n * 3 * 8 * 4);
+  if (int rc = claimed()) return rc;
   u8* valid = flags;
   u8* onc = flags + n;
   const u32* gt = (const u32*)comb_[custom_curve_];
-  const int K = inv_batch_for(n, INV_BATCH_N);
-  const size_t T = (n + K - 1) / K;
-  FnEcdsaPrep<CvCustomDomain> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};   // the short domain's: n alone
-  launch_fn(f1, T);
+  // the short domain's prep, in its unit (group 17): it reads n from that unit's block
+  launch_inv<Route::unit, FnEcdsaPrep<CvCustomDomain>>(scalar_inv(n), n, hash, hash_len, shift, r, s, pre, u12, valid);
   FnEdcEcdsaLadder f2{n, u12, pub, gt, tbl, proj, onc};
   bk.launch(f2, n);
   if (custom_[(size_t)(custom_curve_ - CURVE_CUSTOM0)].ncand != RT_NO_MAXWELL) {
     FnEdcEcdsaEq f3{n, proj, valid, onc, r, ok, st};
     bk.launch(f3, n);
-  } else {
-    const int Kn = norm_batch_for(n);
-    const size_t Tn = (n + Kn - 1) / Kn;
-    FnEdcEcdsaEqAffine f3{Tn, n, Kn, proj, valid, onc, r, pre, ok, st};
-    bk.launch(f3, Tn);
+    return E_OK;
   }
-  return E_OK;
+  return launch_inv<Route::here, FnEdcEcdsaEqAffine>(field_inv(n), n, proj, valid, onc, r, pre, ok, st);
 }
 
 template <class BK>
 template <int U>
 int Engine<BK>::edc_sign_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv, const u8* nonces,
                                int drbg_hash, int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
-  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
-  u8* kg = (u8*)scratch(S_U12, n * (64 + 1));                    // k*G affine + infinity flags
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  if (!proj || !kg || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  u32* proj = claim<u32>(S_JAC, n * 3 * 8 * 4);
+  u8* kg = claim<u8>(S_U12, n * (64 + 1));                       // k*G affine + infinity flags
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  u8* drawn = nonces ? nullptr : claim<u8>(S_TBL, n * 32);
+  if (int rc = claimed()) return rc;
   u8* kg_inf = kg + n * 64;
   const u32* gt = (const u32*)comb_[custom_curve_];
+  // the nonces and the finish are the short domain's, in its unit (group 17): they read n from that unit's block
   if (!nonces) {
-    u8* drawn = (u8*)scratch(S_TBL, n * 32);
-    if (!drawn) return fail(E_NOMEM, "scratch allocation failed");
-    if (drbg_hash == 0) {
-      FnRtSignNonce<Sha256> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
-      launch_fn(f, n);
-    } else if (drbg_hash == 1) {
-      FnRtSignNonce<Sha384> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
-      launch_fn(f, n);
-    } else {
-      FnRtSignNonce<Sha512> f{n, hash, hash_len, shift, priv, CUSTOM_SIGN_MAX_DRAWS, drawn};
-      launch_fn(f, n);
-    }
+    draw_nonces(drbg_hash, n, hash, hash_len, shift, priv, drawn);
     nonces = drawn;
   }
   FnEdcSignMul f1{n, nonces, gt, proj};
   bk.launch(f1, n);
-  const int Kn = norm_batch_for(n);
-  const size_t Tn = (n + Kn - 1) / Kn;
-  FnEdcSignNorm f2{Tn, n, Kn, proj, pre, kg, kg_inf};
-  bk.launch(f2, Tn);
-  const int Kf = inv_batch_for(n, INV_BATCH_N);
-  const size_t T = (n + Kf - 1) / Kf;
-  FnRtSignFinish f3{T, n, Kf, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre,
-                    out_r, out_s, out_recid, out_ok};
-  launch_fn(f3, T);
-  return E_OK;
+  launch_inv<Route::here, FnEdcSignNorm>(field_inv(n), n, proj, pre, kg, kg_inf);
+  return launch_inv<Route::unit, FnRtSignFinish>(scalar_inv(n), n, hash, hash_len, shift, priv, nonces, kg, kg_inf,
+                                                 canonical, pre, out_r, out_s, out_recid, out_ok);
 }
 
 template <class BK>
@@ -4147,11 +4138,11 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
   const Form form = form_for<CV>(n);
   const bool wide = form != Form::FULL;
   const size_t slots = wide ? (size_t)W::template stride<true>() : (size_t)W::template stride<false>();
-  typename W::VT* tbl = (typename W::VT*)scratch(S_TBL, n * slots * sizeof(typename W::VT));
-  u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
-  u32* u12 = (u32*)scratch(S_U12, n * 2 * W::LN * 4);
-  u8* valid = (u8*)scratch(S_VALID, n);
-  if (!tbl || !pre || !u12 || !valid) return fail(E_NOMEM, "scratch allocation failed");
+  auto* tbl = claim<typename W::VT>(S_TBL, n * slots * sizeof(typename W::VT));
+  u32* pre = claim<u32>(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
+  u32* u12 = claim<u32>(S_U12, n * 2 * W::LN * 4);
+  u8* valid = claim<u8>(S_VALID, n);
+  if (int rc = claimed()) return rc;
   if constexpr (CV::ENDO && W::L <= 8 && ELL_SPLIT_SMALL_VERIFY) {
     // (the two-kernel form on a FULL grid was measured too, round 4: 8.22 -> 8.37 ms per 2^20 --
     // the table kernel alone takes 0.65 ms where building the table inside ecdsa_main costs
@@ -4173,6 +4164,8 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
         FnEcdsaPrepTableR fptr{n, pu, hash, hash_len, shift, r, s, pre, u12, valid, pub, tbl};
         bk.launch_coop(fptr, pu + (n + 3) / 4);
       } else {
+        // a geometry of its own, not scalar_inv()'s: the prep shares the launch with the table, so K
+        // comes from inv_batch_beside() and the prep's threads are padded to whole workgroups
         const int Ks = inv_batch_beside(n, INV_BATCH_N);
         const size_t Ts = (n + Ks - 1) / Ks;
         const size_t tpad = (Ts + 127) & ~(size_t)127;          // whole workgroups of either kind
@@ -4185,8 +4178,8 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
       }
       // most SIMDs would idle beside this batch: the half ladders and the comb of every item as
       // three parts, then the join
-      u32* jac = (u32*)scratch(S_JAC, n * 3 * 3 * W::NS * 4);
-      if (!jac) return fail(E_NOMEM, "scratch allocation failed");
+      u32* jac = claim<u32>(S_JAC, n * 3 * 3 * W::NS * 4);
+      if (int rc = claimed()) return rc;
       const size_t units = part_units(form, n, 3);
       if (form == Form::PARTS_WAVE) {         // every part on a wave of its own, lanes-per-item arithmetic
         FnEcdsaPartsK256<false> fc{n, u12, comb_of<CV>(), tbl, jac};
@@ -4208,9 +4201,9 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
       // (one inversion per item), then the ladder and the comb of every item on a WAVE each (the
       // row layer, coop_mont.h), and the one-lane join
       typedef CoopNist<CV> CW;
-      u32* jac = (u32*)scratch(S_JAC, n * 2 * 3 * W::NS * 4);
-      typename CW::A* gt = (typename CW::A*)scratch(S_TBL, n * CW::TABLE_BYTES);
-      if (!jac || !gt) return fail(E_NOMEM, "scratch allocation failed");
+      u32* jac = claim<u32>(S_JAC, n * 2 * 3 * W::NS * 4);
+      auto* gt = claim<typename CW::A>(S_TBL, n * CW::TABLE_BYTES);
+      if (int rc = claimed()) return rc;
       // the prep on a wave per item, the window table of the key on another, one launch ...
       FnEcdsaPrepTableN<CV> fpt{n, hash, hash_len, shift, r, s, pre, u12, valid, pub, gt};
       bk.launch_coop(fpt, 2 * n);
@@ -4221,10 +4214,7 @@ int Engine<BK>::ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, c
       return launch_fn(fj, n);
     }
   }
-  const int K = inv_batch_for(n, INV_BATCH_N);
-  size_t T = (n + K - 1) / K;
-  FnEcdsaPrep<CV> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};
-  launch_fn(f1, T);
+  launch_inv<Route::unit, FnEcdsaPrep<CV>>(scalar_inv(n), n, hash, hash_len, shift, r, s, pre, u12, valid);
   if constexpr (CV::ENDO && W::L <= 8) {
     if (wide) {                             // at most three waves per SIMD: the register-rich tuning
       FnEcdsaMain<CV, 3, true> f2{n, u12, valid, r, pub, comb_of<CV>(), tbl, ok, st};
@@ -4240,14 +4230,11 @@ template <class CV>
 int Engine<BK>::ecdsa_base_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
                                  const typename Work<CV>::A* tg, const typename Work<CV>::A* tq, u8* ok) {
   typedef Work<CV> W;
-  u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
-  u32* u12 = (u32*)scratch(S_U12, n * 2 * W::LN * 4);
-  u8* valid = (u8*)scratch(S_VALID, n);
-  if (!pre || !u12 || !valid) return fail(E_NOMEM, "scratch allocation failed");
-  const int K = inv_batch_for(n, INV_BATCH_N);
-  const size_t T = (n + K - 1) / K;
-  FnEcdsaPrep<CV> f1{T, n, K, hash, hash_len, shift, r, s, pre, u12, valid};
-  launch_fn(f1, T);
+  u32* pre = claim<u32>(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
+  u32* u12 = claim<u32>(S_U12, n * 2 * W::LN * 4);
+  u8* valid = claim<u8>(S_VALID, n);
+  if (int rc = claimed()) return rc;
+  launch_inv<Route::unit, FnEcdsaPrep<CV>>(scalar_inv(n), n, hash, hash_len, shift, r, s, pre, u12, valid);
   launch_paired<FnEcdsaBase, CV>(n, u12, valid, r, tg, tq, ok);
   return E_OK;
 }
@@ -4274,21 +4261,17 @@ int Engine<BK>::ensure_ed_comb() {
 template <class BK>
 template <int U>
 int Engine<BK>::ed_normalize_chunk(size_t n, const u32* ext, u8* out_xy, u8* out_inf, EdWork::P* raw) {
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
-  const int K = norm_batch_for(n);
-  size_t T = (n + K - 1) / K;
-  FnEdNormalize f{T, n, K, ext, pre, out_xy, out_inf, raw};
-  bk.launch(f, T);
-  return E_OK;
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  if (int rc = claimed()) return rc;
+  return launch_inv<Route::here, FnEdNormalize>(field_inv(n), n, ext, pre, out_xy, out_inf, raw);
 }
 
 template <class BK>
 template <int U>
 int Engine<BK>::ed_mul_var_chunk(size_t n, const u8* k, const u8* xy, u8* out_xy, u8* out_inf, EdWork::P* raw) {
-  EdWork::P* tbl = (EdWork::P*)scratch(S_TBL, n * 8 * sizeof(EdWork::P));
-  u32* ext = (u32*)scratch(S_JAC, n * 4 * 8 * 4);
-  if (!tbl || !ext) return fail(E_NOMEM, "scratch allocation failed");
+  auto* tbl = claim<EdWork::P>(S_TBL, n * 8 * sizeof(EdWork::P));
+  u32* ext = claim<u32>(S_JAC, n * 4 * 8 * 4);
+  if (int rc = claimed()) return rc;
   if (n <= coop_grid()) {
     FnEdMulC fc{n, nullptr, nullptr, k, xy, nullptr, ext};
     bk.launch_coop(fc, n);
@@ -4312,8 +4295,8 @@ int Engine<BK>::ed_mul_fixed_chunk(size_t n, const u8* k, u8* out_xy, u8* out_in
     bk.launch_coop(fc, n);
     return E_OK;
   }
-  u32* ext = (u32*)scratch(S_JAC, n * 4 * 8 * 4);
-  if (!ext) return fail(E_NOMEM, "scratch allocation failed");
+  u32* ext = claim<u32>(S_JAC, n * 4 * 8 * 4);
+  if (int rc = claimed()) return rc;
   FnEdMulFixed f{n, k, (const EdWork::P*)comb_[CURVE_ED25519], ext};
   bk.launch(f, n);
   return ed_normalize_chunk(n, ext, out_xy, out_inf, nullptr);
@@ -4323,9 +4306,9 @@ template <class BK>
 template <int U>
 int Engine<BK>::ed_mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                       u8* out_xy, u8* out_inf) {
-  u32* ext = (u32*)scratch(S_JAC, n * 4 * 8 * 4);
-  EdWork::P* tbl = (EdWork::P*)scratch(S_TBL, n * 16 * sizeof(EdWork::P));
-  if (!tbl || !ext) return fail(E_NOMEM, "scratch allocation failed");
+  u32* ext = claim<u32>(S_JAC, n * 4 * 8 * 4);
+  auto* tbl = claim<EdWork::P>(S_TBL, n * 16 * sizeof(EdWork::P));
+  if (int rc = claimed()) return rc;
   if (n <= coop_grid()) {
     FnEdMulC fc{n, k1, xy1, k2, xy2, (const EdWork::P*)comb_[CURVE_ED25519], ext};
     bk.launch_coop(fc, n);
@@ -4371,8 +4354,8 @@ template <class BK>
 template <int U>
 int Engine<BK>::ed_base_mul_chunk(size_t n, const u8* k1, const EdWork::P* t1, const u8* k2, const EdWork::P* t2,
                                   u8* out_xy, u8* out_inf) {
-  u32* ext = (u32*)scratch(S_JAC, n * 4 * 8 * 4);
-  if (!ext) return fail(E_NOMEM, "scratch allocation failed");
+  u32* ext = claim<u32>(S_JAC, n * 4 * 8 * 4);
+  if (int rc = claimed()) return rc;
   if (k2) {
     FnEdMulBase2 f{n, k1, t1, k2, t2, ext};
     bk.launch(f, n);
@@ -4395,17 +4378,13 @@ int Engine<BK>::edc_base_table(const u8* xy, int window_bits, CombTable& out) {
     FnEdBaseCombGen<true> g{m, first, dpt, dk, dp, bits};
     bk.launch(g, m);
   }, [&](size_t m, const u8* dk, const u8* dp, u8*, u8*, void* dst) {
-    u32* proj = (u32*)scratch(S_JAC, m * 3 * 8 * 4);
-    u32* pre = (u32*)scratch(S_PRE, m * 8 * 4);
-    EdcWork::P* tbl = (EdcWork::P*)scratch(S_TBL, m * 8 * sizeof(EdcWork::P));
-    if (!proj || !pre || !tbl) return fail(E_NOMEM, "scratch allocation failed");
+    u32* proj = claim<u32>(S_JAC, m * 3 * 8 * 4);
+    u32* pre = claim<u32>(S_PRE, m * 8 * 4);
+    auto* tbl = claim<EdcWork::P>(S_TBL, m * 8 * sizeof(EdcWork::P));
+    if (int nm = claimed()) return nm;
     FnEdcMulVar f{m, dk, dp, tbl, proj};
     bk.launch(f, m);
-    const int K = norm_batch_for(m);
-    const size_t T = (m + K - 1) / K;
-    FnEdcBaseNormalize h{T, m, K, proj, pre, (EdcWork::A*)dst};
-    bk.launch(h, T);
-    return (int)E_OK;
+    return launch_inv<Route::here, FnEdcBaseNormalize>(field_inv(m), m, proj, pre, (EdcWork::A*)dst);
   }, out);
   bk.free_(dpt);
   return rc;
@@ -4416,9 +4395,9 @@ template <class BK>
 template <int U>
 int Engine<BK>::edc_base_mul_chunk(size_t n, const u8* k1, const EdcWork::A* t1, const u8* k2, const EdcWork::A* t2,
                                    u8* out_xy, u8* out_inf) {
-  u32* proj = (u32*)scratch(S_JAC, n * 3 * 8 * 4);
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  if (!proj || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  u32* proj = claim<u32>(S_JAC, n * 3 * 8 * 4);
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  if (int rc = claimed()) return rc;
   if (k2) {
     FnEdcMulBase2 f{n, k1, t1, k2, t2, proj};
     bk.launch(f, n);
@@ -4426,19 +4405,15 @@ int Engine<BK>::edc_base_mul_chunk(size_t n, const u8* k1, const EdcWork::A* t1,
     FnEdcMulBase f{n, k1, t1, proj};
     bk.launch(f, n);
   }
-  const int K = norm_batch_for(n);
-  const size_t T = (n + K - 1) / K;
-  FnEdcNormalize g{T, n, K, proj, pre, out_xy, out_inf};
-  bk.launch(g, T);
-  return E_OK;
+  return launch_inv<Route::here, FnEdcNormalize>(field_inv(n), n, proj, pre, out_xy, out_inf);
 }
 
 template <class BK>
 template <int U>
 int Engine<BK>::x25519_chunk(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad) {
-  u32* xz = (u32*)scratch(S_JAC, n * 2 * 8 * 4);
-  u32* pre = (u32*)scratch(S_PRE, n * 8 * 4);
-  if (!xz || !pre) return fail(E_NOMEM, "scratch allocation failed");
+  u32* xz = claim<u32>(S_JAC, n * 2 * 8 * 4);
+  u32* pre = claim<u32>(S_PRE, n * 8 * 4);
+  if (int rc = claimed()) return rc;
   if (n <= coop_grid()) {
     FnX25519C fc{n, k, x, xz, out_bad};
     bk.launch_coop(fc, out_bad ? 2 * n : n);
@@ -4450,11 +4425,7 @@ int Engine<BK>::x25519_chunk(size_t n, const u8* k, const u8* x, u8* out_x, u8* 
       bk.launch(fv, n);
     }
   }
-  const int K = norm_batch_for(n);
-  size_t T = (n + K - 1) / K;
-  FnX25519Normalize g{T, n, K, xz, pre, out_x, out_inf};
-  bk.launch(g, T);
-  return E_OK;
+  return launch_inv<Route::here, FnX25519Normalize>(field_inv(n), n, xz, pre, out_x, out_inf);
 }
 
 
@@ -4494,8 +4465,8 @@ int Engine<BK>::codec_chunk(int op, size_t n, const u8* in, size_t len, int flag
   // validate: curve equation, then (flag) n * P == O through the variable-base ladder
   u8* tmp = nullptr;
   if (flag) {
-    tmp = (u8*)scratch(S_U12, n * (3 * (size_t)W::BYTES + 1));
-    if (!tmp) return fail(E_NOMEM, "scratch allocation failed");
+    tmp = claim<u8>(S_U12, n * (3 * (size_t)W::BYTES + 1));
+    if (int rc = claimed()) return rc;
   }
   FnValidatePoint<CV> f{n, in, inf, status, tmp};
   bk.launch(f, n);
@@ -4513,8 +4484,8 @@ template <class CV>
 int Engine<BK>::point_add_chunk(size_t n, const u8* xy1, const u8* inf1, const u8* xy2, const u8* inf2,
                                 u8* out_xy, u8* out_inf) {
   typedef Work<CV> W;
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  if (!jac) return fail(E_NOMEM, "scratch allocation failed");
+  u32* jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
+  if (int rc = claimed()) return rc;
   FnPointAdd<CV> f{n, xy1, inf1, xy2, inf2, jac};
   bk.launch(f, n);
   return normalize_chunk<CV>(n, jac, out_xy, out_inf, nullptr);
@@ -4540,8 +4511,8 @@ template <class CV>
 int Engine<BK>::sign_det_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* priv,
                                int canonical, u8* out_r, u8* out_s, u8* out_recid, u8* out_ok) {
   typedef Work<CV> W;
-  u8* nonces = (u8*)scratch(S_TBL, n * W::NBYTES);        // the sign pipeline uses S_JAC / S_U12 / S_PRE
-  if (!nonces) return fail(E_NOMEM, "scratch allocation failed");
+  u8* nonces = claim<u8>(S_TBL, n * W::NBYTES);           // the sign pipeline uses S_JAC / S_U12 / S_PRE
+  if (int rc = claimed()) return rc;
   FnDetNonce<CV> f{n, hash, hash_len, shift, priv, nonces};
   bk.launch(f, n);
   return sign_chunk<CV>(n, hash, hash_len, shift, priv, nonces, canonical, out_r, out_s, out_recid, out_ok);
@@ -4558,10 +4529,11 @@ int Engine<BK>::recover_chunk(size_t n, const u8* hash, int hash_len, const u8* 
     const size_t B = W::BYTES, NB = W::NBYTES;
     // scalars, the x-coordinates and the decompressed points R live across the ladder kernels,
     // which use S_TBL / S_JAC / S_PRE only
-    u8* buf = (u8*)scratch(S_U12, n * (2 * NB + 3 * B));
-    u8* flags = (u8*)scratch(S_VALID, 3 * n);
-    u32* pre = (u32*)scratch(S_PRE, n * W::LN * 4);
-    if (!buf || !flags || !pre) return fail(E_NOMEM, "scratch allocation failed");
+    u8* buf = claim<u8>(S_U12, n * (2 * NB + 3 * B));
+    u8* flags = claim<u8>(S_VALID, 3 * n);
+    u32* pre = claim<u32>(S_PRE, n * W::LN * 4);
+    int rc = claimed();
+    if (rc) return rc;
     u8* s1 = buf;
     u8* s2 = s1 + n * NB;
     u8* xs = s2 + n * NB;
@@ -4569,7 +4541,6 @@ int Engine<BK>::recover_chunk(size_t n, const u8* hash, int hash_len, const u8* 
     u8* odd = flags;
     u8* dec_ok = flags + n;
     u8* inf = flags + 2 * n;
-    int rc = E_OK;
     bool front = false;
     if constexpr (CV::ID == CURVE_SECP256K1 && CoopK256::AVAILABLE) {
       if (n <= coop_grid()) {                          // a handful of items: R's square root beside r^-1, one launch
@@ -4579,10 +4550,8 @@ int Engine<BK>::recover_chunk(size_t n, const u8* hash, int hash_len, const u8* 
       }
     }
     if (!front) {
-      const int Kr = inv_batch_for(n, INV_BATCH_N);
-      size_t T = (n + Kr - 1) / Kr;
-      FnRecoverPrep<CV> f1{T, n, Kr, hash, hash_len, r, s, recid, pre, xs, odd, s1, s2, out_status};
-      launch_fn(f1, T);
+      launch_inv<Route::unit, FnRecoverPrep<CV>>(scalar_inv(n), n, hash, hash_len, r, s, recid, pre, xs, odd, s1, s2,
+                                                 out_status);
       rc = decompress_chunk<CV>(n, xs, odd, rxy, dec_ok);
       if (rc) return rc;
     }
@@ -4606,8 +4575,8 @@ template <class BK>
 template <int U>
 int Engine<BK>::ed_point_add_chunk(size_t n, const u8* xy1, const u8* inf1, const u8* xy2, const u8* inf2,
                                    u8* out_xy, u8* out_inf) {
-  u32* ext = (u32*)scratch(S_JAC, n * 4 * 8 * 4);
-  if (!ext) return fail(E_NOMEM, "scratch allocation failed");
+  u32* ext = claim<u32>(S_JAC, n * 4 * 8 * 4);
+  if (int rc = claimed()) return rc;
   FnEdPointAdd f{n, xy1, inf1, xy2, inf2, ext};
   bk.launch(f, n);
   return ed_normalize_chunk(n, ext, out_xy, out_inf, nullptr);
@@ -4628,8 +4597,8 @@ int Engine<BK>::ed_codec_chunk(int op, size_t n, const u8* in, int flag, const u
   }
   u8* tmp = nullptr;
   if (flag) {
-    tmp = (u8*)scratch(S_U12, n * (3 * 32 + 1));
-    if (!tmp) return fail(E_NOMEM, "scratch allocation failed");
+    tmp = claim<u8>(S_U12, n * (3 * 32 + 1));
+    if (int rc = claimed()) return rc;
   }
   FnEdValidatePoint f{n, in, inf, status, tmp};
   bk.launch(f, n);
@@ -4648,9 +4617,9 @@ template <int U>
 int Engine<BK>::eddsa_chunk(size_t n, size_t o, const u8* msgs, const u64* off, size_t msg_len,
                             const u8* sigs, const u8* pubs, u8* ok, u8* err) {
   if (n <= coop_grid()) {
-    u32* ext = (u32*)scratch(S_JAC, 2 * n * 3 * 8 * 4);
-    u8* flags = (u8*)scratch(S_VALID, 2 * n);
-    if (!ext || !flags) return fail(E_NOMEM, "scratch allocation failed");
+    u32* ext = claim<u32>(S_JAC, 2 * n * 3 * 8 * 4);
+    u8* flags = claim<u8>(S_VALID, 2 * n);
+    if (int rc = claimed()) return rc;
     FnEddsaPartsC fc{n, off ? msgs : msgs + o * msg_len, off ? off + o : nullptr, msg_len, sigs + o * 64,
                      pubs + o * 32, (const EdWork::P*)comb_[CURVE_ED25519], ext, flags};
     bk.launch_coop(fc, 2 * n);
@@ -4658,8 +4627,8 @@ int Engine<BK>::eddsa_chunk(size_t n, size_t o, const u8* msgs, const u64* off, 
     bk.launch(fj, n);
     return E_OK;
   }
-  EdWork::P* tbl = (EdWork::P*)scratch(S_TBL, n * 8 * sizeof(EdWork::P));
-  if (!tbl) return fail(E_NOMEM, "scratch allocation failed");
+  auto* tbl = claim<EdWork::P>(S_TBL, n * 8 * sizeof(EdWork::P));
+  if (int rc = claimed()) return rc;
   FnEddsaVerify f{n, off ? msgs : msgs + o * msg_len, off ? off + o : nullptr, msg_len,
                   sigs + o * 64, pubs + o * 32, (const EdWork::P*)comb_[CURVE_ED25519], tbl,
                   ok + o, err ? err + o : nullptr};
@@ -4681,10 +4650,10 @@ template <class BK>
 template <int U>
 int Engine<BK>::eddsa_sign_chunk(size_t n, size_t o, const u8* secrets, const u8* msgs, const u64* off,
                                  size_t msg_len, u8* sig, u8* pub) {
-  u8* scal = (u8*)scratch(S_U12, 2 * n * 32);                     // a and r, big-endian
-  u8* xy = (u8*)scratch(S_TBL, 2 * n * 64);                       // A = a G and R = r G, affine
-  u8* inf = (u8*)scratch(S_VALID, 2 * n);
-  if (!scal || !xy || !inf) return fail(E_NOMEM, "scratch allocation failed");
+  u8* scal = claim<u8>(S_U12, 2 * n * 32);                        // a and r, big-endian
+  u8* xy = claim<u8>(S_TBL, 2 * n * 64);                          // A = a G and R = r G, affine
+  u8* inf = claim<u8>(S_VALID, 2 * n);
+  if (int rc = claimed()) return rc;
   const u8* m0 = off ? msgs : msgs + o * msg_len;
   const u64* off0 = off ? off + o : nullptr;
   FnEddsaSignPre f1{n, secrets + o * 32, m0, off0, msg_len, scal};
@@ -4702,9 +4671,9 @@ int Engine<BK>::sign_chunk(size_t n, const u8* hash, int hash_len, int shift, co
                            const u8* nonces, int canonical, u8* out_r, u8* out_s, u8* out_recid,
                            u8* out_ok) {
   typedef Work<CV> W;
-  u32* jac = (u32*)scratch(S_JAC, n * 3 * W::NS * 4);
-  u8* kg = (u8*)scratch(S_U12, n * (2 * W::BYTES + 1));          // k*G affine + infinity flags
-  if (!jac || !kg) return fail(E_NOMEM, "scratch allocation failed");
+  u32* jac = claim<u32>(S_JAC, n * 3 * W::NS * 4);
+  u8* kg = claim<u8>(S_U12, n * (2 * W::BYTES + 1));             // k*G affine + infinity flags
+  if (int rc = claimed()) return rc;
   u8* kg_inf = kg + n * 2 * W::BYTES;
   // a handful of items: k*G (comb + its own inversion) and k^-1 mod n on a wave each, one launch;
   // then the finish without an inversion of its own
@@ -4712,12 +4681,14 @@ int Engine<BK>::sign_chunk(size_t n, const u8* hash, int hash_len, int shift, co
   constexpr bool row_nist = !CV::ENDO && CoopNist<CV>::AVAILABLE;
   if constexpr (row_k256 || row_nist) {
     if (n <= coop_grid_of<CV>()) {
-      u32* kinv = (u32*)scratch(S_PRE, n * 2 * (W::LN > W::NS ? W::LN : W::NS) * 4);
-      if (!kinv) return fail(E_NOMEM, "scratch allocation failed");
+      u32* kinv = claim<u32>(S_PRE, n * 2 * (W::LN > W::NS ? W::LN : W::NS) * 4);
+      if (int rc = claimed()) return rc;
       u32* pre2 = kinv + n * (W::LN > W::NS ? W::LN : W::NS);
       typedef typename std::conditional<row_k256, CoopK256, CoopNist<CV>>::type CW;
       FnSignPartsC<CV, CW> fc{n, nonces, comb_of<CV>(), kg, kg_inf, kinv};
       bk.launch_coop(fc, 2 * n);
+      // a geometry of its own, not scalar_inv()'s: k^-1 is there already (kinv), so the finish
+      // shares no inversion -- one item per thread
       FnSignFinish<CV> f2{n, n, 1, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre2,
                           out_r, out_s, out_recid, out_ok, kinv};
       return launch_fn(f2, n);
@@ -4726,14 +4697,10 @@ int Engine<BK>::sign_chunk(size_t n, const u8* hash, int hash_len, int shift, co
   launch_paired<FnSignMul, CV>(n, nonces, comb_of<CV>(), jac);
   int rc = normalize_chunk<CV>(n, jac, kg, kg_inf, nullptr);
   if (rc) return rc;
-  u32* pre = (u32*)scratch(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
-  if (!pre) return fail(E_NOMEM, "scratch allocation failed");
-  const int Kf = inv_batch_for(n, INV_BATCH_N);
-  size_t T = (n + Kf - 1) / Kf;
-  FnSignFinish<CV> f2{T, n, Kf, hash, hash_len, shift, priv, nonces, kg, kg_inf, canonical, pre,
-                      out_r, out_s, out_recid, out_ok, nullptr};
-  launch_fn(f2, T);
-  return E_OK;
+  u32* pre = claim<u32>(S_PRE, n * (W::LN > W::NS ? W::LN : W::NS) * 4);
+  if ((rc = claimed())) return rc;
+  return launch_inv<Route::unit, FnSignFinish<CV>>(scalar_inv(n), n, hash, hash_len, shift, priv, nonces, kg, kg_inf,
+                                                   canonical, pre, out_r, out_s, out_recid, out_ok, nullptr);
 }
 
 }  // namespace ell

@@ -576,6 +576,29 @@ def check_batch(ctx, spec, bt, n, form="host", cid=None):
     return dx, dst
 
 
+def check_derive_wire_regrow(make_ctx, spec, w, forms, sizes=(3, 257, 3)):
+    """custom_ed_derive_wire in ONE context on one curve at n = 3, 257 and 3 again, each size through
+    every form: the scratch arena regrows between the calls, under the decoder's passes, which work in
+    buffers that the derive chunk holds.  w: one of random_batch()'s wire sets, of at least max(sizes)
+    items.  Every result equals the same batch in a fresh context of its own, and the model's answer."""
+    ctx = make_ctx()
+    try:
+        cid = define(ctx, spec)
+        got = [(n, form, run_derive_wire(ctx, cid, w["k"][:n], w["enc"][:n], form)) for n in sizes for form in forms]
+    finally:
+        ctx.close()
+    for n, form, (ox, st, err) in got:
+        fresh = make_ctx()
+        try:
+            fx, fst, ferr = run_derive_wire(fresh, define(fresh, spec), w["k"][:n], w["enc"][:n], form)
+        finally:
+            fresh.close()
+        tag = (spec["name"], n, form)
+        assert (ox == fx).all() and (st == fst).all() and (err == ferr).all(), tag
+        assert (ox == w["x"][:n]).all() and (st == w["st"][:n]).all() and (err == w["err"][:n]).all(), tag
+    return got
+
+
 def check_symmetry(ctx, spec, n, seed, form="host", cid=None):
     """derive(a, b G) = derive(b, a G) through the engine alone: G from custom_ed_decompress, a G and
     b G from mul_var, the second leg over the wire through custom_ed_encode_points"""

@@ -65,6 +65,14 @@ def test_random_batch_matches_model(ctx, batch, n):
         CK.check_batch(ctx, spec, bt, n, other, cid)
 
 
+def test_derive_wire_while_the_scratch_regrows():
+    """one context, one curve, n = 3, 257, 3 through both forms, each against a context of its own"""
+    spec = CK.spec_of("curve1174")
+    bt = CK.random_batch(spec, 257, seed=sum(map(ord, "curve1174")), distinct=31)
+    got = CK.check_derive_wire_regrow(lambda: elliptic_amd.Context(0), spec, bt["wire"]["comp"], ["host", "dev_torch"])
+    assert len(got) == 6 and set(bt["wire"]["comp"]["st"].tolist()) == {0, 3}      # shared secrets, and keys that do not decode
+
+
 def test_ed25519_by_hand_equals_the_preset(ctx):
     """a = -1 and d = -121665 / 121666 over 2^255 - 19 as a user-defined curve: pointFromY against
     ellgpu_decompress on ed25519, row for row"""

@@ -121,6 +121,14 @@ def test_random_batch_matches_model(ctx, batches, n):
         assert all((u == v).all() for u, v in zip(a, b))
 
 
+def test_derive_wire_while_the_scratch_regrows(hs):
+    """one context, one curve, n = 3, 257, 3 through both forms, each against a context of its own"""
+    spec = CK.spec_of("curve1174")
+    bt = CK.random_batch(spec, 257, SEED["curve1174"], distinct=31)
+    got = CK.check_derive_wire_regrow(lambda: elliptic_amd.Context(0, lib_path=hs), spec, bt["wire"]["comp"], ["host", "dev_np"])
+    assert len(got) == 6 and set(bt["wire"]["comp"]["st"].tolist()) == {0, 3}      # shared secrets, and keys that do not decode
+
+
 @pytest.mark.parametrize("name", ["curve1174", "p224_d11"])
 def test_ecdh_symmetry(ctx, name):
     CK.check_symmetry(ctx, CK.spec_of(name), 5, seed=1)
