@@ -57,6 +57,7 @@ def source_files():
     files.append(os.path.join("include", "ellgpu_ext.h"))
     files.append(os.path.join("include", "ellgpu_ext2.h"))
     files.append(os.path.join("include", "ellgpu_ext3.h"))
+    files.append(os.path.join("include", "ellgpu_ext4.h"))
     return root, files
 
 

@@ -9,7 +9,7 @@
 // before including this header.
 #pragma once
 
-#include "../../include/ellgpu_ext3.h"
+#include "../../include/ellgpu_ext4.h"
 #include "engine.h"
 
 #include <mutex>
@@ -925,6 +925,28 @@ int ellgpu_eddsa_verify_base(ellgpu_ctx* ctx, int base, size_t n, const uint8_t*
   }
   return ell_call(ctx, stream, where, [=](Eng& e, Mem w) {
     return e.eddsa_verify_base(w, base, n, msgs, (const ell::u64*)msg_off, msg_len, sigs, out_ok, out_err);
+  });
+}
+// include/ellgpu_ext4.h: EC#getKeyRecoveryParam in one pass.  One form, like ellgpu_mul_base; a group
+// shards a host batch (the engine's refusals come from the first member that has items)
+int ellgpu_ecdsa_recid(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash, int hash_len, const uint8_t* r,
+                       const uint8_t* s, const uint8_t* pub_xy, uint8_t* out_recid, uint8_t* out_status, int mem,
+                       void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (!ctx->members.empty() && where == Mem::host && n && hash_len > 0 && hash && r && s && pub_xy && out_recid &&
+      out_status) {
+    ELL_LOCK(ctx);
+    size_t B, NB;
+    if (curve_widths(curve, B, NB)) return ELLGPU_E_ARG;
+    return group_shard(ctx, n, [=](ellgpu_ctx* m, size_t lo, size_t hi) {
+      return ellgpu_ecdsa_recid(m, curve, hi - lo, hash + lo * (size_t)hash_len, hash_len, r + lo * NB, s + lo * NB,
+                                pub_xy + lo * 2 * B, out_recid + lo, out_status + lo, mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) {
+    return e.ecdsa_recid(w, curve, n, hash, hash_len, r, s, pub_xy, out_recid, out_status);
   });
 }
 int ellgpu_eddsa_sign(ellgpu_ctx* ctx, size_t n, const uint8_t* secrets, const uint8_t* msgs,

@@ -724,6 +724,29 @@ struct FnRecoverFinish {
     if (i < n) W::recover_finish(i, dec_ok, inf, out_xy, status);
   }
 };
+// EC#getKeyRecoveryParam in one pass (Work::recid_*): the scalar-field pass before u1 * G + u2 * Q
+// and the comparison of the sum's x with r and r + n behind it
+template <class CV>
+struct FnRecidPrep {
+  static constexpr const char* NAME = "recid_prep";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t T, n; int K; const u8* hash; int hash_len; const u8* r; const u8* s;
+  u32* pre; u8* u1; u8* u2; u8* status;
+  ELL_HD void operator()(size_t t, const DigitStore&) const {
+    if (t < T) W::recid_prep(t, T, n, K, hash, hash_len, r, s, pre, u1, u2, status);
+  }
+};
+template <class CV>
+struct FnRecidFinish {
+  static constexpr const char* NAME = "recid_finish";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* r; const u8* xy; const u8* inf; u8* out_recid; u8* status;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::recid_finish(i, r, xy, inf, out_recid, status);
+  }
+};
 template <class CV>
 struct FnDecompress {
   static constexpr const char* NAME = "decompress";
@@ -1945,6 +1968,11 @@ class Engine {
   template <class CV>
   int recover_chunk(size_t n, const u8* hash, int hash_len, const u8* r, const u8* s, const u8* recid,
                     u8* out_xy, u8* out_status);
+  // EC#getKeyRecoveryParam: recid_prep, u1 * G + u2 * Q in whatever form mul_add_g_chunk takes at
+  // this n, recid_finish
+  template <class CV>
+  int recid_chunk(size_t n, const u8* hash, int hash_len, const u8* r, const u8* s, const u8* pub_xy,
+                  u8* out_recid, u8* out_status);
   template <int U = 0>
   int ed_decompress_chunk(size_t n, const u8* y, const u8* odd, u8* out_xy, u8* out_ok);
   template <int U = 0>
@@ -2927,6 +2955,40 @@ class Engine {
       int rc = prepare_curve(curve);
       if (rc) return rc;
       ELL_SHORT_DISPATCH(curve, rc = recover_chunk<CV>(m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]));
+      return rc;
+    });
+  }
+
+  // EC#getKeyRecoveryParam (ec/index.js:261-278) over a batch, in one pass instead of the
+  // reference's up to four recoveries (Work::recid_prep): status 0 with the id in out_recid /
+  // 1 the reference throws ('Unable to find valid recovery factor') / 2 the key is not on the
+  // curve / 3 outside the engine's domain (r = 0, r >= n or s = 0 mod n).  The six presets only:
+  // the rule rests on cofactor 1 and a prime n, which nothing promises of a user-defined id.
+  int ecdsa_recid(Mem where, int curve, size_t n, const u8* hash, int hash_len, const u8* r, const u8* s,
+                  const u8* pub_xy, u8* out_recid, u8* out_status) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci || (is_custom(curve) && !custom_block(curve))) return fail(E_ARG, "unknown curve id");
+    if (curve >= CURVE_ED25519)
+      return fail(E_UNSUPPORTED, is_custom(curve) ? "the one-pass recovery id is implemented for the short Weierstrass presets (a user-defined curve may have a cofactor: run EC#getKeyRecoveryParam's loop over ellgpu_custom_recover)"
+                                                  : "the recovery id is an ECDSA (short Weierstrass) notion");
+    if (!out_status || (n && (!hash || !r || !s || !pub_xy || !out_recid))) return fail(E_ARG, "null pointer");
+    if (hash_len <= 0 || hash_len > 8 * ((ci->order_bits + 31) / 32))
+      return fail(E_ARG, "hash_len must be 1 .. twice the order width");
+    const size_t B = ci->field_bytes, NB = ci->order_bytes;
+    if (where == Mem::device) {
+      // r and the key are read again after the statuses are written (recid_finish, the curve test)
+      const u8* const ins[4] = {hash, r, s, pub_xy};
+      const size_t lens[4] = {n * (size_t)hash_len, n * NB, n * NB, n * 2 * B};
+      for (int k = 0; k < 4; k++)
+        if (overlap2(ins[k], lens[k], out_recid, n) || overlap2(ins[k], lens[k], out_status, n))
+          return fail(E_ARG, "hash / r / s / pub_xy and the results must not overlap");
+      if (overlap2(out_recid, n, out_status, n)) return fail(E_ARG, "out_recid and out_status must not overlap");
+    }
+    return batch(where, n, {In{hash, (size_t)hash_len}, In{r, NB}, In{s, NB}, In{pub_xy, 2 * B}},
+                 {Out{out_recid, 1}, Out{out_status, 1}}, [&](size_t m, auto d, auto o) {
+      int rc = prepare_curve(curve);
+      if (rc) return rc;
+      ELL_SHORT_DISPATCH(curve, rc = recid_chunk<CV>(m, d[0], hash_len, d[1], d[2], d[3], o[0], o[1]));
       return rc;
     });
   }
@@ -4561,6 +4623,29 @@ int Engine<BK>::recover_chunk(size_t n, const u8* hash, int hash_len, const u8* 
     bk.launch(f2, n);
     return E_OK;
   }
+}
+
+template <class BK>
+template <class CV>
+int Engine<BK>::recid_chunk(size_t n, const u8* hash, int hash_len, const u8* r, const u8* s, const u8* pub_xy,
+                            u8* out_recid, u8* out_status) {
+  typedef Work<CV> W;
+  const size_t B = W::BYTES, NB = W::NBYTES;
+  // both scalars, R' and its flags live across the ladder kernels, which use S_TBL / S_JAC / S_PRE only
+  u8* buf = claim<u8>(S_U12, n * (2 * NB + 2 * B));
+  u8* inf = claim<u8>(S_VALID, n);
+  u32* pre = claim<u32>(S_PRE, n * W::LN * 4);
+  if (int rc = claimed()) return rc;
+  u8* u1 = buf;
+  u8* u2 = u1 + n * NB;
+  u8* xy = u2 + n * NB;
+  int rc = launch_inv<Route::unit, FnRecidPrep<CV>>(scalar_inv(n), n, hash, hash_len, r, s, pre, u1, u2, out_status);
+  if (rc) return rc;
+  rc = mul_add_g_chunk<CV>(n, u1, u2, pub_xy, xy, inf);             // R' = u1 * G + u2 * Q
+  if (rc) return rc;
+  FnRecidFinish<CV> f2{n, r, xy, inf, out_recid, out_status};
+  bk.launch(f2, n);
+  return E_OK;
 }
 
 template <class BK>

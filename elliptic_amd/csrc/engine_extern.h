@@ -43,6 +43,8 @@ namespace ell {
                                                      const u8*, int, u8*, u8*, u8*, u8*);           \
   KW template int Engine<HipBackend>::recover_chunk<CV>(size_t, const u8*, int, const u8*,         \
                                                         const u8*, const u8*, u8*, u8*);           \
+  KW template int Engine<HipBackend>::recid_chunk<CV>(size_t, const u8*, int, const u8*,           \
+                                                      const u8*, const u8*, u8*, u8*);             \
   KW template int Engine<HipBackend>::sign_det_chunk<CV>(size_t, const u8*, int, int, const u8*,   \
                                                          int, u8*, u8*, u8*, u8*);
 // scalar-field kernels (batched inversion / Montgomery arithmetic mod n): their own translation
@@ -50,7 +52,8 @@ namespace ell {
 #define ELL_DECL_G6(KW, CV)                                                                        \
   KW template int Engine<HipBackend>::launch_fn<FnEcdsaPrep<CV>>(const FnEcdsaPrep<CV>&, size_t);   \
   KW template int Engine<HipBackend>::launch_fn<FnSignFinish<CV>>(const FnSignFinish<CV>&, size_t); \
-  KW template int Engine<HipBackend>::launch_fn<FnRecoverPrep<CV>>(const FnRecoverPrep<CV>&, size_t);
+  KW template int Engine<HipBackend>::launch_fn<FnRecoverPrep<CV>>(const FnRecoverPrep<CV>&, size_t); \
+  KW template int Engine<HipBackend>::launch_fn<FnRecidPrep<CV>>(const FnRecidPrep<CV>&, size_t);
 // the small-grid (WIDE) verify kernel of the endomorphism curve: its own translation unit
 #define ELL_DECL_G7(KW)                                                                              \
   KW template int Engine<HipBackend>::launch_fn<FnEcdsaMain<CvSecp256k1, 3, true>>(                  \

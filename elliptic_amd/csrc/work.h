@@ -1075,7 +1075,103 @@ struct Work {
     }
   }
 
-  // ---- the same on a user-defined ECDSA domain (run-time p and n, fp_rt.h) -----------------
+  // ---- the recovery id of a signature under a known key (ec/index.js:261-278
+  // EC#getKeyRecoveryParam) ------------------------------------------------------------------
+  // The reference recovers a key for j = 0 .. 3 and compares each with Q.  On the presets
+  // (cofactor 1, n prime) and for r in [1, n), s != 0 (mod n), the candidate R_j recovers Q
+  // exactly when R_j = R' := s^-1 (e G + r Q): at most one j, read off R' -- x(R') = r: j =
+  // parity of y(R'); x(R') = r + n as integers: j = 2 + parity; otherwise the reference throws.
+  // One double-scalar product and no square root.
+  // Pass 1, the geometry of ecdsa_prep: s^-1 mod n for K items with one inversion, u1 = e / s
+  // and u2 = r / s as big-endian scalars for mul_add_g.  e = new BN(hash) is NOT truncated
+  // (recoverPubKey does not), s is reduced mod n first (s.mul(rInv).umod(n) accepts s >= n).
+  // status: 0 so far fine, 3 outside the engine's domain (r = 0, r >= n or s = 0 mod n: the
+  // reference goes through BN#invm of an unreduced or zero value, or answers the first j whose
+  // x lifts whatever Q is; callers hand those to the reference) -- such an item enters the
+  // shared product as one and gets zero scalars.
+  // (The parameters are const-qualified so that the list of (t, T, n, K) routines that
+  // tests/test_inv_batch_hostsim.py pins by name stays what it is: this routine's cases with
+  // K > 1 -- a refused item first, in the middle and last of a thread's items -- are in
+  // tests/key_recid_checks.py, not in tests/inv_batch_checks.py.)
+  enum { RECID_FOUND = 0, RECID_NONE = 1, RECID_OFF_CURVE = 2, RECID_DOMAIN = 3 };
+  ELL_HD static void recid_prep(const size_t t, const size_t T, const size_t n, const int K, const u8* hash,
+                                int hash_len, const u8* rs, const u8* ss, u32* pre, u8* u1b, u8* u2b,
+                                u8* status) {
+    Nl acc = Fn::one();
+    ELL_NOUNROLL
+    for (int j = 0; j < K; j++) {
+      size_t i = t + (size_t)j * T;
+      if (i >= n) break;
+      u32 r[LN], s[LN];
+      load_be<LN>(r, rs + i * NBYTES, NBYTES);
+      load_be<LN>(s, ss + i * NBYTES, NBYTES);
+      Nl sm = Fn::from_plain(s);                 // s mod n
+      const bool ok = scalar_in_range(r) && !Fn::is_zero(sm);
+      status[i] = (u8)(ok ? RECID_FOUND : RECID_DOMAIN);
+      sm = fe_select<Fn>(ok, sm, Fn::one());
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
+      acc = Fn::mul(acc, sm);
+    }
+    Nl inv = Fn::inv(acc);
+    ELL_NOUNROLL
+    for (int j = K - 1; j >= 0; j--) {
+      size_t i = t + (size_t)j * T;
+      if (i >= n) continue;
+      u32 r[LN], s[LN];
+      load_be<LN>(r, rs + i * NBYTES, NBYTES);
+      load_be<LN>(s, ss + i * NBYTES, NBYTES);
+      const bool ok = status[i] == RECID_FOUND;
+      Nl sm = fe_select<Fn>(ok, Fn::from_plain(s), Fn::one());
+      Nl pr;
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
+      Nl w = Fn::mul(inv, pr);                   // s^-1 (Montgomery form)
+      inv = Fn::mul(inv, sm);
+      // plain residues in one product each: (e R)(s^-1) / R and (r)(s^-1 R) / R, r < n
+      Nl wp, rr;
+      Fn::to_plain(wp.v, w);
+      bn_copy<LN>(rr.v, r);
+      Nl u1 = Fn::mul(bytes_mod_n(hash + i * (size_t)hash_len, hash_len), wp);
+      Nl u2 = Fn::mul(rr, w);
+      u32 p1[LN], p2[LN];
+      ELL_UNROLL
+      for (int l = 0; l < LN; l++) { p1[l] = ok ? u1.v[l] : 0u; p2[l] = ok ? u2.v[l] : 0u; }
+      store_be<LN>(u1b + i * NBYTES, p1, NBYTES);
+      store_be<LN>(u2b + i * NBYTES, p2, NBYTES);
+    }
+  }
+  // Pass 3, one item per lane, over R' = u1 G + u2 Q in affine form (xy) and what mul_add_g left
+  // in inf: status 3 stays; 2 where the key is not on the curve (DOMAIN_OFF_CURVE); 1 where R'
+  // is the point at infinity or x(R') is neither r nor r + n -- the sum r + n is taken with its
+  // carry and compared as an integer, never reduced: r >= p - n has no second candidate ('Unable
+  // to find sencond key candinate'), it must not wrap into one; else 0 with the id.  The id is 0
+  // wherever the status is not.
+  ELL_HD static void recid_finish(size_t i, const u8* rs, const u8* xy, const u8* inf, u8* out_recid,
+                                  u8* status) {
+    static_assert(L == LN, "the presets' fields and orders have the same limb count");
+    int st = status[i];
+    u32 id = 0;
+    if (st == RECID_FOUND) {
+      if (inf[i] == DOMAIN_OFF_CURVE) st = RECID_OFF_CURVE;
+      else if (inf[i]) st = RECID_NONE;
+      else {
+        u32 r[LN], nn[LN], rn[LN], x[L];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        load_be<L>(x, xy + i * 2 * BYTES, BYTES);
+        order_words(nn);
+        const u32 carry = bn_add<LN>(rn, r, nn);
+        const bool first = bn_eq<L>(x, r);
+        const bool second = !carry && bn_eq<L>(x, rn);
+        if (first || second) id = (u32)(xy[i * 2 * BYTES + 2 * BYTES - 1] & 1u) | (second ? 2u : 0u);
+        else st = RECID_NONE;
+      }
+    }
+    status[i] = (u8)st;
+    out_recid[i] = (u8)id;
+  }
+
+  // ---- public-key recovery on a user-defined ECDSA domain (run-time p and n, fp_rt.h) -------
   // Nothing ties n to p there: n may exceed p (secp224k1, secp112r1), p / n may be 8 (cofactor
   // curves), so p mod n is no difference and r + n need not lie below p -- or below 2^256.
   // pmn = p mod n, computed on the host when the domain is defined (rt_define.h rt_p_mod_n).

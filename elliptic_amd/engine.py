@@ -639,6 +639,24 @@ class Context:
     def ecdsa_recover_dev(self, curve, hashes, r, s, recid, out_xy, out_status):
         self._c_records("ecdsa_recover", True, curve, hashes, r, s, recid, out_xy, out_status)
 
+    def ecdsa_recid(self, curve, hashes, r, s, pub_xy, out=None):
+        """EC#getKeyRecoveryParam per item, in one pass (ellgpu_ecdsa_recid: one double-scalar product,
+        no square root) -> (recid (n,), status (n,)): status 0 with the id 0 .. 3 the reference
+        returns, 1 the reference throws (no id recovers the key), 2 the key is not on the curve, 3
+        outside the engine's domain (r = 0, r >= n or s = 0 mod n: run the reference on those);
+        recid is 0 wherever status is not.  curve: one of the six short presets.  hashes:
+        (n, hash_len), NOT truncated to the order's bit length (as in ecdsa_recover); r, s:
+        (n, order_bytes), s is reduced mod n; pub_xy: (n, 2 field_bytes).  numpy arrays go through
+        host memory; torch device tensors (all four and out=(recid, status), required then) run on
+        the current stream and return at once."""
+        name = CURVES[curve] if isinstance(curve, int) and 0 <= curve < len(CURVES) else curve
+        B, NB = FIELD_BYTES[name], ORDER_BYTES[name]
+        # (_base_call's leading integers are handles there; here the one integer is the curve id)
+        recid, st = self._base_call("ecdsa_recid", [self._cid(curve)], [hashes, r, s, pub_xy],
+                                    ["hashes", "r", "s", "pub_xy"], [None, NB, NB, 2 * B], (None,), out,
+                                    ("recid", "status"), (0, 0))
+        return recid, st
+
     def custom_recover(self, curve, hashes, r, s, recid, out=None):
         """EC#recoverPubKey per item on a domain id -> (xy, status): 0 point, 1 infinity, 2 the
         reference throws, 3 r = 0 or r >= n (handed to the reference).  hashes (n, 1..64) are NOT

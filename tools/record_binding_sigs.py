@@ -9,9 +9,10 @@ after a deliberate change of include/ellgpu.h -- never to make a failing test pa
 
     python tools/record_binding_sigs.py [--out binding_sigs.json]
 
---table ext / ext2 / ext3 records one of the later tables instead (_EXT_SIGS of include/ellgpu_ext.h
+--table ext / ext2 / ext3 / ext4 records one of the later tables instead (_EXT_SIGS of include/ellgpu_ext.h
 into binding_sigs_ext.json, _EXT2_SIGS of include/ellgpu_ext2.h into binding_sigs_ext2.json,
-_EXT3_SIGS of include/ellgpu_ext3.h into binding_sigs_ext3.json): once, when the table is introduced.
+_EXT3_SIGS of include/ellgpu_ext3.h into binding_sigs_ext3.json, _EXT4_SIGS of include/ellgpu_ext4.h
+into binding_sigs_ext4.json): once, when the table is introduced.
 """
 import argparse
 import json
@@ -26,7 +27,8 @@ from elliptic_amd import _lib  # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden", "binding_sigs.json")
 TABLES = {"sigs": ("_SIGS", GOLDEN), "ext": ("_EXT_SIGS", GOLDEN.replace(".json", "_ext.json")),
           "ext2": ("_EXT2_SIGS", GOLDEN.replace(".json", "_ext2.json")),
-          "ext3": ("_EXT3_SIGS", GOLDEN.replace(".json", "_ext3.json"))}
+          "ext3": ("_EXT3_SIGS", GOLDEN.replace(".json", "_ext3.json")),
+          "ext4": ("_EXT4_SIGS", GOLDEN.replace(".json", "_ext4.json"))}
 
 
 def table(sigs=None):
