@@ -335,4 +335,67 @@ ELL_HD void store_be(u8* p, const u32 (&a)[L], int nb) {
 // little-endian bytes (ed25519 / x25519 wire order is handled by the host
 // layer; the C ABI is big-endian everywhere, see include/ellgpu.h)
 
+// ---- limb planes: an element's stored limbs at base[(first + l) * n + i] ------------------
+// (E: Fe<N> of any field -- the 9 stored limbs of the 29-bit secp256k1 field included)
+template <class E>
+ELL_HD E load_limbs(const u32* base, size_t n, size_t i, int first = 0) {
+  E r;
+  ELL_UNROLL
+  for (int l = 0; l < (int)(sizeof(E) / sizeof(u32)); l++) r.v[l] = base[(size_t)(first + l) * n + i];
+  return r;
+}
+template <class E>
+ELL_HD void store_limbs(u32* base, size_t n, size_t i, int first, const E& a) {
+  ELL_UNROLL
+  for (int l = 0; l < (int)(sizeof(E) / sizeof(u32)); l++) base[(size_t)(first + l) * n + i] = a.v[l];
+}
+
+// ---- one inversion shared by K items (Montgomery's trick) --------------------------------------
+// Thread t of T takes the items t, t + T, ... below n, at most K of them.  The forward pass
+// stores the running product of the items' factors in pre (limb planes 0 ..) before multiplying
+// each factor in; the product is inverted once; the backward pass, in reverse order, hands every
+// item the inverse of its factor (inverse of the running product times the item's prefix) and
+// multiplies the factor back in.  The contract of the two callables:
+//   enter(i)        returns item i's factor -- ONE where the item is refused (zero, out of range,
+//                   a status that is not OK ...); it may record the item's status
+//   leave(i, finv)  does the item's work with finv = 1 / factor and returns the SAME factor again,
+//                   decided from the same flag.  A refused item is one in BOTH passes: a zero would
+//                   poison the other K - 1 items of the thread, a factor that differs between the
+//                   passes would hand every earlier item a wrong inverse.
+struct InvShare {
+  size_t t, T, n;
+  int cnt;                                                   // the thread's items
+  ELL_HD InvShare(size_t t_, size_t T_, size_t n_, int K) : t(t_), T(T_), n(n_), cnt(0) {
+    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
+    if (cnt > K) cnt = K;
+  }
+  ELL_HD size_t item(int j) const { return t + (size_t)j * T; }
+};
+template <class F, class Enter>
+ELL_HD typename F::El inv_share_forward(const InvShare& g, u32* pre, Enter&& enter) {
+  typename F::El acc = F::one();
+  ELL_NOUNROLL
+  for (int j = 0; j < g.cnt; j++) {
+    const size_t i = g.item(j);
+    const typename F::El f = enter(i);
+    store_limbs(pre, g.n, i, 0, acc);
+    acc = F::mul(acc, f);
+  }
+  return acc;
+}
+template <class F, class Leave>
+ELL_HD void inv_share_backward(const InvShare& g, const u32* pre, typename F::El inv, Leave&& leave) {
+  ELL_NOUNROLL
+  for (int j = g.cnt - 1; j >= 0; j--) {
+    const size_t i = g.item(j);
+    const typename F::El finv = F::mul(inv, load_limbs<typename F::El>(pre, g.n, i));
+    inv = F::mul(inv, leave(i, finv));
+  }
+}
+// both passes around one F::inv, for the routines that need nothing between them
+template <class F, class Enter, class Leave>
+ELL_HD void inv_share(const InvShare& g, u32* pre, Enter&& enter, Leave&& leave) {
+  inv_share_backward<F>(g, pre, F::inv(inv_share_forward<F>(g, pre, enter)), leave);
+}
+
 }  // namespace ell

@@ -131,8 +131,8 @@ struct EdcEcdsa {
   // EC#verify's last lines with _maxwellTrick: false for the identity, else eqXToP(r)
   ELL_HD static void eq_maxwell(size_t i, size_t n, const u32* proj, const u8* valid, const u8* on_curve,
                                 const u8* rs, u8* out_ok, u8* out_st) {
-    const El X = EdcKey::load_plane(proj, n, i, 0), Y = EdcKey::load_plane(proj, n, i, 8),
-             Z = EdcKey::load_plane(proj, n, i, 16);
+    const El X = load_limbs<El>(proj, n, i, 0), Y = load_limbs<El>(proj, n, i, 8),
+             Z = load_limbs<El>(proj, n, i, 16);
     u32 r[8], nn[8], pp[8], xc[8];
     load_be<8>(r, rs + i * 32, 32);
     El rx = F::mul(F::from_plain(r), Z);                  // r.toRed(red): r mod p
@@ -158,32 +158,21 @@ struct EdcEcdsa {
   // ... without it: getX().umod(n) == r, thread t: items t, t + T, ...
   ELL_HD static void eq_affine(size_t t, size_t T, size_t n, int K, const u32* proj, const u8* valid,
                                const u8* on_curve, const u8* rs, u32* pre, u8* out_ok, u8* out_st) {
-    int cnt = 0;
-    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
-    if (cnt > K) cnt = K;
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < cnt; j++) {
-      const size_t i = t + (size_t)j * T;
-      El z = EdcKey::load_plane(proj, n, i, 16);
-      z = fe_select<F>(F::is_zero(z), F::one(), z);
-      EdcKey::store_plane(pre, n, i, 0, acc);
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = cnt - 1; j >= 0; j--) {
-      const size_t i = t + (size_t)j * T;
-      const El X = EdcKey::load_plane(proj, n, i, 0), Y = EdcKey::load_plane(proj, n, i, 8),
-               Z = EdcKey::load_plane(proj, n, i, 16);
-      const El zinv = F::mul(inv, EdcKey::load_plane(pre, n, i, 0));
-      inv = F::mul(inv, fe_select<F>(F::is_zero(Z), F::one(), Z));
-      u32 x[8], xn[8], r[8];
-      F::to_plain(x, F::mul(X, zinv));
-      Fn::to_plain(xn, Fn::from_plain(x));                // x mod n: into the order field and out
-      load_be<8>(r, rs + i * 32, 32);
-      WD::store_verdict(i, valid[i], on_curve[i] != 0, bn_eq<8>(xn, r) && !is_infinity(X, Y, Z), out_ok, out_st);
-    }
+    inv_share<F>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        const El z = load_limbs<El>(proj, n, i, 16);
+        return fe_select<F>(F::is_zero(z), F::one(), z);
+      },
+      [&](size_t i, const El& zinv) {
+        const El X = load_limbs<El>(proj, n, i, 0), Y = load_limbs<El>(proj, n, i, 8),
+                 Z = load_limbs<El>(proj, n, i, 16);
+        u32 x[8], xn[8], r[8];
+        F::to_plain(x, F::mul(X, zinv));
+        Fn::to_plain(xn, Fn::from_plain(x));                // x mod n: into the order field and out
+        load_be<8>(r, rs + i * 32, 32);
+        WD::store_verdict(i, valid[i], on_curve[i] != 0, bn_eq<8>(xn, r) && !is_infinity(X, Y, Z), out_ok, out_st);
+        return fe_select<F>(F::is_zero(Z), F::one(), Z);
+      });
   }
 
   // k*G for EC#sign: k = _truncateToN(nonce, true) as the short domain loads it
@@ -205,12 +194,12 @@ struct EdcEcdsa {
   // affine k*G and kp.isInfinity() for Work::rt_sign_finish
   ELL_HD static void sign_norm(size_t t, size_t T, size_t n, int K, const u32* proj, u32* pre, u8* kg_xy, u8* kg_inf) {
     EdcWork::normalize(t, T, n, K, proj, pre, kg_xy, nullptr);
+    const InvShare g(t, T, n, K);
     ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      const size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      kg_inf[i] = is_infinity(EdcKey::load_plane(proj, n, i, 0), EdcKey::load_plane(proj, n, i, 8),
-                              EdcKey::load_plane(proj, n, i, 16)) ? 1 : 0;
+    for (int j = 0; j < g.cnt; j++) {
+      const size_t i = g.item(j);
+      kg_inf[i] = is_infinity(load_limbs<El>(proj, n, i, 0), load_limbs<El>(proj, n, i, 8),
+                              load_limbs<El>(proj, n, i, 16)) ? 1 : 0;
     }
   }
 };

@@ -43,16 +43,6 @@ struct EdcKey {
     F::to_plain(w, a);
     store_be<8>(p, w, 32);
   }
-  ELL_HD static void store_plane(u32* pl, size_t n, size_t i, int first, const El& a) {
-    ELL_UNROLL
-    for (int l = 0; l < 8; l++) pl[(size_t)(first + l) * n + i] = a.v[l];
-  }
-  ELL_HD static El load_plane(const u32* pl, size_t n, size_t i, int first) {
-    El r;
-    ELL_UNROLL
-    for (int l = 0; l < 8; l++) r.v[l] = pl[(size_t)(first + l) * n + i];
-    return r;
-  }
   // nd: 16 limb planes of n words, the numerator then the denominator, Montgomery form
   ELL_HD static void put_fraction(u32* nd, size_t n, size_t i, const El& v, bool from_y) {
     const El v2 = F::sqr(v);
@@ -64,8 +54,8 @@ struct EdcKey {
       num = F::sub(F::one(), F::mul(EdcWork::ca(), v2));
       den = F::sub(F::one(), F::mul(EdcWork::cd(), v2));
     }
-    store_plane(nd, n, i, 0, num);
-    store_plane(nd, n, i, 8, den);
+    store_limbs(nd, n, i, 0, num);
+    store_limbs(nd, n, i, 8, den);
   }
   // pointFromX (from_y == 0) / pointFromY: the known coordinate into pts, the fraction into nd
   ELL_HD static void front_coord(size_t i, size_t n, const u8* vs, const u8* odd, int from_y, u8* pts, u8* st,
@@ -102,37 +92,26 @@ struct EdcKey {
     store_fe(pts + i * 64 + 32, y);
     if (nk) put_fraction(nd, n, i, x, false);
     else {
-      store_plane(nd, n, i, 0, F::zero());
-      store_plane(nd, n, i, 8, F::zero());
+      store_limbs(nd, n, i, 0, F::zero());
+      store_limbs(nd, n, i, 8, F::zero());
     }
     st[i] = (u8)s;
     need[i] = (u8)nk;
   }
   // num / den into the numerator's planes, thread t: items t, t + T, ...
   ELL_HD static void quotient(size_t t, size_t T, size_t n, int K, u32* nd, u32* pre) {
-    int cnt = 0;
-    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
-    if (cnt > K) cnt = K;
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < cnt; j++) {
-      const size_t i = t + (size_t)j * T;
-      El z = load_plane(nd, n, i, 8);
-      z = fe_select<F>(F::is_zero(z), F::one(), z);
-      store_plane(pre, n, i, 0, acc);
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = cnt - 1; j >= 0; j--) {
-      const size_t i = t + (size_t)j * T;
-      const El den = load_plane(nd, n, i, 8);
-      const bool dz = F::is_zero(den);
-      const El dinv = F::mul(inv, load_plane(pre, n, i, 0));
-      inv = F::mul(inv, fe_select<F>(dz, F::one(), den));
-      const El q = F::mul(load_plane(nd, n, i, 0), dinv);
-      store_plane(nd, n, i, 0, fe_select<F>(dz, F::zero(), q));
-    }
+    inv_share<F>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        const El z = load_limbs<El>(nd, n, i, 8);
+        return fe_select<F>(F::is_zero(z), F::one(), z);
+      },
+      [&](size_t i, const El& dinv) {
+        const El q = F::mul(load_limbs<El>(nd, n, i, 0), dinv);
+        const El den = load_limbs<El>(nd, n, i, 8);
+        const bool dz = F::is_zero(den);
+        store_limbs(nd, n, i, 0, fe_select<F>(dz, F::zero(), q));
+        return fe_select<F>(dz, F::one(), den);
+      });
   }
   // a x^2 + y^2 == 1 + d x^2 y^2
   ELL_HD static bool on_curve(const El& x, const El& y) { return EdcWork::on_curve(x, y); }
@@ -147,7 +126,7 @@ struct EdcKey {
     u32 s = st_in[i];
     const u32 nk = need[i];
     if (nk & 3u) {
-      const El q = load_plane(nd, n, i, 0);
+      const El q = load_limbs<El>(nd, n, i, 0);
       El r = F::sqrt(q);
       const bool ok = F::eq(F::sqr(r), q);
       const bool want_odd = (nk & NEED_ODD) != 0;
@@ -198,36 +177,25 @@ struct EdcKey {
   // shared product as one and gets a zeroed x.  err (may be null): the decoder's own status.
   ELL_HD static void derive_finish(size_t t, size_t T, size_t n, int K, const u32* proj, const u8* dec_st,
                                    const u8* valid, u32* pre, u8* out_x, u8* status, u8* err) {
-    int cnt = 0;
-    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
-    if (cnt > K) cnt = K;
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < cnt; j++) {
-      const size_t i = t + (size_t)j * T;
-      El z = load_plane(proj, n, i, 16);
-      const u32 ds = dec_st ? dec_st[i] : (u32)ST_OK;
-      int st = DERIVE_OK;
-      if (ds != ST_OK) st = DERIVE_UNDECODED;
-      else if (!valid[i]) st = DERIVE_NOT_VALIDATED;
-      else if (F::is_zero(z)) st = DERIVE_Z0;
-      status[i] = (u8)st;
-      if (err) err[i] = (u8)ds;
-      z = fe_select<F>(st == DERIVE_OK, z, F::one());
-      store_plane(pre, n, i, 0, acc);
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = cnt - 1; j >= 0; j--) {
-      const size_t i = t + (size_t)j * T;
-      const bool ok = status[i] == DERIVE_OK;
-      const El z = fe_select<F>(ok, load_plane(proj, n, i, 16), F::one());
-      const El zinv = F::mul(inv, load_plane(pre, n, i, 0));
-      inv = F::mul(inv, z);
-      const El x = F::mul(load_plane(proj, n, i, 0), zinv);
-      store_fe(out_x + i * 32, fe_select<F>(ok, x, F::zero()));
-    }
+    inv_share<F>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        const El z = load_limbs<El>(proj, n, i, 16);
+        const u32 ds = dec_st ? dec_st[i] : (u32)ST_OK;
+        int st = DERIVE_OK;
+        if (ds != ST_OK) st = DERIVE_UNDECODED;
+        else if (!valid[i]) st = DERIVE_NOT_VALIDATED;
+        else if (F::is_zero(z)) st = DERIVE_Z0;
+        status[i] = (u8)st;
+        if (err) err[i] = (u8)ds;
+        return fe_select<F>(st == DERIVE_OK, z, F::one());
+      },
+      [&](size_t i, const El& zinv) {
+        const bool ok = status[i] == DERIVE_OK;
+        const El z = fe_select<F>(ok, load_limbs<El>(proj, n, i, 16), F::one());
+        const El x = F::mul(load_limbs<El>(proj, n, i, 0), zinv);
+        store_fe(out_x + i * 32, fe_select<F>(ok, x, F::zero()));
+        return z;
+      });
   }
   // KeyPair#validate in its order: 1 'Invalid public key' ((0, 1)), 2 'Public key is not a point',
   // 3 'Public key * N != O' (proj, the ladder's order * P: null without the order test; the
@@ -237,7 +205,7 @@ struct EdcKey {
     if (inf[i]) st = VAL_INF;
     else if (!valid[i]) st = VAL_NOT_POINT;
     else if (proj) {
-      const bool id = F::is_zero(load_plane(proj, n, i, 0)) && F::eq(load_plane(proj, n, i, 8), load_plane(proj, n, i, 16));
+      const bool id = F::is_zero(load_limbs<El>(proj, n, i, 0)) && F::eq(load_limbs<El>(proj, n, i, 8), load_limbs<El>(proj, n, i, 16));
       if (!id) st = VAL_ORDER;
     }
     status[i] = (u8)st;

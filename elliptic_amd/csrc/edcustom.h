@@ -261,53 +261,33 @@ struct EdcWork {
   template <bool RAW = false>
   ELL_HD static void normalize(size_t t, size_t T, size_t n, int K, const u32* proj, u32* pre,
                                u8* out_xy, u8* out_inf, A* raw = nullptr) {
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      El z;
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) z.v[l] = proj[(size_t)(2 * 8 + l) * n + i];
-      z = fe_select<F>(F::is_zero(z), F::one(), z);
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      El X, Y, Z, pr;
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) {
-        X.v[l] = proj[(size_t)(0 * 8 + l) * n + i];
-        Y.v[l] = proj[(size_t)(1 * 8 + l) * n + i];
-        Z.v[l] = proj[(size_t)(2 * 8 + l) * n + i];
-        pr.v[l] = pre[(size_t)l * n + i];
-      }
-      bool zz = F::is_zero(Z);                      // only off the curve / on incomplete curves
-      El z = fe_select<F>(zz, F::one(), Z);
-      El zinv = F::mul(inv, pr);
-      inv = F::mul(inv, z);
-      El x = F::mul(X, zinv);
-      El y = F::mul(Y, zinv);
-      if (zz) { x = F::zero(); y = F::zero(); }
-      if constexpr (RAW) {
-        A e;
-        e.x = x;
-        e.y = y;
-        raw[i] = e;
-      } else {
-        u32 w[8];
-        F::to_plain(w, x);
-        store_be<8>(out_xy + i * 64, w, 32);
-        F::to_plain(w, y);
-        store_be<8>(out_xy + i * 64 + 32, w, 32);
-        if (out_inf) out_inf[i] = 0;
-      }
-    }
+    inv_share<F>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        const El z = load_limbs<El>(proj, n, i, 2 * 8);
+        return fe_select<F>(F::is_zero(z), F::one(), z);
+      },
+      [&](size_t i, const El& zinv) {
+        const El Z = load_limbs<El>(proj, n, i, 2 * 8);
+        const bool zz = F::is_zero(Z);                // only off the curve / on incomplete curves
+        const El z = fe_select<F>(zz, F::one(), Z);
+        El x = F::mul(load_limbs<El>(proj, n, i, 0 * 8), zinv);
+        El y = F::mul(load_limbs<El>(proj, n, i, 1 * 8), zinv);
+        if (zz) { x = F::zero(); y = F::zero(); }
+        if constexpr (RAW) {
+          A e;
+          e.x = x;
+          e.y = y;
+          raw[i] = e;
+        } else {
+          u32 w[8];
+          F::to_plain(w, x);
+          store_be<8>(out_xy + i * 64, w, 32);
+          F::to_plain(w, y);
+          store_be<8>(out_xy + i * 64 + 32, w, 32);
+          if (out_inf) out_inf[i] = 0;
+        }
+        return z;
+      });
   }
 };
 

@@ -620,46 +620,24 @@ struct EdWork {
   // x == 0 && y == 1.  raw != null stores cached(x, y, 1, xy) for the comb.
   ELL_HD static void normalize(size_t t, size_t T, size_t n, int K, const u32* ext, u32* pre,
                                u8* out_xy, u8* out_inf, P* raw) {
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      El z;
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) z.v[l] = ext[(size_t)(2 * 8 + l) * n + i];
-      // Z == 0 cannot happen for a point on the curve (complete formulas); an
-      // off-curve input must still not poison the other K-1 items of the batch
-      z = fe_select<F>(F::is_zero(z), F::one(), z);
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      El X, Y, Z, pr;
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) {
-        X.v[l] = ext[(size_t)(0 * 8 + l) * n + i];
-        Y.v[l] = ext[(size_t)(1 * 8 + l) * n + i];
-        Z.v[l] = ext[(size_t)(2 * 8 + l) * n + i];
-        pr.v[l] = pre[(size_t)l * n + i];
-      }
-      Z = fe_select<F>(F::is_zero(Z), F::one(), Z);
-      El zinv = F::mul(inv, pr);
-      inv = F::mul(inv, Z);
-      El x = F::mul(X, zinv);
-      El y = F::mul(Y, zinv);
+    // Z == 0 cannot happen for a point on the curve (complete formulas); an
+    // off-curve input must still not poison the other K-1 items of the batch
+    auto factor = [&](size_t i) {
+      const El z = load_limbs<El>(ext, n, i, 2 * 8);
+      return fe_select<F>(F::is_zero(z), F::one(), z);
+    };
+    inv_share<F>(InvShare(t, T, n, K), pre, factor, [&](size_t i, const El& zinv) {
+      const El z = factor(i);
+      El x = F::mul(load_limbs<El>(ext, n, i, 0 * 8), zinv);
+      El y = F::mul(load_limbs<El>(ext, n, i, 1 * 8), zinv);
       if (out_xy) {
         store_be<8>(out_xy + i * 64, x.v, 32);
         store_be<8>(out_xy + i * 64 + 32, y.v, 32);
       }
       if (out_inf) out_inf[i] = (F::is_zero(x) && F::eq(y, F::one())) ? 1 : 0;
       if (raw) raw[i] = to_cached(from_affine(x, y));
-    }
+      return z;
+    });
   }
 };
 

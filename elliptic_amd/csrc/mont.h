@@ -106,41 +106,22 @@ struct MontWork {
   // getX: X / Z with one inversion per K items; Z == 0 -> out_inf = 1
   ELL_HD static void normalize(size_t t, size_t T, size_t n, int K, const u32* xz, u32* pre,
                                u8* out_x, u8* out_inf) {
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      El z;
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) z.v[l] = xz[(size_t)(8 + l) * n + i];
-      bool inf = F::is_zero(z);
-      bn_select<8>(z.v, inf, F::one().v, z.v);
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      El X, Z, pr;
-      ELL_UNROLL
-      for (int l = 0; l < 8; l++) {
-        X.v[l] = xz[(size_t)l * n + i];
-        Z.v[l] = xz[(size_t)(8 + l) * n + i];
-        pr.v[l] = pre[(size_t)l * n + i];
-      }
-      bool inf = F::is_zero(Z);
-      bn_select<8>(Z.v, inf, F::one().v, Z.v);
-      El zinv = F::mul(inv, pr);
-      inv = F::mul(inv, Z);
-      El x = F::mul(X, zinv);
-      if (inf) x = F::zero();
-      store_be<8>(out_x + i * 32, x.v, 32);
-      out_inf[i] = inf ? 1 : 0;
-    }
+    inv_share<F>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        El z = load_limbs<El>(xz, n, i, 8);
+        bn_select<8>(z.v, F::is_zero(z), F::one().v, z.v);
+        return z;
+      },
+      [&](size_t i, const El& zinv) {
+        El Z = load_limbs<El>(xz, n, i, 8);
+        const bool inf = F::is_zero(Z);
+        bn_select<8>(Z.v, inf, F::one().v, Z.v);
+        El x = F::mul(load_limbs<El>(xz, n, i, 0), zinv);
+        if (inf) x = F::zero();
+        store_be<8>(out_x + i * 32, x.v, 32);
+        out_inf[i] = inf ? 1 : 0;
+        return Z;
+      });
   }
 };
 

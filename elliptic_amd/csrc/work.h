@@ -599,45 +599,24 @@ struct Work {
   enum { DERIVE_OK = 0, DERIVE_NOT_VALIDATED = 1, DERIVE_INF = 2, DERIVE_UNDECODED = 3 };
   ELL_HD static void rt_derive_finish(size_t t, size_t T, size_t n, int K, const u32* jac, const u8* dec_st,
                                       const u8* valid, u32* pre, u8* out_x, u8* status, u8* err) {
-    auto load_z = [&](size_t i) {
-      El z;
-      ELL_UNROLL
-      for (int l = 0; l < NS; l++) z.v[l] = jac[(size_t)(2 * NS + l) * n + i];
-      return z;
-    };
-    int cnt = 0;
-    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
-    if (cnt > K) cnt = K;
-    El acc = F::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < cnt; j++) {
-      size_t i = t + (size_t)j * T;
-      El z = load_z(i);
-      int st = DERIVE_OK;
-      if (dec_st[i] != DECODE_OK) st = DERIVE_UNDECODED;
-      else if (!valid[i]) st = DERIVE_NOT_VALIDATED;
-      else if (F::is_zero(z)) st = DERIVE_INF;
-      status[i] = (u8)st;
-      if (err) err[i] = dec_st[i];
-      z = fe_select<F>(st == DERIVE_OK, z, F::one());
-      ELL_UNROLL
-      for (int l = 0; l < NS; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = F::mul(acc, z);
-    }
-    El inv = F::inv(acc);
-    ELL_NOUNROLL
-    for (int j = cnt - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      const bool ok = status[i] == DERIVE_OK;
-      El z = fe_select<F>(ok, load_z(i), F::one());
-      El pr, X;
-      ELL_UNROLL
-      for (int l = 0; l < NS; l++) { pr.v[l] = pre[(size_t)l * n + i]; X.v[l] = jac[(size_t)l * n + i]; }
-      El zinv = F::mul(inv, pr);
-      inv = F::mul(inv, z);
-      El x = F::mul(X, F::sqr(zinv));
-      store_fe(out_x + i * BYTES, fe_select<F>(ok, x, F::zero()));
-    }
+    inv_share<F>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        const El z = load_limbs<El>(jac, n, i, 2 * NS);
+        int st = DERIVE_OK;
+        if (dec_st[i] != DECODE_OK) st = DERIVE_UNDECODED;
+        else if (!valid[i]) st = DERIVE_NOT_VALIDATED;
+        else if (F::is_zero(z)) st = DERIVE_INF;
+        status[i] = (u8)st;
+        if (err) err[i] = dec_st[i];
+        return fe_select<F>(st == DERIVE_OK, z, F::one());
+      },
+      [&](size_t i, const El& zinv) {
+        const bool ok = status[i] == DERIVE_OK;
+        const El z = fe_select<F>(ok, load_limbs<El>(jac, n, i, 2 * NS), F::one());
+        const El x = F::mul(load_limbs<El>(jac, n, i, 0), F::sqr(zinv));
+        store_fe(out_x + i * BYTES, fe_select<F>(ok, x, F::zero()));
+        return z;
+      });
   }
   // validate's last pass, KeyPair#validate's tests in its order: 1 'Invalid public key' (inf[i]
   // set; inf may be null), 2 'Public key is not a point', 3 'Public key * N != O' (jac, the
@@ -821,20 +800,15 @@ struct Work {
   // form (used to build the comb tables).
   ELL_HD static void normalize(size_t t, size_t T, size_t n, int K, const u32* jac, u32* pre,
                                u8* out_xy, u8* out_inf, A* raw_aff) {
-    // Both passes are software-pipelined by hand (round 4): item j + 1's words are requested
-    // before item j's multiplications, so that the thread's chain -- K items and one inversion,
-    // on a grid of n / K threads that leaves most SIMDs a single wave -- does not also wait for
-    // HBM once per item.
-    auto load_z = [&](size_t i) {
-      El z;
-      ELL_UNROLL
-      for (int l = 0; l < NS; l++) z.v[l] = jac[(size_t)(2 * NS + l) * n + i];
-      return z;
-    };
-    // items of this thread: t, t + T, ... below n
-    int cnt = 0;
-    if (t < n) cnt = (int)((n - 1 - t) / T) + 1;
-    if (cnt > K) cnt = K;
+    // The one deliberate exception to the shared skeleton (common.h inv_share): both passes are
+    // software-pipelined by hand (round 4): item j + 1's words are requested before item j's
+    // multiplications, so that the thread's chain -- K items and one inversion, on a grid of
+    // n / K threads that leaves most SIMDs a single wave -- does not also wait for HBM once per
+    // item.  An enter / leave pair sees one item at a time and cannot ask for the next one's
+    // words, so this routine keeps its own loops and takes only the item count and the plane
+    // accessors from there.  Its refused item (Z = 0) is one in both passes like everyone's.
+    auto load_z = [&](size_t i) { return load_limbs<El>(jac, n, i, 2 * NS); };
+    const int cnt = InvShare(t, T, n, K).cnt;
     El acc = F::one();
     El znext = cnt > 0 ? load_z(t) : F::one();
     ELL_NOUNROLL
@@ -844,8 +818,7 @@ struct Work {
       if (j + 1 < cnt) znext = load_z(i + T);
       bool inf = F::is_zero(z);
       z = fe_select<F>(inf, F::one(), z);
-      ELL_UNROLL
-      for (int l = 0; l < NS; l++) pre[(size_t)l * n + i] = acc.v[l];
+      store_limbs(pre, n, i, 0, acc);
       acc = F::mul(acc, z);
     }
     El inv = F::inv(acc);
@@ -853,8 +826,7 @@ struct Work {
     El prn;
     auto load_item = [&](size_t i, J& p, El& pr) {
       p = load_jac(jac, n, i);
-      ELL_UNROLL
-      for (int l = 0; l < NS; l++) pr.v[l] = pre[(size_t)l * n + i];
+      pr = load_limbs<El>(pre, n, i);
     };
     if (cnt > 0) load_item(t + (size_t)(cnt - 1) * T, pn, prn);
     ELL_NOUNROLL
@@ -929,55 +901,36 @@ struct Work {
   ELL_HD static void ecdsa_prep(size_t t, size_t T, size_t n, int K, const u8* hash,
                                 int hash_len, int shift, const u8* rs, const u8* ss, u32* pre,
                                 u32* u12, u8* valid) {
-    Nl acc = Fn::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      u32 r[LN], s[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      load_be<LN>(s, ss + i * NBYTES, NBYTES);
-      bool ok = scalar_in_range(r) && scalar_in_range(s);
-      valid[i] = ok ? 1 : 0;
-      Nl sm = Fn::from_plain(s);
-      sm = fe_select<Fn>(ok, sm, Fn::one());
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = Fn::mul(acc, sm);
-    }
-    Nl inv = Fn::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      u32 r[LN], s[LN], e[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      load_be<LN>(s, ss + i * NBYTES, NBYTES);
-      load_hash(e, hash + i * (size_t)hash_len, hash_len, shift);
-      bool ok = valid[i] != 0;
-      Nl sm = fe_select<Fn>(ok, Fn::from_plain(s), Fn::one());
-      Nl pr;
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
-      Nl w = Fn::mul(inv, pr);                       // s^-1 (Montgomery form: s^-1 R)
-      inv = Fn::mul(inv, sm);
-      // u = x * s^-1 as a PLAIN residue in one Montgomery product: (x) * (s^-1 R) / R, x < R
-      // unreduced on the left, s^-1 R < n on the right -- no conversion of x in, none of u out
-      // (round 3: 7 instead of 11 products per item)
-      Nl er, rr;
-      bn_copy<LN>(er.v, e);
-      bn_copy<LN>(rr.v, r);
-      Nl u1 = Fn::mul(er, w);
-      Nl u2 = Fn::mul(rr, w);
-      u32 p1[LN], p2[LN];
-      bn_copy<LN>(p1, u1.v);
-      bn_copy<LN>(p2, u2.v);
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) {
-        u12[(size_t)(0 * LN + l) * n + i] = ok ? p1[l] : 0u;
-        u12[(size_t)(1 * LN + l) * n + i] = ok ? p2[l] : 0u;
-      }
-    }
+    inv_share<Fn>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        u32 r[LN], s[LN];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        load_be<LN>(s, ss + i * NBYTES, NBYTES);
+        const bool ok = scalar_in_range(r) && scalar_in_range(s);
+        valid[i] = ok ? 1 : 0;
+        return fe_select<Fn>(ok, Fn::from_plain(s), Fn::one());
+      },
+      [&](size_t i, const Nl& w) {                   // w = s^-1 (Montgomery form: s^-1 R)
+        u32 r[LN], s[LN], e[LN];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        load_be<LN>(s, ss + i * NBYTES, NBYTES);
+        load_hash(e, hash + i * (size_t)hash_len, hash_len, shift);
+        const bool ok = valid[i] != 0;
+        const Nl sm = fe_select<Fn>(ok, Fn::from_plain(s), Fn::one());
+        // u = x * s^-1 as a PLAIN residue in one Montgomery product: (x) * (s^-1 R) / R, x < R
+        // unreduced on the left, s^-1 R < n on the right -- no conversion of x in, none of u out
+        // (round 3: 7 instead of 11 products per item)
+        Nl er, rr;
+        bn_copy<LN>(er.v, e);
+        bn_copy<LN>(rr.v, r);
+        Nl u1 = Fn::mul(er, w);
+        Nl u2 = Fn::mul(rr, w);
+        ELL_UNROLL
+        for (int l = 0; l < LN; l++) { u1.v[l] = ok ? u1.v[l] : 0u; u2.v[l] = ok ? u2.v[l] : 0u; }
+        store_limbs(u12, n, i, 0 * LN, u1);
+        store_limbs(u12, n, i, 1 * LN, u2);
+        return sm;
+      });
   }
 
   // ---- public-key recovery (ec/index.js:231-259 EC#recoverPubKey) ----------------------
@@ -1000,6 +953,34 @@ struct Work {
     Nl him = Fn::from_plain(hi);
     return Fn::add(Fn::from_plain(lo), Fn::from_plain(him.v));
   }
+  // the checks both recovery routines make of (r, j); pmn = p mod n
+  ELL_HD static int recover_check(const u32 (&r)[LN], u32 jj, const u32 (&pmn)[LN]) {
+    if (!scalar_in_range(r)) return RECOVER_DOMAIN;
+    if (jj > 3 || ((jj >> 1) != 0 && bn_geq<LN>(r, pmn))) return RECOVER_THROWS;
+    return RECOVER_POINT;
+  }
+  // the backward body both recovery routines share: s1 = -e/r and s2 = s/r from rinv = 1/r, zeroed
+  // where the item is refused; returns r's factor as the forward bodies entered it.  e = new
+  // BN(msg), up to 64 bytes, and s, possibly >= n, are both only reduced mod n.
+  ELL_HD static Nl recover_scalars(size_t i, const Nl& rinv, const u8* hash, int hash_len, const u8* rs,
+                                   const u8* ss, u8* s1b, u8* s2b, const u8* status) {
+    u32 r[LN], s[LN];
+    load_be<LN>(r, rs + i * NBYTES, NBYTES);
+    load_be<LN>(s, ss + i * NBYTES, NBYTES);
+    const bool ok = status[i] == RECOVER_POINT;
+    const Nl rm = fe_select<Fn>(ok, Fn::from_plain(r), Fn::one());
+    Nl e = bytes_mod_n(hash + i * (size_t)hash_len, hash_len);
+    Nl s1 = Fn::neg(Fn::mul(e, rinv));
+    Nl s2 = Fn::mul(Fn::from_plain(s), rinv);
+    u32 p1[LN], p2[LN];
+    Fn::to_plain(p1, s1);
+    Fn::to_plain(p2, s2);
+    ELL_UNROLL
+    for (int l = 0; l < LN; l++) { p1[l] = ok ? p1[l] : 0u; p2[l] = ok ? p2[l] : 0u; }
+    store_be<LN>(s1b + i * NBYTES, p1, NBYTES);
+    store_be<LN>(s2b + i * NBYTES, p2, NBYTES);
+    return rm;
+  }
   ELL_HD static void recover_prep(size_t t, size_t T, size_t n, int K, const u8* hash, int hash_len,
                                   const u8* rs, const u8* ss, const u8* recid, u32* pre, u8* xs,
                                   u8* odd, u8* s1b, u8* s2b, u8* status) {
@@ -1012,67 +993,37 @@ struct Work {
       for (int i = 0; i < LN; i++) nn[i] = C::n[i];
       bn_sub<LN>(pmn, pp, nn);                   // p mod n = p - n  (n < p < 2n for every preset)
     }
-    Nl acc = Fn::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      u32 r[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      u32 jj = recid[i];
-      bool second = (jj >> 1) != 0;
-      int st = RECOVER_POINT;
-      if (!scalar_in_range(r)) st = RECOVER_DOMAIN;
-      else if (jj > 3 || (second && bn_geq<LN>(r, pmn))) st = RECOVER_THROWS;
-      status[i] = (u8)st;
-      u32 x[LN], rn[LN];
-      bn_add<LN>(rn, r, nn);                     // r + n < p when the second candidate exists
-      bn_select<LN>(x, second && st == RECOVER_POINT, rn, r);
-      store_be<LN>(xs + i * BYTES, x, BYTES);
-      odd[i] = (u8)(jj & 1);
-      Nl rm = fe_select<Fn>(st == RECOVER_POINT, Fn::from_plain(r), Fn::one());
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = Fn::mul(acc, rm);
-    }
-    Nl inv = Fn::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      u32 r[LN], s[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      load_be<LN>(s, ss + i * NBYTES, NBYTES);
-      bool ok = status[i] == RECOVER_POINT;
-      Nl rm = fe_select<Fn>(ok, Fn::from_plain(r), Fn::one());
-      Nl pr;
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
-      Nl rinv = Fn::mul(inv, pr);
-      inv = Fn::mul(inv, rm);
-      Nl e = bytes_mod_n(hash + i * (size_t)hash_len, hash_len);
-      Nl s1 = Fn::neg(Fn::mul(e, rinv));
-      Nl s2 = Fn::mul(Fn::from_plain(s), rinv);
-      u32 p1[LN], p2[LN];
-      Fn::to_plain(p1, s1);
-      Fn::to_plain(p2, s2);
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) { p1[l] = ok ? p1[l] : 0u; p2[l] = ok ? p2[l] : 0u; }
-      store_be<LN>(s1b + i * NBYTES, p1, NBYTES);
-      store_be<LN>(s2b + i * NBYTES, p2, NBYTES);
-    }
+    inv_share<Fn>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        u32 r[LN];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        const u32 jj = recid[i];
+        const int st = recover_check(r, jj, pmn);
+        status[i] = (u8)st;
+        u32 x[LN], rn[LN];
+        bn_add<LN>(rn, r, nn);                   // r + n < p when the second candidate exists
+        bn_select<LN>(x, (jj >> 1) != 0 && st == RECOVER_POINT, rn, r);
+        store_be<LN>(xs + i * BYTES, x, BYTES);
+        odd[i] = (u8)(jj & 1);
+        return fe_select<Fn>(st == RECOVER_POINT, Fn::from_plain(r), Fn::one());
+      },
+      [&](size_t i, const Nl& rinv) { return recover_scalars(i, rinv, hash, hash_len, rs, ss, s1b, s2b, status); });
   }
-  // Pass 4: fold the decompression result and the infinity flag into the status; no point is
-  // reported for items whose status is not RECOVER_POINT
-  ELL_HD static void recover_finish(size_t i, const u8* dec_ok, const u8* inf, u8* out_xy, u8* status) {
+  // Pass 4: fold the decompression result (decoded: did the candidate's x lift to a point) and
+  // the infinity flag into the status; no point is reported for items whose status is not
+  // RECOVER_POINT
+  ELL_HD static void recover_fold(size_t i, bool decoded, const u8* inf, u8* out_xy, u8* status) {
     int st = status[i];
-    if (st == RECOVER_POINT && !dec_ok[i]) st = RECOVER_THROWS;          // 'invalid point'
+    if (st == RECOVER_POINT && !decoded) st = RECOVER_THROWS;            // 'invalid point'
     else if (st == RECOVER_POINT && inf[i]) st = RECOVER_INF;
     status[i] = (u8)st;
     if (st != RECOVER_POINT) {
       ELL_NOUNROLL
       for (int b = 0; b < 2 * BYTES; b++) out_xy[i * 2 * BYTES + b] = 0;
     }
+  }
+  ELL_HD static void recover_finish(size_t i, const u8* dec_ok, const u8* inf, u8* out_xy, u8* status) {
+    recover_fold(i, dec_ok[i] != 0, inf, out_xy, status);
   }
 
   // ---- the recovery id of a signature under a known key (ec/index.js:261-278
@@ -1089,57 +1040,42 @@ struct Work {
   // reference goes through BN#invm of an unreduced or zero value, or answers the first j whose
   // x lifts whatever Q is; callers hand those to the reference) -- such an item enters the
   // shared product as one and gets zero scalars.
-  // (The parameters are const-qualified so that the list of (t, T, n, K) routines that
-  // tests/test_inv_batch_hostsim.py pins by name stays what it is: this routine's cases with
-  // K > 1 -- a refused item first, in the middle and last of a thread's items -- are in
-  // tests/key_recid_checks.py, not in tests/inv_batch_checks.py.)
+  // (This routine's cases with K > 1 -- a refused item first, in the middle and last of a
+  // thread's items -- are in tests/key_recid_checks.py, not in tests/inv_batch_checks.py; its
+  // const-qualified parameters keep it out of the list of routines the latter pins by name.)
   enum { RECID_FOUND = 0, RECID_NONE = 1, RECID_OFF_CURVE = 2, RECID_DOMAIN = 3 };
   ELL_HD static void recid_prep(const size_t t, const size_t T, const size_t n, const int K, const u8* hash,
                                 int hash_len, const u8* rs, const u8* ss, u32* pre, u8* u1b, u8* u2b,
                                 u8* status) {
-    Nl acc = Fn::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      u32 r[LN], s[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      load_be<LN>(s, ss + i * NBYTES, NBYTES);
-      Nl sm = Fn::from_plain(s);                 // s mod n
-      const bool ok = scalar_in_range(r) && !Fn::is_zero(sm);
-      status[i] = (u8)(ok ? RECID_FOUND : RECID_DOMAIN);
-      sm = fe_select<Fn>(ok, sm, Fn::one());
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = Fn::mul(acc, sm);
-    }
-    Nl inv = Fn::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      u32 r[LN], s[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      load_be<LN>(s, ss + i * NBYTES, NBYTES);
-      const bool ok = status[i] == RECID_FOUND;
-      Nl sm = fe_select<Fn>(ok, Fn::from_plain(s), Fn::one());
-      Nl pr;
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
-      Nl w = Fn::mul(inv, pr);                   // s^-1 (Montgomery form)
-      inv = Fn::mul(inv, sm);
-      // plain residues in one product each: (e R)(s^-1) / R and (r)(s^-1 R) / R, r < n
-      Nl wp, rr;
-      Fn::to_plain(wp.v, w);
-      bn_copy<LN>(rr.v, r);
-      Nl u1 = Fn::mul(bytes_mod_n(hash + i * (size_t)hash_len, hash_len), wp);
-      Nl u2 = Fn::mul(rr, w);
-      u32 p1[LN], p2[LN];
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) { p1[l] = ok ? u1.v[l] : 0u; p2[l] = ok ? u2.v[l] : 0u; }
-      store_be<LN>(u1b + i * NBYTES, p1, NBYTES);
-      store_be<LN>(u2b + i * NBYTES, p2, NBYTES);
-    }
+    inv_share<Fn>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        u32 r[LN], s[LN];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        load_be<LN>(s, ss + i * NBYTES, NBYTES);
+        const Nl sm = Fn::from_plain(s);         // s mod n
+        const bool ok = scalar_in_range(r) && !Fn::is_zero(sm);
+        status[i] = (u8)(ok ? RECID_FOUND : RECID_DOMAIN);
+        return fe_select<Fn>(ok, sm, Fn::one());
+      },
+      [&](size_t i, const Nl& w) {               // w = s^-1 (Montgomery form)
+        u32 r[LN], s[LN];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        load_be<LN>(s, ss + i * NBYTES, NBYTES);
+        const bool ok = status[i] == RECID_FOUND;
+        const Nl sm = fe_select<Fn>(ok, Fn::from_plain(s), Fn::one());
+        // plain residues in one product each: (e R)(s^-1) / R and (r)(s^-1 R) / R, r < n
+        Nl wp, rr;
+        Fn::to_plain(wp.v, w);
+        bn_copy<LN>(rr.v, r);
+        Nl u1 = Fn::mul(bytes_mod_n(hash + i * (size_t)hash_len, hash_len), wp);
+        Nl u2 = Fn::mul(rr, w);
+        u32 p1[LN], p2[LN];
+        ELL_UNROLL
+        for (int l = 0; l < LN; l++) { p1[l] = ok ? u1.v[l] : 0u; p2[l] = ok ? u2.v[l] : 0u; }
+        store_be<LN>(u1b + i * NBYTES, p1, NBYTES);
+        store_be<LN>(u2b + i * NBYTES, p2, NBYTES);
+        return sm;
+      });
   }
   // Pass 3, one item per lane, over R' = u1 G + u2 Q in affine form (xy) and what mul_add_g left
   // in inf: status 3 stays; 2 where the key is not on the curve (DOMAIN_OFF_CURVE); 1 where R'
@@ -1183,74 +1119,32 @@ struct Work {
     static_assert(CV::RT_ORDER && L == 8 && LN == 8, "user-defined domains only");
     u32 nn[LN];
     order_words(nn);
-    Nl acc = Fn::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
-      u32 r[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      u32 jj = recid[i];
-      bool second = (jj >> 1) != 0;
-      int st = RECOVER_POINT;
-      if (!scalar_in_range(r)) st = RECOVER_DOMAIN;
-      else if (jj > 3 || (second && bn_geq<LN>(r, pmn))) st = RECOVER_THROWS;
-      status[i] = (u8)st;
-      // x = (r + [second] n) mod p: the sum may carry out of 2^256; from_plain reduces its low
-      // words whatever their size, and the carry is worth 2^256, whose Montgomery form is R^2 mod p
-      u32 add[LN], sum[LN];
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) add[l] = (second && st == RECOVER_POINT) ? nn[l] : 0u;
-      const u32 carry = bn_add<LN>(sum, r, add);
-      El top;
-      ELL_UNROLL
-      for (int l = 0; l < L; l++) top.v[l] = carry ? ELL_RT.r2[l] : 0u;
-      store_fe(xs + i * BYTES, F::add(F::from_plain(sum), top));
-      odd[i] = (u8)(jj & 1);
-      Nl rm = fe_select<Fn>(st == RECOVER_POINT, Fn::from_plain(r), Fn::one());
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = Fn::mul(acc, rm);
-    }
-    Nl inv = Fn::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
-      u32 r[LN], s[LN];
-      load_be<LN>(r, rs + i * NBYTES, NBYTES);
-      load_be<LN>(s, ss + i * NBYTES, NBYTES);
-      bool ok = status[i] == RECOVER_POINT;
-      Nl rm = fe_select<Fn>(ok, Fn::from_plain(r), Fn::one());
-      Nl pr;
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
-      Nl rinv = Fn::mul(inv, pr);
-      inv = Fn::mul(inv, rm);
-      // e = new BN(msg), up to 64 bytes, and s, possibly >= n: both only reduced mod n
-      Nl e = bytes_mod_n(hash + i * (size_t)hash_len, hash_len);
-      Nl s1 = Fn::neg(Fn::mul(e, rinv));
-      Nl s2 = Fn::mul(Fn::from_plain(s), rinv);
-      u32 p1[LN], p2[LN];
-      Fn::to_plain(p1, s1);
-      Fn::to_plain(p2, s2);
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) { p1[l] = ok ? p1[l] : 0u; p2[l] = ok ? p2[l] : 0u; }
-      store_be<LN>(s1b + i * NBYTES, p1, NBYTES);
-      store_be<LN>(s2b + i * NBYTES, p2, NBYTES);
-    }
+    inv_share<Fn>(InvShare(t, T, n, K), pre,
+      [&](size_t i) {
+        u32 r[LN];
+        load_be<LN>(r, rs + i * NBYTES, NBYTES);
+        const u32 jj = recid[i];
+        const int st = recover_check(r, jj, pmn);
+        status[i] = (u8)st;
+        // x = (r + [second] n) mod p: the sum may carry out of 2^256; from_plain reduces its low
+        // words whatever their size, and the carry is worth 2^256, whose Montgomery form is R^2 mod p
+        u32 add[LN], sum[LN];
+        ELL_UNROLL
+        for (int l = 0; l < LN; l++) add[l] = ((jj >> 1) != 0 && st == RECOVER_POINT) ? nn[l] : 0u;
+        const u32 carry = bn_add<LN>(sum, r, add);
+        El top;
+        ELL_UNROLL
+        for (int l = 0; l < L; l++) top.v[l] = carry ? ELL_RT.r2[l] : 0u;
+        store_fe(xs + i * BYTES, F::add(F::from_plain(sum), top));
+        odd[i] = (u8)(jj & 1);
+        return fe_select<Fn>(st == RECOVER_POINT, Fn::from_plain(r), Fn::one());
+      },
+      [&](size_t i, const Nl& rinv) { return recover_scalars(i, rinv, hash, hash_len, rs, ss, s1b, s2b, status); });
   }
   // the last pass on a domain: dec_st is rt_decompress's status, whose 'invalid point' (2) and
   // 'Assertion failed' (3) are both the reference throwing
   ELL_HD static void rt_recover_finish(size_t i, const u8* dec_st, const u8* inf, u8* out_xy, u8* status) {
-    int st = status[i];
-    if (st == RECOVER_POINT && dec_st[i] != DECODE_OK) st = RECOVER_THROWS;
-    else if (st == RECOVER_POINT && inf[i]) st = RECOVER_INF;
-    status[i] = (u8)st;
-    if (st != RECOVER_POINT) {
-      ELL_NOUNROLL
-      for (int b = 0; b < 2 * BYTES; b++) out_xy[i * 2 * BYTES + b] = 0;
-    }
+    recover_fold(i, dec_st[i] == DECODE_OK, inf, out_xy, status);
   }
 
   // ---- EC#sign's own nonces (ec/index.js:136-158): HmacDRBG over the curve's hash
@@ -1435,31 +1329,17 @@ struct Work {
     ELL_UNROLL
     for (int l = 0; l < LN; l++) { nn[l] = C::n[l]; one1[l] = l == 0 ? 1u : 0u; }
     bn_sub<LN>(nm1, nn, one1);
-    Nl acc = Fn::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
+    const InvShare g(t, T, n, K);
+    const Nl acc = inv_share_forward<Fn>(g, pre, [&](size_t i) {
       u32 k[LN];
       load_nonce(k, nonces + i * NBYTES);
-      bool ok = !bn_is_zero<LN>(k) && !bn_eq<LN>(k, one1) && !bn_geq<LN>(k, nm1) && kg_inf[i] == 0;
+      const bool ok = !bn_is_zero<LN>(k) && !bn_eq<LN>(k, one1) && !bn_geq<LN>(k, nm1) && kg_inf[i] == 0;
       out_ok[i] = ok ? 1 : 0;
-      Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = Fn::mul(acc, km);
-    }
-    Nl inv = Fn::one();
-    if (kinv_in) {
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) inv.v[l] = kinv_in[(size_t)l * n + t];      // (K = 1: item t, prefix = one)
-    } else {
-      inv = Fn::inv(acc);
-    }
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
+      return fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
+    });
+    // (kinv_in -- K = 1: item t, prefix = one)
+    const Nl inv = kinv_in ? load_limbs<Nl>(kinv_in, n, t) : Fn::inv(acc);
+    inv_share_backward<Fn>(g, pre, inv, [&](size_t i, const Nl& kinv) {
       u32 k[LN], e[LN], d[LN], x[L], y[L];
       load_nonce(k, nonces + i * NBYTES);
       load_hash(e, hash + i * (size_t)hash_len, hash_len, shift);
@@ -1467,12 +1347,7 @@ struct Work {
       load_be<L>(x, kg_xy + i * 2 * BYTES, BYTES);
       load_be<L>(y, kg_xy + i * 2 * BYTES + BYTES, BYTES);
       bool ok = out_ok[i] != 0;
-      Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
-      Nl pr;
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
-      Nl kinv = Fn::mul(inv, pr);
-      inv = Fn::mul(inv, km);
+      const Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
       // r = x mod n: x < p < 2n for every preset, so at most one subtraction
       static_assert(LN <= L, "order wider than field");
       u32 nx[L], xr[L];
@@ -1513,7 +1388,8 @@ struct Work {
       store_be<LN>(out_s + i * NBYTES, sp, NBYTES);
       out_recid[i] = (u8)recid;
       out_ok[i] = ok ? 1 : 0;
-    }
+      return km;
+    });
   }
 
   // ---- EC#sign on a user-defined ECDSA domain (run-time p and n, fp_rt.h) ---------------------
@@ -1620,25 +1496,13 @@ struct Work {
     static_assert(CV::RT_ORDER && L == 8 && LN == 8, "user-defined domains only");
     u32 nn[LN];
     order_words(nn);
-    Nl acc = Fn::one();
-    ELL_NOUNROLL
-    for (int j = 0; j < K; j++) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) break;
+    inv_share<Fn>(InvShare(t, T, n, K), pre, [&](size_t i) {
       u32 k[LN];
       rt_load_nonce(k, nonces + i * NBYTES);
-      bool ok = rt_nonce_ok(k) && kg_inf[i] == 0;
+      const bool ok = rt_nonce_ok(k) && kg_inf[i] == 0;
       out_ok[i] = ok ? 1 : 0;
-      Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pre[(size_t)l * n + i] = acc.v[l];
-      acc = Fn::mul(acc, km);
-    }
-    Nl inv = Fn::inv(acc);
-    ELL_NOUNROLL
-    for (int j = K - 1; j >= 0; j--) {
-      size_t i = t + (size_t)j * T;
-      if (i >= n) continue;
+      return fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
+    }, [&](size_t i, const Nl& kinv) {
       u32 k[LN], e[LN], d[LN], x[L], y[L];
       rt_load_nonce(k, nonces + i * NBYTES);
       rt_load_msg(e, hash + i * (size_t)hash_len, hash_len, shift);
@@ -1646,12 +1510,7 @@ struct Work {
       load_be<L>(x, kg_xy + i * 2 * BYTES, BYTES);
       load_be<L>(y, kg_xy + i * 2 * BYTES + BYTES, BYTES);
       bool ok = out_ok[i] != 0;
-      Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
-      Nl pr;
-      ELL_UNROLL
-      for (int l = 0; l < LN; l++) pr.v[l] = pre[(size_t)l * n + i];
-      Nl kinv = Fn::mul(inv, pr);
-      inv = Fn::mul(inv, km);
+      const Nl km = fe_select<Fn>(ok, Fn::from_plain(k), Fn::one());
       // r = x mod n, a general reduction (x < p < 2^256, n anything): into the order field and out
       u32 r[LN];
       Fn::to_plain(r, Fn::from_plain(x));
@@ -1682,7 +1541,8 @@ struct Work {
       store_be<LN>(out_s + i * NBYTES, sp, NBYTES);
       out_recid[i] = (u8)(ok ? recid : 0u);
       out_ok[i] = ok ? 1 : 0;
-    }
+      return km;
+    });
   }
 
   // JPoint#eqXToP (short.js:908-925): X == r*Z^2, retry with r+n while < p.
