@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/ellgpu.h, include/ellgpu_ext.h, include/ellgpu_ext2.h,
-include/ellgpu_ext3.h and include/ellgpu_ext4.h.
+include/ellgpu_ext3.h, include/ellgpu_ext4.h and include/ellgpu_addn.h.
 
 `load()` opens the in-tree libellgpu.so (built by __graft_entry__.build() /
 elliptic_amd/build.py with hipcc for gfx950).  There is no fallback of any
@@ -133,6 +133,12 @@ _EXT4_SIGS = {
 }
 EXT4_SYMBOLS = sorted(_EXT4_SIGS)
 
+# ... and include/ellgpu_addn.h, a sixth table (tests/golden/addn_binding_sigs.json)
+_SUM_SIGS = {
+    "ellgpu_mul_sum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_void_p]),
+}
+SUM_SYMBOLS = sorted(_SUM_SIGS)
+
 # ELLGPU_VERSION of the include/ellgpu.h this table was written against: load() refuses any other
 # library (a prototype changed -- e.g. ellgpu_ecdsa_verify's out_status -- and a stale table would
 # pass garbage for the added arguments)
@@ -158,7 +164,7 @@ def load(path=None, optional=()):
         raise ImportError("%s reports ABI version 0x%06x, this binding was written for 0x%06x (include/ellgpu.h "
                           "ELLGPU_VERSION): rebuild the library from this tree" % (path, got, ABI_VERSION))
     for name, (res, args) in (list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_EXT2_SIGS.items())
-                              + list(_EXT3_SIGS.items()) + list(_EXT4_SIGS.items())):
+                              + list(_EXT3_SIGS.items()) + list(_EXT4_SIGS.items()) + list(_SUM_SIGS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -54,6 +54,7 @@ def source_files():
     files = sorted(os.path.join("elliptic_amd", "csrc", f) for f in os.listdir(CSRC)
                    if f.endswith((".h", ".hip")) and os.path.isfile(os.path.join(CSRC, f)))
     files.append(os.path.join("include", "ellgpu.h"))
+    files.append(os.path.join("include", "ellgpu_addn.h"))     # (at its sorted place: the last two entries are pinned)
     files.append(os.path.join("include", "ellgpu_ext.h"))
     files.append(os.path.join("include", "ellgpu_ext2.h"))
     files.append(os.path.join("include", "ellgpu_ext3.h"))

@@ -9,7 +9,7 @@
 // before including this header.
 #pragma once
 
-#include "../../include/ellgpu_ext4.h"
+#include "../../include/ellgpu_addn.h"
 #include "engine.h"
 
 #include <mutex>
@@ -948,6 +948,26 @@ int ellgpu_ecdsa_recid(ellgpu_ctx* ctx, int curve, size_t n, const uint8_t* hash
   return ell_call(ctx, stream, where, [=](Eng& e, Mem w) {
     return e.ecdsa_recid(w, curve, n, hash, hash_len, r, s, pub_xy, out_recid, out_status);
   });
+}
+// include/ellgpu_addn.h: n sums of m terms k * P each.  One form, like ellgpu_mul_base; a group shards
+// a host batch by whole sums (fewer sums than members, or operands that the engine refuses anyway:
+// the first member)
+int ellgpu_mul_sum(ellgpu_ctx* ctx, int curve, size_t n, size_t m, const uint8_t* k, const uint8_t* xy,
+                   uint8_t* out_xy, uint8_t* out_inf, int mem, void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (where == Mem::host && ctx->members.size() > 1 && n >= ctx->members.size() && m && k && xy && out_xy &&
+      out_inf && m <= SIZE_MAX / n / 256) {
+    ELL_LOCK(ctx);
+    size_t B, NB;
+    if (curve_widths(curve, B, NB)) return ELLGPU_E_ARG;
+    return group_shard(ctx, n, [=](ellgpu_ctx* mb, size_t lo, size_t hi) {
+      return ellgpu_mul_sum(mb, curve, hi - lo, m, k + lo * m * B, xy + lo * m * 2 * B, out_xy + lo * 2 * B,
+                            out_inf + lo, mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) { return e.mul_sum(w, curve, n, m, k, xy, out_xy, out_inf); });
 }
 int ellgpu_eddsa_sign(ellgpu_ctx* ctx, size_t n, const uint8_t* secrets, const uint8_t* msgs,
                       const uint64_t* msg_off, size_t msg_len, uint8_t* out_sig, uint8_t* out_pub) {

@@ -115,6 +115,39 @@ struct FnMulAdd2 {
     if (i < n) W::mul_add2(i, n, k1, xy1, k2, xy2, tbl, ds, jac);
   }
 };
+// sums of many k * P terms (Work::sum_pair, sum_fold, sum_mark): mul_add2's ladder over the pairs of
+// neighbouring terms, the halving steps over the partial sums, the off-curve mark on the results
+template <class CV>
+struct FnSumPairs {
+  static constexpr const char* NAME = "sum_pairs";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = FnMulAdd2<CV>::DS_PER_LANE;
+  static constexpr int MIN_WAVES = FnMulAdd2<CV>::MIN_WAVES;
+  size_t rows, len, m, q0; const u8* k; const u8* xy; typename W::J* tbl; u32* jac; u8* flag;
+  ELL_HD void operator()(size_t i, const DigitStore& ds) const {
+    if (i < rows * len) W::sum_pair(i, rows, len, m, q0, k, xy, tbl, ds, jac, flag);
+  }
+};
+template <class CV>
+struct FnSumFold {
+  static constexpr const char* NAME = "sum_fold";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t rows, stride, len; u32* jac; u8* flag; u32* cjac; u8* cflag; size_t cn, c0;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < rows * ((len + 1) / 2)) W::sum_fold(i, rows, stride, len, jac, flag, cjac, cflag, cn, c0);
+  }
+};
+template <class CV>
+struct FnSumMark {
+  static constexpr const char* NAME = "sum_mark";
+  typedef Work<CV> W;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* cflag; u8* out_xy; u8* out_inf;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) W::sum_mark(i, cflag, out_xy, out_inf);
+  }
+};
 template <class CV, int MW = 0>
 struct FnMulAddG {
   static constexpr const char* NAME = "mul_add_g";
@@ -1528,6 +1561,7 @@ class Engine {
     size_t comb_max_bytes;    // ELLGPU_COMB_MAX_BYTES: fixed-base tables above this are treated as unallocatable (0 = no limit)
     int prep_k;
     int norm_k;
+    size_t sum_slice;         // ELLGPU_SUM_SLICE: most pairs of terms per launch of a sum (mul_sum); default CHUNK
   };
   Tuning tune_;
   void init_tuning() {
@@ -1561,6 +1595,13 @@ class Engine {
     tune_.prep_k = e ? atoi(e) : 0;
     e = getenv("ELLGPU_NORM_K");
     tune_.norm_k = e ? atoi(e) : 0;
+    // ELLGPU_SUM_SLICE  most pairs of terms that one launch of mul_sum takes (minimum 1); a sum with
+    //                   more pairs is walked in slices of that many.  Default: CHUNK.  A developer /
+    //                   test override: it lets small sums reach the slice path.
+    e = getenv("ELLGPU_SUM_SLICE");
+    tune_.sum_slice = e ? (size_t)strtoull(e, nullptr, 10) : CHUNK;
+    if (tune_.sum_slice < 1) tune_.sum_slice = 1;
+    if (tune_.sum_slice > CHUNK) tune_.sum_slice = CHUNK;
   }
   bool split_small_verify() const { return tune_.split_verify; }
   size_t coop_grid() const { return CoopK256::AVAILABLE ? tune_.coop_grid : 0; }
@@ -1826,6 +1867,11 @@ class Engine {
   template <class CV>
   int mul_add_g_chunk(size_t n, const u8* k1, const u8* k2, const u8* xy2, u8* out_xy,
                       u8* out_inf);
+  // n sums of m terms each (mul_sum): sum_pairs, the halving steps of sum_fold, one normalisation
+  // per sum, sum_mark.  Either the pairs and the results of all n sums fit one chunk
+  // (sum_group_max), or n == 1 and the sum is walked in slices.
+  template <class CV>
+  int sum_chunk(size_t n, size_t m, const u8* k, const u8* xy, u8* out_xy, u8* out_inf);
   template <class CV>
   int ecdsa_chunk(size_t n, const u8* hash, int hash_len, int shift, const u8* r, const u8* s,
                   const u8* pub, u8* ok, u8* st);
@@ -2993,6 +3039,55 @@ class Engine {
     });
   }
 
+  // n sums of m terms k * P each (include/ellgpu_addn.h): _wnafMulAdd / _endoWnafMulAdd on any number
+  // of points.  The short curves only: the presets and user-defined short ids, plain and domain.
+  // An item of the batch is a whole sum (strides m B and m 2 B); a chunk is a group of sums whose
+  // pairs of terms and results fit one launch (sum_group_max), or one slice after the other of a sum
+  // that is longer than that (sum_chunk).  One item per lane at every n: form_for is not consulted.
+  // Sums per chunk: the pairs (ceil(m / 2) per sum) fit the slice size, and the pairs and the results
+  // together CHUNK entries of Jacobian scratch.  0: one sum has more pairs than that -- slices.
+  size_t sum_group_max(size_t m) const {
+    const size_t P = m / 2 + (m & 1);
+    const size_t a = tune_.sum_slice / P, b = CHUNK / (P + 1);
+    return a < b ? a : b;
+  }
+  int mul_sum(Mem where, int curve, size_t n, size_t m, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci || (is_custom(curve) && !custom_block(curve))) return fail(E_ARG, "unknown curve id");
+    if (curve == CURVE_ED25519 || custom_is_edwards(curve))
+      return fail(E_UNSUPPORTED, "sums of k * P terms are implemented for the short Weierstrass curves; Edwards curves are a later change (ellgpu_mul_add2 takes two terms there)");
+    if (curve == CURVE_CURVE25519 || custom_is_mont(curve))
+      return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");     // mont.js:155-157
+    if (m == 0) return fail(E_ARG, "m must be at least 1");
+    const size_t B = ci->field_bytes;
+    if (n && (m > SIZE_MAX / n || n * m > SIZE_MAX / (2 * B))) return fail(E_ARG, "n * m terms do not fit size_t");
+    if (n && (!k || !xy || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
+    if (n == 0) return E_OK;
+    if (where == Mem::device) {
+      // the flags of the terms are folded into out_inf after the results are written
+      const u8* const ins[2] = {k, xy};
+      const size_t lens[2] = {n * m * B, n * m * 2 * B};
+      for (int i = 0; i < 2; i++)
+        if (overlap2(ins[i], lens[i], out_xy, n * 2 * B) || overlap2(ins[i], lens[i], out_inf, n))
+          return fail(E_ARG, "k / xy and the results must not overlap");
+      if (overlap2(out_xy, n * 2 * B, out_inf, n)) return fail(E_ARG, "out_xy and out_inf must not overlap");
+    }
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t G = sum_group_max(m);
+    return batch(where, n, {In{k, m * B}, In{xy, m * 2 * B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}},
+                 [&](size_t c, auto d, auto r) {
+      return for_chunks(c, G ? G : 1, [&](size_t o, size_t g) {
+        int rc = E_OK;
+        const u8* kk = d[0] + o * m * B;
+        const u8* pp = d[1] + o * m * 2 * B;
+        if (is_custom(curve)) rc = sum_chunk<CvCustom>(g, m, kk, pp, r[0] + o * 2 * B, r[1] + o);
+        else ELL_SHORT_DISPATCH(curve, rc = sum_chunk<CV>(g, m, kk, pp, r[0] + o * 2 * B, r[1] + o));
+        return rc;
+      });
+    });
+  }
+
   // EdDSA (ed25519).  msgs: concatenated message bytes; off (n + 1 offsets, in the memory the
   // other operands are in) or, if null, a uniform stride msg_len.  Whole-buffer operands: a host
   // call goes through staged_whole(), and tests the offsets it can read.
@@ -3800,6 +3895,67 @@ int Engine<BK>::mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u8* 
     bk.launch(g, n);
   }
   return rc;
+}
+
+// Scratch: never more Jacobian entries or window tables than mul_add2_chunk claims for CHUNK items.
+// S_JAC holds three runs of planes -- the pairs' (at most `cap` entries), the slices' partial sums
+// (nsl entries, none when every sum is whole) and the compact results (n) -- and S_VALID the flags
+// of the same entries, a byte each; S_TBL the pairs' window tables.
+template <class BK>
+template <class CV>
+int Engine<BK>::sum_chunk(size_t n, size_t m, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
+  typedef Work<CV> W;
+  const size_t P = m / 2 + (m & 1);
+  const bool whole = n <= sum_group_max(m);
+  size_t s = P, nsl = 0;                  // pairs per launch and row; slices of the one sum
+  if (!whole) {
+    if (n != 1) return fail(E_ARG, "a sum that is walked in slices is a chunk of its own");
+    s = tune_.sum_slice;
+    nsl = (P - 1) / s + 1;
+    if (s + nsl + 1 > CHUNK) {            // the slices' partial sums and the result share the pairs' scratch
+      s = CHUNK / 2;
+      nsl = (P - 1) / s + 1;
+    }
+    if (nsl + 1 > CHUNK / 2) return fail(E_ARG, "m: too many terms for one sum");
+  }
+  const size_t cap = whole ? n * P : s;
+  const size_t E = 3 * (size_t)W::NS;       // words of a Jacobian entry
+  u32* jac = claim<u32>(S_JAC, (cap + nsl + n) * E * 4);
+  auto* tbl = claim<typename W::J>(S_TBL, cap * 2 * W::TBLJ * sizeof(typename W::J));
+  u8* flag = claim<u8>(S_VALID, cap + nsl + n);
+  if (int rc = claimed()) return rc;
+  u32* pjac = jac + cap * E;
+  u8* pflag = flag + cap;
+  u32* cjac = pjac + nsl * E;
+  u8* cflag = pflag + nsl;
+  // the halving steps of `rows` rows of `len` partial sums; the last one (the copy step of a row
+  // that starts with one partial) writes entry d0 + row of the dn-entry planes dst / dflag
+  auto fold = [&](size_t rows, size_t len, u32* src, u8* sflag, u32* dst, u8* dflag, size_t dn, size_t d0) {
+    const size_t stride = len;
+    for (;; len = (len + 1) / 2) {
+      FnSumFold<CV> f{rows, stride, len, src, sflag, dst, dflag, dn, d0};
+      bk.launch(f, rows * ((len + 1) / 2));
+      if (len <= 2) break;
+    }
+  };
+  if (whole) {
+    FnSumPairs<CV> f{n, P, m, 0, k, xy, tbl, jac, flag};
+    bk.launch(f, n * P);
+    fold(n, P, jac, flag, cjac, cflag, n, 0);
+  } else {
+    for (size_t sl = 0; sl < nsl; sl++) {
+      const size_t q0 = sl * s, len = P - q0 < s ? P - q0 : s;
+      FnSumPairs<CV> f{1, len, m, q0, k, xy, tbl, jac, flag};
+      bk.launch(f, len);
+      fold(1, len, jac, flag, pjac, pflag, nsl, sl);
+    }
+    fold(1, nsl, pjac, pflag, cjac, cflag, 1, 0);
+  }
+  int rc = normalize_chunk<CV>(n, cjac, out_xy, out_inf, nullptr);
+  if (rc) return rc;
+  FnSumMark<CV> g{n, cflag, out_xy, out_inf};
+  bk.launch(g, n);
+  return E_OK;
 }
 
 template <class BK>

@@ -23,7 +23,8 @@ namespace ell {
                                                            const Work<CV>::A*, const Work<CV>::A*, u8*);
 #define ELL_DECL_G2(KW, CV)                                                                  \
   KW template int Engine<HipBackend>::mul_add2_chunk<CV>(size_t, const u8*, const u8*,       \
-                                                         const u8*, const u8*, u8*, u8*);
+                                                         const u8*, const u8*, u8*, u8*);    \
+  KW template int Engine<HipBackend>::sum_chunk<CV>(size_t, size_t, const u8*, const u8*, u8*, u8*);
 #define ELL_DECL_G3(KW, CV)                                                                   \
   KW template int Engine<HipBackend>::mul_add_g_chunk<CV>(size_t, const u8*, const u8*,       \
                                                           const u8*, u8*, u8*);
@@ -85,6 +86,8 @@ namespace ell {
                                                                 Work<CvCustom>::A*);                 \
   KW template int Engine<HipBackend>::mul_add2_chunk<CvCustom>(size_t, const u8*, const u8*,         \
                                                                const u8*, const u8*, u8*, u8*);      \
+  KW template int Engine<HipBackend>::sum_chunk<CvCustom>(size_t, size_t, const u8*, const u8*, u8*, \
+                                                          u8*);                                      \
   KW template int Engine<HipBackend>::point_add_chunk<CvCustom>(size_t, const u8*, const u8*, const u8*, \
                                                                 const u8*, u8*, u8*);                \
   KW template int Engine<HipBackend>::edc_chunk<0>(int, size_t, const u8*, const u8*, const u8*,     \

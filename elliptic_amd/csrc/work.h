@@ -324,6 +324,79 @@ struct Work {
     store_jac(jac, n, i, r);
   }
 
+  // ---- sums of many k * P terms (_wnafMulAdd / _endoWnafMulAdd on any number of points,
+  // base.js:128-253, short.js:434-450) ----------------------------------------------------------
+  // The terms of a sum are taken two at a time through mul_add2's ladder, the partial sums stay
+  // in Jacobian form and are added on the device (sum_fold); the caller normalises once per sum.
+  // One lane per pair.  A launch covers `rows` sums (or one slice of one sum) of `len` pairs each:
+  // lane idx is pair q0 + idx % len of sum idx / len, i.e. the terms 2 q and 2 q + 1 of that sum's
+  // m; ks / xys are the scalars and points of the first of the rows.  A lone last term (m odd)
+  // fills its second slot with the scalar 0 on its own point.  flag[idx]: 1 where one of the two
+  // points is not on the curve (the sum is then outside the engine's domain, see on_curve).
+  ELL_HD static void sum_pair(size_t idx, size_t rows, size_t len, size_t m, size_t q0, const u8* ks,
+                              const u8* xys, J* tbl_all, const DigitStore& ds, u32* jac, u8* flag) {
+    const size_t j = idx / len;
+    const size_t q = q0 + (idx - j * len);
+    const size_t t1 = j * m + 2 * q;
+    const bool lone = 2 * q + 1 >= m;
+    const size_t t2 = lone ? t1 : t1 + 1;
+    u32 k1[L], k2[L];
+    load_be<L>(k1, ks + t1 * BYTES, BYTES);
+    load_be<L>(k2, ks + t2 * BYTES, BYTES);
+    if (lone) {
+      ELL_UNROLL
+      for (int l = 0; l < L; l++) k2[l] = 0;
+    }
+    A p1 = load_affine(xys, t1);
+    A p2 = load_affine(xys, t2);
+    flag[idx] = (on_curve(p1) && on_curve(p2)) ? (u8)0 : (u8)1;
+    J* tbl = tbl_all + idx * 2 * TBLJ;
+    u32 negmask = 0;
+    prepare_var(k1, p1, ds, 0, 2 * NSV, tbl, negmask);
+    prepare_var(k2, p2, ds, NSV, 2 * NSV, tbl + TBLJ, negmask);
+    J r = LD::template run_w4<2 * NSV, NWIN>(ds, tbl, negmask);
+    store_jac(jac, rows * len, idx, r);
+  }
+  // One halving step of every row at once, in place.  The planes hold `rows` rows of `stride`
+  // entries, of which the first `len` of each row are live partial sums; h = ceil(len / 2).  Lane
+  // idx is entry i = idx % h of row idx / h: P[i] += P[i + h] where i + h < len, and the flags are
+  // ORed.  Reads come from entries >= h and the lane's own, writes go to entries < h: no hazard
+  // within a launch.  (The idle lanes of the launch's last wave repeat its last entry, common.h
+  // fill_lane: they are lanes of that entry's own wave, whose loads all precede its first store --
+  // every word of the sum depends on every word of both operands -- so they store what it stores.)
+  // The full G::add: two equal partials, P + (-P), O + P and O + O are ordinary
+  // inputs here.  The step that leaves one partial (h == 1; len == 1 is the copy step of a row that
+  // starts with one) writes it to entry c0 + row of the compact planes cjac / cflag of cn entries.
+  ELL_HD static void sum_fold(size_t idx, size_t rows, size_t stride, size_t len, u32* jac, u8* flag,
+                              u32* cjac, u8* cflag, size_t cn, size_t c0) {
+    const size_t h = (len + 1) / 2;
+    const size_t row = idx / h;
+    const size_t i = idx - row * h;
+    const size_t a = row * stride + i;
+    const size_t N = rows * stride;
+    J p = load_jac(jac, N, a);
+    u8 f = flag[a];
+    const bool pair = i + h < len;
+    if (pair) {
+      p = G::add(p, load_jac(jac, N, a + h));
+      f |= flag[a + h];
+    }
+    if (h == 1) {
+      store_jac(cjac, cn, c0 + row, p);
+      cflag[c0 + row] = f;
+    } else if (pair) {
+      store_jac(jac, N, a, p);
+      flag[a] = f;
+    }
+  }
+  // behind the normalisation of the compact results: a set flag is out_inf = 2 and a zeroed result
+  ELL_HD static void sum_mark(size_t i, const u8* cflag, u8* out_xy, u8* out_inf) {
+    if (!cflag[i]) return;
+    out_inf[i] = (u8)DOMAIN_OFF_CURVE;
+    ELL_NOUNROLL
+    for (int b = 0; b < 2 * BYTES; b++) out_xy[i * 2 * BYTES + b] = 0;
+  }
+
   // k1*G + k2*P2 -> Jacobian (the shape ECDSA verify uses): window ladder for P2, then the
   // comb's mixed additions for G onto the same accumulator (no second point, no Jacobian add)
   ELL_HD static void mul_add_g_item(size_t i, size_t n, const u8* k1s, const u8* k2s,

@@ -455,6 +455,35 @@ class Context:
     def mul_add2_dev(self, curve, k1, p1, k2, p2, out_xy, out_inf):
         self._c_rows("mul_add2", True, curve, k1, p1, k2, p2, out_xy, out_inf)
 
+    def mul_sum(self, curve, k, xy, out=None):
+        """n sums of m terms, sum_i k[j, i] * P[j, i] -> (xy (n, 2 field_bytes), inf (n,)): inf 0 a
+        point, 1 the sum is the point at infinity, 2 (STATUS_OFF_CURVE) a term's point is not on the
+        curve; xy is zeroed wherever inf is not 0 (ellgpu_mul_sum: _wnafMulAdd on any number of
+        points, the partial sums added on the device, one normalisation per sum).  curve: a short
+        preset or a define_short / define_short_domain id.  k: (n, m, field_bytes), used as it
+        stands (not reduced mod n); xy: (n, m, 2 field_bytes).  numpy arrays go through host memory;
+        torch device tensors (k, xy and out=(xy, inf), required then) run on the current stream and
+        return at once."""
+        B = FIELD_BYTES[CURVES[curve] if isinstance(curve, int) and 0 <= curve < len(CURVES) else curve]
+        dev = self._is_tensor(k)
+        if not dev:
+            k, xy = _u8(k), _u8(xy)
+        if len(k.shape) != 3 or int(k.shape[2]) != B:
+            raise ValueError("k must be (n, m, %d)" % B)
+        n, m = int(k.shape[0]), int(k.shape[1])
+        shapes = [(n, m, B), (n, m, 2 * B), (n, 2 * B), (n,)]
+        if dev:
+            self._dev_operands([k, xy], ["k", "xy"], out, ("xy", "inf"), shapes)
+            res = list(out)
+        else:
+            if xy.shape != shapes[1]:
+                raise ValueError("xy must be (n, m, %d)" % (2 * B))
+            res = self._outs(out, shapes[2:])
+        addr = [a.data_ptr() if dev else a.ctypes.data for a in [k, xy] + res]
+        self._check(self._lib.ellgpu_mul_sum(self._ctx, self._cid(curve), n, m, *addr, 1 if dev else 0,
+                                             self._stream() if dev else None))
+        return res[0], res[1]
+
     def point_add(self, curve, xy1, xy2, inf1=None, inf2=None):
         """Point#add per pair of affine points (infinity through the optional flags) -> (xy, inf)"""
         B = FIELD_BYTES[curve]

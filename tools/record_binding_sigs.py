@@ -12,7 +12,8 @@ after a deliberate change of include/ellgpu.h -- never to make a failing test pa
 --table ext / ext2 / ext3 / ext4 records one of the later tables instead (_EXT_SIGS of include/ellgpu_ext.h
 into binding_sigs_ext.json, _EXT2_SIGS of include/ellgpu_ext2.h into binding_sigs_ext2.json,
 _EXT3_SIGS of include/ellgpu_ext3.h into binding_sigs_ext3.json, _EXT4_SIGS of include/ellgpu_ext4.h
-into binding_sigs_ext4.json): once, when the table is introduced.
+into binding_sigs_ext4.json; --table addn: _SUM_SIGS of include/ellgpu_addn.h into
+addn_binding_sigs.json): once, when the table is introduced.
 """
 import argparse
 import json
@@ -28,7 +29,11 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "binding_sigs.json")
 TABLES = {"sigs": ("_SIGS", GOLDEN), "ext": ("_EXT_SIGS", GOLDEN.replace(".json", "_ext.json")),
           "ext2": ("_EXT2_SIGS", GOLDEN.replace(".json", "_ext2.json")),
           "ext3": ("_EXT3_SIGS", GOLDEN.replace(".json", "_ext3.json")),
-          "ext4": ("_EXT4_SIGS", GOLDEN.replace(".json", "_ext4.json"))}
+          "ext4": ("_EXT4_SIGS", GOLDEN.replace(".json", "_ext4.json")),
+          # (addn_binding_sigs.json, not binding_sigs_addn.json: tests/test_dev_streams_hostsim.py takes every
+          # binding_sigs*.json for a table whose `mem` calls tests/dev_stream_checks.py schedules; ellgpu_mul_sum
+          # is tested in flight in tests/test_mul_sum_gpu.py until that table names it)
+          "addn": ("_SUM_SIGS", os.path.join(os.path.dirname(GOLDEN), "addn_binding_sigs.json"))}
 
 
 def table(sigs=None):
