@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/ellgpu.h, include/ellgpu_ext.h, include/ellgpu_ext2.h,
-include/ellgpu_ext3.h, include/ellgpu_ext4.h and include/ellgpu_addn.h.
+include/ellgpu_ext3.h, include/ellgpu_ext4.h, include/ellgpu_addn.h and elliptic_amd/include/ellgpu_edsum.h.
 
 `load()` opens the in-tree libellgpu.so (built by __graft_entry__.build() /
 elliptic_amd/build.py with hipcc for gfx950).  There is no fallback of any
@@ -139,6 +139,12 @@ _SUM_SIGS = {
 }
 SUM_SYMBOLS = sorted(_SUM_SIGS)
 
+# ... and elliptic_amd/include/ellgpu_edsum.h, a seventh table (tests/golden/edsum_binding_sigs.json)
+_EDSUM_SIGS = {
+    "ellgpu_ed_mul_sum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_void_p]),
+}
+EDSUM_SYMBOLS = sorted(_EDSUM_SIGS)
+
 # ELLGPU_VERSION of the include/ellgpu.h this table was written against: load() refuses any other
 # library (a prototype changed -- e.g. ellgpu_ecdsa_verify's out_status -- and a stale table would
 # pass garbage for the added arguments)
@@ -164,7 +170,8 @@ def load(path=None, optional=()):
         raise ImportError("%s reports ABI version 0x%06x, this binding was written for 0x%06x (include/ellgpu.h "
                           "ELLGPU_VERSION): rebuild the library from this tree" % (path, got, ABI_VERSION))
     for name, (res, args) in (list(_SIGS.items()) + list(_EXT_SIGS.items()) + list(_EXT2_SIGS.items())
-                              + list(_EXT3_SIGS.items()) + list(_EXT4_SIGS.items()) + list(_SUM_SIGS.items())):
+                              + list(_EXT3_SIGS.items()) + list(_EXT4_SIGS.items()) + list(_SUM_SIGS.items())
+                              + list(_EDSUM_SIGS.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

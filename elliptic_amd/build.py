@@ -53,6 +53,8 @@ def source_files():
     root = os.path.normpath(os.path.join(HERE, ".."))
     files = sorted(os.path.join("elliptic_amd", "csrc", f) for f in os.listdir(CSRC)
                    if f.endswith((".h", ".hip")) and os.path.isfile(os.path.join(CSRC, f)))
+    # (the public header that came after include/'s six were pinned: between the csrc files and include/)
+    files.append(os.path.join("elliptic_amd", "include", "ellgpu_edsum.h"))
     files.append(os.path.join("include", "ellgpu.h"))
     files.append(os.path.join("include", "ellgpu_addn.h"))     # (at its sorted place: the last two entries are pinned)
     files.append(os.path.join("include", "ellgpu_ext.h"))

@@ -9,7 +9,7 @@
 // before including this header.
 #pragma once
 
-#include "../../include/ellgpu_addn.h"
+#include "../include/ellgpu_edsum.h"
 #include "engine.h"
 
 #include <mutex>
@@ -968,6 +968,26 @@ int ellgpu_mul_sum(ellgpu_ctx* ctx, int curve, size_t n, size_t m, const uint8_t
     });
   }
   return ell_call(ctx, stream, where, [=](Eng& e, Mem w) { return e.mul_sum(w, curve, n, m, k, xy, out_xy, out_inf); });
+}
+// elliptic_amd/include/ellgpu_edsum.h: the same on ed25519 and user-defined Edwards ids (B = 32); one
+// form, sharded like ellgpu_mul_sum
+int ellgpu_ed_mul_sum(ellgpu_ctx* ctx, int curve, size_t n, size_t m, const uint8_t* k, const uint8_t* xy,
+                      uint8_t* out_xy, uint8_t* out_inf, int mem, void* stream) {
+  if (!ctx) return set_err(ELLGPU_E_ARG, "null context");
+  Mem where;
+  if (int rc = mem_of(mem, stream, where)) return rc;
+  if (where == Mem::host && ctx->members.size() > 1 && n >= ctx->members.size() && m && k && xy && out_xy &&
+      out_inf && m <= SIZE_MAX / n / 256) {
+    ELL_LOCK(ctx);
+    size_t B, NB;
+    if (curve_widths(curve, B, NB)) return ELLGPU_E_ARG;
+    B = 32;                                             // (whatever the id: the engine refuses the others)
+    return group_shard(ctx, n, [=](ellgpu_ctx* mb, size_t lo, size_t hi) {
+      return ellgpu_ed_mul_sum(mb, curve, hi - lo, m, k + lo * m * B, xy + lo * m * 2 * B, out_xy + lo * 2 * B,
+                               out_inf + lo, mem, nullptr);
+    });
+  }
+  return ell_call(ctx, stream, where, [=](Eng& e, Mem w) { return e.ed_mul_sum(w, curve, n, m, k, xy, out_xy, out_inf); });
 }
 int ellgpu_eddsa_sign(ellgpu_ctx* ctx, size_t n, const uint8_t* secrets, const uint8_t* msgs,
                       const uint64_t* msg_off, size_t msg_len, uint8_t* out_sig, uint8_t* out_pub) {

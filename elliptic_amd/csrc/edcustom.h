@@ -17,10 +17,11 @@
 
 #include "fp_rt.h"
 #include "ladder.h"
+#include "edsum.h"
 
 namespace ell {
 
-struct EdcWork {
+struct EdcWork : EdSum<EdcWork> {
   typedef FpMontRT F;
   typedef F::El El;
   static constexpr int L = 8;
@@ -180,6 +181,19 @@ struct EdcWork {
     recode_w4<8, NNIB, true>(k2, ds, 1, 2);
     store_proj(out, n, i, run_w4<2>(ds, tbl));
   }
+  // ---- sums of many k * P terms: what EdSum (edsum.h) asks of a work class.  An entry of the
+  // partial sums is the projective (X, Y, Z) that `add` takes: three planes, no T.
+  static constexpr int SUM_PLANES = 3;
+  ELL_HD static void store_sum(u32* out, size_t n, size_t i, const P& p) { store_proj(out, n, i, p); }
+  ELL_HD static P load_sum(const u32* proj, size_t n, size_t i) {
+    P r;
+    r.X = load_limbs<El>(proj, n, i, 0 * 8);
+    r.Y = load_limbs<El>(proj, n, i, 1 * 8);
+    r.Z = load_limbs<El>(proj, n, i, 2 * 8);
+    return r;
+  }
+  ELL_HD static P sum_add(const P& p, const P& q) { return add(p, q); }
+  ELL_HD static bool sum_on_curve(const P& p) { return on_curve(p.X, p.Y); }      // load_affine: (x, y, 1)
   // ---- fixed-base tables of caller-chosen points (BasePoint#precompute; Engine::define_ed_base) ----
   // acc + k * B over B's table: an unsigned comb of 256 / bits windows x (2^bits - 1) entries,
   // entry (w, d) = (d << (bits w)) * B, the width read from the header slot (8 or 16: one walk serves

@@ -13,6 +13,7 @@
 
 #include "curve_consts.h"
 #include "ladder.h"
+#include "edsum.h"
 #include "sha512.h"
 #include "hmac_drbg512.h"
 
@@ -22,7 +23,7 @@
 
 namespace ell {
 
-struct EdWork {
+struct EdWork : EdSum<EdWork> {
   typedef Fp25519 F;
   typedef F::El El;
   typedef consts::ED25519_C C;
@@ -255,6 +256,29 @@ struct EdWork {
     recode_w4<8, NNIB, true>(k2, ds, 1, 2);
     store_ext(ext, n, i, run_w4<2>(ds, tbl));
   }
+
+  // ---- sums of many k * P terms: what EdSum (edsum.h) asks of a work class -------------------
+  // An entry of the partial sums is FOUR planes, X, Y, Z and T: the fold is add(p, to_cached(q)),
+  // which reads T of both operands, and store_ext leaves T out (its readers normalise).  run_w4
+  // produces T after its last window.  The normalisation reads the first three planes of the
+  // compact entries as it reads any store_ext buffer.
+  static constexpr int SUM_PLANES = 4;
+  ELL_HD static void store_sum(u32* ext, size_t n, size_t i, const P& p) {
+    store_limbs(ext, n, i, 0 * 8, p.a);
+    store_limbs(ext, n, i, 1 * 8, p.b);
+    store_limbs(ext, n, i, 2 * 8, p.c);
+    store_limbs(ext, n, i, 3 * 8, p.d);
+  }
+  ELL_HD static P load_sum(const u32* ext, size_t n, size_t i) {
+    P r;
+    r.a = load_limbs<El>(ext, n, i, 0 * 8);
+    r.b = load_limbs<El>(ext, n, i, 1 * 8);
+    r.c = load_limbs<El>(ext, n, i, 2 * 8);
+    r.d = load_limbs<El>(ext, n, i, 3 * 8);
+    return r;
+  }
+  ELL_HD static P sum_add(const P& p, const P& q) { return add(p, to_cached(q)); }
+  ELL_HD static bool sum_on_curve(const P& p) { return on_curve(p.a, p.b); }      // from_affine: (x, y, 1, xy)
 
   // EdwardsCurve#pointFromY (edwards.js:71-97, c = 1, a = -1): x^2 = (y^2 - 1)/(d y^2 + 1),
   // x with the requested parity.  ok = 0 when there is no such point -- also for the

@@ -1306,6 +1306,57 @@ struct FnEdcNormalize {
     if (t < T) EdcWork::normalize(t, T, n, K, proj, pre, out_xy, out_inf);
   }
 };
+// sums of many k * P terms on the Edwards curves (edsum.h: sum_pair, sum_fold, sum_mark), over the
+// work class EW = EdWork (ed25519) or EdcWork (user-defined ids): the pair kernel with the LDS
+// columns and the register budget of that family's mul_add2 kernel
+template <class EW>
+struct EdSumKernels;
+template <>
+struct EdSumKernels<EdWork> {
+  typedef FnEdMulAdd2 MulAdd2;
+  static constexpr int MIN_WAVES = 1;
+  static constexpr const char* PAIRS = "ed_sum_pairs";
+  static constexpr const char* FOLD = "ed_sum_fold";
+  static constexpr const char* MARK = "ed_sum_mark";
+};
+template <>
+struct EdSumKernels<EdcWork> {
+  typedef FnEdcMulAdd2 MulAdd2;
+  static constexpr int MIN_WAVES = FnEdcMulAdd2::MIN_WAVES;
+  static constexpr const char* PAIRS = "edc_sum_pairs";
+  static constexpr const char* FOLD = "edc_sum_fold";
+  static constexpr const char* MARK = "edc_sum_mark";
+};
+template <class EW>
+struct FnEdSumPairs {
+  static constexpr const char* NAME = EdSumKernels<EW>::PAIRS;
+  static constexpr int DS_PER_LANE = EdSumKernels<EW>::MulAdd2::DS_PER_LANE;
+  static constexpr int MIN_WAVES = EdSumKernels<EW>::MIN_WAVES;
+  size_t rows, len, m, q0; const u8* k; const u8* xy; typename EW::P* tbl; u32* ext; u8* flag;
+  ELL_HD void operator()(size_t i, const DigitStore& ds) const {
+    if (i < rows * len) EW::sum_pair(i, rows, len, m, q0, k, xy, tbl, ds, ext, flag);
+  }
+};
+// (the fold is left to the register allocator: 176 VGPRs on ed25519, 168 on user-defined ids, no
+// scratch; held to 168 / 128 registers the ed25519 fold spills 44 / 228 bytes)
+template <class EW>
+struct FnEdSumFold {
+  static constexpr const char* NAME = EdSumKernels<EW>::FOLD;
+  static constexpr int DS_PER_LANE = 0;
+  size_t rows, stride, len; u32* ext; u8* flag; u32* cext; u8* cflag; size_t cn, c0;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < rows * ((len + 1) / 2)) EW::sum_fold(i, rows, stride, len, ext, flag, cext, cflag, cn, c0);
+  }
+};
+template <class EW>
+struct FnEdSumMark {
+  static constexpr const char* NAME = EdSumKernels<EW>::MARK;
+  static constexpr int DS_PER_LANE = 0;
+  size_t n; const u8* cflag; u8* out_xy; u8* out_inf;
+  ELL_HD void operator()(size_t i, const DigitStore&) const {
+    if (i < n) EW::sum_mark(i, cflag, out_xy, out_inf);
+  }
+};
 // fixed-base tables of caller-chosen points on user-defined Edwards curves (EdcWork::comb_add)
 struct FnEdcMulBase {
   static constexpr const char* NAME = "edc_mul_base";
@@ -1923,6 +1974,12 @@ class Engine {
   template <int U = 0>
   int ed_mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u8* k2, const u8* xy2,
                         u8* out_xy, u8* out_inf);
+  // n sums of m terms each on an Edwards curve (ed_mul_sum), EW = EdWork on ed25519, EdcWork on a
+  // user-defined id: sum_chunk's shape over that work class -- the pair kernel, the halving steps,
+  // one normalisation per sum, the mark.  Either the pairs and the results of all n sums fit one
+  // chunk (sum_group_max), or n == 1 and the sum is walked in slices.
+  template <class EW>
+  int ed_sum_chunk(size_t n, size_t m, const u8* k, const u8* xy, u8* out_xy, u8* out_inf);
   template <int U = 0>
   int x25519_chunk(size_t n, const u8* k, const u8* x, u8* out_x, u8* out_inf, u8* out_bad);
   // user-defined Edwards curves: op 0 = k*P, 1 = k1*P1 + k2*P2, 2 = P1 + P2 (a, b = the inf flags)
@@ -3084,6 +3141,46 @@ class Engine {
         if (is_custom(curve)) rc = sum_chunk<CvCustom>(g, m, kk, pp, r[0] + o * 2 * B, r[1] + o);
         else ELL_SHORT_DISPATCH(curve, rc = sum_chunk<CV>(g, m, kk, pp, r[0] + o * 2 * B, r[1] + o));
         return rc;
+      });
+    });
+  }
+
+  // The same on the Edwards curves (elliptic_amd/include/ellgpu_edsum.h): ed25519 and user-defined
+  // Edwards ids, plain and domain -- a domain id is the plain curve it also is.  B = 32 everywhere.
+  // The identity comes out as the family's normalisation writes it ((0, 1); out_inf 1 on ed25519, 0
+  // on a user-defined id), the unified law takes torsion points and the identity as ordinary terms.
+  // Chunks and slices as mul_sum's; one item per lane at every n: coop_grid() is not consulted.
+  int ed_mul_sum(Mem where, int curve, size_t n, size_t m, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
+    const CurveInfo* ci = curve_info(curve);
+    if (!ci || (is_custom(curve) && !custom_block(curve))) return fail(E_ARG, "unknown curve id");
+    if (curve == CURVE_CURVE25519 || custom_is_mont(curve))
+      return fail(E_UNSUPPORTED, "Not supported on Montgomery curve");     // mont.js:155-157
+    if (curve != CURVE_ED25519 && !custom_is_edwards(curve))
+      return fail(E_UNSUPPORTED, "sums of k * P terms on the short Weierstrass curves are ellgpu_mul_sum's; this entry point takes ed25519 and user-defined Edwards ids");
+    if (m == 0) return fail(E_ARG, "m must be at least 1");
+    const size_t B = 32;
+    if (n && (m > SIZE_MAX / n || n * m > SIZE_MAX / (2 * B))) return fail(E_ARG, "n * m terms do not fit size_t");
+    if (n && (!k || !xy || !out_xy || !out_inf)) return fail(E_ARG, "null pointer");
+    if (n == 0) return E_OK;
+    if (where == Mem::device) {
+      // the flags of the terms are folded into out_inf after the results are written
+      const u8* const ins[2] = {k, xy};
+      const size_t lens[2] = {n * m * B, n * m * 2 * B};
+      for (int i = 0; i < 2; i++)
+        if (overlap2(ins[i], lens[i], out_xy, n * 2 * B) || overlap2(ins[i], lens[i], out_inf, n))
+          return fail(E_ARG, "k / xy and the results must not overlap");
+      if (overlap2(out_xy, n * 2 * B, out_inf, n)) return fail(E_ARG, "out_xy and out_inf must not overlap");
+    }
+    CustomScope sc(this, curve);
+    if (sc.rc) return sc.rc;
+    const size_t G = sum_group_max(m);
+    return batch(where, n, {In{k, m * B}, In{xy, m * 2 * B}}, {Out{out_xy, 2 * B}, Out{out_inf, 1}},
+                 [&](size_t c, auto d, auto r) {
+      return for_chunks(c, G ? G : 1, [&](size_t o, size_t g) {
+        const u8* kk = d[0] + o * m * B;
+        const u8* pp = d[1] + o * m * 2 * B;
+        return is_custom(curve) ? ed_sum_chunk<EdcWork>(g, m, kk, pp, r[0] + o * 2 * B, r[1] + o)
+                                : ed_sum_chunk<EdWork>(g, m, kk, pp, r[0] + o * 2 * B, r[1] + o);
       });
     });
   }
@@ -4543,6 +4640,72 @@ int Engine<BK>::ed_mul_add2_chunk(size_t n, const u8* k1, const u8* xy1, const u
     bk.launch(g, n);
   }
   return rc;
+}
+
+// sum_chunk<CV> over an Edwards work class.  Scratch: never more entries or window tables than that
+// family's mul_add2 chunk claims for CHUNK items (ed_mul_add2_chunk: four planes of 8 words per
+// item; edc_chunk: three).  S_JAC holds three runs of planes -- the pairs' (at most `cap` entries),
+// the slices' partial sums (nsl entries, none when every sum is whole) and the compact results (n)
+// -- and S_VALID the flags of the same entries, a byte each; S_TBL the pairs' window tables.
+template <class BK>
+template <class EW>
+int Engine<BK>::ed_sum_chunk(size_t n, size_t m, const u8* k, const u8* xy, u8* out_xy, u8* out_inf) {
+  constexpr bool ED = std::is_same<EW, EdWork>::value;
+  const size_t P = m / 2 + (m & 1);
+  const bool whole = n <= sum_group_max(m);
+  size_t s = P, nsl = 0;                  // pairs per launch and row; slices of the one sum
+  if (!whole) {
+    if (n != 1) return fail(E_ARG, "a sum that is walked in slices is a chunk of its own");
+    s = tune_.sum_slice;
+    nsl = (P - 1) / s + 1;
+    if (s + nsl + 1 > CHUNK) {            // the slices' partial sums and the result share the pairs' scratch
+      s = CHUNK / 2;
+      nsl = (P - 1) / s + 1;
+    }
+    if (nsl + 1 > CHUNK / 2) return fail(E_ARG, "m: too many terms for one sum");
+  }
+  const size_t cap = whole ? n * P : s;
+  const size_t E = (size_t)EW::SUM_PLANES * 8;     // words of an entry
+  u32* ext = claim<u32>(S_JAC, (cap + nsl + n) * E * 4);
+  auto* tbl = claim<typename EW::P>(S_TBL, cap * 16 * sizeof(typename EW::P));
+  u8* flag = claim<u8>(S_VALID, cap + nsl + n);
+  u32* pre = ED ? nullptr : claim<u32>(S_PRE, n * 8 * 4);      // (ed_normalize_chunk claims its own)
+  if (int rc = claimed()) return rc;
+  u32* pext = ext + cap * E;
+  u8* pflag = flag + cap;
+  u32* cext = pext + nsl * E;
+  u8* cflag = pflag + nsl;
+  // the halving steps of `rows` rows of `len` partial sums; the last one (the copy step of a row
+  // that starts with one partial) writes entry d0 + row of the dn-entry planes dst / dflag
+  auto fold = [&](size_t rows, size_t len, u32* src, u8* sflag, u32* dst, u8* dflag, size_t dn, size_t d0) {
+    const size_t stride = len;
+    for (;; len = (len + 1) / 2) {
+      FnEdSumFold<EW> f{rows, stride, len, src, sflag, dst, dflag, dn, d0};
+      bk.launch(f, rows * ((len + 1) / 2));
+      if (len <= 2) break;
+    }
+  };
+  if (whole) {
+    FnEdSumPairs<EW> f{n, P, m, 0, k, xy, tbl, ext, flag};
+    bk.launch(f, n * P);
+    fold(n, P, ext, flag, cext, cflag, n, 0);
+  } else {
+    for (size_t sl = 0; sl < nsl; sl++) {
+      const size_t q0 = sl * s, len = P - q0 < s ? P - q0 : s;
+      FnEdSumPairs<EW> f{1, len, m, q0, k, xy, tbl, ext, flag};
+      bk.launch(f, len);
+      fold(1, len, ext, flag, pext, pflag, nsl, sl);
+    }
+    fold(1, nsl, pext, pflag, cext, cflag, 1, 0);
+  }
+  if constexpr (ED) {
+    if (int rc = ed_normalize_chunk(n, cext, out_xy, out_inf, nullptr)) return rc;
+  } else {
+    launch_inv<Route::here, FnEdcNormalize>(field_inv(n), n, cext, pre, out_xy, out_inf);
+  }
+  FnEdSumMark<EW> g{n, cflag, out_xy, out_inf};
+  bk.launch(g, n);
+  return E_OK;
 }
 
 // ---- fixed-base tables of caller-chosen points on Edwards curves ---------------------------------

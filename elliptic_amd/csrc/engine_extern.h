@@ -77,7 +77,7 @@ namespace ell {
       const FnMulJoin<CvSecp256k1>&, size_t);
 // user-defined short curves (CvCustom): scalar multiplication, point addition and the wire
 // formats (pointFromX, decodePoint, the DER parser, the wire verify's status), ECDH, key validation
-// and SEC1 encoding; user-defined Edwards (edc_chunk; the tables of caller-chosen bases: edc_base_*; the key
+// and SEC1 encoding; user-defined Edwards (edc_chunk, ed_sum_chunk<EdcWork>; the tables of caller-chosen bases: edc_base_*; the key
 // side: edk_*_chunk) and Montgomery (montc_chunk) curves
 #define ELL_DECL_CUSTOM(KW)                                                                          \
   KW template int Engine<HipBackend>::mul_var_chunk<CvCustom>(size_t, const u8*, const u8*, u8*, u8*, \
@@ -92,6 +92,8 @@ namespace ell {
                                                                 const u8*, u8*, u8*);                \
   KW template int Engine<HipBackend>::edc_chunk<0>(int, size_t, const u8*, const u8*, const u8*,     \
                                                    const u8*, const u8*, const u8*, u8*, u8*);       \
+  KW template int Engine<HipBackend>::ed_sum_chunk<EdcWork>(size_t, size_t, const u8*, const u8*,   \
+                                                            u8*, u8*);                               \
   KW template int Engine<HipBackend>::edc_base_table<0>(const u8*, int, Engine<HipBackend>::CombTable&); \
   KW template int Engine<HipBackend>::edc_base_mul_chunk<0>(size_t, const u8*, const EdcWork::A*,    \
                                                             const u8*, const EdcWork::A*, u8*, u8*); \
@@ -177,7 +179,8 @@ namespace ell {
   KW template int Engine<HipBackend>::ed_base_mul_chunk<0>(size_t, const u8*, const EdWork::P*, \
                                                            const u8*, const EdWork::P*, u8*, u8*); \
   KW template int Engine<HipBackend>::ed_mul_add2_chunk<0>(size_t, const u8*, const u8*,     \
-                                                           const u8*, const u8*, u8*, u8*);
+                                                           const u8*, const u8*, u8*, u8*);  \
+  KW template int Engine<HipBackend>::ed_sum_chunk<EdWork>(size_t, size_t, const u8*, const u8*, u8*, u8*);
 #define ELL_DECL_X(KW) \
   KW template int Engine<HipBackend>::x25519_chunk<0>(size_t, const u8*, const u8*, u8*, u8*, u8*);
 

@@ -465,6 +465,22 @@ class Context:
         torch device tensors (k, xy and out=(xy, inf), required then) run on the current stream and
         return at once."""
         B = FIELD_BYTES[CURVES[curve] if isinstance(curve, int) and 0 <= curve < len(CURVES) else curve]
+        return self._sum_call("ellgpu_mul_sum", B, curve, k, xy, out)
+
+    def ed_mul_sum(self, curve, k, xy, out=None):
+        """mul_sum on the Edwards curves (ellgpu_ed_mul_sum): curve is "ed25519" or a define_edwards /
+        define_edwards_domain id, k (n, m, 32), xy (n, m, 64) -> (xy (n, 64), inf (n,)).  The partial
+        sums are added on the device through the curve's unified law (torsion points and the identity
+        (0, 1) are ordinary terms), one normalisation per sum.  inf: 0 a point; the identity is (0, 1)
+        with inf 1 on ed25519 and inf 0 on a user-defined id, as mul_add2 writes it there; 2
+        (STATUS_OFF_CURVE) a term's point is not on the curve, xy zeroed.  numpy arrays go through
+        host memory; torch device tensors (k, xy and out=(xy, inf), required then) run on the current
+        stream and return at once.  mul_sum keeps refusing these curves, this method the short ones."""
+        return self._sum_call("ellgpu_ed_mul_sum", 32, curve, k, xy, out)
+
+    def _sum_call(self, symbol, B, curve, k, xy, out):
+        """ellgpu_mul_sum / ellgpu_ed_mul_sum: (ctx, curve, n, m, k, xy, out_xy, out_inf, mem, stream),
+        one symbol for both kinds of memory"""
         dev = self._is_tensor(k)
         if not dev:
             k, xy = _u8(k), _u8(xy)
@@ -480,8 +496,8 @@ class Context:
                 raise ValueError("xy must be (n, m, %d)" % (2 * B))
             res = self._outs(out, shapes[2:])
         addr = [a.data_ptr() if dev else a.ctypes.data for a in [k, xy] + res]
-        self._check(self._lib.ellgpu_mul_sum(self._ctx, self._cid(curve), n, m, *addr, 1 if dev else 0,
-                                             self._stream() if dev else None))
+        self._check(getattr(self._lib, symbol)(self._ctx, self._cid(curve), n, m, *addr, 1 if dev else 0,
+                                               self._stream() if dev else None))
         return res[0], res[1]
 
     def point_add(self, curve, xy1, xy2, inf1=None, inf2=None):

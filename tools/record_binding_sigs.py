@@ -13,7 +13,8 @@ after a deliberate change of include/ellgpu.h -- never to make a failing test pa
 into binding_sigs_ext.json, _EXT2_SIGS of include/ellgpu_ext2.h into binding_sigs_ext2.json,
 _EXT3_SIGS of include/ellgpu_ext3.h into binding_sigs_ext3.json, _EXT4_SIGS of include/ellgpu_ext4.h
 into binding_sigs_ext4.json; --table addn: _SUM_SIGS of include/ellgpu_addn.h into
-addn_binding_sigs.json): once, when the table is introduced.
+addn_binding_sigs.json; --table edsum: _EDSUM_SIGS of elliptic_amd/include/ellgpu_edsum.h into
+edsum_binding_sigs.json): once, when the table is introduced.
 """
 import argparse
 import json
@@ -33,7 +34,9 @@ TABLES = {"sigs": ("_SIGS", GOLDEN), "ext": ("_EXT_SIGS", GOLDEN.replace(".json"
           # (addn_binding_sigs.json, not binding_sigs_addn.json: tests/test_dev_streams_hostsim.py takes every
           # binding_sigs*.json for a table whose `mem` calls tests/dev_stream_checks.py schedules; ellgpu_mul_sum
           # is tested in flight in tests/test_mul_sum_gpu.py until that table names it)
-          "addn": ("_SUM_SIGS", os.path.join(os.path.dirname(GOLDEN), "addn_binding_sigs.json"))}
+          "addn": ("_SUM_SIGS", os.path.join(os.path.dirname(GOLDEN), "addn_binding_sigs.json")),
+          # (named like addn's, for the same reason: ellgpu_ed_mul_sum is tested in flight in tests/test_ed_mul_sum_gpu.py)
+          "edsum": ("_EDSUM_SIGS", os.path.join(os.path.dirname(GOLDEN), "edsum_binding_sigs.json"))}
 
 
 def table(sigs=None):
